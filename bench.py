@@ -20,6 +20,11 @@
 Inference shards by image (weak scaling, no data-path collective); training all-reduces one float32 gradient bucket.
 --gpus N > 1 without a torchrun environment re-launches this script under torch.distributed.run with N local ranks.
 --dry-run: no kernels, no GPU: the launcher, rendezvous (gloo), barrier and max-over-ranks timing only (CI on a CPU box).
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  --full adds
+everything else the benchmark measures: the per-launch survey and roofline objects, box calibration, clocks, latencies,
+forward-only diagnostics, the training losses and the CPU baseline (--no-cpu-baseline drops the last one).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
+(float32 / float64); the inputs are seeded, so two builds can be compared output for output.
 Every step reads a DIFFERENT input batch from a rotation larger than the 256 MiB Infinity Cache.
 Inference steps keep TWO batches in flight (consecutive steps alternate between two HIP streams / plans; SQDET_SERVE_LANES=1: one):
 all K batches' work is inside the timed region, which ends with flush_pipeline() + a device-wide synchronize.
@@ -71,8 +76,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--config", default="sqdet_infer", choices=sorted(CONFIGS))
     # defaults per config (sqdet_infer: 200 steps ~ 0.14 s of GPU time; short runs reproduce it within a few %)
-    ap.add_argument("--steps", type=int, default=0)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: the config's)")
     ap.add_argument("--warmup", type=int, default=-1)
+    ap.add_argument("--full", action="store_true",
+                    help="also the diagnostics: per-launch survey, roofline, box calibration, clocks, latencies, losses, CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB; rank 0)")
     ap.add_argument("--spinup-ms", type=float, default=250.0, help="untimed steps for this long before the timed region (clock settle)")
     ap.add_argument("--batch", type=int, default=0, help="images per GPU per step (default: the config's)")
     ap.add_argument("--height", type=int, default=0)
@@ -88,7 +97,11 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     c = CONFIGS[a.config]
     a.kind, a.arch, a.metric, a.sample = c["kind"], c["arch"], c["metric"], bool(c.get("sample"))
-    a.steps = a.steps or c["steps"]
+    a.steps = c["steps"] if a.steps is None else a.steps
+    if a.steps < 1:
+        fail("--steps must be >= 1, got %d" % a.steps)
+    if a.layer_table and not a.full:
+        fail("--layer-table needs --full (the per-launch survey runs only there)")
     a.warmup = a.warmup if a.warmup >= 0 else c["warmup"]
     a.batch = a.batch or c["batch"]
     a.height = a.height or c["height"]
@@ -350,6 +363,46 @@ def rotation_count(batch_bytes):
     return max(4, int(np.ceil(1.3 * MALL_BYTES / float(batch_bytes))))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_MAX_PARAMS = 1 << 22       # a larger parameter vector is dumped as a fixed, seeded sample of this many values
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 or float64 only), DUMP_LIMIT_BYTES at most in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def infer_outputs(out):
+    """What the last timed inference step hands its caller: filter_prediction_batch's rows (boxes [B,M,4], probs [B,M], classes
+    [B,M], anchor indices [B,M], counts [B]).  Rows past an image's count carry no result and are written as zeros."""
+    boxes, probs, cls, idx, cnt = [torch.as_tensor(t).cpu().numpy() for t in out[:5]]
+    cnt = cnt.astype(np.int64)
+    valid = np.arange(probs.shape[1])[None, :] < cnt[:, None]
+    return {"boxes": np.where(valid[..., None], boxes, 0).astype(np.float32),
+            "probs": np.where(valid, probs, 0).astype(np.float32),
+            "classes": np.where(valid, cls, 0).astype(np.float32),
+            "anchor_index": np.where(valid, idx, 0).astype(np.float64),
+            "count": cnt.astype(np.float32)}
+
+
+def train_outputs(out, trainer):
+    """What the last timed training step leaves its caller: the step's losses and the updated float32 parameter vector (a fixed,
+    seeded sample of DUMP_MAX_PARAMS values, with their indices, when the vector is longer)."""
+    res = {k: v.detach().float().cpu().numpy() for k, v in out.items() if isinstance(v, torch.Tensor) and v.numel() == 1}
+    flat = trainer.flat_params.detach().float().cpu().numpy()
+    if flat.size > DUMP_MAX_PARAMS:
+        idx = np.sort(np.random.RandomState(0).choice(flat.size, DUMP_MAX_PARAMS, replace=False))
+        res["params_sample_index"] = idx.astype(np.float64)
+        flat = flat[idx]
+    res["params"] = flat
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ inference
 def build_infer_model(args, device_index):
     import squeezedet_amd as S
@@ -599,19 +652,22 @@ def run_infer(args, rank, local_rank, world, device):
     model.flush_pipeline()
     torch.cuda.synchronize()
 
-    # untimed per-launch survey to find the dominant kernel (HIP events on the launch stream)
-    _, ms0 = plan.forward_timed(xs[0])
-    for k in range(1, 3):
-        _, ms = plan.forward_timed(xs[k % nrot])
-        ms0 = [min(a, b) for a, b in zip(ms0, ms)]
-    dom = int(np.argmax(ms0))
+    if args.full:
+        # untimed per-launch survey to find the dominant kernel (HIP events on the launch stream)
+        _, ms0 = plan.forward_timed(xs[0])
+        for k in range(1, 3):
+            _, ms = plan.forward_timed(xs[k % nrot])
+            ms0 = [min(a, b) for a, b in zip(ms0, ms)]
+        dom = int(np.argmax(ms0))
     spin_up(step, args.spinup_ms, model.flush_pipeline)
-    box = box_calibration(device)                         # ~6 ms of fixed microkernels: what THIS box sustains (untimed)
-    # (the clock read-out sits AHEAD of the last spin-up: its first call loads and initialises amdsmi, tens of milliseconds with
-    # the GPU idle, and a 20-step timed region that starts behind such a gap reads up to 10 % below a 200-step one)
-    clocks = {"before": gpu_state(local_rank)}
+    box = clocks = None
+    if args.full:
+        box = box_calibration(device)                     # ~6 ms of fixed microkernels: what THIS box sustains (untimed)
+        # (the clock read-out sits AHEAD of the last spin-up: its first call loads and initialises amdsmi, tens of milliseconds with
+        # the GPU idle, and a 20-step timed region that starts behind such a gap reads up to 10 % below a 200-step one)
+        clocks = {"before": gpu_state(local_rank)}
     spin_up(step, min(args.spinup_ms, 20.0), model.flush_pipeline)
-    if os.environ.get("SQDET_BENCH_NO_PROBE") != "1":     # (A/B knob: what the live event pairs cost the step)
+    if args.full and os.environ.get("SQDET_BENCH_NO_PROBE") != "1":     # (A/B knob: what the live event pairs cost the step)
         plan.set_probe(dom, args.steps)
 
     # ---- timed region: EXACTLY `steps` steps between barrier+synchronize pairs ----
@@ -626,9 +682,28 @@ def run_infer(args, rank, local_rank, world, device):
     own = time.perf_counter() - t0           # this rank's own time (before the barrier): the line's rank_ms_per_step
     barrier(world, device)
     elapsed = time.perf_counter() - t0
-    clocks["after"] = gpu_state(local_rank)
+    if args.full:
+        clocks["after"] = gpu_state(local_rank)
     elapsed = max_over_ranks(elapsed, world, device, own)
     ranks_seen, devices = rank_census(rank, local_rank, world, device)
+    # (the rows of the last timed step, read before any later step can reuse its pipeline slot)
+    counts = np.asarray(out[4].cpu() if isinstance(out[4], torch.Tensor) else out[4])
+    assert (counts >= 0).all() and (counts <= 64).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, infer_outputs(out))
+
+    def head():
+        res = result_head(args, aggregate_throughput(args.batch, args.steps, world, elapsed), world, elapsed, ranks_seen, devices, clocks)
+        res["config"] = {"workload": "%s %s inference, batch=%d per GPU, synthetic %dx%d images (%d distinct batches in rotation), full hot "
+                                     "path (forward + interpret_output + filter_prediction + filtered rows to pinned host memory), inputs "
+                                     "resident in HBM%s" % (args.arch, args.dtype, args.batch, args.width, args.height, nrot,
+                                                         "; %d batches in flight (consecutive steps alternate between %d HIP streams)" % (lanes, lanes) if lanes >= 2 else ""),
+                         "name": args.config, "global_batch": args.batch * world,
+                         "parallelism": "dp%d (independent image shards, no collective)" % world}
+        return res
+
+    if not args.full:
+        return head() if rank == 0 else None
 
     probe_ms = plan.read_probe(args.steps)
     plan.set_probe(-1, 0)
@@ -661,11 +736,8 @@ def run_infer(args, rank, local_rank, world, device):
         if sp:
             single = (float(np.mean(sp)), single_step_ms)
     latency = batch_latency(model, step, lanes, xs[0])
-    counts = np.asarray(out[4].cpu() if isinstance(out[4], torch.Tensor) else out[4])
-    assert (counts >= 0).all() and (counts <= 64).all()
     if rank != 0:
         return None
-    value = aggregate_throughput(args.batch, args.steps, world, elapsed)
     name, flops, nbytes = layers[dom]
     avg_ms = float(np.mean(probe_ms)) if probe_ms else float(ms0[dom])
     roof = launch_roofline(flops, nbytes, avg_ms, args.dtype)
@@ -719,13 +791,7 @@ def run_infer(args, rank, local_rank, world, device):
         with open(args.layer_table, "w") as fh:
             json.dump({"layers": table, "forward_ms_sum": sum(ms0), "step_ms": elapsed / args.steps * 1e3,
                        "build_fingerprint": build_fingerprint()}, fh, indent=1)
-    res = result_head(args, value, world, elapsed, ranks_seen, devices, clocks)
-    res["config"] = {"workload": "%s %s inference, batch=%d per GPU, synthetic %dx%d images (%d distinct batches in rotation), full hot "
-                                 "path (forward + interpret_output + filter_prediction + filtered rows to pinned host memory), inputs "
-                                 "resident in HBM%s" % (args.arch, args.dtype, args.batch, args.width, args.height, nrot,
-                                                     "; %d batches in flight (consecutive steps alternate between %d HIP streams)" % (lanes, lanes) if lanes >= 2 else ""),
-                     "name": args.config, "global_batch": args.batch * world,
-                     "parallelism": "dp%d (independent image shards, no collective)" % world}
+    res = head()
     res["roofline"] = roof
     # chip-level view of the timed steps: the forward's algorithmic flops over the step time, and the composite roofline -- the sum over
     # the launches of max(bytes / 8 TB/s, flops / 2.5 PF/s) -- over the step time
@@ -882,8 +948,10 @@ def run_train(args, rank, local_rank, world, device):
         out = step(i)
     torch.cuda.synchronize()
     spin_up(step, args.spinup_ms)
-    box = box_calibration(device)
-    clocks = {"before": gpu_state(local_rank)}            # (ahead of the last spin-up: see run_infer)
+    box = clocks = None
+    if args.full:
+        box = box_calibration(device)
+        clocks = {"before": gpu_state(local_rank)}        # (ahead of the last spin-up: see run_infer)
     spin_up(step, min(args.spinup_ms, 20.0))
     barrier(world, device)
     torch.cuda.synchronize()
@@ -896,12 +964,26 @@ def run_train(args, rank, local_rank, world, device):
     own = time.perf_counter() - t0
     barrier(world, device)
     elapsed = time.perf_counter() - t0
-    clocks["after"] = gpu_state(local_rank)
+    if args.full:
+        clocks["after"] = gpu_state(local_rank)
     elapsed = max_over_ranks(elapsed, world, device, own)
     ranks_seen, devices = rank_census(rank, local_rank, world, device)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, train_outputs(out, tr))
     value = aggregate_throughput(args.batch, args.steps, world, elapsed)
+    res = result_head(args, value, world, elapsed, ranks_seen, devices, clocks)
+    res["config"] = {"workload": "%s %s training, batch=%d per GPU, synthetic %dx%d images + KITTI-like ground truth (%d distinct batches "
+                                 "in rotation): GPU label build + forward + loss + backward + gradient all-reduce + clipped Momentum"
+                                 % (args.arch, "float32" if args.dtype == "fp32" else "mixed-precision (float16 activations)", args.batch,
+                                    args.width, args.height, nrot),
+                     "name": args.config, "global_batch": args.batch * world,
+                     "parallelism": "dp%d (one flat float32 gradient bucket all-reduced over RCCL per step)" % world}
+    res["hipgraph"] = bool(use_graph)
+    res["skipped_steps"] = tr.skipped_steps
+    if not args.full:
+        return res
     fwd, bwd = training_flops_per_image(model)
     step_ms = elapsed / args.steps * 1e3
     peak = MFMA_F32_PEAK_TFLOPS if args.dtype == "fp32" else MFMA_F16_PEAK_TFLOPS
@@ -916,18 +998,9 @@ def run_train(args, rank, local_rank, world, device):
     roof["avg_launch_ms"] = round(step_ms, 4)
     roof["algorithmic_flops_per_launch"] = flops
     roof["dominant_kernel"] = kernel_roofline(dominant_kernel_from_stats(args.config), pk, args.dtype)
-    res = result_head(args, value, world, elapsed, ranks_seen, devices, clocks)
-    res["config"] = {"workload": "%s %s training, batch=%d per GPU, synthetic %dx%d images + KITTI-like ground truth (%d distinct batches "
-                                 "in rotation): GPU label build + forward + loss + backward + gradient all-reduce + clipped Momentum"
-                                 % (args.arch, "float32" if args.dtype == "fp32" else "mixed-precision (float16 activations)", args.batch,
-                                    args.width, args.height, nrot),
-                     "name": args.config, "global_batch": args.batch * world,
-                     "parallelism": "dp%d (one flat float32 gradient bucket all-reduced over RCCL per step)" % world}
     res["roofline"] = roof
     res["box"] = box
     res["host_issue_ms_per_step"] = round(t_issued / args.steps * 1e3, 4)
-    res["hipgraph"] = bool(use_graph)
-    res["skipped_steps"] = tr.skipped_steps
     res["losses"] = {k: float(out[k]) for k in ("class_loss", "conf_loss", "bbox_loss")}
     if not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline_train(args, args.cpu_baseline_seconds)

@@ -114,3 +114,54 @@ def make_label_case(name):
         rois.append(r[:LABEL_MAX_OBJECTS])
         sizes.append((h, w))
     return cfg, rois, sizes
+
+
+# ---- KITTI evaluation (dataset/kitti.py:100-159): a tiny seeded dataset and two detection tables ----
+KITTI_CLASSES = ("car", "pedestrian", "cyclist")       # kitti.py:22
+
+
+def make_kitti_case(root, n_images=48):
+    """Writes a tiny KITTI tree under `root` (training/label_2/<idx>.txt + ImageSets/val.txt; >= 41 objects per class: the
+    evaluator samples 41 recall points) and returns (image indices, {"perfect": all_boxes, "half": all_boxes}): every ground
+    truth box detected, or every other image's boxes replaced by a false positive far away."""
+    import os
+    from squeezedet_amd import kitti_eval as K
+    rs = np.random.RandomState(0)
+    os.makedirs(os.path.join(root, "training", "label_2"))
+    os.makedirs(os.path.join(root, "ImageSets"))
+    idxs, gts = ["%06d" % i for i in range(n_images)], {}
+    for idx in idxs:
+        rows = []
+        for k in range(3):
+            cls = KITTI_CLASSES[k]
+            x1, y1 = rs.uniform(10 + 300 * k, 200 + 300 * k), rs.uniform(50, 150)
+            w, h = rs.uniform(60, 120), rs.uniform(60, 120)
+            rows.append((cls, x1, y1, x1 + w, y1 + h))
+        gts[idx] = rows
+        with open(os.path.join(root, "training", "label_2", idx + ".txt"), "w") as f:
+            for cls, x1, y1, x2, y2 in rows:
+                f.write("%s 0.00 0 -1.50 %.2f %.2f %.2f %.2f 1.50 1.60 3.90 1.00 1.70 20.00 -1.50\n" % (cls.capitalize(), x1, y1, x2, y2))
+    with open(os.path.join(root, "ImageSets", "val.txt"), "w") as f:
+        f.write("\n".join(idxs) + "\n")
+    perfect, half = K.new_all_boxes(3, len(idxs)), K.new_all_boxes(3, len(idxs))
+    for i, idx in enumerate(idxs):
+        for cls, x1, y1, x2, y2 in gts[idx]:
+            box = [(x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1]            # what filter_prediction would return
+            sc = float(rs.uniform(0.5, 0.9))       # distinct scores: the evaluator samples recall through score thresholds
+            K.add_detections(perfect, i, [box], [sc], [KITTI_CLASSES.index(cls)])
+            if i % 2 == 0:
+                K.add_detections(half, i, [box], [sc], [KITTI_CLASSES.index(cls)])
+            else:                                                             # a false positive far away instead
+                K.add_detections(half, i, [[box[0], box[1] + 200, box[2], box[3]]], [0.95], [KITTI_CLASSES.index(cls)])
+    return idxs, {"perfect": perfect, "half": half}
+
+
+def kitti_detection_digest(det_dir):
+    """sha256 over the detection files in det_dir (sorted by name): what the evaluator was handed."""
+    import hashlib
+    import os
+    h = hashlib.sha256()
+    for fn in sorted(os.listdir(det_dir)):
+        with open(os.path.join(det_dir, fn), "rb") as f:
+            h.update(fn.encode() + b"\0" + f.read() + b"\0")
+    return h.hexdigest()

@@ -121,6 +121,61 @@ def main():
         out[name + "_aidx"], out[name + "_delta"], out[name + "_bbox"], out[name + "_label"], out[name + "_count"] = a, d, bb, lb, cnt
         print(name, "->", int(cnt.sum()), "objects; anchors of image 0:", a[0, :cnt[0]].tolist())
     np.savez(os.path.join(HERE, "labels.npz"), **out)
+    live_reference(ns)
+    kitti_evaluator()
+
+
+# inputs of the oracle-vs-reference cross-check (tests/test_oracle_golden.py::test_oracle_vs_live_reference)
+LIVE_SEEDS = range(20, 26)
+LIVE_CONFIG_FIELDS = ("IMAGE_WIDTH", "IMAGE_HEIGHT", "CLASSES", "ANCHOR_PER_GRID", "ANCHORS", "EXP_THRESH", "TOP_N_DETECTION",
+                      "PROB_THRESH", "NMS_THRESH", "PLOT_PROB_THRESH", "BATCH_SIZE", "WEIGHT_DECAY", "LEARNING_RATE",
+                      "MAX_GRAD_NORM", "MOMENTUM", "LR_DECAY_FACTOR", "LOSS_COEF_BBOX", "LOSS_COEF_CONF_POS",
+                      "LOSS_COEF_CONF_NEG", "LOSS_COEF_CLASS", "EPSILON", "DECAY_STEPS")
+
+
+def live_boxes(seed, n=200):
+    rs = np.random.RandomState(seed)
+    bx = np.stack([rs.uniform(0, 600, n), rs.uniform(0, 383, n), rs.uniform(1, 300, n), rs.uniform(1, 200, n)], 1).astype(np.float32)
+    return bx, rs.uniform(0, 1, n).astype(np.float32)
+
+
+def live_reference(ns):
+    """util.nms / util.batch_iou on seeded boxes and the squeezeDet config's fields, as the reference computes them ->
+    live_reference.npz."""
+    out = {}
+    for seed in LIVE_SEEDS:
+        bx, pr = live_boxes(seed)
+        out["nms_keep_%d" % seed] = np.array(ns.util.nms(bx, pr, 0.4))
+        out["iou_vs_row3_%d" % seed] = ns.util.batch_iou(bx, bx[3])
+    mc = ns.cfg_squeezeDet.kitti_squeezeDet_config()
+    for k in LIVE_CONFIG_FIELDS:
+        out["config_" + k] = np.array(mc[k])
+    out["config_ANCHOR_BOX_sha256"] = np.array(sha(np.asarray(mc.ANCHOR_BOX)))
+    np.savez(os.path.join(HERE, "live_reference.npz"), **out)
+
+
+def kitti_evaluator():
+    """The reference's own KITTI C++ evaluator (built into oracle/_ref/ by oracle/Makefile) on cases.make_kitti_case: the digest
+    of the detection files it was handed and the AP files it wrote -> kitti_eval.npz."""
+    import subprocess
+    import tempfile
+    from squeezedet_amd import kitti_eval as K
+    root = os.path.dirname(os.path.dirname(HERE))
+    subprocess.run(["make", "-s", "-C", os.path.join(root, "oracle")], check=True)
+    tool = os.path.join(root, "oracle", "_ref", "evaluate_object")
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        idxs, tables = cases.make_kitti_case(os.path.join(tmp, "KITTI"))
+        for name, table in sorted(tables.items()):
+            ev = os.path.join(tmp, "eval_" + name)
+            aps, _ = K.evaluate_detections(tool, os.path.join(tmp, "KITTI"), "val", ev, 100, idxs, cases.KITTI_CLASSES, table)
+            det = os.path.join(ev, "detection_files_100")
+            out[name + "_detections_sha256"] = np.array(cases.kitti_detection_digest(os.path.join(det, "data")))
+            for cls in cases.KITTI_CLASSES:
+                with open(os.path.join(det, "stats_%s_ap.txt" % cls)) as f:
+                    out["%s_stats_%s_ap" % (name, cls)] = np.array(f.read())
+            print("kitti", name, "->", aps)
+    np.savez(os.path.join(HERE, "kitti_eval.npz"), **out)
 
 
 if __name__ == "__main__":

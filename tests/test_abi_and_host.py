@@ -365,3 +365,25 @@ def test_tools_and_scripts_parse():
     for p in sorted(glob.glob(os.path.join(root, "tools", "*.sh"))):
         r = subprocess.run(["bash", "-n", p], capture_output=True, text=True)
         assert r.returncode == 0, (p, r.stderr)
+
+
+def test_bench_dump_helpers(tmp_path):
+    """bench.py --dump-outputs: the inference rows past an image's count are written as zeros, every array is float32 / float64,
+    and a parameter vector longer than the limit is dumped as the same seeded sample every time."""
+    import bench
+    cnt = torch.tensor([2, 0], dtype=torch.int32)
+    boxes, probs = torch.rand(2, 4, 4), torch.rand(2, 4)
+    cls, idx = torch.randint(0, 3, (2, 4), dtype=torch.int32), torch.randint(0, 16848, (2, 4), dtype=torch.int32)
+    d = bench.infer_outputs((boxes, probs, cls, idx, cnt))
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values())
+    assert np.array_equal(d["boxes"][0, :2], boxes[0, :2].numpy()) and not d["boxes"][0, 2:].any() and not d["probs"][1].any()
+    assert np.array_equal(d["anchor_index"][0, :2], idx[0, :2].numpy()) and d["count"].tolist() == [2.0, 0.0]
+    bench.dump_outputs(str(tmp_path / "o"), d)
+    assert np.array_equal(np.load(tmp_path / "o" / "probs.npy"), d["probs"])
+
+    class Tr:
+        flat_params = torch.arange(bench.DUMP_MAX_PARAMS + 10, dtype=torch.float32)
+    t1 = bench.train_outputs({"loss": torch.tensor(1.5), "conf_loss": torch.tensor(0.5)}, Tr())
+    t2 = bench.train_outputs({"loss": torch.tensor(1.5)}, Tr())
+    assert t1["loss"] == 1.5 and t1["params"].size == bench.DUMP_MAX_PARAMS
+    assert np.array_equal(t1["params"], t2["params"]) and np.array_equal(t1["params"], t1["params_sample_index"].astype(np.float32))

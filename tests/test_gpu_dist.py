@@ -26,7 +26,7 @@ def _torchrun(script_args, port, extra_env=None, timeout=600, nproc=1):
 def test_bench_under_rccl_world1():
     """bench.py launched exactly as the driver launches it for N > 1 (SQDET_FORCE_DIST=1 makes the one-rank job take the
     distributed path): init_process_group(nccl), barrier, all_reduce(MAX) of the time -- and the JSON contract."""
-    out = _torchrun(["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"], 29611, {"SQDET_FORCE_DIST": "1"})
+    out = _torchrun(["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"], 29611, {"SQDET_FORCE_DIST": "1"})
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
     assert res["n_gpus"] == 1 and res["steps"] == 5 and res["value"] > 1000 and res["scaling"] == "weak"
@@ -35,8 +35,8 @@ def test_bench_under_rccl_world1():
 
 def test_training_bench_under_rccl_world1():
     """The N > 1 entry point of the training configs (gradient all-reduce over RCCL inside the step), one rank."""
-    out = _torchrun(["bench.py", "--gpus", "1", "--config", "sqdet_train_fp32", "--batch", "4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
-                    29612, {"SQDET_FORCE_DIST": "1"})
+    out = _torchrun(["bench.py", "--gpus", "1", "--config", "sqdet_train_fp32", "--batch", "4", "--steps", "3", "--warmup", "1", "--full",
+                     "--no-cpu-baseline"], 29612, {"SQDET_FORCE_DIST": "1"})
     res = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["value"] > 10 and res["config"]["name"] == "sqdet_train_fp32"
     assert all(v == v and abs(v) < 1e6 for v in res["losses"].values())
@@ -81,3 +81,28 @@ def test_bench_two_ranks_share_one_gpu():
     assert res["ranks_seen"] == 2 and res["n_gpus"] == 2 and res["shared_device"] is True, res
     assert len(res["devices"]) == 2 and res["devices"][0]["uuid"] == res["devices"][1]["uuid"], res["devices"]
     assert res["value"] > 1000 and res["config"]["global_batch"] == 64, res
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields only, times exactly --steps steps, and --dump-outputs writes the last
+    timed step's rows as float32 / float64 .npy files; a second run with the same arguments computes the same rows."""
+    import numpy as np
+    lines = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    res = lines[0]
+    assert res["steps"] == 7 and res["ms_per_step"] > 0 and res["value"] > 1000 and res["higher_is_better"] is True
+    assert res["unit"] == "images/s" and res["dtype"] == "f16" and res["metric"].startswith("images/sec")
+    assert "roofline" not in res and "cpu_baseline" not in res and res["clocks"] is None
+    got = [{n: np.load(tmp_path / ("out%d" % k) / (n + ".npy")) for n in ("boxes", "probs", "classes", "anchor_index", "count")}
+           for k in range(2)]
+    a = got[0]
+    assert a["count"].shape == (32,) and a["boxes"].shape[:2] == a["probs"].shape == a["classes"].shape == a["anchor_index"].shape
+    assert a["probs"].shape[0] == 32 and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert ((a["count"] >= 0) & (a["count"] <= a["probs"].shape[1])).all()
+    for n in a:
+        assert np.array_equal(a[n], got[1][n]), n

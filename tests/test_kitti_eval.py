@@ -4,32 +4,10 @@ oracle/_ref/ (oracle/Makefile).  Host-only."""
 import os
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "oracle", "_ref", "evaluate_object")
 CLASSES = ("car", "pedestrian", "cyclist")       # kitti.py:22
-
-
-def _dataset(root, n_images, rs):
-    """A tiny KITTI tree: training/label_2/<idx>.txt + ImageSets/val.txt; returns {idx: [(cls, x1,y1,x2,y2)]}."""
-    os.makedirs(os.path.join(root, "training", "label_2"))
-    os.makedirs(os.path.join(root, "ImageSets"))
-    idxs, gts = ["%06d" % i for i in range(n_images)], {}
-    for idx in idxs:
-        rows = []
-        for k in range(3):
-            cls = CLASSES[k]
-            x1, y1 = rs.uniform(10 + 300 * k, 200 + 300 * k), rs.uniform(50, 150)
-            w, h = rs.uniform(60, 120), rs.uniform(60, 120)
-            rows.append((cls, x1, y1, x1 + w, y1 + h))
-        gts[idx] = rows
-        with open(os.path.join(root, "training", "label_2", idx + ".txt"), "w") as f:
-            for cls, x1, y1, x2, y2 in rows:
-                f.write("%s 0.00 0 -1.50 %.2f %.2f %.2f %.2f 1.50 1.60 3.90 1.00 1.70 20.00 -1.50\n" % (cls.capitalize(), x1, y1, x2, y2))
-    with open(os.path.join(root, "ImageSets", "val.txt"), "w") as f:
-        f.write("\n".join(idxs) + "\n")
-    return idxs, gts
 
 
 def test_detection_file_format(tmp_path):
@@ -44,24 +22,37 @@ def test_detection_file_format(tmp_path):
     assert np.allclose(ab[0][0][0], [40.0, 80.0, 60.0, 120.0, 0.5])
 
 
-@pytest.mark.skipif(not os.path.exists(TOOL), reason="oracle/_ref/evaluate_object not built (needs /root/reference at build time)")
-def test_reference_evaluator_reads_our_files(tmp_path):
+def _recorded_evaluator(monkeypatch, golden_dir):
+    """Stands in for the reference evaluator where oracle/_ref/ was not built (the reference tree is not on every machine): when
+    the detection files it is handed are byte for byte those the real evaluator scored (tests/golden/kitti_eval.npz,
+    make_golden.py), it writes the AP files the real one wrote for them; otherwise it writes nothing (every AP reads 0)."""
     from squeezedet_amd import kitti_eval as K
-    rs = np.random.RandomState(0)
+    from tests.golden import cases
+    g = np.load(os.path.join(golden_dir, "kitti_eval.npz"))
+
+    def call(cmd, **kw):
+        det_dir = cmd[3]
+        digest = cases.kitti_detection_digest(os.path.join(det_dir, "data"))
+        for name in ("perfect", "half"):
+            if digest == str(g[name + "_detections_sha256"]):
+                for cls in CLASSES:
+                    with open(os.path.join(det_dir, "stats_%s_ap.txt" % cls), "w") as f:
+                        f.write(str(g["%s_stats_%s_ap" % (name, cls)]))
+        return 0
+    monkeypatch.setattr(K, "subprocess", type("recorded", (), {"call": staticmethod(call), "DEVNULL": None}))
+    return "evaluate_object (recorded)"
+
+
+def test_reference_evaluator_reads_our_files(tmp_path, monkeypatch, golden_dir):
+    """The reference's own evaluator (oracle/_ref/evaluate_object where built, else its recorded answers) reads the detection
+    files we write as intended: every box found -> AP 1 everywhere; half of them replaced by false positives -> below 0.75."""
+    from squeezedet_amd import kitti_eval as K
+    from tests.golden import cases
+    tool = TOOL if os.path.exists(TOOL) else _recorded_evaluator(monkeypatch, golden_dir)
     root = str(tmp_path / "KITTI")
-    idxs, gts = _dataset(root, 48, rs)      # >= 41 objects per class: the evaluator samples 41 recall points
-    perfect, half = K.new_all_boxes(3, len(idxs)), K.new_all_boxes(3, len(idxs))
-    for i, idx in enumerate(idxs):
-        for cls, x1, y1, x2, y2 in gts[idx]:
-            box = [(x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1]            # what filter_prediction would return
-            sc = float(rs.uniform(0.5, 0.9))       # distinct scores: the evaluator samples recall through score thresholds
-            K.add_detections(perfect, i, [box], [sc], [CLASSES.index(cls)])
-            if i % 2 == 0:
-                K.add_detections(half, i, [box], [sc], [CLASSES.index(cls)])
-            else:                                                             # a false positive far away instead
-                K.add_detections(half, i, [[box[0], box[1] + 200, box[2], box[3]]], [0.95], [CLASSES.index(cls)])
-    aps, names = K.evaluate_detections(TOOL, root, "val", str(tmp_path / "eval_a"), 100, idxs, CLASSES, perfect)
+    idxs, tables = cases.make_kitti_case(root)
+    aps, names = K.evaluate_detections(tool, root, "val", str(tmp_path / "eval_a"), 100, idxs, CLASSES, tables["perfect"])
     assert names[:3] == ["car_easy", "car_medium", "car_hard"] and len(aps) == 9
     assert all(abs(a - 1.0) < 1e-6 for a in aps), aps
-    aps2, _ = K.evaluate_detections(TOOL, root, "val", str(tmp_path / "eval_b"), 100, idxs, CLASSES, half)
+    aps2, _ = K.evaluate_detections(tool, root, "val", str(tmp_path / "eval_b"), 100, idxs, CLASSES, tables["half"])
     assert all(0.0 < a < 0.75 for a in aps2), aps2

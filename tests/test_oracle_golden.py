@@ -92,24 +92,30 @@ def test_filter_prediction_uniform0_known_answer(golden_dir):
     np.testing.assert_allclose(g["uniform0_probs"][:3], [0.99974638, 0.99969339, 0.99956030], rtol=1e-7)
 
 
-@pytest.mark.skipif(not ref.available(), reason="reference tree not mounted")
-def test_oracle_vs_live_reference():
-    ns = ref.load()
-    for seed in range(20, 26):
-        rs = np.random.RandomState(seed)
-        n = 200
-        bx = np.stack([rs.uniform(0, 600, n), rs.uniform(0, 383, n), rs.uniform(1, 300, n), rs.uniform(1, 200, n)], 1).astype(np.float32)
-        pr = rs.uniform(0, 1, n).astype(np.float32)
-        assert O.nms(bx, pr, 0.4) == ns.util.nms(bx, pr, 0.4)
-        np.testing.assert_array_equal(O.batch_iou(bx, bx[3]), ns.util.batch_iou(bx, bx[3]))
-    mc_ref = ns.cfg_squeezeDet.kitti_squeezeDet_config()
+def test_oracle_vs_live_reference(golden_dir):
+    """util.nms / util.batch_iou on seeded boxes and the squeezeDet config's fields: the oracle against what the reference
+    computes -- its recorded outputs (tests/golden/live_reference.npz, make_golden.py) and, where the reference tree is
+    present, the live functions as well."""
+    from tests.golden import make_golden as MG
+    g = np.load(os.path.join(golden_dir, "live_reference.npz"))
+    ns = ref.load() if ref.available() else None
+    for seed in MG.LIVE_SEEDS:
+        bx, pr = MG.live_boxes(seed)
+        keep, iou = O.nms(bx, pr, 0.4), O.batch_iou(bx, bx[3])
+        assert keep == g["nms_keep_%d" % seed].tolist()
+        np.testing.assert_array_equal(iou, g["iou_vs_row3_%d" % seed])
+        if ns is not None:
+            assert keep == ns.util.nms(bx, pr, 0.4)
+            np.testing.assert_array_equal(iou, ns.util.batch_iou(bx, bx[3]))
     mc = O.kitti_squeezeDet_config()
-    for k in ("IMAGE_WIDTH", "IMAGE_HEIGHT", "CLASSES", "ANCHOR_PER_GRID", "ANCHORS", "EXP_THRESH", "TOP_N_DETECTION",
-              "PROB_THRESH", "NMS_THRESH", "PLOT_PROB_THRESH", "BATCH_SIZE", "WEIGHT_DECAY", "LEARNING_RATE",
-              "MAX_GRAD_NORM", "MOMENTUM", "LR_DECAY_FACTOR", "LOSS_COEF_BBOX", "LOSS_COEF_CONF_POS",
-              "LOSS_COEF_CONF_NEG", "LOSS_COEF_CLASS", "EPSILON", "DECAY_STEPS"):
-        assert mc[k] == mc_ref[k], k
-    np.testing.assert_array_equal(mc.ANCHOR_BOX, mc_ref.ANCHOR_BOX)
+    mc_ref = ns.cfg_squeezeDet.kitti_squeezeDet_config() if ns is not None else None
+    for k in MG.LIVE_CONFIG_FIELDS:
+        assert np.array_equal(np.array(mc[k]), g["config_" + k]), k
+        if mc_ref is not None:
+            assert mc[k] == mc_ref[k], k
+    assert sha(np.asarray(mc.ANCHOR_BOX)) == str(g["config_ANCHOR_BOX_sha256"])
+    if mc_ref is not None:
+        np.testing.assert_array_equal(mc.ANCHOR_BOX, mc_ref.ANCHOR_BOX)
 
 
 _LABEL_CFG = {"squeezeDet": O.kitti_squeezeDet_config, "squeezeDetPlus": O.kitti_squeezeDetPlus_config, "res50": O.kitti_res50_config}
@@ -140,12 +146,25 @@ def test_label_assignment_matches_reference(golden_dir, name):
         assert aidx[0, 0] == 0 and aidx[0, int(cnt[0]) - 1] >= A - 9
 
 
-@pytest.mark.skipif(not ref.available(), reason="reference tree not mounted")
 def test_label_golden_regenerates_from_live_reference(golden_dir):
-    """The committed labels.npz is what the reference's read_batch returns today (scaled boxes included)."""
+    """The committed labels.npz is what the reference's read_batch returns for today's cases: per image the object count, the
+    class labels and the boxes scaled to the network input (imdb.py:186-190, bit for bit) follow from cases.make_label_case's
+    annotations; where the reference tree is present, its read_batch is run live on the first two cases as well."""
+    g = np.load(os.path.join(golden_dir, "labels.npz"))
+    for name in cases.LABEL_CASES:
+        cfg, rois, sizes = cases.make_label_case(name)
+        mc = _LABEL_CFG[cfg]()
+        for b in range(len(rois)):
+            r, (h, w) = np.asarray(rois[b], np.float64), sizes[b]
+            sx, sy = mc.IMAGE_WIDTH / float(w), mc.IMAGE_HEIGHT / float(h)
+            n = len(r)
+            assert int(g[name + "_count"][b]) == n, "%s image %d" % (name, b)
+            assert np.array_equal(r[:, :4] * np.array([sx, sy, sx, sy]), g[name + "_bbox"][b, :n]), "%s image %d boxes" % (name, b)
+            assert g[name + "_label"][b, :n].tolist() == [int(c) for c in r[:, 4]], "%s image %d labels" % (name, b)
+    if not ref.available():
+        return
     from oracle import ref_imdb_half as ref_imdb
     ns = ref.load()
-    g = np.load(os.path.join(golden_dir, "labels.npz"))
     for name in cases.LABEL_CASES[:2]:
         cfg, rois, sizes = cases.make_label_case(name)
         mc = ns.cfg_squeezeDet.kitti_squeezeDet_config()

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq 1 $N); do
   for which in alt default; do
     if [ $which = alt ]; then export SQDET_LIB=$R/$ALT; else unset SQDET_LIB; fi
-    python $R/bench.py --no-cpu-baseline --steps ${STEPS:-100} --warmup ${WARMUP:-10} 2>/dev/null | python -c "
+    python $R/bench.py --full --no-cpu-baseline --steps ${STEPS:-100} --warmup ${WARMUP:-10} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 sl=(d.get('roofline') or {}).get('single_lane') or {}

@@ -15,11 +15,11 @@ sumstats() { python $R/profiles/summarize.py $(find $1 -name "*kernel_stats.csv"
 if [ "$PHASE" = "A" ]; then
   for c in sqdet_infer sqdetplus_infer sqdet_infer_384 sqdet_sample_b1; do
     P=$c; [ $c = sqdet_infer ] && P=""; PRE=${P:+${P}_}
-    python $R/bench.py --config $c --no-cpu-baseline --layer-table $OUT/${PRE}layer_table.json > /dev/null 2>>$OUT/collect.log
-    rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks --output-format csv -- python $R/bench.py --config $c --no-cpu-baseline > /dev/null 2>&1
-    sumstats $OUT/ks $OUT/${PRE}kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --config $c --no-cpu-baseline"
-    SQDET_SERVE_LANES=1 rocprofv3 --kernel-trace --stats -d $OUT/ks1 -o ks --output-format csv -- python $R/bench.py --config $c --no-cpu-baseline > /dev/null 2>&1
-    sumstats $OUT/ks1 $OUT/${PRE}kernel_stats_1lane.txt "SQDET_SERVE_LANES=1 rocprofv3 --kernel-trace --stats -- python bench.py --config $c --no-cpu-baseline"
+    python $R/bench.py --full --config $c --no-cpu-baseline --layer-table $OUT/${PRE}layer_table.json > /dev/null 2>>$OUT/collect.log
+    rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks --output-format csv -- python $R/bench.py --full --config $c --no-cpu-baseline > /dev/null 2>&1
+    sumstats $OUT/ks $OUT/${PRE}kernel_stats.txt "rocprofv3 --kernel-trace --stats -- python bench.py --full --config $c --no-cpu-baseline"
+    SQDET_SERVE_LANES=1 rocprofv3 --kernel-trace --stats -d $OUT/ks1 -o ks --output-format csv -- python $R/bench.py --full --config $c --no-cpu-baseline > /dev/null 2>&1
+    sumstats $OUT/ks1 $OUT/${PRE}kernel_stats_1lane.txt "SQDET_SERVE_LANES=1 rocprofv3 --kernel-trace --stats -- python bench.py --full --config $c --no-cpu-baseline"
     PMC_CONFIG=$c rocprofv3 --pmc FETCH_SIZE -d $OUT/pf -o fetch --output-format csv -- python $R/tools/pmc_forward.py > /dev/null 2>&1
     PMC_CONFIG=$c rocprofv3 --pmc WRITE_SIZE -d $OUT/pw -o write --output-format csv -- python $R/tools/pmc_forward.py > /dev/null 2>&1
     LAYERS=$(python -c "import json; print(','.join(l['layer'] for l in json.load(open('$OUT/${PRE}layer_table.json'))['layers']))")
@@ -27,12 +27,12 @@ if [ "$PHASE" = "A" ]; then
     rm -rf $OUT/pf $OUT/pw
   done
   for c in sqdet_train_fp32 res50_train_fp16 sqdet_train_fp16; do
-    rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks --output-format csv -- python $R/bench.py --config $c --no-cpu-baseline --no-graph > /dev/null 2>&1
-    sumstats $OUT/ks $OUT/kernel_stats_$c.txt "rocprofv3 --kernel-trace --stats -- python bench.py --config $c --no-cpu-baseline --no-graph"
+    rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks --output-format csv -- python $R/bench.py --full --config $c --no-cpu-baseline --no-graph > /dev/null 2>&1
+    sumstats $OUT/ks $OUT/kernel_stats_$c.txt "rocprofv3 --kernel-trace --stats -- python bench.py --full --config $c --no-cpu-baseline --no-graph"
     CSVS=""
     for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES"; do
       D=$OUT/pk_$(echo $grp | cut -d' ' -f1)
-      rocprofv3 --pmc $grp -d $D -o pk --output-format csv -- python $R/bench.py --config $c --no-cpu-baseline --no-graph --steps 4 --warmup 2 > /dev/null 2>&1
+      rocprofv3 --pmc $grp -d $D -o pk --output-format csv -- python $R/bench.py --full --config $c --no-cpu-baseline --no-graph --steps 4 --warmup 2 > /dev/null 2>&1
       CSVS="$CSVS $(find $D -name "*counter_collection.csv" | head -1)"
     done
     (cd $R && python profiles/pmc_kernels.py $OUT/pmc_kernels_$c.json $c $CSVS >> $OUT/collect.log 2>&1)
@@ -45,10 +45,10 @@ if [ "$PHASE" = "A" ]; then
   ls -la $OUT; tail -30 $OUT/collect.log
 else
   for c in sqdet_infer sqdet_infer_384 sqdet_sample_b1 sqdetplus_infer sqdet_train_fp32 res50_train_fp16 sqdet_train_fp16; do
-    python $R/bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+    python $R/bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   done
-  python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_sqdet_infer_20steps.json 2>> $OUT/bench_sqdet_infer.err
-  SQDET_SERVE_LANES=1 python $R/bench.py --no-cpu-baseline > $OUT/bench_sqdet_infer_1lane.json 2>> $OUT/bench_sqdet_infer.err
+  python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_sqdet_infer_20steps.json 2>> $OUT/bench_sqdet_infer.err
+  SQDET_SERVE_LANES=1 python $R/bench.py --full --no-cpu-baseline > $OUT/bench_sqdet_infer_1lane.json 2>> $OUT/bench_sqdet_infer.err
   python $R/tools/nextrows_bench.py > $OUT/nextrows_bench.json 2>/dev/null
   for f in $OUT/bench_*.json; do python -c "
 import json,sys

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 FP=$(cd $R && python -c "import bench; print(bench.build_fingerprint())")
 for c in $CONFIGS; do
-  rocprofv3 --kernel-trace --stats -d $OUT/ks_$c -o ks --output-format csv -- python $R/bench.py --config $c --no-cpu-baseline --no-graph > $OUT/kstats_$c.log 2>&1
-  python $R/profiles/summarize.py $(find $OUT/ks_$c -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$c.txt "rocprofv3 --kernel-trace --stats -- python bench.py --config $c --no-cpu-baseline --no-graph" $FP >> $OUT/kstats_$c.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/ks_$c -o ks --output-format csv -- python $R/bench.py --full --config $c --no-cpu-baseline --no-graph > $OUT/kstats_$c.log 2>&1
+  python $R/profiles/summarize.py $(find $OUT/ks_$c -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$c.txt "rocprofv3 --kernel-trace --stats -- python bench.py --full --config $c --no-cpu-baseline --no-graph" $FP >> $OUT/kstats_$c.log 2>&1
   rm -rf $OUT/ks_$c
 done

@@ -36,7 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--input_path", default="./data/sample.png", help="glob of input images")
     ap.add_argument("--out_dir", default="./data/out/")
-    ap.add_argument("--demo_net", default="squeezeDet", choices=["squeezeDet", "squeezeDet+", "resnet50"])
+    ap.add_argument("--demo_net", default="squeezeDet", choices=["squeezeDet", "squeezeDet+", "resnet50", "vgg16"])
     ap.add_argument("--weights", default="")
     ap.add_argument("--gpu", default="0")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
@@ -46,7 +46,7 @@ def main():
     from squeezedet_amd import nets, ops, synthetic, weights
     from squeezedet_amd.nn_skeleton import Session
     mc, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
-               "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet)}[a.demo_net]
+               "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[a.demo_net]
     mc = mc()
     mc.BATCH_SIZE = 1
     mc.LOAD_PRETRAINED_MODEL = False          # parameters are restored below (demo.py:171-172)

@@ -37,7 +37,7 @@ typedef void* sqdet_stream_t;
 enum { SQDET_OK = 0, SQDET_EINVAL = -1, SQDET_EUNSUPPORTED = -2, SQDET_EHIP = -3, SQDET_ESTATE = -4 };
 enum { SQDET_F32 = 0, SQDET_F16 = 1 };
 enum { SQDET_PAD_SAME = 0, SQDET_PAD_VALID = 1 };
-enum { SQDET_ARCH_SQUEEZEDET = 0, SQDET_ARCH_SQUEEZEDET_PLUS = 1, SQDET_ARCH_RESNET50 = 2 };
+enum { SQDET_ARCH_SQUEEZEDET = 0, SQDET_ARCH_SQUEEZEDET_PLUS = 1, SQDET_ARCH_RESNET50 = 2, SQDET_ARCH_VGG16 = 3 };
 
 const char* sqdet_version(void);
 const char* sqdet_last_error(void);
@@ -46,7 +46,9 @@ const char* sqdet_last_error(void);
  * "fire_fuse": 0 = plan heuristic (default), 1 = one launch per fire module wherever the kernels cover it, 2 = never
  * fuse, 3 = no streaming kernel, 4 = fire modules and the pools behind them stay apart, 5 = no fire-module chains, 6 = chains on
  * the late (small) maps only, 7 = a run's first module as squeeze conv + chain launch instead of one streaming launch,
- * 8 = no streaming expand + next-squeeze launches (a pooled module then ends its run). */
+ * 8 = no streaming expand + next-squeeze launches (a pooled module then ends its run).
+ * "conv_pool": 1 = a 3x3 conv and the 2x2/s2 SAME max-pool behind it are one launch wherever the tile kernel takes the shape
+ * (default), 0 = never (plans created afterwards and sqdet_conv2d_maxpool2_*). */
 int sqdet_set_option(const char* name, int value);
 
 /* ------------------------------------------------------------------ conv --
@@ -149,6 +151,16 @@ int sqdet_maxpool_nhwc_fwd(const void* x, void* y, int n, int h, int w, int c, i
  * for sqdet_maxpool_nhwc_bwd_idx.  window_index: [n,ho,wo,c] uint8. */
 int sqdet_maxpool_nhwc_fwd_idx(const void* x, void* y, unsigned char* window_index, int n, int h, int w, int c, int k,
                                int stride, int pad_mode, int dtype, sqdet_stream_t stream);
+
+/* conv 3x3/s1/SAME (+ ReLU when relu = 1) followed by max_pool 2x2/s2/SAME in ONE launch (VGG16's conv1_2+pool1 .. conv4_3+pool4,
+ * nets/vgg16_convDet.py:40-78): the conv's full-resolution output never reaches HBM.  x: [n,h,w,cin]; w_packed: packed 3x3 kernel;
+ * bias: float32 [cout] (required); y: [n,ceil(h/2),ceil(w/2),cout].  Bitwise sqdet_conv2d_nhwc_fwd followed by
+ * sqdet_maxpool_nhwc_fwd(k 2, stride 2, SAME).  SQDET_EUNSUPPORTED where sqdet_conv2d_maxpool2_supported says 0 (among others:
+ * Cin not a multiple of 8 halves / 4 floats, Cout not a multiple of 4, conv_algo = generic, option "conv_pool" = 0). */
+int sqdet_conv2d_maxpool2_nhwc_fwd(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w,
+                                   int cin, int cout, int relu, int dtype, sqdet_stream_t stream);
+/* 1 if sqdet_conv2d_maxpool2_nhwc_fwd takes the shape, else 0 (callers branch instead of catching SQDET_EUNSUPPORTED). */
+int sqdet_conv2d_maxpool2_supported(int n, int h, int w, int cin, int cout, int dtype);
 
 /* ------------------------------------------------------------------ stem --
  * conv1 + pool1 in one launch: relu(conv2d(x, W, stride 2) + b) followed by max_pool 3x3/s2

@@ -12,7 +12,7 @@ SQDET_OK = 0
 SQDET_EUNSUPPORTED = -2
 F32, F16 = 0, 1
 PAD_SAME, PAD_VALID = 0, 1
-ARCH_SQUEEZEDET, ARCH_SQUEEZEDET_PLUS, ARCH_RESNET50 = 0, 1, 2
+ARCH_SQUEEZEDET, ARCH_SQUEEZEDET_PLUS, ARCH_RESNET50, ARCH_VGG16 = 0, 1, 2, 3
 
 _lib = None
 
@@ -38,6 +38,8 @@ SIGNATURES = {
     "sqdet_maxpool_nhwc_fwd": (ci, [vp, vp] + [ci] * 8 + [vp]),
     "sqdet_maxpool_nhwc_fwd_idx": (ci, [vp, vp, vp] + [ci] * 8 + [vp]),
     "sqdet_maxpool_nhwc_bwd_idx": (ci, [vp, vp, vp, vp] + [ci] * 9 + [vp]),
+    "sqdet_conv2d_maxpool2_nhwc_fwd": (ci, [vp, vp, vp, vp] + [ci] * 7 + [vp]),
+    "sqdet_conv2d_maxpool2_supported": (ci, [ci] * 6),
     "sqdet_stem_conv_pool_fwd": (ci, [vp, vp, vp, vp] + [ci] * 8 + [vp]),
     "sqdet_stem_conv_pool_squeeze_supported": (ci, [ci] * 9),
     "sqdet_stem_conv_pool_squeeze_fwd": (ci, [vp] * 6 + [ci] * 9 + [vp]),

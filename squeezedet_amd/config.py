@@ -177,3 +177,16 @@ def kitti_res50_config_for_input(image_height, image_width):
         n = -(-n // 2)            # res4a
         g.append(n)
     return _finish(_kitti_common(mc), g[0], g[1], RES50_ANCHOR_SHAPES)
+
+
+def kitti_vgg16_config_for_input(image_height, image_width):
+    """VGG16+ConvDet on another input size: the grid is what the four 2x2/s2 SAME pools give (nets/vgg16_convDet.py:44-78, every
+    conv 3x3/s1/SAME); 375x1242 -> 24x78, the grid of kitti_vgg16_config."""
+    mc = base_model_config("KITTI")
+    mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT = int(image_width), int(image_height)
+    _kitti_common(mc)
+    mc.BATCH_SIZE = 5
+    gh, gw = int(image_height), int(image_width)
+    for _ in range(4):
+        gh, gw = -(-gh // 2), -(-gw // 2)
+    return _finish(mc, gh, gw, SQUEEZEDET_ANCHOR_SHAPES)

@@ -4,39 +4,61 @@
 
 namespace sqdet {
 
-template <typename T, int MT>
+template <typename T, int MT, bool POOL2>
 static bool dispatch_ntw(const TileArgs& a, int ntw, int grid_y, size_t lds, hipStream_t st) {
   switch (ntw) {
-    case 1: launch_tile<T, MT, 1>(a, grid_y, lds, st); return true;
-    case 2: launch_tile<T, MT, 2>(a, grid_y, lds, st); return true;
-    case 3: launch_tile<T, MT, 3>(a, grid_y, lds, st); return true;
-    case 4: launch_tile<T, MT, 4>(a, grid_y, lds, st); return true;
-    case 5: launch_tile<T, MT, 5>(a, grid_y, lds, st); return true;
-    case 6: launch_tile<T, MT, 6>(a, grid_y, lds, st); return true;
+    case 1: launch_tile<T, MT, 1, false, POOL2>(a, grid_y, lds, st); return true;
+    case 2: launch_tile<T, MT, 2, false, POOL2>(a, grid_y, lds, st); return true;
+    case 3: launch_tile<T, MT, 3, false, POOL2>(a, grid_y, lds, st); return true;
+    case 4: launch_tile<T, MT, 4, false, POOL2>(a, grid_y, lds, st); return true;
+    case 5: launch_tile<T, MT, 5, false, POOL2>(a, grid_y, lds, st); return true;
+    case 6: launch_tile<T, MT, 6, false, POOL2>(a, grid_y, lds, st); return true;
     default: return false;
   }
 }
 
-template <typename T>
+template <typename T, bool POOL2>
 static bool dispatch_tile(const TileArgs& a, int mt, int ntw, bool splitk, int grid_y, size_t lds, hipStream_t st) {
   if (splitk) {
-    if (ntw != 5) return false;
+    if (POOL2 || ntw != 5) return false;   // (the split-K ConvDet kernel has no pooled epilogue)
     return convdet_tile_launch(a, sizeof(T) == 2 ? SQDET_F16 : SQDET_F32, st) == SQDET_OK;
   }
   if (mt == 8) {  // one wave = all 8 tile rows x a slice of a group (4 waves along the cout tiles)
     switch (ntw) {
-      case 1: launch_tile<T, 8, 1>(a, grid_y, lds, st); return true;
-      case 2: launch_tile<T, 8, 2>(a, grid_y, lds, st); return true;
-      case 3: launch_tile<T, 8, 3>(a, grid_y, lds, st); return true;
-      case 4: launch_tile<T, 8, 4>(a, grid_y, lds, st); return true;
+      case 1: launch_tile<T, 8, 1, false, POOL2>(a, grid_y, lds, st); return true;
+      case 2: launch_tile<T, 8, 2, false, POOL2>(a, grid_y, lds, st); return true;
+      case 3: launch_tile<T, 8, 3, false, POOL2>(a, grid_y, lds, st); return true;
+      case 4: launch_tile<T, 8, 4, false, POOL2>(a, grid_y, lds, st); return true;
       default: return false;
     }
   }
-  return mt == 4 ? dispatch_ntw<T, 4>(a, ntw, grid_y, lds, st) : dispatch_ntw<T, 2>(a, ntw, grid_y, lds, st);
+  return mt == 4 ? dispatch_ntw<T, 4, POOL2>(a, ntw, grid_y, lds, st) : dispatch_ntw<T, 2, POOL2>(a, ntw, grid_y, lds, st);
 }
+
+// the forms dispatch_tile has an instantiation for
+static bool tile_form_exists(int mt, int ntw, bool splitk, bool pool2) {
+  if (splitk) return !pool2 && ntw == 5;
+  return ntw >= 1 && (mt == 8 ? ntw <= 4 : ntw <= 6);
+}
+
+static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool pool2, bool dry);
 
 // Eligibility + configuration.  *handled = false means "use the generic kernels".
 int conv3x3_tile_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled) {
+  return tile_launch_impl(c, g, dtype, st, handled, false, false);
+}
+
+// The POOL2 form: c describes the conv (Ho = H, Wo = W), c.y the POOLED tensor [N, ceil(H/2), ceil(W/2), y_cstride].  Plain convs
+// only (whole input rows, no accumulate, a bias); the wave layout is the one conv3x3_tile_launch picks for the unpooled conv.
+// dry: only decide whether the form takes the shape (*handled), launch nothing.
+int conv3x3_pool2_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry) {
+  *handled = false;
+  if (tune(TUNE_CONV_POOL) == 0) return SQDET_OK;
+  if (c.x_cstride != c.Cin || c.x_coffset != 0 || c.accum || !c.bias || c.relu_of || c.res || c.scores) return SQDET_OK;
+  return tile_launch_impl(c, g, dtype, st, handled, true, dry);
+}
+
+static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool pool2, bool dry) {
   *handled = false;
   if (conv_algo() != 0) return SQDET_OK;
   if (c.k != 3 || c.stride != 1 || c.pt != 1 || c.pl != 1 || g.gather) return SQDET_OK;
@@ -111,8 +133,15 @@ int conv3x3_tile_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStre
     }
   }
   if (c.scores && !splitk) return SQDET_OK;   // only the ConvDet kernel has the score epilogue (the caller reports UNSUPPORTED)
-  const bool ok = dtype == SQDET_F16 ? dispatch_tile<f16>(a, mt, ntw, splitk, grid_y, lds, st)
-                                     : dispatch_tile<float>(a, mt, ntw, splitk, grid_y, lds, st);
+  if (pool2 && !tile_form_exists(mt, ntw, splitk, pool2)) return SQDET_OK;   // (split K: "not handled")
+  if (dry) { *handled = true; return SQDET_OK; }
+  bool ok;
+  if (pool2)
+    ok = dtype == SQDET_F16 ? dispatch_tile<f16, true>(a, mt, ntw, splitk, grid_y, lds, st)
+                            : dispatch_tile<float, true>(a, mt, ntw, splitk, grid_y, lds, st);
+  else
+    ok = dtype == SQDET_F16 ? dispatch_tile<f16, false>(a, mt, ntw, splitk, grid_y, lds, st)
+                            : dispatch_tile<float, false>(a, mt, ntw, splitk, grid_y, lds, st);
   if (!ok) return SQDET_OK;
   SQDET_CHECK_HIP(hipGetLastError());
   *handled = true;
@@ -169,7 +198,57 @@ int conv3x3_pair_launch(const void* x, const void* w3, const float* b3, const vo
   return SQDET_OK;
 }
 
+// ---- conv3x3/s1/SAME + ReLU + max_pool 2x2/s2/SAME in one launch (VGG16, nets/vgg16_convDet.py:40-78) ----
+static ConvArgs pool2_args(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
+                           int relu, const ConvGeom& g) {
+  ConvArgs c;
+  c.x = x; c.wp = w_packed; c.bias = bias; c.y = y;
+  c.N = n; c.H = h; c.W = w; c.Cin = cin; c.Cout = cout; c.k = 3; c.stride = 1; c.pt = 1; c.pl = 1; c.Ho = h; c.Wo = w;
+  c.P = (int)((long)n * h * w); c.ntiles = 0;
+  c.nchunk = g.nchunk; c.steps = g.steps; c.ngroups = g.ngroups;
+  c.y_cstride = cout; c.y_coffset = 0; c.relu = relu;
+  c.x_cstride = cin; c.x_coffset = 0; c.accum = 0; c.res = nullptr; c.relu_of = nullptr;
+  c.scores = nullptr; c.score_apg = 0; c.score_classes = 0;
+  return c;
+}
+
+bool conv2d_maxpool2_eligible(int n, int h, int w, int cin, int cout, int dtype) {
+  if ((dtype != SQDET_F16 && dtype != SQDET_F32) || n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cout % 4 != 0) return false;
+  if ((long)n * h * w > (1L << 30)) return false;
+  const ConvGeom g = conv_geom(3, cin, cout, dtype);
+  const ConvArgs c = pool2_args(nullptr, nullptr, nullptr, nullptr, n, h, w, cin, cout, 1, g);
+  ConvArgs cb = c;
+  cb.bias = reinterpret_cast<const float*>(16);   // (a bias is part of the form; only its presence is looked at)
+  bool ok = false;
+  conv3x3_pool2_launch(cb, g, dtype, nullptr, &ok, true);
+  return ok;
+}
+
+int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
+                           int relu, int dtype, hipStream_t st) {
+  SQDET_REQUIRE(x && w_packed && bias && y, "conv2d_maxpool2: null pointer");
+  SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "conv2d_maxpool2: bad dtype %d", dtype);
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0, "conv2d_maxpool2: bad dims");
+  SQDET_UNSUPPORTED(!conv2d_maxpool2_eligible(n, h, w, cin, cout, dtype),
+                    "conv2d_maxpool2: shape not covered (see sqdet_conv2d_maxpool2_supported)");
+  const ConvGeom g = conv_geom(3, cin, cout, dtype);
+  bool handled = false;
+  const int rc = conv3x3_pool2_launch(pool2_args(x, w_packed, bias, y, n, h, w, cin, cout, relu, g), g, dtype, st, &handled, false);
+  if (rc != SQDET_OK) return rc;
+  SQDET_UNSUPPORTED(!handled, "conv2d_maxpool2: the tile kernel did not take this shape");
+  return SQDET_OK;
+}
+
 }  // namespace sqdet
+
+extern "C" int sqdet_conv2d_maxpool2_supported(int n, int h, int w, int cin, int cout, int dtype) {
+  return sqdet::conv2d_maxpool2_eligible(n, h, w, cin, cout, dtype) ? 1 : 0;
+}
+
+extern "C" int sqdet_conv2d_maxpool2_nhwc_fwd(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w,
+                                              int cin, int cout, int relu, int dtype, sqdet_stream_t stream) {
+  return sqdet::conv2d_maxpool2_launch(x, w_packed, bias, y, n, h, w, cin, cout, relu, dtype, sqdet::as_stream(stream));
+}
 
 #ifdef SQDET_C3_TIMELINE
 extern "C" int sqdet_debug_c3_timeline(unsigned long long* host, int count) {

@@ -131,9 +131,16 @@ __device__ unsigned long long g_c3_tl[16384 * 8];
 #define C3TL(k) do {} while (0)
 #endif
 
-// (the <8, 3> float16 form -- SqueezeDet+ fire6 / fire7 -- runs three workgroups per CU: its register budget is 168; checked spill-free)
-template <typename T, int MT, int NTW, bool PAIR = false>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3) ? 3 : 1) void conv3x3_tile(TileArgs a) {
+// POOL2: the epilogue takes max_pool 2x2/s2/SAME of relu(conv + b) and writes only the pooled tensor [N, ceil(H/2), ceil(W/2), Cout]
+// (VGG16's conv1_2+pool1 .. conv4_3+pool4, nets/vgg16_convDet.py:40-78).  SAME with k = s = 2 pads at the bottom / right only, so the
+// windows start at even rows and columns and an 8 x 16 tile pools to 4 x 8 on its own: a window's two rows are accumulator rows m, m + 1
+// of one wave (MT even, m0 even), its two columns lanes j, j ^ 1 (one DPP quad_perm).  Bias and ReLU, then the max in float32, then the
+// rounding: the rounding is monotone, so the result is bitwise the conv's stored tensor pooled by maxpool_kernel.  Pixels beyond H / W
+// (computed from the zero halo: after bias + ReLU real non-negative numbers) enter the max as -inf.
+// (the <8, 3> float16 form -- SqueezeDet+ fire6 / fire7 -- runs three workgroups per CU: its register budget is 168; checked spill-free;
+// its POOL2 form does not fit that budget and runs one)
+template <typename T, int MT, int NTW, bool PAIR = false, bool POOL2 = false>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3 && !POOL2) ? 3 : 1) void conv3x3_tile(TileArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifdef SQDET_C3_TIMELINE
   unsigned long long c3tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -310,7 +317,36 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3) ? 3 : 
 
   if (!active) return;
 
-  if (ox < a.c.W) {
+  if constexpr (POOL2) {
+    static_assert(PLAIN, "the pooled epilogue has no accumulate / ReLU-backward form");
+    const bool col_ok = ox < a.c.W;
+    const int Ho = (a.c.H + 1) >> 1, Wo = (a.c.W + 1) >> 1;
+    constexpr float NEG = -__builtin_huge_valf();
+#pragma unroll
+    for (int m = 0; m < MT; m += 2) {
+      const int oy = oy0 + m0 + m;   // even
+      if (oy >= a.c.H) break;        // (wave-uniform: the DPP below runs with every lane of the wave)
+      const bool row1_ok = oy + 1 < a.c.H;
+      f32x4 v[NTW];
+#pragma unroll
+      for (int t = 0; t < NTW; ++t) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float p = acc[m][t][e] + bias[t][e], q = acc[m + 1][t][e] + bias[t][e];
+          if (a.c.relu) { p = fmaxf(p, 0.f); q = fmaxf(q, 0.f); }
+          float r = col_ok ? p : NEG;
+          r = col_ok && row1_ok ? fmaxf(r, q) : r;
+          // the window's other column: lane j ^ 1 (quad_perm [1, 0, 3, 2])
+          const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r), 0xB1, 0xF, 0xF, false));
+          v[t][e] = fmaxf(r, o);
+        }
+      }
+      if (col_ok && (j & 1) == 0) {
+        T* dst = y + (((size_t)n * Ho + (oy >> 1)) * Wo + (ox >> 1)) * a.c.y_cstride + y_coffset + cb;
+        store_couts<T, NTW>(dst, v, nt_valid);
+      }
+    }
+  } else if (ox < a.c.W) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
       const int oy = oy0 + m0 + m;
@@ -339,7 +375,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3) ? 3 : 
   }
   };
   auto epilogue = [&](const float* bias_l, int y_coffset) __attribute__((always_inline)) {
-    if (!a.c.accum && !a.c.relu_of) epilogue_t(bias_l, y_coffset, std::true_type{});
+    if constexpr (POOL2) epilogue_t(bias_l, y_coffset, std::true_type{});   // (the launcher takes plain convs only)
+    else if (!a.c.accum && !a.c.relu_of) epilogue_t(bias_l, y_coffset, std::true_type{});
     else epilogue_t(bias_l, y_coffset, std::false_type{});
   };
   if constexpr (!PAIR) {
@@ -397,14 +434,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3) ? 3 : 
   }
 }
 
-template <typename T, int MT, int NTW, bool PAIR = false>
+template <typename T, int MT, int NTW, bool PAIR = false, bool POOL2 = false>
 static void launch_tile(const TileArgs& a, int grid_y, size_t lds, hipStream_t st) {
+  static_assert(!(PAIR && POOL2), "the PAIR form writes the concat tensor unpooled");
   static PerDevice once;   // > 64 KiB of dynamic LDS has to be allowed once per kernel and device
   if (lds > 65536)
-    (void)once.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_tile<T, MT, NTW, PAIR>),
+    (void)once.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_tile<T, MT, NTW, PAIR, POOL2>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
   const dim3 grid((unsigned)((a.c.N * a.tiles_x * a.tiles_y + 7) / 8 * 8), (unsigned)grid_y);
-  hipLaunchKernelGGL((conv3x3_tile<T, MT, NTW, PAIR>), grid, dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv3x3_tile<T, MT, NTW, PAIR, POOL2>), grid, dim3(256), lds, st, a);
 }
 
 // the split-K (ConvDet) kernel lives in convdet.hip: that file is compiled with the accumulators in AGPRs

@@ -94,8 +94,11 @@ int conv_algo();
 // experiment knobs set through sqdet_set_option (0 = built-in heuristic)
 // fire_fuse: 0 / 1 = a fire module is one fused launch wherever a fused kernel takes it (the default since round 5), 2 = never,
 // 10 = the round-1..4 rule (only maps of <= 100 k pixels); stem_algo: 0 phase kernel (stem4.hip), else persistent strip-lane kernel (stem3.hip), else strip kernel (in-register pool), whichever is eligible first; 3 skips the phase kernel; 2 strip kernel only
+// conv_pool: 1 (the default) = a 3x3 conv followed by a 2x2/s2 SAME max-pool is one launch of conv3x3_tile's POOL2 form wherever it
+// takes the shape (plans and sqdet_conv2d_maxpool2_*), 0 = never
 // g1_wr / g1_mbw / g1_ntw: conv1x1_pipe's wave layout (waves along the pixel blocks: 1, 2, 4), pixel blocks per wave (2, 4, 8) and cout tiles per wave -- tools/g1_sweep.py
-enum { TUNE_C1_WAVES = 0, TUNE_C1_MT = 1, TUNE_C1_MIN_TILES = 2, TUNE_FIRE_FUSE = 3, TUNE_STEM_ALGO = 4, TUNE_DBG = 5, TUNE_G1_WR = 6, TUNE_G1_MBW = 7, TUNE_G1_NTW = 8, TUNE_G1_NS = 9 };
+enum { TUNE_C1_WAVES = 0, TUNE_C1_MT = 1, TUNE_C1_MIN_TILES = 2, TUNE_FIRE_FUSE = 3, TUNE_STEM_ALGO = 4, TUNE_DBG = 5, TUNE_G1_WR = 6, TUNE_G1_MBW = 7, TUNE_G1_NTW = 8, TUNE_G1_NS = 9,
+       TUNE_CONV_POOL = 10 };
 int tune(int which);
 
 // fire2.hip: persistent streaming fused fire for the large, few-channel modules
@@ -132,6 +135,8 @@ int fire_dma_launch(const void* sq_in, const void* w1, const float* b1, const vo
                     const float* bs2, void* s_out, int n, int h, int w, int s, int e1, int e3, int s2, int pool, int dtype,
                     hipStream_t st, bool* handled);
 int conv3x3_tile_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled);
+// conv3x3.hip: the same with max_pool 2x2/s2/SAME in the epilogue (y = the pooled tensor); dry = eligibility only
+int conv3x3_pool2_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry);
 // conv3x3.hip: both expands of a fire module from ONE staged squeeze tile (the tile kernel's PAIR form)
 bool conv3x3_pair_eligible(int n, int h, int w, int s, int e1, int e3, int dtype);
 int conv3x3_pair_launch(const void* sq_in, const void* w3, const float* b3, const void* w1, const float* b1, void* y, int n, int h, int w,

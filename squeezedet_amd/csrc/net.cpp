@@ -1,6 +1,7 @@
 // Host-side executor: the plan that replaces SqueezeDet._add_forward_graph /
-// SqueezeDetPlus._add_forward_graph / ResNet50ConvDet._add_forward_graph (reference
-// src/nets/squeezeDet.py:30-79, src/nets/squeezeDetPlus.py:30-79, src/nets/resnet50_convDet.py:31-169).
+// SqueezeDetPlus._add_forward_graph / ResNet50ConvDet._add_forward_graph / VGG16ConvDet._add_forward_graph (reference
+// src/nets/squeezeDet.py:30-79, src/nets/squeezeDetPlus.py:30-79, src/nets/resnet50_convDet.py:31-169,
+// src/nets/vgg16_convDet.py:31-90).
 // It owns no device memory: packed parameters and the activation workspace are bound by the
 // caller (sqdet_net_bind).
 #include <math.h>
@@ -57,6 +58,9 @@ int fire_expand_stream_launch(const void* sq_in, const void* w1, const float* b1
 bool conv3x3_pair_eligible(int n, int h, int w, int s, int e1, int e3, int dtype);
 int conv3x3_pair_launch(const void* sq_in, const void* w3, const float* b3, const void* w1, const float* b1, void* y, int n, int h, int w,
                         int s, int e1, int e3, int dtype, hipStream_t st, bool* handled);
+bool conv2d_maxpool2_eligible(int n, int h, int w, int cin, int cout, int dtype);
+int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
+                           int relu, int dtype, hipStream_t st);
 int conv_algo();
 int tune(int which);
 }  // namespace sqdet
@@ -108,6 +112,7 @@ struct Layer {
   int fs, fe1, fe3;
   int kp_s, bp_s, kp_1, bp_1, kp_3, bp_3;
   int fire_pool = 0;   // L_FIRE: the 3x3/s2 SAME max-pool that follows is taken inside the kernel (ho, wo = pooled dims)
+  int conv_pool = 0;   // L_CONV (3x3/s1/SAME): the 2x2/s2 SAME max-pool that follows is taken in the epilogue (ho, wo = pooled dims)
   // L_CHAIN: in_buf holds the module's squeeze tensor (fs channels); fs2 > 0: the next module's squeeze tensor goes to
   // out_buf, else the concat tensor does; kp_s2 / bp_s2 = the next module's squeeze parameters; the packed stream
   int fs2 = 0, kp_s2 = -1, bp_s2 = -1;
@@ -400,6 +405,7 @@ int run_layer_part(sqdet_net* net, const Layer& L, const void* input, void* pred
     const void* wp = net->param_mem + net->params[L.kparam].offset;
     const float* b = reinterpret_cast<const float*>(
         net->param_mem + (L.fold >= 0 ? net->folds[L.fold].fbias_off : net->params[L.bparam].offset));
+    if (L.conv_pool) return conv2d_maxpool2_launch(x, wp, b, y, nb, L.h, L.w, L.cin, L.cout, L.relu, net->dtype, st);
     if (net->scores && &L == &net->layers.back())   // (validated by sqdet_net_set_scores)
       return convdet_scored_launch(x, wp, b, y, net->scores + (size_t)n0 * L.h * L.w * net->apg, nb, L.h, L.w, L.cin, net->apg,
                                    net->classes, net->dtype, st);
@@ -726,6 +732,45 @@ void fuse_stem_squeeze(sqdet_net* net, size_t esz) {
   net->layers[0] = f;
 }
 
+// 3x3/s1/SAME conv + the 2x2/s2 SAME max-pool behind it (VGG16's conv1_2+pool1 .. conv4_3+pool4) -> one L_CONV launch of the tile
+// kernel's POOL2 form wherever it takes the shape: the conv's full-resolution output never reaches HBM.  As in fuse_fire_pools the pooled
+// tensor goes where the conv's output would have gone (the pool's output buffer is the one the conv reads), so the ping-pong buffers
+// swap roles for every later layer.  "conv_pool" = 0: not.
+void fuse_conv_pools(sqdet_net* net, size_t esz) {
+  if (conv_algo() != 0 || tune(10) == 0) return;   // ("conv_pool")
+  std::vector<Layer> out;
+  std::vector<Layer> in = net->layers;
+  bool fused_any = false;
+  for (size_t i = 0; i < in.size(); ++i) {
+    const Layer& c = in[i];
+    const bool ok = i + 1 < in.size() && c.type == L_CONV && c.k == 3 && c.stride == 1 && c.pad_mode == SQDET_PAD_SAME && c.fold < 0 &&
+                    !c.accum && c.y_cstride == c.cout && c.y_coffset == 0 && c.out_buf >= 0 && in[i + 1].type == L_POOL &&
+                    in[i + 1].k == 2 && in[i + 1].stride == 2 && in[i + 1].pad_mode == SQDET_PAD_SAME && in[i + 1].in_buf == c.out_buf &&
+                    conv2d_maxpool2_eligible(net->batch, c.h, c.w, c.cin, c.cout, net->dtype);
+    if (!ok) { out.push_back(c); continue; }
+    const Layer& p = in[i + 1];
+    Layer f = c;
+    f.conv_pool = 1;
+    f.name = c.name + "+" + p.name;
+    f.ho = p.ho; f.wo = p.wo;
+    for (size_t k = i + 2; k < in.size(); ++k) {
+      auto sw = [](int b) { return b == BUF_A ? BUF_B : (b == BUF_B ? BUF_A : b); };
+      in[k].in_buf = sw(in[k].in_buf);
+      in[k].out_buf = sw(in[k].out_buf);
+    }
+    fused_any = true;
+    // algorithmic bytes: conv input + POOLED output + weights + bias
+    f.bytes = c.bytes - (double)net->batch * c.ho * c.wo * c.cout * (double)esz + (double)net->batch * p.ho * p.wo * c.cout * (double)esz;
+    out.push_back(f);
+    ++i;
+  }
+  net->layers.swap(out);
+  if (fused_any) {   // either buffer may now hold what the other was sized for
+    const size_t m = net->buf_elems[BUF_A] > net->buf_elems[BUF_B] ? net->buf_elems[BUF_A] : net->buf_elems[BUF_B];
+    net->buf_elems[BUF_A] = net->buf_elems[BUF_B] = m;
+  }
+}
+
 // conv1 + pool1 -> one L_STEM launch when the fused kernel applies (decided at plan creation).
 void fuse_stem(sqdet_net* net, size_t esz) {
   if (conv_algo() != 0 || net->layers.size() < 2) return;
@@ -753,7 +798,8 @@ void fuse_stem(sqdet_net* net, size_t esz) {
 extern "C" int sqdet_net_create(sqdet_net_t** out, int arch, int dtype, int batch, int img_h, int img_w, int classes,
                                 int anchors_per_grid) {
   SQDET_REQUIRE(out, "net_create: null out");
-  SQDET_REQUIRE(arch == SQDET_ARCH_SQUEEZEDET || arch == SQDET_ARCH_SQUEEZEDET_PLUS || arch == SQDET_ARCH_RESNET50,
+  SQDET_REQUIRE(arch == SQDET_ARCH_SQUEEZEDET || arch == SQDET_ARCH_SQUEEZEDET_PLUS || arch == SQDET_ARCH_RESNET50 ||
+                    arch == SQDET_ARCH_VGG16,
                 "net_create: bad arch %d", arch);
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "net_create: bad dtype %d", dtype);
   SQDET_REQUIRE(batch > 0 && img_h >= 64 && img_w >= 64 && classes > 0 && anchors_per_grid > 0, "net_create: bad dims");
@@ -784,6 +830,15 @@ extern "C" int sqdet_net_create(sqdet_net_t** out, int arch, int dtype, int batc
     for (const char* n : {"3b", "3c", "3d"}) b.res_block("conv3_x", n, 128, 512, false, false);
     b.res_block("conv4_x", "4a", 256, 1024, true, true);
     for (const char* n : {"4b", "4c", "4d", "4e", "4f"}) b.res_block("conv4_x", n, 256, 1024, false, false);
+  } else if (arch == SQDET_ARCH_VGG16) {
+    // vgg16_convDet.py:33-84: five blocks of 3x3/s1/SAME convs + ReLU in tf.variable_scope('convN'), 2x2/s2 SAME pools behind the first four
+    const struct { int convs, cout; } blocks[5] = {{2, 64}, {2, 128}, {3, 256}, {3, 512}, {3, 512}};
+    for (int bi = 0; bi < 5; ++bi) {
+      const std::string scope = "conv" + std::to_string(bi + 1);
+      for (int ci = 0; ci < blocks[bi].convs; ++ci)
+        b.conv_layer(scope + "/" + scope + "_" + std::to_string(ci + 1), blocks[bi].cout, 3, 1, SQDET_PAD_SAME, 1, false);
+      if (bi < 4) b.pool_layer("pool" + std::to_string(bi + 1), 2, 2, SQDET_PAD_SAME);
+    }
   } else {
     const FireSpec* f = kSqueezeDetPlusFires;
     b.conv_layer("conv1", 96, 7, 2, SQDET_PAD_VALID, 1, false);
@@ -794,8 +849,8 @@ extern "C" int sqdet_net_create(sqdet_net_t** out, int arch, int dtype, int batc
     b.pool_layer("pool8", 3, 2, SQDET_PAD_VALID);
     b.fire_layer(f[7]); b.fire_layer(f[8]); b.fire_layer(f[9]);
   }
-  // dropout11 / drop4 is the identity at inference (keep_prob = 1.0, nn_skeleton.py:78)
-  b.conv_layer(arch == SQDET_ARCH_RESNET50 ? "conv5" : "conv12", nout, 3, 1, SQDET_PAD_SAME, 0, true);
+  // dropout11 / drop4 / drop6 is the identity at inference (keep_prob = 1.0, nn_skeleton.py:78)
+  b.conv_layer(arch == SQDET_ARCH_RESNET50 ? "conv5" : arch == SQDET_ARCH_VGG16 ? "conv6" : "conv12", nout, 3, 1, SQDET_PAD_SAME, 0, true);
   net->gh = b.h; net->gw = b.w; net->out_ch = nout;
   fuse_stem(net, b.esz);
   fuse_fires(net, b.esz);
@@ -803,6 +858,7 @@ extern "C" int sqdet_net_create(sqdet_net_t** out, int arch, int dtype, int batc
   fuse_chains(net, b.esz);
   fuse_expand_pairs(net, b.esz);
   fuse_stem_squeeze(net, b.esz);
+  fuse_conv_pools(net, b.esz);
   net->fold_scratch_off = net->param_bytes;
   net->param_bytes = align_up(net->param_bytes + net->fold_scratch_bytes, 256);
   size_t off = 0;

@@ -2,7 +2,7 @@
 // (reference src/nn_skeleton.py:565-586): tf.nn.max_pool with TF SAME/VALID semantics --
 // SAME-padded cells never win (they are skipped, which equals -inf padding).
 // Pure HBM streaming: one thread owns one output pixel x 16 bytes of channels.
-#include "common.h"
+#include "conv_common.h"   // (tune)
 
 namespace sqdet {
 
@@ -87,6 +87,43 @@ __global__ __launch_bounds__(256) void maxpool3_kernel(const T* __restrict__ x, 
     for (int t = 0; t < 9; ++t) m = ok[t] ? vmax<T>(m, v[t]) : m;
     *reinterpret_cast<vec*>(y + idx * V) = m;
   }
+}
+
+// 2x2 window, stride 2 (VGG16's pools, nets/vgg16_convDet.py:44-78, where no conv epilogue takes them): maxpool3_kernel's shape --
+// the four loads issued from clamped addresses before the reduce, XCD-ordered slices.  The windows do not overlap, so every input
+// byte is read once.
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W,
+                                                       int C, int pt, int pl, int Ho, int Wo) {
+  constexpr int V = PoolTr<T>::V;
+  typedef typename PoolTr<T>::vec vec;
+  const int cv = C / V;
+  const size_t total = (size_t)N * Ho * Wo * cv;
+  const unsigned per = (gridDim.x + 7) / 8;
+  const size_t slice = (size_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
+  const size_t idx = slice * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % cv);
+  size_t p = idx / cv;
+  const int ox = (int)(p % Wo); p /= Wo;
+  const int oy = (int)(p % Ho);
+  const int n = (int)(p / Ho);
+  const int y0 = oy * 2 - pt, x0 = ox * 2 - pl;
+  vec v[4];
+  bool ok[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int iy = y0 + (t >> 1), ix = x0 + (t & 1);
+    ok[t] = iy >= 0 && iy < H && ix >= 0 && ix < W;
+    const int cy = min(max(iy, 0), H - 1), cx = min(max(ix, 0), W - 1);   // clamped: a valid address, masked below
+    v[t] = *reinterpret_cast<const vec*>(x + (((size_t)n * H + cy) * W + cx) * C + c * V);
+  }
+  vec m;
+#pragma unroll
+  for (int e = 0; e < V; ++e) m[e] = (T)(-__builtin_huge_valf());
+#pragma unroll
+  for (int t = 0; t < 4; ++t) m = ok[t] ? vmax<T>(m, v[t]) : m;
+  *reinterpret_cast<vec*>(y + idx * V) = m;
 }
 
 // The training forward's pool: maxpool3_kernel that also records WHICH cell won -- 3 * (window row) + (window column) of the
@@ -196,6 +233,15 @@ int maxpool_launch(const void* x, void* y, int n, int h, int w, int c, int k, in
     else
       hipLaunchKernelGGL(maxpool3_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (float*)y,
                          n, h, w, c, stride, pt, pl, Ho, Wo);
+  } else if (k == 2 && stride == 2 && tune(TUNE_DBG) != 95) {   // ("dbg" 95: the generic kernel -- tests)
+    blocks = ((total + 255) / 256 + 7) / 8 * 8;
+    SQDET_UNSUPPORTED(blocks > 0x7fffffffULL, "maxpool: too many outputs");
+    if (dtype == SQDET_F16)
+      hipLaunchKernelGGL(maxpool2_kernel<f16>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16*)x, (f16*)y, n, h, w, c, pt, pl,
+                         Ho, Wo);
+    else
+      hipLaunchKernelGGL(maxpool2_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (float*)y, n, h, w, c,
+                         pt, pl, Ho, Wo);
   } else if (dtype == SQDET_F16)
     hipLaunchKernelGGL(maxpool_kernel<f16>, dim3((unsigned)blocks), dim3(256), 0, st, (const f16*)x, (f16*)y, n, h, w,
                        c, k, stride, pt, pl, Ho, Wo);

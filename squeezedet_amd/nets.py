@@ -1,5 +1,6 @@
-"""SqueezeDet / SqueezeDet+ model classes with the reference's constructor and graph
-(reference src/nets/squeezeDet.py:19-106, src/nets/squeezeDetPlus.py:19-106).  The graph is
+"""SqueezeDet / SqueezeDet+ / ResNet50+ConvDet / VGG16+ConvDet model classes with the reference's constructor and graph
+(reference src/nets/squeezeDet.py:19-106, src/nets/squeezeDetPlus.py:19-106, src/nets/resnet50_convDet.py:20-169,
+src/nets/vgg16_convDet.py:20-90).  The graph is
 declared with the same builder calls as the reference; `preds` is executed by the native plan
 (sqdet_net_forward) and, equivalently, op by op through the builders' own HIP kernels."""
 import os
@@ -137,4 +138,41 @@ class SqueezeDetPlus(_FireNet):
         dropout11 = self._dropout(fire11, self.keep_prob, name="drop11")
         num_output = mc.ANCHOR_PER_GRID * (mc.CLASSES + 1 + 4)
         self.preds = self._conv_layer("conv12", dropout11, filters=num_output, size=3, stride=1, padding="SAME",
+                                      xavier=False, relu=False, stddev=0.0001)
+
+
+class VGG16ConvDet(_FireNet):
+    """VGG16 conv1_1..conv5_3 + ConvDet (nets/vgg16_convDet.py:20-90).  Inference only: the trainers take the fire-module
+    and ResNet50 nets."""
+    NATIVE_ARCH = "vgg16"
+
+    def _add_forward_graph(self):
+        """NN architecture (nets/vgg16_convDet.py:31-90)."""
+        mc = self.mc
+        self._load_pretrained()
+        with self.variable_scope("conv1"):
+            conv1_1 = self._conv_layer("conv1_1", self.image_input, filters=64, size=3, stride=1, freeze=True)
+            conv1_2 = self._conv_layer("conv1_2", conv1_1, filters=64, size=3, stride=1, freeze=True)
+            pool1 = self._pooling_layer("pool1", conv1_2, size=2, stride=2)
+        with self.variable_scope("conv2"):
+            conv2_1 = self._conv_layer("conv2_1", pool1, filters=128, size=3, stride=1, freeze=True)
+            conv2_2 = self._conv_layer("conv2_2", conv2_1, filters=128, size=3, stride=1, freeze=True)
+            pool2 = self._pooling_layer("pool2", conv2_2, size=2, stride=2)
+        with self.variable_scope("conv3"):
+            conv3_1 = self._conv_layer("conv3_1", pool2, filters=256, size=3, stride=1)
+            conv3_2 = self._conv_layer("conv3_2", conv3_1, filters=256, size=3, stride=1)
+            conv3_3 = self._conv_layer("conv3_3", conv3_2, filters=256, size=3, stride=1)
+            pool3 = self._pooling_layer("pool3", conv3_3, size=2, stride=2)
+        with self.variable_scope("conv4"):
+            conv4_1 = self._conv_layer("conv4_1", pool3, filters=512, size=3, stride=1)
+            conv4_2 = self._conv_layer("conv4_2", conv4_1, filters=512, size=3, stride=1)
+            conv4_3 = self._conv_layer("conv4_3", conv4_2, filters=512, size=3, stride=1)
+            pool4 = self._pooling_layer("pool4", conv4_3, size=2, stride=2)
+        with self.variable_scope("conv5"):
+            conv5_1 = self._conv_layer("conv5_1", pool4, filters=512, size=3, stride=1)
+            conv5_2 = self._conv_layer("conv5_2", conv5_1, filters=512, size=3, stride=1)
+            conv5_3 = self._conv_layer("conv5_3", conv5_2, filters=512, size=3, stride=1)
+        dropout5 = self._dropout(conv5_3, self.keep_prob, name="drop6")
+        num_output = mc.ANCHOR_PER_GRID * (mc.CLASSES + 1 + 4)
+        self.preds = self._conv_layer("conv6", dropout5, filters=num_output, size=3, stride=1, padding="SAME",
                                       xavier=False, relu=False, stddev=0.0001)

@@ -121,7 +121,9 @@ class ModelSkeleton:
     def _conv_layer(self, layer_name, inputs, filters, size, stride, padding="SAME", freeze=False, xavier=False,
                     relu=True, stddev=0.001):
         """Convolutional layer constructor (nn_skeleton.py:471-563): kernel '<layer>/kernels'
-        [size,size,Cin,filters] HWIO, '<layer>/biases' [filters]; conv2d -> bias_add -> relu."""
+        [size,size,Cin,filters] HWIO, '<layer>/biases' [filters]; conv2d -> bias_add -> relu.  Inside variable_scope(s)
+        the names carry the scopes ('conv1/conv1_1/kernels', nets/vgg16_convDet.py:40-42); the pretrained pickle is looked
+        up by the layer name alone, as the reference does."""
         mc = self.mc
         channels = int(inputs.get_shape()[3])
         use_pretrained_param = False
@@ -148,12 +150,13 @@ class ModelSkeleton:
         else:
             kernel = _truncated_normal((size, size, channels, filters), stddev, self._gen, "cpu")
             biases = torch.zeros(filters)
-        self._new_param(layer_name + "/kernels", kernel, not freeze)
-        self._new_param(layer_name + "/biases", biases, not freeze)
+        name = "/".join(self._scope + [layer_name])
+        self._new_param(name + "/kernels", kernel, not freeze)
+        self._new_param(name + "/biases", biases, not freeze)
 
         n, h, w, _ = inputs.get_shape()
         out_shape = (n, _out_size(h, size, stride, padding), _out_size(w, size, stride, padding), filters)
-        out = Node(self, "conv", [inputs], out_shape, layer_name, size=size, stride=stride, padding=padding, relu=relu)
+        out = Node(self, "conv", [inputs], out_shape, name, size=size, stride=stride, padding=padding, relu=relu)
         # nn_skeleton.py:549-561 analytical counters
         self.model_size_counter.append((layer_name, (1 + size * size * channels) * filters))
         num_flops = (1 + 2 * channels * size * size) * filters * out_shape[1] * out_shape[2]
@@ -387,6 +390,15 @@ class ModelSkeleton:
                     fused = ops.stem_conv_pool(xin, pk, bf, src.attrs["padding"], node.attrs["padding"])
                 except SqdetError:
                     fused = None
+            if (fused is None and node.attrs["size"] == 2 and node.attrs["stride"] == 2 and node.attrs["padding"] == "SAME"
+                    and src.op == "conv" and src.consumers == 1 and src not in env and src not in self._fetching
+                    and src.attrs["size"] == 3 and src.attrs["stride"] == 1 and src.attrs["padding"] == "SAME" and src.attrs["relu"]):
+                # a VGG16 conv + pool pair (nets/vgg16_convDet.py:40-78) as one launch, like the native plan's: the conv's output
+                # never reaches HBM.  Shapes the fused form does not take: conv, then pool
+                xin = self._eval(src.inputs[0], env, use_plan)
+                n_, h_, w_, cin_ = [int(d) for d in xin.shape]
+                if ops.conv2d_maxpool2_supported(n_, h_, w_, cin_, int(src.shape[3]), xin.dtype):
+                    fused = ops.conv2d_maxpool2_nhwc(xin, self._packed_conv(src.name), self.params[src.name + "/biases"], True)
             if fused is not None:
                 v = fused
             else:

@@ -127,6 +127,25 @@ def maxpool_nhwc_idx(x, size, stride, padding="SAME"):
     return y, idx
 
 
+def conv2d_maxpool2_supported(n, h, w, cin, cout, dtype):
+    """Shapes the fused 3x3 conv + 2x2/s2 SAME max-pool launch covers (sqdet_conv2d_maxpool2_supported)."""
+    return lib().sqdet_conv2d_maxpool2_supported(int(n), int(h), int(w), int(cin), int(cout), dtype_code(dtype)) != 0
+
+
+def conv2d_maxpool2_nhwc(x, packed, bias, relu=True):
+    """max_pool 2x2/s2/SAME(relu?(conv2d 3x3/s1/SAME(x) + b)) in one launch (VGG16's conv + pool pairs,
+    nets/vgg16_convDet.py:40-78): bitwise conv2d_nhwc followed by maxpool_nhwc(x, 2, 2, "SAME")."""
+    n, h, w, cin = [int(v) for v in x.shape]
+    if packed.k != 3 or cin != packed.cin or x.dtype != packed.dtype:
+        raise _lib.SqdetError("conv2d_maxpool2_nhwc: input [%d ch, %s] does not match the packed 3x3 kernel [k %d, %d ch, %s]"
+                              % (cin, x.dtype, packed.k, packed.cin, packed.dtype))
+    y = torch.empty((n, -(-h // 2), -(-w // 2), packed.cout), dtype=x.dtype, device=x.device)
+    check(lib().sqdet_conv2d_maxpool2_nhwc_fwd(_dev(x, "x"), _dev(packed.data, "packed"), _dev(bias, "bias", torch.float32), _dev(y, "y"),
+                                               n, h, w, cin, packed.cout, int(bool(relu)), dtype_code(x.dtype), stream_ptr()),
+          "sqdet_conv2d_maxpool2_nhwc_fwd")
+    return y
+
+
 def stem_supported(cout, k):
     """Shapes the fused conv1 + pool1 launch covers (sqdet_stem_conv_pool_fwd): SqueezeDet, SqueezeDet+ and ResNet50 stems."""
     return (k == 3 and cout == 64) or (k == 7 and cout in (64, 96))
@@ -946,7 +965,7 @@ class NetPlan:
     nets/squeezeDetPlus.py:30-79) as one native plan; device memory is torch-allocated."""
 
     ARCH = {"squeezeDet": _lib.ARCH_SQUEEZEDET, "squeezeDet+": _lib.ARCH_SQUEEZEDET_PLUS,
-            "resnet50": _lib.ARCH_RESNET50}
+            "resnet50": _lib.ARCH_RESNET50, "vgg16": _lib.ARCH_VGG16}
 
     def set_bn_epsilon(self, eps):
         check(lib().sqdet_net_set_bn_epsilon(self._h, float(eps)), "sqdet_net_set_bn_epsilon")

@@ -55,6 +55,12 @@ def step_normalisation(global_num_objects, local_batch, world):
     return 0, 1.0 / world
 
 
+def _reject_vgg16(model, trainer):
+    from .nets import VGG16ConvDet
+    if isinstance(model, VGG16ConvDet):
+        raise NotImplementedError("%s: VGG16ConvDet is inference only (no backward of its 2x2 pools, no VGG16 trainer)" % trainer)
+
+
 class _TrainerBase:
     """Flat float32 parameter / gradient / momentum buffers over the trainable variables of a model built with
     mc.IS_TRAINING = True, the gradient all-reduce and the optimizer step.
@@ -322,6 +328,7 @@ class SqueezeDetTrainer(_TrainerBase):
     """model: a squeezedet_amd.nets.SqueezeDet built with mc.IS_TRAINING = True and dtype float32."""
 
     def __init__(self, model, process_group=None, **kw):
+        _reject_vgg16(model, "SqueezeDetTrainer")
         _TrainerBase.__init__(self, model, process_group, **kw)
         self.layers = self._layer_list()
         # every trainable kernel is re-packed (forward order; backward-data order for all but the lowest trainable conv) by
@@ -557,6 +564,7 @@ class ResNet50ConvDetTrainer(_TrainerBase):
     kernel + sqdet_fold_batchnorm_bwd for d(kernels), d(gamma), d(beta).  float32, like the reference."""
 
     def __init__(self, model, process_group=None, **kw):
+        _reject_vgg16(model, "ResNet50ConvDetTrainer")
         _TrainerBase.__init__(self, model, process_group, **kw)
         m = model
         order, seen = [], set()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Whole-plan forward benchmark for any native arch (squeezeDet, squeezeDet+, resnet50): per-launch
+"""Whole-plan forward benchmark for any native arch (squeezeDet, squeezeDet+, resnet50, vgg16): per-launch
 milliseconds from HIP events (sqdet_net_forward_timed) with algorithmic GB/s and TFLOP/s, then the
 untimed-launch throughput of sqdet_net_forward.
 
@@ -17,7 +17,7 @@ from squeezedet_amd import ops  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", default="resnet50", choices=["squeezeDet", "squeezeDet+", "resnet50"])
+    ap.add_argument("--arch", default="resnet50", choices=["squeezeDet", "squeezeDet+", "resnet50", "vgg16"])
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--height", type=int, default=375)
     ap.add_argument("--width", type=int, default=1242)

@@ -146,9 +146,10 @@ int sqdet_subsample_nhwc(const void* x, void* y, int n, int h, int w, int c, int
  * SAME-padded cells never win.  x: [n,h,w,c] -> y: [n,ho,wo,c]. */
 int sqdet_maxpool_nhwc_fwd(const void* x, void* y, int n, int h, int w, int c, int k, int stride, int pad_mode,
                            int dtype, sqdet_stream_t stream);
-/* The training forward's pool (k = 3): also records, per output element, which window cell won -- one byte,
- * 3 * row + column of the FIRST maximum in row-major order (tf.nn.max_pool's gradient convention), 255 if none did --
- * for sqdet_maxpool_nhwc_bwd_idx.  window_index: [n,ho,wo,c] uint8. */
+/* The training forward's pool (k = 3, any stride, or k = 2, stride 2): also records, per output element, which window cell
+ * won -- one byte, k * row + column of the FIRST maximum in row-major order (tf.nn.max_pool's gradient convention); a window
+ * that nothing wins (all -inf / NaN) names its first valid cell -- for sqdet_maxpool_nhwc_bwd_idx.  window_index: [n,ho,wo,c]
+ * uint8.  y is bitwise sqdet_maxpool_nhwc_fwd's. */
 int sqdet_maxpool_nhwc_fwd_idx(const void* x, void* y, unsigned char* window_index, int n, int h, int w, int c, int k,
                                int stride, int pad_mode, int dtype, sqdet_stream_t stream);
 
@@ -159,8 +160,14 @@ int sqdet_maxpool_nhwc_fwd_idx(const void* x, void* y, unsigned char* window_ind
  * Cin not a multiple of 8 halves / 4 floats, Cout not a multiple of 4, conv_algo = generic, option "conv_pool" = 0). */
 int sqdet_conv2d_maxpool2_nhwc_fwd(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w,
                                    int cin, int cout, int relu, int dtype, sqdet_stream_t stream);
-/* 1 if sqdet_conv2d_maxpool2_nhwc_fwd takes the shape, else 0 (callers branch instead of catching SQDET_EUNSUPPORTED). */
+/* 1 if sqdet_conv2d_maxpool2_nhwc_fwd takes the shape, else 0 (callers branch instead of catching SQDET_EUNSUPPORTED).  The same
+ * answer holds for sqdet_conv2d_maxpool2_nhwc_fwd_idx. */
 int sqdet_conv2d_maxpool2_supported(int n, int h, int w, int cin, int cout, int dtype);
+/* sqdet_conv2d_maxpool2_nhwc_fwd that also writes the pool's window index [n,ceil(h/2),ceil(w/2),cout] uint8 (the training forward
+ * of VGG16's conv3_3+pool3 and conv4_3+pool4): y bitwise sqdet_conv2d_maxpool2_nhwc_fwd's, window_index bitwise
+ * sqdet_maxpool_nhwc_fwd_idx(k 2, stride 2, SAME) of the unfused conv's stored output. */
+int sqdet_conv2d_maxpool2_nhwc_fwd_idx(const void* x, const void* w_packed, const float* bias, void* y, unsigned char* window_index,
+                                       int n, int h, int w, int cin, int cout, int relu, int dtype, sqdet_stream_t stream);
 
 /* ------------------------------------------------------------------ stem --
  * conv1 + pool1 in one launch: relu(conv2d(x, W, stride 2) + b) followed by max_pool 3x3/s2
@@ -393,13 +400,13 @@ int sqdet_convert_scale(const void* src, int src_dtype, void* dst, int dst_dtype
 /* tf.nn.max_pool gradient: dx[cell] = sum of dy over the windows whose first maximum the cell is. */
 int sqdet_maxpool_nhwc_bwd(const void* x, const void* dy, void* dx, int n, int h, int w, int c, int k, int stride,
                            int pad_mode, int dtype, sqdet_stream_t stream);
-/* The same for a pool whose input x is a ReLU output (every pool of the reference's nets): dx is also zeroed where
+/* The same for a pool whose input x is a ReLU output (every pool of the reference's trained nets): dx is also zeroed where
  * x <= 0, i.e. the ReLU backward of the layer below is taken here instead of in a pass of its own. */
 int sqdet_maxpool_nhwc_bwd_relu(const void* x, const void* dy, void* dx, int n, int h, int w, int c, int k, int stride,
                                 int pad_mode, int dtype, sqdet_stream_t stream);
-/* Both from the window index of sqdet_maxpool_nhwc_fwd_idx (k = 3, stride 2) instead of x: reads three quarter-size
+/* Both from the window index of sqdet_maxpool_nhwc_fwd_idx (k = 3 or 2, stride 2) instead of x: reads three quarter-size
  * maps (index, dy and -- relu != 0 -- the pooled y, whose sign is the sign of x at every cell that receives anything)
- * and writes dx [n,h,w,c]; bitwise the results of the two functions above. */
+ * and writes every cell of dx [n,h,w,c] (cells no window covers: zero); bitwise the results of the two functions above. */
 int sqdet_maxpool_nhwc_bwd_idx(const unsigned char* window_index, const void* y, const void* dy, void* dx, int n, int h,
                                int w, int c, int k, int stride, int pad_mode, int dtype, int relu, sqdet_stream_t stream);
 

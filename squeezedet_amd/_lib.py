@@ -40,6 +40,7 @@ SIGNATURES = {
     "sqdet_maxpool_nhwc_bwd_idx": (ci, [vp, vp, vp, vp] + [ci] * 9 + [vp]),
     "sqdet_conv2d_maxpool2_nhwc_fwd": (ci, [vp, vp, vp, vp] + [ci] * 7 + [vp]),
     "sqdet_conv2d_maxpool2_supported": (ci, [ci] * 6),
+    "sqdet_conv2d_maxpool2_nhwc_fwd_idx": (ci, [vp] * 5 + [ci] * 7 + [vp]),
     "sqdet_stem_conv_pool_fwd": (ci, [vp, vp, vp, vp] + [ci] * 8 + [vp]),
     "sqdet_stem_conv_pool_squeeze_supported": (ci, [ci] * 9),
     "sqdet_stem_conv_pool_squeeze_fwd": (ci, [vp] * 6 + [ci] * 9 + [vp]),

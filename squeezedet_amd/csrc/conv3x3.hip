@@ -4,20 +4,20 @@
 
 namespace sqdet {
 
-template <typename T, int MT, bool POOL2>
+template <typename T, int MT, bool POOL2, bool PIDX>
 static bool dispatch_ntw(const TileArgs& a, int ntw, int grid_y, size_t lds, hipStream_t st) {
   switch (ntw) {
-    case 1: launch_tile<T, MT, 1, false, POOL2>(a, grid_y, lds, st); return true;
-    case 2: launch_tile<T, MT, 2, false, POOL2>(a, grid_y, lds, st); return true;
-    case 3: launch_tile<T, MT, 3, false, POOL2>(a, grid_y, lds, st); return true;
-    case 4: launch_tile<T, MT, 4, false, POOL2>(a, grid_y, lds, st); return true;
-    case 5: launch_tile<T, MT, 5, false, POOL2>(a, grid_y, lds, st); return true;
-    case 6: launch_tile<T, MT, 6, false, POOL2>(a, grid_y, lds, st); return true;
+    case 1: launch_tile<T, MT, 1, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+    case 2: launch_tile<T, MT, 2, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+    case 3: launch_tile<T, MT, 3, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+    case 4: launch_tile<T, MT, 4, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+    case 5: launch_tile<T, MT, 5, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+    case 6: launch_tile<T, MT, 6, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
     default: return false;
   }
 }
 
-template <typename T, bool POOL2>
+template <typename T, bool POOL2, bool PIDX = false>
 static bool dispatch_tile(const TileArgs& a, int mt, int ntw, bool splitk, int grid_y, size_t lds, hipStream_t st) {
   if (splitk) {
     if (POOL2 || ntw != 5) return false;   // (the split-K ConvDet kernel has no pooled epilogue)
@@ -25,14 +25,14 @@ static bool dispatch_tile(const TileArgs& a, int mt, int ntw, bool splitk, int g
   }
   if (mt == 8) {  // one wave = all 8 tile rows x a slice of a group (4 waves along the cout tiles)
     switch (ntw) {
-      case 1: launch_tile<T, 8, 1, false, POOL2>(a, grid_y, lds, st); return true;
-      case 2: launch_tile<T, 8, 2, false, POOL2>(a, grid_y, lds, st); return true;
-      case 3: launch_tile<T, 8, 3, false, POOL2>(a, grid_y, lds, st); return true;
-      case 4: launch_tile<T, 8, 4, false, POOL2>(a, grid_y, lds, st); return true;
+      case 1: launch_tile<T, 8, 1, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+      case 2: launch_tile<T, 8, 2, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+      case 3: launch_tile<T, 8, 3, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
+      case 4: launch_tile<T, 8, 4, false, POOL2, PIDX>(a, grid_y, lds, st); return true;
       default: return false;
     }
   }
-  return mt == 4 ? dispatch_ntw<T, 4, POOL2>(a, ntw, grid_y, lds, st) : dispatch_ntw<T, 2, POOL2>(a, ntw, grid_y, lds, st);
+  return mt == 4 ? dispatch_ntw<T, 4, POOL2, PIDX>(a, ntw, grid_y, lds, st) : dispatch_ntw<T, 2, POOL2, PIDX>(a, ntw, grid_y, lds, st);
 }
 
 // the forms dispatch_tile has an instantiation for
@@ -41,7 +41,8 @@ static bool tile_form_exists(int mt, int ntw, bool splitk, bool pool2) {
   return ntw >= 1 && (mt == 8 ? ntw <= 4 : ntw <= 6);
 }
 
-static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool pool2, bool dry);
+static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool pool2, bool dry,
+                            unsigned char* widx = nullptr);
 
 // Eligibility + configuration.  *handled = false means "use the generic kernels".
 int conv3x3_tile_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled) {
@@ -50,15 +51,17 @@ int conv3x3_tile_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStre
 
 // The POOL2 form: c describes the conv (Ho = H, Wo = W), c.y the POOLED tensor [N, ceil(H/2), ceil(W/2), y_cstride].  Plain convs
 // only (whole input rows, no accumulate, a bias); the wave layout is the one conv3x3_tile_launch picks for the unpooled conv.
-// dry: only decide whether the form takes the shape (*handled), launch nothing.
-int conv3x3_pool2_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry) {
+// dry: only decide whether the form takes the shape (*handled), launch nothing.  widx != nullptr: the PIDX form, which also writes
+// the pool's window index [N, ceil(H/2), ceil(W/2), Cout] -- the same shapes, the same wave layout.
+int conv3x3_pool2_launch(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry, unsigned char* widx) {
   *handled = false;
   if (tune(TUNE_CONV_POOL) == 0) return SQDET_OK;
   if (c.x_cstride != c.Cin || c.x_coffset != 0 || c.accum || !c.bias || c.relu_of || c.res || c.scores) return SQDET_OK;
-  return tile_launch_impl(c, g, dtype, st, handled, true, dry);
+  return tile_launch_impl(c, g, dtype, st, handled, true, dry, widx);
 }
 
-static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool pool2, bool dry) {
+static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool pool2, bool dry,
+                            unsigned char* widx) {
   *handled = false;
   if (conv_algo() != 0) return SQDET_OK;
   if (c.k != 3 || c.stride != 1 || c.pt != 1 || c.pl != 1 || g.gather) return SQDET_OK;
@@ -77,6 +80,7 @@ static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hip
   a.stage_chunks = g.nchunk;
   a.wp1 = nullptr; a.bias1 = nullptr; a.y_coffset1 = 0;
   a.dma = 0; a.chunk_pitch = CHUNK_BYTES;
+  if (widx) a.widx = widx;
   if ((long)c.N * a.tiles_x * a.tiles_y > 0x7fffffffL) return SQDET_OK;
   if (a.total_tiles * 16 > 1024) return SQDET_OK;     // (the kernel keeps the bias in LDS: up to 1024 couts)
 
@@ -136,7 +140,10 @@ static int tile_launch_impl(const ConvArgs& c, const ConvGeom& g, int dtype, hip
   if (pool2 && !tile_form_exists(mt, ntw, splitk, pool2)) return SQDET_OK;   // (split K: "not handled")
   if (dry) { *handled = true; return SQDET_OK; }
   bool ok;
-  if (pool2)
+  if (pool2 && widx)
+    ok = dtype == SQDET_F16 ? dispatch_tile<f16, true, true>(a, mt, ntw, splitk, grid_y, lds, st)
+                            : dispatch_tile<float, true, true>(a, mt, ntw, splitk, grid_y, lds, st);
+  else if (pool2)
     ok = dtype == SQDET_F16 ? dispatch_tile<f16, true>(a, mt, ntw, splitk, grid_y, lds, st)
                             : dispatch_tile<float, true>(a, mt, ntw, splitk, grid_y, lds, st);
   else
@@ -225,7 +232,7 @@ bool conv2d_maxpool2_eligible(int n, int h, int w, int cin, int cout, int dtype)
 }
 
 int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
-                           int relu, int dtype, hipStream_t st) {
+                           int relu, int dtype, hipStream_t st, unsigned char* widx = nullptr) {
   SQDET_REQUIRE(x && w_packed && bias && y, "conv2d_maxpool2: null pointer");
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "conv2d_maxpool2: bad dtype %d", dtype);
   SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0, "conv2d_maxpool2: bad dims");
@@ -233,7 +240,7 @@ int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bia
                     "conv2d_maxpool2: shape not covered (see sqdet_conv2d_maxpool2_supported)");
   const ConvGeom g = conv_geom(3, cin, cout, dtype);
   bool handled = false;
-  const int rc = conv3x3_pool2_launch(pool2_args(x, w_packed, bias, y, n, h, w, cin, cout, relu, g), g, dtype, st, &handled, false);
+  const int rc = conv3x3_pool2_launch(pool2_args(x, w_packed, bias, y, n, h, w, cin, cout, relu, g), g, dtype, st, &handled, false, widx);
   if (rc != SQDET_OK) return rc;
   SQDET_UNSUPPORTED(!handled, "conv2d_maxpool2: the tile kernel did not take this shape");
   return SQDET_OK;
@@ -248,6 +255,13 @@ extern "C" int sqdet_conv2d_maxpool2_supported(int n, int h, int w, int cin, int
 extern "C" int sqdet_conv2d_maxpool2_nhwc_fwd(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w,
                                               int cin, int cout, int relu, int dtype, sqdet_stream_t stream) {
   return sqdet::conv2d_maxpool2_launch(x, w_packed, bias, y, n, h, w, cin, cout, relu, dtype, sqdet::as_stream(stream));
+}
+
+extern "C" int sqdet_conv2d_maxpool2_nhwc_fwd_idx(const void* x, const void* w_packed, const float* bias, void* y,
+                                                  unsigned char* window_index, int n, int h, int w, int cin, int cout, int relu,
+                                                  int dtype, sqdet_stream_t stream) {
+  SQDET_REQUIRE(window_index, "conv2d_maxpool2_idx: null window index");
+  return sqdet::conv2d_maxpool2_launch(x, w_packed, bias, y, n, h, w, cin, cout, relu, dtype, sqdet::as_stream(stream), window_index);
 }
 
 #ifdef SQDET_C3_TIMELINE

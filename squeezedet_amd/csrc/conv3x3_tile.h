@@ -38,7 +38,11 @@ struct TileArgs {
   int stage_chunks; // cout-split mode: K-chunks of the halo tile resident in LDS at a time (deep K is walked in stages)
   // PAIR form (expand1x1 || expand3x3 of a fire module from ONE staged squeeze tile, nets/squeezeDetPlus.py:81-106): the packed 1x1
   // kernel / bias of the same Cin -> Cout shape and the channel offset of its slice of y's rows; the whole tile is resident
-  const void* wp1;
+  // (POOL2 + PIDX form, which never has a PAIR: in wp1's place the pool's window index [N, ceil(H/2), ceil(W/2), Cout] uint8)
+  union {
+    const void* wp1;
+    unsigned char* widx;
+  };
   const float* bias1;
   int y_coffset1;
   // staging: dma != 0: the halo tile arrives by LDS-DMA (stage_tile_dma), chunk pitch 12288 B = 192 pixels (whole 1-KiB DMA blocks);
@@ -139,8 +143,14 @@ __device__ unsigned long long g_c3_tl[16384 * 8];
 // (computed from the zero halo: after bias + ReLU real non-negative numbers) enter the max as -inf.
 // (the <8, 3> float16 form -- SqueezeDet+ fire6 / fire7 -- runs three workgroups per CU: its register budget is 168; checked spill-free;
 // its POOL2 form does not fit that budget and runs one)
-template <typename T, int MT, int NTW, bool PAIR = false, bool POOL2 = false>
+// PIDX (with POOL2, the training forward): also writes the window index, bitwise maxpool2_idx_kernel on the conv's STORED tensor.
+// The cells are ranked after rounding to T (two float32 values one half apart round to the same f16: a tie, which the stored
+// tensor resolves to the first cell).  Within a lane rows m, m + 1 by a strict '>' from -inf; across lanes j, j ^ 1 value and index
+// by DPP, the larger value or on an equal value the smaller index: the row-major first maximum.  Pixels past H / W never win; a
+// lane without a valid pixel offers index 255, so a window that nothing wins names its first valid cell.
+template <typename T, int MT, int NTW, bool PAIR = false, bool POOL2 = false, bool PIDX = false>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3 && !POOL2) ? 3 : 1) void conv3x3_tile(TileArgs a) {
+  static_assert(!PIDX || POOL2, "the window index belongs to the pooled epilogue");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 #ifdef SQDET_C3_TIMELINE
   unsigned long long c3tl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -328,8 +338,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3 && !POO
       if (oy >= a.c.H) break;        // (wave-uniform: the DPP below runs with every lane of the wave)
       const bool row1_ok = oy + 1 < a.c.H;
       f32x4 v[NTW];
+      unsigned wi[NTW];
 #pragma unroll
       for (int t = 0; t < NTW; ++t) {
+        wi[t] = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float p = acc[m][t][e] + bias[t][e], q = acc[m + 1][t][e] + bias[t][e];
@@ -339,11 +351,31 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3 && !POO
           // the window's other column: lane j ^ 1 (quad_perm [1, 0, 3, 2])
           const float o = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, r), 0xB1, 0xF, 0xF, false));
           v[t][e] = fmaxf(r, o);
+          if constexpr (PIDX) {
+            const float pr = (float)(T)p, qr = (float)(T)q;
+            const int c0 = j & 1;
+            float bv = col_ok && pr > NEG ? pr : NEG;
+            int bi = col_ok ? c0 : 255;
+            const bool qw = col_ok && row1_ok && qr > bv;
+            bv = qw ? qr : bv;
+            bi = qw ? 2 + c0 : bi;
+            const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, bv), 0xB1, 0xF, 0xF, false));
+            const int oi = __builtin_amdgcn_update_dpp(0, bi, 0xB1, 0xF, 0xF, false);
+            bi = ov > bv || (ov == bv && oi < bi) ? oi : bi;
+            wi[t] |= (unsigned)bi << (8 * e);
+          }
         }
       }
       if (col_ok && (j & 1) == 0) {
-        T* dst = y + (((size_t)n * Ho + (oy >> 1)) * Wo + (ox >> 1)) * a.c.y_cstride + y_coffset + cb;
+        const size_t po = ((size_t)n * Ho + (oy >> 1)) * Wo + (ox >> 1);
+        T* dst = y + po * a.c.y_cstride + y_coffset + cb;
         store_couts<T, NTW>(dst, v, nt_valid);
+        if constexpr (PIDX) {
+          unsigned* di = reinterpret_cast<unsigned*>(a.widx + po * a.c.Cout + cb);   // (Cout and cb multiples of 4)
+#pragma unroll
+          for (int t = 0; t < NTW; ++t)
+            if (t < nt_valid) di[t] = wi[t];
+        }
       }
     }
   } else if (ox < a.c.W) {
@@ -434,15 +466,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && MT == 8 && NTW == 3 && !POO
   }
 }
 
-template <typename T, int MT, int NTW, bool PAIR = false, bool POOL2 = false>
+template <typename T, int MT, int NTW, bool PAIR = false, bool POOL2 = false, bool PIDX = false>
 static void launch_tile(const TileArgs& a, int grid_y, size_t lds, hipStream_t st) {
   static_assert(!(PAIR && POOL2), "the PAIR form writes the concat tensor unpooled");
   static PerDevice once;   // > 64 KiB of dynamic LDS has to be allowed once per kernel and device
   if (lds > 65536)
-    (void)once.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_tile<T, MT, NTW, PAIR, POOL2>),
+    (void)once.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_tile<T, MT, NTW, PAIR, POOL2, PIDX>),
                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
   const dim3 grid((unsigned)((a.c.N * a.tiles_x * a.tiles_y + 7) / 8 * 8), (unsigned)grid_y);
-  hipLaunchKernelGGL((conv3x3_tile<T, MT, NTW, PAIR, POOL2>), grid, dim3(256), lds, st, a);
+  hipLaunchKernelGGL((conv3x3_tile<T, MT, NTW, PAIR, POOL2, PIDX>), grid, dim3(256), lds, st, a);
 }
 
 // the split-K (ConvDet) kernel lives in convdet.hip: that file is compiled with the accumulators in AGPRs

@@ -136,7 +136,8 @@ int fire_dma_launch(const void* sq_in, const void* w1, const float* b1, const vo
                     hipStream_t st, bool* handled);
 int conv3x3_tile_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled);
 // conv3x3.hip: the same with max_pool 2x2/s2/SAME in the epilogue (y = the pooled tensor); dry = eligibility only
-int conv3x3_pool2_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry);
+int conv3x3_pool2_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry,
+                         unsigned char* widx = nullptr);
 // conv3x3.hip: both expands of a fire module from ONE staged squeeze tile (the tile kernel's PAIR form)
 bool conv3x3_pair_eligible(int n, int h, int w, int s, int e1, int e3, int dtype);
 int conv3x3_pair_launch(const void* sq_in, const void* w3, const float* b3, const void* w1, const float* b1, void* y, int n, int h, int w,

@@ -60,7 +60,7 @@ int conv3x3_pair_launch(const void* sq_in, const void* w3, const float* b3, cons
                         int s, int e1, int e3, int dtype, hipStream_t st, bool* handled);
 bool conv2d_maxpool2_eligible(int n, int h, int w, int cin, int cout, int dtype);
 int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
-                           int relu, int dtype, hipStream_t st);
+                           int relu, int dtype, hipStream_t st, unsigned char* widx = nullptr);
 int conv_algo();
 int tune(int which);
 }  // namespace sqdet

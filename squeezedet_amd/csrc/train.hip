@@ -343,6 +343,64 @@ __global__ void maxpool3s2_bwd_idx_kernel(const unsigned char* __restrict__ widx
   }
 }
 
+// The 2x2 / stride-2 form from the window index (pool.hip maxpool2_idx_kernel): the windows do not overlap, so one thread per
+// output vector writes its whole 2x2 block of dx -- dy at the winner, zero elsewhere; no gather, no accumulation.  Threads run
+// over the ceil((H + pt) / 2) x ceil((W + pl) / 2) blocks: a block past Ho / Wo (VALID with an odd H or W: the last row or
+// column belongs to no window) is written as zeros, so every dx cell is written.  The winner's value is (T)(0.f + (float)dy),
+// the sum maxpool_bwd_kernel forms (-0 -> +0): bitwise sqdet_maxpool_nhwc_bwd / _bwd_relu.  relu: (y > 0) at the winner, the
+// pooled value being the winner's x.
+template <typename T>
+__global__ void maxpool2s2_bwd_idx_kernel(const unsigned char* __restrict__ widx, const T* __restrict__ y,
+                                          const T* __restrict__ dy, T* __restrict__ dx, int N, int H, int W, int C, int pt,
+                                          int pl, int Ho, int Wo, int BA, int BB, int relu) {
+  typedef typename Vec16<T>::type V;
+  constexpr int EV = 16 / sizeof(T);
+  const int cvn = C / EV;
+  const size_t total = (size_t)N * BA * BB * cvn;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int cv = (int)(idx % cvn);
+    size_t p = idx / cvn;
+    const int b = (int)(p % BB); p /= BB;
+    const int a = (int)(p % BA);
+    const int n = (int)(p / BA);
+    V o[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int e = 0; e < EV; ++e) o[q][e] = (T)0.f;
+    if (a < Ho && b < Wo) {
+      const size_t oo = (((size_t)n * Ho + a) * Wo + b) * C + cv * EV;
+      unsigned char bp[EV];
+      if constexpr (EV == 8) {
+        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 w2 = *reinterpret_cast<const u32x2*>(widx + oo);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bp[e] = (unsigned char)(w2[e >> 2] >> (8 * (e & 3)));
+      } else {
+        const unsigned int w1 = *reinterpret_cast<const unsigned int*>(widx + oo);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bp[e] = (unsigned char)(w1 >> (8 * e));
+      }
+      const V d = *reinterpret_cast<const V*>(dy + oo);
+      V yv;
+      if (relu) yv = *reinterpret_cast<const V*>(y + oo);
+#pragma unroll
+      for (int e = 0; e < EV; ++e) {
+        const T gv = (T)(0.f + (float)d[e]);
+        const T v = relu && !(yv[e] > (T)0) ? (T)0.f : gv;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q][e] = bp[e] == q ? v : o[q][e];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int iy = 2 * a + (q >> 1) - pt, ix = 2 * b + (q & 1) - pl;
+      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+      *reinterpret_cast<V*>(dx + ((((size_t)n * H + iy) * W + ix) * C + cv * EV)) = o[q];
+    }
+  }
+}
+
 // max-pool backward, generic gather form (deterministic): an input cell receives dy of every window whose
 // FIRST maximum (row-major scan, as tf.nn.max_pool's argmax) it is.
 template <typename T>
@@ -878,9 +936,23 @@ extern "C" int sqdet_maxpool_nhwc_bwd_idx(const unsigned char* window_index, con
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "maxpool_bwd_idx: bad dtype");
   const int ev = 16 / (int)dtype_size(dtype);
   SQDET_REQUIRE(window_index && dy && dx && (y || !relu) && n > 0 && h > 0 && w > 0 && c > 0 && c % ev == 0, "maxpool_bwd_idx: bad arguments");
-  SQDET_UNSUPPORTED(k != 3 || stride != 2, "maxpool_bwd_idx: 3x3 / stride-2 pools only (every pool of the reference's nets)");
+  SQDET_UNSUPPORTED((k != 3 && k != 2) || stride != 2, "maxpool_bwd_idx: 3x3 and 2x2 windows of stride 2 only");
+  SQDET_REQUIRE(k == 3 || pad_mode == SQDET_PAD_SAME || (pad_mode == SQDET_PAD_VALID && h >= 2 && w >= 2),
+                "maxpool_bwd_idx: bad pad_mode, or VALID with h,w < 2");
   const int Ho = out_size(h, k, stride, pad_mode), Wo = out_size(w, k, stride, pad_mode);
   const int pt = pad_before(h, k, stride, pad_mode), pl = pad_before(w, k, stride, pad_mode);
+  if (k == 2) {
+    const int BA = (h + pt + 1) / 2, BB = (w + pl + 1) / 2;
+    const dim3 grid(grid_for((size_t)n * BA * BB * (c / ev), 16384));
+    if (dtype == SQDET_F16)
+      hipLaunchKernelGGL(maxpool2s2_bwd_idx_kernel<f16>, grid, dim3(256), 0, as_stream(stream), window_index, (const f16*)y,
+                         (const f16*)dy, (f16*)dx, n, h, w, c, pt, pl, Ho, Wo, BA, BB, relu);
+    else
+      hipLaunchKernelGGL(maxpool2s2_bwd_idx_kernel<float>, grid, dim3(256), 0, as_stream(stream), window_index, (const float*)y,
+                         (const float*)dy, (float*)dx, n, h, w, c, pt, pl, Ho, Wo, BA, BB, relu);
+    SQDET_CHECK_HIP(hipGetLastError());
+    return SQDET_OK;
+  }
   const int BA = (h + pt + 1) / 2, BB = (w + pl + 1) / 2;
   const dim3 grid(grid_for((size_t)n * BA * BB * (c / ev), 16384));
   if (dtype == SQDET_F16)

@@ -142,8 +142,8 @@ class SqueezeDetPlus(_FireNet):
 
 
 class VGG16ConvDet(_FireNet):
-    """VGG16 conv1_1..conv5_3 + ConvDet (nets/vgg16_convDet.py:20-90).  Inference only: the trainers take the fire-module
-    and ResNet50 nets."""
+    """VGG16 conv1_1..conv5_3 + ConvDet (nets/vgg16_convDet.py:20-90).  Trained by train.VGG16ConvDetTrainer (conv1 / conv2
+    frozen, as the reference)."""
     NATIVE_ARCH = "vgg16"
 
     def _add_forward_graph(self):

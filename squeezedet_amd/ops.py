@@ -146,6 +146,21 @@ def conv2d_maxpool2_nhwc(x, packed, bias, relu=True):
     return y
 
 
+def conv2d_maxpool2_nhwc_idx(x, packed, bias, relu=True):
+    """conv2d_maxpool2_nhwc that also returns the pool's uint8 window index (sqdet_conv2d_maxpool2_nhwc_fwd_idx): (y, idx), bitwise
+    maxpool_nhwc_idx(conv2d_nhwc(x, ...), 2, 2, "SAME") -- the training forward's pair, without the full-resolution conv output."""
+    n, h, w, cin = [int(v) for v in x.shape]
+    if packed.k != 3 or cin != packed.cin or x.dtype != packed.dtype:
+        raise _lib.SqdetError("conv2d_maxpool2_nhwc_idx: input [%d ch, %s] does not match the packed 3x3 kernel [k %d, %d ch, %s]"
+                              % (cin, x.dtype, packed.k, packed.cin, packed.dtype))
+    y = torch.empty((n, -(-h // 2), -(-w // 2), packed.cout), dtype=x.dtype, device=x.device)
+    idx = torch.empty(tuple(y.shape), dtype=torch.uint8, device=x.device)
+    check(lib().sqdet_conv2d_maxpool2_nhwc_fwd_idx(_dev(x, "x"), _dev(packed.data, "packed"), _dev(bias, "bias", torch.float32),
+                                                   _dev(y, "y"), _dev(idx, "idx"), n, h, w, cin, packed.cout, int(bool(relu)),
+                                                   dtype_code(x.dtype), stream_ptr()), "sqdet_conv2d_maxpool2_nhwc_fwd_idx")
+    return y, idx
+
+
 def stem_supported(cout, k):
     """Shapes the fused conv1 + pool1 launch covers (sqdet_stem_conv_pool_fwd): SqueezeDet, SqueezeDet+ and ResNet50 stems."""
     return (k == 3 and cout == 64) or (k == 7 and cout in (64, 96))

@@ -26,6 +26,8 @@ def synthetic_params(model, seed=0):
             sigma = math.sqrt(2.0 / (shp[0] * shp[1] * shp[2]))
             if name.startswith("conv1/"):
                 sigma /= 64.0   # inputs are pixel-scale (rms ~74): bring activations to O(1)
+            if name == "conv1/conv1_2/kernels":
+                sigma *= 64.0   # VGG16's second conv reads conv1_1's O(1) output, not pixels: plain He
             if name.startswith("conv12"):
                 sigma *= 2.0    # preds of std ~2: scores spread without saturating
             if name.startswith("conv5/"):

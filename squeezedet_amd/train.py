@@ -58,7 +58,7 @@ def step_normalisation(global_num_objects, local_batch, world):
 def _reject_vgg16(model, trainer):
     from .nets import VGG16ConvDet
     if isinstance(model, VGG16ConvDet):
-        raise NotImplementedError("%s: VGG16ConvDet is inference only (no backward of its 2x2 pools, no VGG16 trainer)" % trainer)
+        raise NotImplementedError("%s does not train VGG16ConvDet: use VGG16ConvDetTrainer" % trainer)
 
 
 class _TrainerBase:
@@ -415,7 +415,7 @@ class SqueezeDetTrainer(_TrainerBase):
                         y = None        # e.g. set_option("conv_algo", 1): the separate conv + pool kernels below
                     if y is not None:
                         saved.append(("conv", node, cur, None))
-                        saved.append(("pool", nxt[2], None, y, None))
+                        saved.append(("pool", nxt[2], None, y, None, None))
                         acts[nxt[2].name] = y
                         cur = y
                         skip_pool = nxt[2]
@@ -439,7 +439,7 @@ class SqueezeDetTrainer(_TrainerBase):
                     y, widx = ops.maxpool_nhwc_idx(cur, 3, 2, node.attrs["padding"])
                 else:
                     y, widx = ops.maxpool_nhwc(cur, node.attrs["size"], node.attrs["stride"], node.attrs["padding"]), None
-                saved.append(("pool", node, cur, y, widx))
+                saved.append(("pool", node, cur, y, widx, tuple(cur.shape[1:3])))
                 acts[node.name] = y
                 cur = y
             else:
@@ -462,6 +462,21 @@ class SqueezeDetTrainer(_TrainerBase):
         # ---------------- loss ----------------
         self._join_labels()
         g, dpreds, ious, losses = self._loss(preds, mask, delta, box, lab, num_objects)
+        self._chain_backward(saved, g, tuple(int(v) for v in x.shape), "conv12", dm if keep != 1.0 else None)
+        out = collections.OrderedDict(class_loss=losses[0], conf_loss=losses[1], bbox_loss=losses[2], ious=ious, preds=preds,
+                                      dpreds=dpreds, num_objects=num_objects)
+        if keep_activations:
+            out["activations"] = acts
+        return out
+
+    def _chain_backward(self, saved, g, wkey, drop_name, dm):
+        """Backward of a linear chain of layer records into the flat gradient bucket.  saved: the forward's records in order --
+        ("conv", node, x, y), ("pool", node, x, y, window index or None, (h, w) of x), ("fire", (sq, e1, e3), x, s, y); a conv
+        record's y may be None where a fused launch never wrote it (its gradient is then masked by the pool backward above
+        it).  g: gradient w.r.t. the last record's output; wkey: the WgradPlan key (the input shape); drop_name: the conv
+        reading the dropout, dm its keep mask (None: no dropout)."""
+        m, P = self.model, self.model.params
+        keep = m.keep_prob
         # ---------------- backward ----------------
         self.flat_grads.zero_()
         gs = 1.0 / self.loss_scale      # g: gradient w.r.t. the current layer's OUTPUT (pre-activation mask applied below)
@@ -469,7 +484,6 @@ class SqueezeDetTrainer(_TrainerBase):
         # weight gradients: every conv's gradient kernel writes its partial slabs into a workspace of its own and ONE launch
         # at the end sums them all (ops.WgradPlan); the first step of an input shape runs the per-conv two-launch form and
         # records what the plan needs
-        wkey = tuple(int(v) for v in x.shape)
         wplan = self._wplan_get(wkey)
         witems = []
 
@@ -500,6 +514,11 @@ class SqueezeDetTrainer(_TrainerBase):
             if r[0] == "conv" and r[1].attrs["relu"] and r[3] is not None:
                 return r[3]
             return None
+
+        def relu_below(rj):
+            """The record rj ends in a ReLU (a pool backward masks with its own x or, from the window index, with y)."""
+            r = saved[rj]
+            return r[0] == "fire" or (r[0] == "conv" and r[1].attrs["relu"])
         for ri in range(len(saved) - 1, first_tr - 1, -1):
             rec = saved[ri]
             need_dx = ri > first_tr     # nothing trainable (and no image gradient) below the first trainable layer
@@ -510,11 +529,11 @@ class SqueezeDetTrainer(_TrainerBase):
                 if node.attrs["relu"] and not masked:
                     ops.relu_bwd(y, g)
                 k = node.attrs["size"]
-                cin, cout = int(xin.shape[3]), int(y.shape[3])
+                cin, cout = int(xin.shape[3]), int(node.shape[3])
                 self._wgrad(lambda xin=xin, g=g, k=k, cin=cin, cout=cout, name=name: wg(name, xin, g, k, cin, cout), g)
                 masked = False
                 if need_dx:
-                    if name == "conv12" and keep != 1.0:
+                    if name == drop_name and dm is not None:
                         g = ops.conv2d_bwd_data(g, bwd(name))
                         g = ops.scale_mask(g, dm, 1.0 / keep, relu_of=below)      # dropout backward (+ the ReLU backward below it)
                         masked = below is not None
@@ -522,12 +541,13 @@ class SqueezeDetTrainer(_TrainerBase):
                         g = ops.conv2d_bwd_data(g, bwd(name), relu_of=below)
                         masked = below is not None
             elif rec[0] == "pool":
-                _, node, xin, y, widx = rec
+                _, node, xin, y, widx, in_hw = rec
+                relu = ri > 0 and relu_below(ri - 1)
                 if widx is not None:
-                    g = ops.maxpool_bwd_idx(widx, y, g, xin.shape[1:3], 3, 2, node.attrs["padding"], relu=below is not None)
+                    g = ops.maxpool_bwd_idx(widx, y, g, in_hw, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=relu)
                 else:
-                    g = ops.maxpool_bwd(xin, g, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=below is not None)
-                masked = below is not None
+                    g = ops.maxpool_bwd(xin, g, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=relu)
+                masked = relu
             else:
                 _, (sq, e1, e3), xin, s, y = rec
                 ne1, ne3, ns = e1.shape[3], e3.shape[3], sq.shape[3]
@@ -549,9 +569,94 @@ class SqueezeDetTrainer(_TrainerBase):
             wplan.reduce(gs)
         elif self.plan_wgrads:
             self._wplan_put(wkey, ops.WgradPlan(witems))
+
+
+class VGG16ConvDetTrainer(SqueezeDetTrainer):
+    """Training step of VGG16ConvDet (nets/vgg16_convDet.py:31-90 + nn_skeleton.py:285-361).  conv1_1 .. conv2_2 are frozen
+    (:40-50), so the forward up to pool2 runs on the inference graph (its fused conv + pool launches, nothing kept) and the
+    backward stops at conv3_1: a weight gradient, no input gradient.  The trainable region conv3_1 .. conv6 is a linear chain
+    and takes SqueezeDetTrainer's backward.  Its two conv + 2x2 pool pairs (conv3_3 + pool3, conv4_3 + pool4) run as ONE
+    launch that also writes the pool's window index (sqdet_conv2d_maxpool2_nhwc_fwd_idx) where it covers the shape, else as
+    conv + maxpool_nhwc_idx; either way the pool backward reads the index, so the full-resolution conv output is not kept."""
+
+    def __init__(self, model, process_group=None, **kw):
+        from .nets import VGG16ConvDet
+        if not isinstance(model, VGG16ConvDet):
+            raise SqdetError("VGG16ConvDetTrainer trains VGG16ConvDet")
+        _TrainerBase.__init__(self, model, process_group, **kw)
+        m = model
+        chain = []
+        n = m.preds
+        while n.op != "placeholder":
+            chain.append(n)
+            n = n.inputs[0]
+        chain.reverse()
+        first = next(i for i, n in enumerate(chain) if n.op == "conv" and m.trainable[n.name + "/kernels"])
+        self.boundary = chain[first].inputs[0]          # the last frozen activation (pool2)
+        self.region = chain[first:]                     # conv / pool / dropout nodes, forward order
+        for n in self.region:
+            if n.op not in ("conv", "pool", "dropout") or (n.op == "conv" and not m.trainable[n.name + "/kernels"]):
+                raise SqdetError("VGG16ConvDetTrainer: unsupported node %s (%s) in the trainable region" % (n.name, n.op))
+            if n.op == "pool" and (n.attrs["size"], n.attrs["stride"]) != (2, 2):
+                raise SqdetError("VGG16ConvDetTrainer: pool %s is not 2x2 / stride 2" % n.name)
+        # the conv reading the dropout: its backward is the dropout's too
+        self.drop_conv = next((n.name for n in self.region if n.op == "conv" and n.inputs[0].op == "dropout"), None)
+        kernels = collections.OrderedDict((n.name, self.view[n.name + "/kernels"]) for n in self.region if n.op == "conv")
+        self.packplan = ops.PackPlan(kernels, self.adt, bwd_names=set(kernels) - {chain[first].name})
+        self._frozen_packed = {}
+
+    def forward_backward(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None,
+                         keep_activations=False, num_objects=None, num_objects_is_global=False):
+        m, P = self.model, self.model.params
+        self.packplan.run()
+        (xb,) = m.run([self.boundary], {m.image_input: images}, use_plan=False)
+        B = int(xb.shape[0])
+        t, mask, delta, box, lab, num_objects = self._labels(B, input_mask, box_delta_input, box_input, labels, num_objects, num_objects_is_global)
+        acts = {self.boundary.name: xb}
+        saved, cur, dm, skip = [], xb, None, None
+        for i, n in enumerate(self.region):
+            if n is skip:
+                continue
+            if n.op == "dropout":
+                keep = n.attrs["keep_prob"]
+                if dropout_mask is None:
+                    dropout_mask = self._dropout_mask(cur.shape, keep)
+                dm = self._mask_tensor(dropout_mask, t)
+                cur = ops.scale_mask(cur, dm, 1.0 / keep)
+                acts["drop"] = cur
+            elif n.op == "conv":
+                nxt = self.region[i + 1] if i + 1 < len(self.region) else None
+                pk, bias = self.packplan.fwd[n.name], P[n.name + "/biases"]
+                if (not keep_activations and nxt is not None and nxt.op == "pool" and nxt.attrs["padding"] == "SAME"
+                        and n.attrs["size"] == 3 and n.attrs["stride"] == 1 and n.attrs["padding"] == "SAME"
+                        and ops.conv2d_maxpool2_supported(B, int(cur.shape[1]), int(cur.shape[2]), int(cur.shape[3]),
+                                                          int(n.shape[3]), self.adt)):
+                    # conv + pool + window index in one launch: the conv's output never reaches HBM
+                    y, widx = ops.conv2d_maxpool2_nhwc_idx(cur, pk, bias, n.attrs["relu"])
+                    saved.append(("conv", n, cur, None))
+                    saved.append(("pool", nxt, None, y, widx, tuple(cur.shape[1:3])))
+                    acts[nxt.name] = y
+                    cur, skip = y, nxt
+                    continue
+                y = ops.conv2d_nhwc(cur, pk, bias, n.attrs["stride"], n.attrs["padding"], n.attrs["relu"])
+                saved.append(("conv", n, cur, y))
+                acts[n.name] = y
+                cur = y
+            else:
+                y, widx = ops.maxpool_nhwc_idx(cur, 2, 2, n.attrs["padding"])
+                # the pool's input is not kept: the backward reads the index, y and dy (and masks the conv's ReLU itself)
+                if saved and saved[-1][0] == "conv":
+                    saved[-1] = saved[-1][:3] + (None,)
+                saved.append(("pool", n, None, y, widx, tuple(cur.shape[1:3])))
+                acts[n.name] = y
+                cur = y
+        preds = cur
+        self._join_labels()
+        g, dpreds, ious, losses = self._loss(preds, mask, delta, box, lab, num_objects)
+        self._chain_backward(saved, g, tuple(int(v) for v in xb.shape), self.drop_conv, dm)
         out = collections.OrderedDict(class_loss=losses[0], conf_loss=losses[1], bbox_loss=losses[2], ious=ious, preds=preds,
                                       dpreds=dpreds, num_objects=num_objects)
-        if keep_activations:
+        if keep_activations:     # names as the oracle's `override`: the conv layer names, pool2, pool3, pool4, drop
             out["activations"] = acts
         return out
 

@@ -36,15 +36,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, default=0, help="images per GPU per step (default: 20 squeezeDet, 8 resnet50)")
-    ap.add_argument("--arch", default="squeezeDet", choices=["squeezeDet", "resnet50"],
-                    help="squeezeDet = BASELINE.json configs[2]; resnet50 = configs[4] (ResNet50+ConvDet, 1242x375, in float32)")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="images per GPU per step (default: 20 squeezeDet, 8 resnet50, 5 vgg16 -- the reference's BATCH_SIZE)")
+    ap.add_argument("--arch", default="squeezeDet", choices=["squeezeDet", "resnet50", "vgg16"],
+                    help="squeezeDet = BASELINE.json configs[2]; resnet50 = configs[4] (ResNet50+ConvDet, 1242x375, in float32); "
+                         "vgg16 = VGG16+ConvDet, 1242x375")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="f32 = the reference's training dtype; f16 = mixed precision (float16 activations / activation gradients, "
                          "float32 master weights, weight gradients and optimizer, dynamic loss scale) -- configs[4] is resnet50 + f16")
     args = ap.parse_args()
     if args.batch <= 0:
-        args.batch = 20 if args.arch == "squeezeDet" else 8
+        args.batch = {"squeezeDet": 20, "resnet50": 8, "vgg16": 5}[args.arch]
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -54,12 +56,13 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     import squeezedet_amd as S
     from squeezedet_amd import nets, synthetic
-    from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer
-    mc = S.kitti_squeezeDet_config() if args.arch == "squeezeDet" else S.kitti_res50_config()
+    from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer, VGG16ConvDetTrainer
+    mc = {"squeezeDet": S.kitti_squeezeDet_config, "resnet50": S.kitti_res50_config, "vgg16": S.kitti_vgg16_config}[args.arch]()
     mc.LOAD_PRETRAINED_MODEL = False
     mc.IS_TRAINING = True
     mc.BATCH_SIZE = args.batch
-    cls, trainer = (nets.SqueezeDet, SqueezeDetTrainer) if args.arch == "squeezeDet" else (nets.ResNet50ConvDet, ResNet50ConvDetTrainer)
+    cls, trainer = {"squeezeDet": (nets.SqueezeDet, SqueezeDetTrainer), "resnet50": (nets.ResNet50ConvDet, ResNet50ConvDetTrainer),
+                    "vgg16": (nets.VGG16ConvDet, VGG16ConvDetTrainer)}[args.arch]
     model = cls(mc, gpu_id=str(local_rank), dtype=torch.float32 if args.dtype == "f32" else torch.float16)
     model.load_params(synthetic.synthetic_params(model, seed=0))      # same weights on every rank
     tr = trainer(model, lazy_overflow_check=True)
@@ -90,7 +93,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     if rank == 0:
-        label = "SqueezeDet 1248x384" if args.arch == "squeezeDet" else "ResNet50+ConvDet 1242x375"
+        label = {"squeezeDet": "SqueezeDet 1248x384", "resnet50": "ResNet50+ConvDet 1242x375", "vgg16": "VGG16+ConvDet 1242x375"}[args.arch]
         prec = "fp32" if args.dtype == "f32" else "fp16 (mixed precision)"
         print(json.dumps({"metric": "images/sec %s %s training" % (label, prec), "value": round(args.batch * world * args.steps / el, 2),
                           "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

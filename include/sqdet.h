@@ -93,8 +93,9 @@ int sqdet_conv2d_add_nhwc_fwd(const void* x, const void* w_packed, const float* 
 /* The same with the shortcut in a tensor of its own (rows of y_cstride channels, like y), left untouched:
  *   y = relu?(conv2d(x, W) + b + residual)
  * -- the training forward keeps every block input for the backward pass (nn_skeleton.py:329-361 differentiates through
- * resnet50_convDet.py:55), so the sum must not overwrite the shortcut.  1x1 convs read the residual tile in their epilogue
- * (conv1x1_pipe); other shapes copy it into y first. */
+ * resnet50_convDet.py:55), so the sum must not overwrite the shortcut.  Only channels [y_coffset, y_coffset+cout) of y are
+ * written, and only the same channels of residual are read; the rest of both rows stays as it was.  1x1 convs read the
+ * residual tile in their epilogue (conv1x1_pipe); other shapes copy that channel slice into y first. */
 int sqdet_conv2d_res_nhwc_fwd(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
                               int n, int h, int w, int cin, int cout, int k, int stride, int pad_mode, int relu,
                               int dtype, int y_cstride, int y_coffset, sqdet_stream_t stream);

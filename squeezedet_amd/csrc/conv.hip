@@ -316,7 +316,8 @@ int conv2d_launch_masked(const void* x, const void* w_packed, const float* bias,
                            x_coffset, accum, relu_of, nullptr, st);
 }
 
-// res != NULL (with accum): y = conv(x) + res instead of y += conv(x); res has y's layout (whole rows of y_cstride channels)
+// res != NULL (with accum): y = conv(x) + res instead of y += conv(x); res has y's layout (rows of y_cstride channels), and only
+// its channels [y_coffset, y_coffset+cout) are read
 int conv2d_launch_res(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
                       int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
                       int x_cstride, int x_coffset, int accum, const void* relu_of, const void* res, hipStream_t st) {
@@ -362,7 +363,14 @@ int conv2d_launch_res(const void* x, const void* w_packed, const float* bias, vo
       rc = conv1x1_tile_launch(a, g, dtype, st, &handled);
       if (rc != SQDET_OK || handled) return rc;
     }
-    SQDET_CHECK_HIP(hipMemcpyAsync(y, a.res, (size_t)P * y_cstride * dtype_size(dtype), hipMemcpyDeviceToDevice, st));
+    // only y's channels [y_coffset, y_coffset+cout) take the residual: the rest of a wider row is another tensor's (a concat)
+    const size_t esz = dtype_size(dtype);
+    if (y_cstride == cout && y_coffset == 0)
+      SQDET_CHECK_HIP(hipMemcpyAsync(y, a.res, (size_t)P * y_cstride * esz, hipMemcpyDeviceToDevice, st));
+    else
+      SQDET_CHECK_HIP(hipMemcpy2DAsync(static_cast<char*>(y) + y_coffset * esz, y_cstride * esz,
+                                       static_cast<const char*>(a.res) + y_coffset * esz, y_cstride * esz, cout * esz, (size_t)P,
+                                       hipMemcpyDeviceToDevice, st));
     a.res = nullptr;
   }
   if (plain || !g.gather) {   // (the tile kernels also take channel-sliced inputs, no bias and y += : the backward-data convs)

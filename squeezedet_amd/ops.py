@@ -70,7 +70,8 @@ def conv2d_nhwc(x, packed, bias, stride=1, padding="SAME", relu=True, out=None, 
     is a [N,Ho,Wo,Ctot] tensor whose channels [out_coffset, out_coffset+Cout) are written
     (fire-module concat without a concat pass).  accumulate=True: out = relu?(conv + b + out), the
     residual add of a ResNet bottleneck (resnet50_convDet.py:55) done in the conv epilogue;
-    residual=<tensor shaped like out>: out = relu?(conv + b + residual), the shortcut left untouched."""
+    residual=<tensor shaped like out>: out = relu?(conv + b + residual), the shortcut left untouched.  Every form writes
+    only channels [out_coffset, out_coffset+Cout) of ``out``; the residual's other channels are not read."""
     if residual is not None:
         n, h, w, cin = [int(v) for v in x.shape]
         ho, wo = _out_size(h, packed.k, stride, padding), _out_size(w, packed.k, stride, padding)

@@ -572,6 +572,20 @@ int sqdet_build_labels(const double* anchors_f64, const double* gt_boxes_f64, co
 int sqdet_preprocess_bgr(const uint8_t* src_bgr_u8, void* dst, int n, int src_h, int src_w, int dst_h, int dst_w,
                          float mean_b, float mean_g, float mean_r, int dtype, sqdet_stream_t stream);
 
+/* Training-time image preparation of imdb.read_batch (dataset/imdb.py:141-186), the reference's order: per image i
+ *   im = float32(u8) - BGR_MEANS      (the means in double: (float)((double)v - mean), rounded once, as NumPy's
+ *                                      `im -= mc.BGR_MEANS` with a float64 BGR_MEANS)
+ *   D[y, x] = im[y + dy, x + dx] inside im, 0.0f outside, D is (src_h - dy) x (src_w - dx)   (the drift)
+ *   flip: D[y, x] = D[y, W' - 1 - x]  (W' = src_w - dx)
+ *   dst[i] = cv2.resize(D, (dst_w, dst_h))   (INTER_LINEAR, float32, coordinates as sqdet_preprocess_bgr)
+ * src: device uint8, src_bytes long; image i is a BGR [src_h, src_w, 3] array at byte src_offsets[i] (device int64 [n]);
+ * geom: device int32 [n,5] = (src_h, src_w, dx, dy, flip) per image; dst [n,dst_h,dst_w,3] in dtype storage.
+ * geom and src_offsets are on the device, so THIS CALL CANNOT VALIDATE THEM: the caller must reject (before the call)
+ * dx >= src_w, dy >= src_h, |dx| or |dy| > 65535, flip not 0/1 and an image that ends past src_bytes (ops.augment_bgr
+ * does).  An image that breaks these rules anyway is left unwritten; no load ever leaves [src, src + src_bytes). */
+int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom, void* dst, int n,
+                      int dst_h, int dst_w, double mean_b, double mean_g, double mean_r, int dtype, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------ utilities --
  * Device -> pinned-host copy issued as a KERNEL: dst is host memory mapped into the device's address space
  * (hipHostMalloc); nbytes a multiple of 16.  Used by the serving loop to hand the <= 64 filtered rows per image

@@ -4,6 +4,7 @@ interpret_output, filter_prediction, and the training step) as hand-written HIP 
 from .config import (base_model_config, kitti_res50_config, kitti_res50_config_for_input,  # noqa: F401
                      kitti_squeezeDet_config, kitti_squeezeDet_config_for_input, kitti_squeezeDetPlus_config,
                      kitti_vgg16_config, kitti_vgg16_config_for_input)
+from .imdb import Batch, BatchReader  # noqa: F401  (NumPy only at import; the GPU half is used lazily)
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch / a GPU

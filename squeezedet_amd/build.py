@@ -46,6 +46,7 @@ SOURCES = [
     ("pool.hip", []),
     ("bn.hip", ["-ffp-contract=off"]),
     ("preproc.hip", ["-ffp-contract=off"]),
+    ("augment.hip", ["-ffp-contract=off"]),
     ("labels.hip", ["-ffp-contract=off"]),
     ("postproc.hip", ["-ffp-contract=off"]),
     ("filter_fast.hip", ["-ffp-contract=off"]),

@@ -1,0 +1,148 @@
+// Training-time image preparation of the reference's batch reader (src/dataset/imdb.py:141-186) on the GPU: per image
+//   im = imread(f).astype(float32);  im -= mc.BGR_MEANS            (float64 means: (float)((double)v - mean), rounded once)
+//   drift by (dx, dy): D[i, j] = im[i + dy, j + dx] inside im, 0.0 outside, D is (H - dy) x (W - dx)
+//   flip: D[i, j] = D[i, W' - 1 - j]
+//   out = cv2.resize(D, (dst_w, dst_h))                              (INTER_LINEAR, float32, coordinates as preproc.hip)
+// -> one launch for a batch of images of different sizes, each at its own byte offset of one flat uint8 buffer.
+//
+// Unlike sqdet_preprocess_bgr (demo.py's order: resize, then subtract the mean) the mean is subtracted BEFORE the
+// interpolation, so the kernel interpolates the float32 mean-subtracted values and the zero padding stays exactly 0.0f.
+// Built with -ffp-contract=off: the same float32 operations in the same order as the CPU restatement.
+#include "common.h"
+
+namespace sqdet {
+
+// Same layout as preprocess_kernel: one 64-thread workgroup = 256 consecutive pixels of one destination row (4 per thread);
+// the image's geometry, its two source rows and the vertical weight are workgroup-uniform; a source pixel pair is one
+// unaligned 8-byte load (reversed when mirrored) wherever both pixels lie inside the image.
+constexpr int APX = 4;   // destination pixels per thread
+
+struct AugGeom {
+  int h, w, dx, dy, flip;
+};
+
+// float32 value of channel c of the pixel whose 3 bytes start at bit 24*k of q, mean-subtracted in double
+__device__ __forceinline__ float sub_mean(unsigned long long q, int k, int c, double mean) {
+  return (float)((double)(unsigned)((q >> (24 * k + 8 * c)) & 255) - mean);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __restrict__ src, size_t src_bytes,
+                                                     const int64_t* __restrict__ offsets, const int32_t* __restrict__ geom,
+                                                     T* __restrict__ dst, int Hd, int Wd, double m0, double m1, double m2) {
+  const int row = blockIdx.y;                     // n * Hd + y
+  const int n = row / Hd, y = row - n * Hd;
+  const AugGeom g{geom[5 * n], geom[5 * n + 1], geom[5 * n + 2], geom[5 * n + 3], geom[5 * n + 4]};
+  const int64_t off = offsets[n];
+  // the host wrapper rejects all of these before the launch; an image that gets here anyway is left unwritten
+  if (g.h <= 0 || g.w <= 0 || g.dx >= g.w || g.dy >= g.h || g.dx < -65535 || g.dx > 65535 || g.dy < -65535 ||
+      g.dy > 65535 || (g.flip & ~1) || off < 0 || (size_t)off > src_bytes ||
+      (size_t)g.h * g.w * 3 > src_bytes - (size_t)off)
+    return;
+  const int Hs = g.h - g.dy, Ws = g.w - g.dx;     // the drifted image D
+  const double scale_x = (double)Ws / (double)Wd, scale_y = (double)Hs / (double)Hd;
+  float fy = (float)((y + 0.5) * scale_y - 0.5);
+  int sy = (int)floorf(fy);
+  fy -= sy;
+  if (sy < 0) { sy = 0; fy = 0.f; }
+  if (sy >= Hs - 1) { sy = Hs - 1; fy = 0.f; }
+  const int sy1 = sy + 1 < Hs ? sy + 1 : sy;
+  const int oy0 = sy + g.dy, oy1 = sy1 + g.dy;    // rows of the original image (outside [0, h): zero padding)
+  const bool r0 = oy0 >= 0 && oy0 < g.h, r1 = oy1 >= 0 && oy1 < g.h;
+  const size_t o0 = (size_t)off + (size_t)(r0 ? oy0 : 0) * g.w * 3, o1 = (size_t)off + (size_t)(r1 ? oy1 : 0) * g.w * 3;
+  const float ay0 = 1.f - fy;
+  const double mean[3] = {m0, m1, m2};
+  const int x0 = (blockIdx.x * 64 + threadIdx.x) * APX;
+  if (x0 >= Wd) return;
+  float out[APX * 3];
+#pragma unroll
+  for (int p = 0; p < APX; ++p) {
+    const int x = x0 + p < Wd ? x0 + p : Wd - 1;
+    float fx = (float)((x + 0.5) * scale_x - 0.5);
+    int sx = (int)floorf(fx);
+    fx -= sx;
+    if (sx < 0) { sx = 0; fx = 0.f; }
+    if (sx >= Ws - 1) { sx = Ws - 1; fx = 0.f; }
+    const int sx1 = sx + 1 < Ws ? sx + 1 : sx;
+    const float ax0 = 1.f - fx;
+    // original columns of D's columns sx and sx1 (mirrored: W' - 1 - column)
+    const int ox = (g.flip ? Ws - 1 - sx : sx) + g.dx, ox1 = (g.flip ? Ws - 1 - sx1 : sx1) + g.dx;
+    const bool c0 = ox >= 0 && ox < g.w, c1 = ox1 >= 0 && ox1 < g.w;
+    // q*: pixel sx in bytes [0, 3), pixel sx1 in bytes [3, 6); ok*: which of the four values are inside the image
+    unsigned long long q0 = 0, q1 = 0;
+    bool ok00 = r0 && c0, ok01 = r0 && c1, ok10 = r1 && c0, ok11 = r1 && c1;
+    const int lo = ox < ox1 ? ox : ox1;           // the pair's left original column (ox1 = ox -+ 1 off the last column)
+    const size_t b0 = o0 + (size_t)lo * 3, b1 = o1 + (size_t)lo * 3;
+    if (sx1 != sx && ok00 && ok01 && ok10 && ok11 && b0 + 8 <= src_bytes && b1 + 8 <= src_bytes) {
+      q0 = *reinterpret_cast<const unsigned long long*>(src + b0);
+      q1 = *reinterpret_cast<const unsigned long long*>(src + b1);
+      if (g.flip) {                                // the pair arrives as (ox - 1, ox): swap the two pixels
+        q0 = ((q0 >> 24) & 0xffffffull) | ((q0 & 0xffffffull) << 24);
+        q1 = ((q1 >> 24) & 0xffffffull) | ((q1 & 0xffffffull) << 24);
+      }
+    } else {                                       // padding, the last column, or the end of the buffer: byte loads
+      const size_t a00 = o0 + (size_t)(c0 ? ox : 0) * 3, a01 = o0 + (size_t)(c1 ? ox1 : 0) * 3;
+      const size_t a10 = o1 + (size_t)(c0 ? ox : 0) * 3, a11 = o1 + (size_t)(c1 ? ox1 : 0) * 3;
+      ok00 = ok00 && a00 + 3 <= src_bytes;
+      ok01 = ok01 && a01 + 3 <= src_bytes;
+      ok10 = ok10 && a10 + 3 <= src_bytes;
+      ok11 = ok11 && a11 + 3 <= src_bytes;
+      for (int k = 0; k < 3; ++k) {
+        if (ok00) q0 |= (unsigned long long)src[a00 + k] << (8 * k);
+        if (ok01) q0 |= (unsigned long long)src[a01 + k] << (8 * (k + 3));
+        if (ok10) q1 |= (unsigned long long)src[a10 + k] << (8 * k);
+        if (ok11) q1 |= (unsigned long long)src[a11 + k] << (8 * (k + 3));
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float s00 = ok00 ? sub_mean(q0, 0, c, mean[c]) : 0.f, s01 = ok01 ? sub_mean(q0, 1, c, mean[c]) : 0.f;
+      const float s10 = ok10 ? sub_mean(q1, 0, c, mean[c]) : 0.f, s11 = ok11 ? sub_mean(q1, 1, c, mean[c]) : 0.f;
+      const float h0 = s00 * ax0 + s01 * fx;
+      const float h1 = s10 * ax0 + s11 * fx;
+      out[p * 3 + c] = h0 * ay0 + h1 * fy;
+    }
+  }
+  T* d = dst + ((size_t)row * Wd + x0) * 3;
+  if (x0 + APX <= Wd && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+    if constexpr (sizeof(T) == 2) {
+      typedef f16 h4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        reinterpret_cast<h4*>(d)[k] = h4{(f16)out[4 * k], (f16)out[4 * k + 1], (f16)out[4 * k + 2], (f16)out[4 * k + 3]};
+    } else {
+      typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+      for (int k = 0; k < 6; ++k) reinterpret_cast<f2*>(d)[k] = f2{out[2 * k], out[2 * k + 1]};
+    }
+  } else if (sizeof(T) == 2 && x0 + APX <= Wd && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+    typedef f16 h2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int k = 0; k < 6; ++k) reinterpret_cast<h2*>(d)[k] = h2{(f16)out[2 * k], (f16)out[2 * k + 1]};
+  } else {
+    for (int p = 0; p < APX && x0 + p < Wd; ++p)
+      for (int c = 0; c < 3; ++c) d[p * 3 + c] = (T)out[p * 3 + c];
+  }
+}
+
+}  // namespace sqdet
+
+extern "C" int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
+                                 void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g, double mean_r,
+                                 int dtype, sqdet_stream_t stream) {
+  using namespace sqdet;
+  SQDET_REQUIRE(src && src_offsets && geom && dst, "augment_bgr: null pointer");
+  SQDET_REQUIRE(n > 0 && dst_h > 0 && dst_w > 0 && src_bytes > 0, "augment_bgr: bad dims");
+  SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "augment_bgr: bad dtype %d", dtype);
+  SQDET_REQUIRE((long)n * dst_h <= 0x7fffffffL / 4, "augment_bgr: too many rows");
+  const dim3 grid((unsigned)((dst_w + 64 * APX - 1) / (64 * APX)), (unsigned)(n * dst_h));
+  SQDET_REQUIRE(grid.y <= 65535u * 1024u, "augment_bgr: too many rows");
+  if (dtype == SQDET_F16)
+    hipLaunchKernelGGL(augment_kernel<f16>, grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets, geom,
+                       (f16*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
+  else
+    hipLaunchKernelGGL(augment_kernel<float>, grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets, geom,
+                       (float*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
+  SQDET_CHECK_HIP(hipGetLastError());
+  return SQDET_OK;
+}

@@ -877,6 +877,53 @@ def preprocess_bgr(images_u8, dst_h, dst_w, bgr_means, dtype=torch.float32):
     return out
 
 
+AUGMENT_MAX_DRIFT = 65535
+
+
+def check_augment_geometry(geom, offsets, src_bytes):
+    """Host-side validation of sqdet_augment_bgr's per-image geometry (the kernel reads it from the device and cannot
+    reject it): geom int [n,5] = (src_h, src_w, dx, dy, flip), offsets int [n] byte offsets into a buffer of src_bytes.
+    Returns (geom int32, offsets int64) as contiguous NumPy arrays; raises SqdetError on any bad row."""
+    g = np.ascontiguousarray(np.asarray(geom).reshape(-1, 5), dtype=np.int64)
+    o = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
+    if len(g) == 0 or len(o) != len(g):
+        raise _lib.SqdetError("augment_bgr: %d geometry rows for %d offsets" % (len(g), len(o)))
+    h, w, dx, dy, flip = g.T
+    bad = ((h <= 0) | (w <= 0) | (dx >= w) | (dy >= h) | (np.abs(dx) > AUGMENT_MAX_DRIFT) | (np.abs(dy) > AUGMENT_MAX_DRIFT)
+           | ((flip != 0) & (flip != 1)) | (o < 0) | (o + h * w * 3 > int(src_bytes)))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise _lib.SqdetError("augment_bgr: image %d has bad geometry (src_h, src_w, dx, dy, flip) = %s at byte offset %d of %d"
+                              % (i, tuple(int(v) for v in g[i]), int(o[i]), int(src_bytes)))
+    return g.astype(np.int32), o
+
+
+def augment_bgr(src_u8, offsets, geom, dst_h, dst_w, bgr_means, dtype=torch.float32, out=None):
+    """imdb.read_batch's image path (dataset/imdb.py:141-186) for a batch: uint8 BGR images at byte `offsets` of the flat
+    device buffer `src_u8`, each with its own (src_h, src_w, dx, dy, flip) row of the host array `geom` -> mean-subtracted
+    (float64 means, rounded once), drifted (zero padding), mirrored, resized (cv2 INTER_LINEAR) NHWC network input
+    [n, dst_h, dst_w, 3] in `dtype` (written into `out` when given).  The geometry is checked on the host before anything is
+    uploaded or launched; a rejected call raises and leaves `out` untouched."""
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
+        raise _lib.SqdetError("augment_bgr: src must be a uint8 tensor")
+    src_bytes = int(src_u8.numel())
+    g, o = check_augment_geometry(geom, offsets, src_bytes)
+    n, dst_h, dst_w = len(g), int(dst_h), int(dst_w)
+    if dst_h <= 0 or dst_w <= 0:
+        raise _lib.SqdetError("augment_bgr: bad output size %dx%d" % (dst_h, dst_w))
+    dev = src_u8.device
+    if out is None:
+        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
+    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
+        raise _lib.SqdetError("augment_bgr: out must be %s [%d,%d,%d,3], got %s %s" % (dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
+    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
+    gd = torch.from_numpy(g).to(dev, non_blocking=True)
+    od = torch.from_numpy(o).to(dev, non_blocking=True)
+    check(lib().sqdet_augment_bgr(_dev(src_u8, "src"), src_bytes, _dev(od, "offsets"), _dev(gd, "geom"), _dev(out, "out"), n,
+                                  dst_h, dst_w, m[0], m[1], m[2], dtype_code(dtype), stream_ptr()), "sqdet_augment_bgr")
+    return out
+
+
 def box_calibration(device, mfma_iters=8192, copy_mib=1024, reps=3):
     """Two fixed microkernels timed with events on the current stream (sqdet_calib_mfma / sqdet_calib_copy): what THIS box
     sustains on a bare MFMA loop (TFLOP/s, float16 16x16x32) and on a plain device copy far larger than the Infinity Cache

@@ -32,6 +32,24 @@ def synthetic_ground_truth(mc, batch, seed, max_objects=8):
     return gt, cls, cnt
 
 
+KITTI_SIZES = [(370, 1224), (374, 1238), (376, 1241), (375, 1242)]
+
+
+def synthetic_dataset(mc, n, seed, max_objects=8):
+    """n seeded uint8 BGR images of the four KITTI sizes and their rois ([cx, cy, w, h, cls] in original pixels, boxes inside
+    the image, as dataset/kitti.py stores them), for --augment."""
+    rs = np.random.RandomState(seed)
+    images, rois = [], []
+    for i in range(n):
+        h, w = KITTI_SIZES[i % 4]
+        images.append(rs.randint(0, 256, size=(h, w, 3)).astype(np.uint8))
+        k = rs.randint(1, max_objects + 1)
+        bw, bh = rs.uniform(20, 300, k), rs.uniform(20, 200, k)
+        x0, y0 = rs.uniform(0, w - bw - 1), rs.uniform(0, h - bh - 1)
+        rois.append([[x0[j] + bw[j] / 2, y0[j] + bh[j] / 2, bw[j], bh[j], int(rs.randint(mc.CLASSES))] for j in range(k)])
+    return images, rois
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -44,6 +62,9 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="f32 = the reference's training dtype; f16 = mixed precision (float16 activations / activation gradients, "
                          "float32 master weights, weight gradients and optimizer, dynamic loss scale) -- configs[4] is resnet50 + f16")
+    ap.add_argument("--augment", action="store_true",
+                    help="read every batch inside the timed step through a resident BatchReader (the reference's drift / flip "
+                         "augmentation, imdb.read_batch) from synthetic uint8 images of the four KITTI sizes, rois in original pixels")
     args = ap.parse_args()
     if args.batch <= 0:
         args.batch = {"squeezeDet": 20, "resnet50": 8, "vgg16": 5}[args.arch]
@@ -74,6 +95,14 @@ def main():
     gt, gcls, gcnt = [torch.from_numpy(a).to(dev) for a in synthetic_ground_truth(mc, args.batch, seed=200 + rank)]
     nobj = float(gcnt.sum().item())      # known to the host: no per-step device -> host sync for sum(input_mask)
     one_step = lambda: tr.step(x, *ops.build_labels(anchors, gt, gcls, gcnt, mc.CLASSES)[:4], num_objects=nobj)
+    if args.augment:
+        reader = S.BatchReader(mc, *synthetic_dataset(mc, 2 * args.batch, seed=300 + rank), seed=rank, device=dev,
+                               dtype=model.dtype, resident=True)
+
+        def one_step():
+            b = reader.read_batch()
+            return tr.step(b.image_input, *ops.build_labels(anchors, b.gt_boxes, b.gt_classes, b.gt_counts, mc.CLASSES)[:4],
+                           num_objects=float(sum(len(l) for l in b.label_per_batch)))
     for _ in range(args.warmup):
         out = one_step()
     torch.cuda.synchronize()
@@ -98,7 +127,8 @@ def main():
         print(json.dumps({"metric": "images/sec %s %s training" % (label, prec), "value": round(args.batch * world * args.steps / el, 2),
                           "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(el / args.steps * 1e3, 3),
-                          "host_issue_ms_per_step": round(t_issued / args.steps * 1e3, 3), "dtype": args.dtype, "data": "synthetic",
+                          "host_issue_ms_per_step": round(t_issued / args.steps * 1e3, 3), "dtype": args.dtype,
+                          "data": "synthetic uint8 + BatchReader drift/flip" if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
                           "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,

@@ -1,0 +1,215 @@
+#!/usr/bin/env python
+"""Evaluates SqueezeDet checkpoints on KITTI (the reference's src/eval.py) in batches, scored on the GPU.
+
+    python eval.py --data_path KITTI --image_set val --checkpoint_path ckpt/model-20000.npz --run_once [--net squeezeDet]
+
+The reference's order per image: det_boxes rescaled to the original image size (float32, eval.py:83-84), then
+filter_prediction, then the rows added to the detection table -- here a whole batch at a time on the device
+(filter_prediction_batch, squeezedet_amd.kitti_ap.KittiEvaluator).  The table is scored by the GPU KITTI evaluator
+(or, with --eval_tool, by an external evaluate_object binary through kitti_eval.evaluate_detections).  Outputs under
+--eval_dir: detection_files_<step>/data/*.txt, the evaluator's stats_<cls>_{ap,detection}.txt, error_analysis/
+det_error_file.txt, and one JSON line per checkpoint in eval_log.jsonl (in place of TF summaries).
+
+Checkpoints are .npz files from squeezedet_amd.weights.save_params.  --run_once: --checkpoint_path is that file;
+otherwise it is a directory polled every --eval_interval_secs for the newest '*-<step>.npz'.  Every image is scored
+once (the last batch is padded; the reference's reader wraps around instead).
+"""
+import argparse
+import glob
+import json
+import os
+import time
+
+import numpy as np
+
+NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dataset", default="KITTI", help="only KITTI is supported")
+    ap.add_argument("--data_path", default="", help="root directory of the KITTI data")
+    ap.add_argument("--image_set", default="test", help="ImageSets/<image_set>.txt")
+    ap.add_argument("--eval_dir", default="/tmp/squeezeDet/eval", help="where results are written")
+    ap.add_argument("--checkpoint_path", default="/tmp/squeezeDet/train", help="a .npz file (--run_once) or a directory")
+    ap.add_argument("--eval_interval_secs", type=int, default=60, help="how often to look for a new checkpoint")
+    ap.add_argument("--run_once", action="store_true", help="evaluate --checkpoint_path once and exit")
+    ap.add_argument("--net", default="squeezeDet", choices=NETS)
+    ap.add_argument("--gpu", default="0", help="gpu id")
+    ap.add_argument("--batch_size", type=int, default=0, help="images per forward pass (default: the config's)")
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16"], help="storage type of the forward pass")
+    ap.add_argument("--eval_tool", default="", help="score with this evaluate_object binary instead of the GPU evaluator")
+    ap.add_argument("--synthetic_weights", action="store_true", help="seeded synthetic weights instead of a checkpoint")
+    return ap.parse_args(argv)
+
+
+def make_model(net, gpu, dtype, batch_size=0):
+    import torch
+    import squeezedet_amd as S
+    from squeezedet_amd import nets
+    cfg, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
+                "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[net]
+    mc = cfg()
+    if batch_size:
+        mc.BATCH_SIZE = int(batch_size)
+    mc.LOAD_PRETRAINED_MODEL = False
+    return mc, cls(mc, gpu, dtype=torch.float16 if dtype == "fp16" else torch.float32)
+
+
+def read_image(path, model):
+    """PIL -> BGR uint8 (what cv2.imread returns) -> ops.preprocess_bgr: network input [1,H,W,3] and (x_scale, y_scale)
+    = network size / original size (imdb.read_image_batch)."""
+    import torch
+    from PIL import Image
+    from squeezedet_amd import ops
+    mc = model.mc
+    rgb = np.asarray(Image.open(path).convert("RGB"))
+    bgr = torch.from_numpy(np.ascontiguousarray(rgb[:, :, ::-1])).to(model.device)
+    orig_h, orig_w = float(rgb.shape[0]), float(rgb.shape[1])
+    x = ops.preprocess_bgr(bgr[None], mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, model.dtype)
+    return x, (mc.IMAGE_WIDTH / orig_w, mc.IMAGE_HEIGHT / orig_h)
+
+
+def detect_batch(model, paths):
+    """Images of `paths` into one batch tensor of mc.BATCH_SIZE (padded with the last image) -> det_boxes, det_probs,
+    det_class (device, BATCH_SIZE rows) and the real images' scales."""
+    import torch
+    mc = model.mc
+    batch = torch.empty((mc.BATCH_SIZE, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, 3), dtype=model.dtype, device=model.device)
+    scales = []
+    for j, p in enumerate(paths):
+        batch[j:j + 1], s = read_image(p, model)
+        scales.append(s)
+    if len(paths) < mc.BATCH_SIZE:
+        batch[len(paths):] = batch[len(paths) - 1:len(paths)]
+    return model.detect(batch) + (scales,)
+
+
+def rescale_boxes(det_boxes, scales):
+    """det_boxes[j, :, 0::2] /= scales[j][0]; det_boxes[j, :, 1::2] /= scales[j][1] (eval.py:83-84) on the device, float32
+    divided by the float32 scale as NumPy does."""
+    import torch
+    n = len(scales)
+    s = torch.tensor(np.tile(np.asarray(scales, np.float32).reshape(n, 1, 2), (1, 1, 2)), device=det_boxes.device)  # x, y, x, y
+    return det_boxes[:n] / s
+
+
+def eval_once(a, model, data, ckpt_path, evaluator):
+    import torch
+    from squeezedet_amd import kitti_eval, weights, synthetic
+    mc = model.mc
+    if a.synthetic_weights:
+        model.load_params(synthetic.synthetic_params(model, seed=0))
+        global_step = "0"
+    else:
+        from squeezedet_amd.kitti_ap import parse_checkpoint_step
+        model.load_params(weights.load_params(ckpt_path))
+        global_step = parse_checkpoint_step(ckpt_path)
+    n = len(data.image_idx)
+    evaluator.reset()
+    t_detect = t_misc = 0.0
+    counts = []
+    for i0 in range(0, n, mc.BATCH_SIZE):
+        paths = data.image_paths[i0:i0 + mc.BATCH_SIZE]
+        t0 = time.time()
+        det_boxes, det_probs, det_class, scales = detect_batch(model, paths)
+        torch.cuda.synchronize(model.device)
+        t1 = time.time()
+        k = len(paths)
+        boxes = rescale_boxes(det_boxes, scales)
+        ob, op, oc, oi, cnt = model.filter_prediction_batch(boxes, det_probs[:k].contiguous(), det_class[:k].contiguous())
+        evaluator.add_rows(ob, op, oc, cnt, i0)
+        counts.append(cnt)
+        torch.cuda.synchronize(model.device)
+        t2 = time.time()
+        t_detect += t1 - t0
+        t_misc += t2 - t1
+        print("im_detect: {:d}/{:d} detect: {:.3f}s misc: {:.3f}s".format(i0 + k, n, t_detect / (i0 // mc.BATCH_SIZE + 1),
+                                                                         t_misc / (i0 // mc.BATCH_SIZE + 1)))
+    num_detection = int(torch.cat(counts).clamp(min=0).sum().item())
+    nb = max(1, (n + mc.BATCH_SIZE - 1) // mc.BATCH_SIZE)
+
+    print("Evaluating detections...")
+    t0 = time.time()
+    result_dir = os.path.join(a.eval_dir, "detection_files_{:s}".format(global_step))
+    det_file_dir = os.path.join(result_dir, "data")
+    evaluator.write_detection_files(det_file_dir, data.image_idx)
+    if a.eval_tool:
+        all_boxes = kitti_eval.new_all_boxes(len(mc.CLASS_NAMES), n)
+        for i, rows in enumerate(evaluator.tables()):
+            for c, x1, y1, x2, y2, s in rows:
+                all_boxes[c][i].append([x1, y1, x2, y2, s])
+        aps, ap_names = kitti_eval.evaluate_detections(a.eval_tool, a.data_path, a.image_set, a.eval_dir, global_step,
+                                                       data.image_idx, mc.CLASS_NAMES, all_boxes)
+    else:
+        aps, ap_names, _ = evaluator.evaluate()
+        evaluator.write_stats(result_dir)
+    t_eval = time.time() - t0
+
+    print("Evaluation summary:")
+    print("  Average number of detections per image: {}:".format(num_detection / float(n)))
+    print("  Timing:")
+    print("    detect: {:.3f}s misc: {:.3f}s eval: {:.3f}s".format(t_detect / nb, t_misc / nb, t_eval))
+    print("  Average precisions:")
+    for cls, ap in zip(ap_names, aps):
+        print("    {}: {:.3f}".format(cls, ap))
+    print("    Mean average precision: {:.3f}".format(np.mean(aps)))
+
+    print("Analyzing detections...")
+    stats = evaluator.analyze()
+    evaluator.write_error_file(os.path.join(result_dir, "error_analysis", "det_error_file.txt"), data.image_idx)
+    print("Detection Analysis:")
+    print("    Number of detections: {}".format(stats["num of detections"]))
+    print("    Number of objects: {}".format(stats["num of objects"]))
+    print("    Percentage of correct detections: {}".format(stats["% correct detections"]))
+    print("    Percentage of localization error: {}".format(stats["% localization error"]))
+    print("    Percentage of classification error: {}".format(stats["% classification error"]))
+    print("    Percentage of background error: {}".format(stats["% background error"]))
+    print("    Percentage of repeated detections: {}".format(stats["% repeated error"]))
+    print("    Recall: {}".format(stats["% recall"]))
+
+    rec = {"global_step": global_step, "checkpoint": ckpt_path, "mAP": float(np.mean(aps)),
+           "APs": dict(zip(ap_names, [float(v) for v in aps])), "num_det_per_image": num_detection / float(n),
+           "timing": {"im_detect": t_detect / nb, "post_proc": t_misc / nb, "eval": t_eval}, "analysis": stats}
+    with open(os.path.join(a.eval_dir, "eval_log.jsonl"), "a") as f:
+        f.write(json.dumps(rec) + "\n")
+    return rec
+
+
+def latest_checkpoint(directory):
+    """The newest '*-<step>.npz' in directory (largest step), or None."""
+    from squeezedet_amd.kitti_ap import parse_checkpoint_step
+    best = None
+    for p in glob.glob(os.path.join(directory, "*-*.npz")):
+        step = parse_checkpoint_step(p)
+        if step.isdigit() and (best is None or int(step) > best[0]):
+            best = (int(step), p)
+    return best[1] if best else None
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    assert a.dataset == "KITTI", "Currently only supports KITTI dataset"
+    from squeezedet_amd.kitti_ap import KittiEvaluator, load_kitti
+    mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size)
+    data = load_kitti(a.data_path, a.image_set, mc)
+    evaluator = KittiEvaluator(mc, data.gt, model.device)
+    os.makedirs(a.eval_dir, exist_ok=True)
+    if a.run_once:
+        return eval_once(a, model, data, a.checkpoint_path, evaluator)
+    seen = set()
+    while True:
+        ckpt = latest_checkpoint(a.checkpoint_path)
+        if ckpt is None:
+            print("No checkpoint file found")
+        elif ckpt not in seen:
+            seen.add(ckpt)
+            print("Evaluating {}...".format(ckpt))
+            eval_once(a, model, data, ckpt, evaluator)
+            continue
+        print("Wait {:d}s for new checkpoints to be saved ... ".format(a.eval_interval_secs))
+        time.sleep(a.eval_interval_secs)
+
+
+if __name__ == "__main__":
+    main()

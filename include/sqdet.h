@@ -586,6 +586,55 @@ int sqdet_preprocess_bgr(const uint8_t* src_bgr_u8, void* dst, int n, int src_h,
 int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom, void* dst, int n,
                       int dst_h, int dst_w, double mean_b, double mean_g, double mean_r, int dtype, sqdet_stream_t stream);
 
+/* ------------------------------------------------------- KITTI evaluation --
+ * Replaces the scoring half of src/eval.py (:69-101) -- the detection files of dataset/kitti.py:100-127, the KITTI C++
+ * evaluator's 2D box metric (dataset/kitti-eval/cpp/evaluate_object.cpp) and kitti.analyze_detections (:182-296) -- with
+ * device tables.  All values are double: exactly what the evaluator reads back from the files the reference writes.
+ *
+ * Detection table (caller-owned, device; `cap` <= SQDET_KITTI_MAX_DETECTIONS rows per image, num_images images):
+ *   det_box double [num_images,cap,4] (x1,y1,x2,y2), det_score double [num_images,cap], det_cls int32 [num_images,cap]
+ *   (0 car, 1 pedestrian, 2 cyclist), det_count int32 [num_images] (zero it to reset), status int32 [2] (zero it to reset).
+ * Ground truth (device): image i owns rows [gt_offsets[i], gt_offsets[i+1]) (<= SQDET_KITTI_MAX_GROUNDTRUTH), gt_box double
+ *   [G,4] (x1,y1,x2,y2), gt_truncation double [G], gt_occlusion int32 [G], gt_type int32 [G] (SQDET_KITTI_* type codes). */
+enum { SQDET_KITTI_MAX_DETECTIONS = 512, SQDET_KITTI_MAX_GROUNDTRUTH = 128, SQDET_KITTI_ANALYSIS_COUNTERS = 8 };
+enum { SQDET_KITTI_CAR = 0, SQDET_KITTI_PEDESTRIAN = 1, SQDET_KITTI_CYCLIST = 2, SQDET_KITTI_VAN = 3, SQDET_KITTI_PERSON_SITTING = 4,
+       SQDET_KITTI_DONTCARE = 5, SQDET_KITTI_OTHER = 6 };
+enum { SQDET_KITTI_ERR_LOC = 0, SQDET_KITTI_ERR_CLS = 1, SQDET_KITTI_ERR_BG = 2, SQDET_KITTI_ERR_MISSED = 3 };
+
+/* Appends n images of filter rows (sqdet_filter_prediction layout: boxes float32 [n,max_out,4] cx,cy,w,h, probs float32
+ * [n,max_out], cls int32 [n,max_out], count int32 [n]) as table images [image_offset, image_offset + n).  Per row, in double:
+ * cx,w /= x_scale and cy,h /= y_scale (scales: double [n,2], NULL = 1), bbox_transform, then x1,y1,x2,y2 rounded as '%.2f'
+ * and the score as '%.3f' print them (half-to-even on the exact value), read back as the nearest double.  Rows are stored
+ * class-major, filter order within a class: the order of the files.  The counts live on the device: a count outside
+ * [0, max_out] or a class outside 0..2 makes the WHOLE call write nothing and marks status; sqdet_kitti_evaluate then
+ * returns SQDET_EINVAL.  max_out > cap: SQDET_EUNSUPPORTED.  Asynchronous. */
+int sqdet_kitti_ingest(const float* boxes, const float* probs, const int32_t* cls, const int32_t* count, const double* scales,
+                       int n, int max_out, double* det_box, double* det_score, int32_t* det_cls, int32_t* det_count,
+                       int32_t* status, int image_offset, int num_images, int cap, sqdet_stream_t stream);
+
+/* Scores the table (the evaluator's cleanData / computeStatistics / getThresholds / eval_class, MIN_OVERLAP 0.7/0.5/0.5):
+ * host_precision double [9,41] (row = class * 3 + difficulty: easy, moderate, hard; precision after the running maximum),
+ * host_ap double [9] (mean of precision[0,4,..,40]), host_evaluated int32 [3] (the class was detected at least once: the
+ * evaluator writes its files only then).  workspace: sqdet_kitti_eval_workspace_bytes(num_gt) of device scratch.
+ * SYNCHRONISES `stream` once, at the end; the host outputs are untouched on failure.  An image over the row limits:
+ * SQDET_EUNSUPPORTED; a rejected ingest in the table: SQDET_EINVAL. */
+size_t sqdet_kitti_eval_workspace_bytes(int num_gt);
+int sqdet_kitti_evaluate(const double* det_box, const double* det_score, const int32_t* det_cls, const int32_t* det_count,
+                         const int32_t* status, int num_images, int cap, const int32_t* gt_offsets, const double* gt_box,
+                         const double* gt_truncation, const int32_t* gt_occlusion, const int32_t* gt_type, int num_gt,
+                         void* workspace, double* host_precision, double* host_ap, int32_t* host_evaluated, sqdet_stream_t stream);
+
+/* kitti.analyze_detections on the table: per image the detections by descending score (stable), the first len(rois) of
+ * them matched by batch_iou against the image's ground-truth rois (roi_offsets as gt_offsets; roi_box double [R,4] cx,cy,w,h
+ * as bbox_transform_inv gives them, roi_cls int32 [R]).  counters int32 [SQDET_KITTI_ANALYSIS_COUNTERS + 1]: detections,
+ * objects, correct, localisation, classification, background, repeated, detected objects, then an over-limit flag.
+ * Records of det_error_file.txt: image i writes rec_count[i] rows from row 2 * roi_offsets[i]: rec_type (SQDET_KITTI_ERR_*),
+ * rec_cls, rec_box double [.,4] (cx,cy,w,h), rec_score (-1 for a missed object); capacity 2R rows.  Asynchronous. */
+int sqdet_kitti_analyze(const double* det_box, const double* det_score, const int32_t* det_cls, const int32_t* det_count,
+                        int num_images, int cap, const int32_t* roi_offsets, const double* roi_box, const int32_t* roi_cls,
+                        int num_rois, int32_t* counters, int32_t* rec_count, int32_t* rec_type, int32_t* rec_cls,
+                        double* rec_box, double* rec_score, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------ utilities --
  * Device -> pinned-host copy issued as a KERNEL: dst is host memory mapped into the device's address space
  * (hipHostMalloc); nbytes a multiple of 16.  Used by the serving loop to hand the <= 64 filtered rows per image

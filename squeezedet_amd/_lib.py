@@ -118,6 +118,10 @@ SIGNATURES = {
     "sqdet_build_labels": (ci, [vp] * 9 + [ci] * 4 + [vp]),
     "sqdet_preprocess_bgr": (ci, [vp, vp] + [ci] * 5 + [cf, cf, cf, ci, vp]),
     "sqdet_augment_bgr": (ci, [vp, sz, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, vp]),
+    "sqdet_kitti_ingest": (ci, [vp] * 5 + [ci, ci] + [vp] * 5 + [ci, ci, ci, vp]),
+    "sqdet_kitti_eval_workspace_bytes": (sz, [ci]),
+    "sqdet_kitti_evaluate": (ci, [vp] * 5 + [ci, ci] + [vp] * 5 + [ci] + [vp] * 4 + [vp]),
+    "sqdet_kitti_analyze": (ci, [vp] * 4 + [ci, ci] + [vp] * 3 + [ci] + [vp] * 6 + [vp]),
     "sqdet_copy_to_mapped_host": (ci, [vp, vp, sz, vp]),
     "sqdet_probe_mfma_layout": (ci, [C.POINTER(C.c_int32), ci]),
     "sqdet_calib_mfma": (ci, [vp, sz, ci, C.POINTER(cd), vp]),

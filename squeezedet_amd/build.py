@@ -50,6 +50,8 @@ SOURCES = [
     ("labels.hip", ["-ffp-contract=off"]),
     ("postproc.hip", ["-ffp-contract=off"]),
     ("filter_fast.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: overlaps, recall steps and the '%.2f' / '%.3f' rounding are bitwise those of the host programs)
+    ("kitti_eval.hip", ["-ffp-contract=off"]),
     ("train.hip", ["-ffp-contract=off"]),
     ("wgrad.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     # (the calibration loops: hipcc's default AGPR form ROTATES the 16x16x32 loop's accumulators -- a[24:27] = mfma(.., a[22:25]) plus

@@ -635,6 +635,34 @@ int sqdet_kitti_analyze(const double* det_box, const double* det_score, const in
                         int num_rois, int32_t* counters, int32_t* rec_count, int32_t* rec_type, int32_t* rec_cls,
                         double* rec_box, double* rec_score, sqdet_stream_t stream);
 
+/* ------------------------------------------------------ training summaries --
+ * Replaces the per-tensor summary ops of the training graph: tf.summary.histogram of every trainable variable and of its
+ * gradient (nn_skeleton.py:353-358) and _activation_summary (nn_skeleton.py:736-755: histogram, tf.nn.zero_fraction,
+ * reduce_mean, reduce_max, reduce_min of a layer's output) -- for MANY segments of ONE buffer in one call, so a whole flat
+ * parameter or gradient bucket of the trainers is one launch (plus a one-workgroup-per-segment finishing launch).
+ *
+ * base: device, dtype storage (SQDET_F32 / SQDET_F16), base_count elements long; segment s is elements
+ * [offsets[s], offsets[s] + counts[s]) of it (device int64 [n_segments]; any element-aligned start, any count incl. 0 and 1;
+ * nothing outside a segment is read -- the 64-element padding of the flat buckets is not counted).  Every element is widened
+ * to float32 first.  edges: device float32 [n_bins + 1], ascending (1 <= n_bins <= 1024); binning is by float32 comparison
+ * only, so the integer fields equal the counts of np.searchsorted(edges, x, side="right") exactly.
+ * records: device, n_segments records of sqdet_tensor_stats_record_bytes(n_bins) bytes (8-byte aligned):
+ *   int64 count        the segment's element count (-1: the segment does not lie inside [0, base_count) and was not read)
+ *   int64 nonfinite    NaN or +-inf elements
+ *   int64 zeros        elements equal to 0 (-0.0 included): tf.nn.zero_fraction * count
+ *   float min, max     over the finite elements; +inf / -inf when there is none
+ *   double sum, sumsq  over the finite elements, accumulated in float64
+ *   int64 under, hist[n_bins], over    finite x < edges[0]; edges[i] <= x < edges[i+1]; x >= edges[n_bins]
+ * sum and sumsq are reduced in a fixed order (per-workgroup partials in `workspace`, then one ordered pass; no float atomics):
+ * two calls on the same data, device and segment table give bitwise the same records.  workspace:
+ * sqdet_tensor_stats_workspace_bytes(n_segments, n_bins) bytes of device scratch, 8-byte aligned.  The call zeroes what it
+ * accumulates into on `stream`, allocates nothing and does not synchronise. */
+size_t sqdet_tensor_stats_record_bytes(int n_bins);
+size_t sqdet_tensor_stats_workspace_bytes(int n_segments, int n_bins);
+int sqdet_tensor_stats_many(const void* base, int64_t base_count, const int64_t* offsets_dev, const int64_t* counts_dev,
+                            int n_segments, const float* edges_dev, int n_bins, void* records_dev, void* workspace,
+                            int dtype, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------ utilities --
  * Device -> pinned-host copy issued as a KERNEL: dst is host memory mapped into the device's address space
  * (hipHostMalloc); nbytes a multiple of 16.  Used by the serving loop to hand the <= 64 filtered rows per image

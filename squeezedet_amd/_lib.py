@@ -122,6 +122,9 @@ SIGNATURES = {
     "sqdet_kitti_eval_workspace_bytes": (sz, [ci]),
     "sqdet_kitti_evaluate": (ci, [vp] * 5 + [ci, ci] + [vp] * 5 + [ci] + [vp] * 4 + [vp]),
     "sqdet_kitti_analyze": (ci, [vp] * 4 + [ci, ci] + [vp] * 3 + [ci] + [vp] * 6 + [vp]),
+    "sqdet_tensor_stats_record_bytes": (sz, [ci]),
+    "sqdet_tensor_stats_workspace_bytes": (sz, [ci, ci]),
+    "sqdet_tensor_stats_many": (ci, [vp, C.c_int64, vp, vp, ci, vp, ci, vp, vp, ci, vp]),
     "sqdet_copy_to_mapped_host": (ci, [vp, vp, sz, vp]),
     "sqdet_probe_mfma_layout": (ci, [C.POINTER(C.c_int32), ci]),
     "sqdet_calib_mfma": (ci, [vp, sz, ci, C.POINTER(cd), vp]),

@@ -53,6 +53,8 @@ SOURCES = [
     # (-ffp-contract=off: overlaps, recall steps and the '%.2f' / '%.3f' rounding are bitwise those of the host programs)
     ("kitti_eval.hip", ["-ffp-contract=off"]),
     ("train.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: sumsq adds the exact float64 square; nothing to contract, and the sums keep the order written)
+    ("summary.hip", ["-ffp-contract=off"]),
     ("wgrad.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     # (the calibration loops: hipcc's default AGPR form ROTATES the 16x16x32 loop's accumulators -- a[24:27] = mfma(.., a[22:25]) plus
     # v_accvgpr copies inside the loop -- so consecutive MFMAs depend on each other and the "bare MFMA loop" of rounds 3-4 read half

@@ -89,6 +89,25 @@ class BatchReader:
                 self._cur_idx += B
         return batch_idx
 
+    # ---------------------------------------------------------------------------------------------- resumable state --
+    def state_dict(self):
+        """Where the reader stands: the generator's state, the current permutation and its cursor, and the dataset length
+        (checked on load).  A reader built the same way that loads it serves the same batches from here on."""
+        kind, keys, pos, has_gauss, cached = self.rs.get_state()
+        return dict(rs_kind=str(kind), rs_keys=np.asarray(keys, np.uint32).copy(), rs_pos=int(pos), rs_has_gauss=int(has_gauss),
+                    rs_cached_gaussian=float(cached), perm_idx=np.asarray(self._perm_idx, np.int64).copy(),
+                    cur_idx=int(self._cur_idx), num_images=len(self._image_idx))
+
+    def load_state_dict(self, d):
+        if int(d["num_images"]) != len(self._image_idx):
+            raise ValueError("BatchReader: state of a dataset of %d images, this one has %d" % (int(d["num_images"]), len(self._image_idx)))
+        perm = [int(v) for v in np.asarray(d["perm_idx"]).reshape(-1)]
+        if sorted(perm) != list(range(len(self._image_idx))) or not 0 <= int(d["cur_idx"]) <= len(perm) + self.mc.BATCH_SIZE:
+            raise ValueError("BatchReader: the saved permutation or cursor does not fit this dataset")
+        self.rs.set_state((str(d["rs_kind"]), np.asarray(d["rs_keys"], np.uint32), int(d["rs_pos"]), int(d["rs_has_gauss"]),
+                           float(d["rs_cached_gaussian"])))
+        self._perm_idx, self._cur_idx = perm, int(d["cur_idx"])
+
     def next_plan(self, shuffle=True):
         """The host half of read_batch: batch order, random draws and box transform (imdb.py:100-190), in NumPy float64 in
         the reference's order.  Advances the reader; needs no GPU."""

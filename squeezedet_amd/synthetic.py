@@ -47,6 +47,24 @@ def synthetic_params(model, seed=0):
     return out
 
 
+KITTI_SIZES = [(370, 1224), (374, 1238), (376, 1241), (375, 1242)]
+
+
+def synthetic_dataset(mc, n, seed, max_objects=8):
+    """n seeded uint8 BGR images of the four KITTI sizes and their rois ([cx, cy, w, h, cls] in original pixels, boxes inside
+    the image, as dataset/kitti.py stores them): the dataset of tools/bench_train.py --augment and of train.py --synthetic."""
+    rs = np.random.RandomState(seed)
+    images, rois = [], []
+    for i in range(n):
+        h, w = KITTI_SIZES[i % 4]
+        images.append(rs.randint(0, 256, size=(h, w, 3)).astype(np.uint8))
+        k = rs.randint(1, max_objects + 1)
+        bw, bh = rs.uniform(20, 300, k), rs.uniform(20, 200, k)
+        x0, y0 = rs.uniform(0, w - bw - 1), rs.uniform(0, h - bh - 1)
+        rois.append([[x0[j] + bw[j] / 2, y0[j] + bh[j] / 2, bw[j], bh[j], int(rs.randint(mc.CLASSES))] for j in range(k)])
+    return images, rois
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # "Planted objects": a detection problem whose DISCRETE outputs (which anchors enter the top-N, their order, their classes,
 # the NMS survivors) have real margins, the way a trained detector's have -- random weights give 16 848 anchor scores that

@@ -19,6 +19,7 @@ loss + backward of a step has no host round trip and can be replayed as one hipG
 """
 import collections
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -322,6 +323,44 @@ class _TrainerBase:
             if n.endswith("/kernels"):
                 tot += float((self.view[n].double() ** 2).sum().item()) * self.mc.WEIGHT_DECAY / 2
         return tot
+
+    # ---- resumable state (the reference saves tf.global_variables(), train.py:240,328-330: variables, momentum, global_step) ----
+    def state_dict(self):
+        """Everything a run needs to continue bitwise, as host values: the flat float32 variables and momentum, the variable
+        names and shapes they were packed from, global_step, the mixed-precision loss scale with its counters, and the dropout
+        counter stream (seed, _mask_calls).  Settles a pending overflow flag first (flush)."""
+        self.flush()
+        return dict(names=list(self.names), shapes=[list(self.view[n].shape) for n in self.names],
+                    flat_params=self.flat_params.detach().cpu().numpy().copy(), flat_accum=self.flat_accum.detach().cpu().numpy().copy(),
+                    global_step=int(self.global_step), loss_scale=float(self.loss_scale), clean_steps=int(self._clean_steps),
+                    skipped_steps=int(self.skipped_steps), seed=int(self.seed), rank=int(self.rank), mask_calls=int(self._mask_calls),
+                    half=bool(self.half))
+
+    def load_state_dict(self, d):
+        """Restores state_dict()'s values into this trainer (same model, same precision).  The frozen variables are not part of
+        it: load them into the model (model.load_params) like any checkpoint.  Every rank takes its own dropout stream: the
+        saved seed is re-based from the saving rank to this one."""
+        names, shapes = [str(n) for n in d["names"]], [tuple(int(v) for v in s) for s in d["shapes"]]
+        if names != list(self.names) or shapes != [tuple(self.view[n].shape) for n in self.names]:
+            raise SqdetError("trainer state: the variable list or a shape differs from this model's")
+        if bool(d["half"]) != self.half:
+            raise SqdetError("trainer state: saved in %s, this trainer runs %s" % (("float32", "float16")[bool(d["half"])], ("float32", "float16")[self.half]))
+        p, a = np.asarray(d["flat_params"], np.float32), np.asarray(d["flat_accum"], np.float32)
+        if p.shape != (self.total,) or a.shape != (self.total,):
+            raise SqdetError("trainer state: flat buffers of %s / %s elements, expected %d" % (p.shape, a.shape, self.total))
+        self.flush()
+        with torch.cuda.device(self.dev):
+            self.flat_params.copy_(torch.from_numpy(p))
+            self.flat_accum.copy_(torch.from_numpy(a))
+        self.global_step, self.loss_scale = int(d["global_step"]), float(d["loss_scale"])
+        self._clean_steps, self.skipped_steps = int(d["clean_steps"]), int(d["skipped_steps"])
+        self.seed, self._mask_calls = int(d["seed"]) - int(d["rank"]) + self.rank, int(d["mask_calls"])
+        # the variables changed under every packed / folded kernel and plan, as after an optimizer step
+        self.model._packed.clear()
+        self.model._plan_stale = True
+        getattr(self, "_frozen_packed", {}).clear()
+        for g in list(getattr(self, "_graphed", ())):     # captured steps carry the loss scale by value: capture again
+            g.reset()
 
 
 class SqueezeDetTrainer(_TrainerBase):
@@ -884,6 +923,14 @@ class GraphedStep:
         self.tr, self.anchors, self.classes = trainer, anchors_f64, int(classes)
         self.graph, self.static, self.out, self.key = None, None, None, None
         self.cache = {}      # (loss scale, input shape) -> (graph, static buffers, outputs): a scale seen before is not re-captured
+        if not hasattr(trainer, "_graphed"):
+            trainer._graphed = weakref.WeakSet()
+        trainer._graphed.add(self)                        # (load_state_dict resets the captured steps of its trainer)
+
+    def reset(self):
+        """Drops every captured graph (and the static buffers it pins): the next step captures again."""
+        self.graph, self.static, self.out, self.key = None, None, None, None
+        self.cache = {}
 
     def _capture(self, x, gt, gcls, gcnt):
         tr = self.tr

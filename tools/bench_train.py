@@ -32,22 +32,7 @@ def synthetic_ground_truth(mc, batch, seed, max_objects=8):
     return gt, cls, cnt
 
 
-KITTI_SIZES = [(370, 1224), (374, 1238), (376, 1241), (375, 1242)]
-
-
-def synthetic_dataset(mc, n, seed, max_objects=8):
-    """n seeded uint8 BGR images of the four KITTI sizes and their rois ([cx, cy, w, h, cls] in original pixels, boxes inside
-    the image, as dataset/kitti.py stores them), for --augment."""
-    rs = np.random.RandomState(seed)
-    images, rois = [], []
-    for i in range(n):
-        h, w = KITTI_SIZES[i % 4]
-        images.append(rs.randint(0, 256, size=(h, w, 3)).astype(np.uint8))
-        k = rs.randint(1, max_objects + 1)
-        bw, bh = rs.uniform(20, 300, k), rs.uniform(20, 200, k)
-        x0, y0 = rs.uniform(0, w - bw - 1), rs.uniform(0, h - bh - 1)
-        rois.append([[x0[j] + bw[j] / 2, y0[j] + bh[j] / 2, bw[j], bh[j], int(rs.randint(mc.CLASSES))] for j in range(k)])
-    return images, rois
+from squeezedet_amd.synthetic import KITTI_SIZES, synthetic_dataset  # noqa: E402,F401  (lives in the package: train.py --synthetic reads it too)
 
 
 def main():

@@ -1,0 +1,278 @@
+#!/usr/bin/env python
+"""Trains SqueezeDet / SqueezeDet+ / ResNet50+ConvDet / VGG16+ConvDet on KITTI (the reference's src/train.py): resumable,
+with on-device summaries.
+
+    python train.py --data_path KITTI --image_set train --train_dir logs/train --net squeezeDet [--pretrained_model_path w.npz]
+    python train.py --synthetic 40 --train_dir /tmp/run --max_steps 100          # seeded synthetic data, no dataset needed
+    python train.py ... --resume                                                  # continue from the newest checkpoint
+
+Per step as the reference (train.py:266-330): a summary step (step % summary_step == 0) runs the eager trainer step with the
+activations kept and hands it to squeezedet_amd.summary.TrainSummary (-> <train_dir>/summaries.jsonl, in place of TF event
+files); every other step is a hipGraph replay (squeezedet_amd.train.GraphedStep) unless --no_graph.  A checkpoint -- written
+at step % checkpoint_step == 0 and at the last step, named by the step -- is the pair model.ckpt-<step>.npz (what eval.py
+polls for and demo.py --weights reads) + state/step-<step>.npz (squeezedet_amd.checkpoint); --resume continues from the
+newest pair bit for bit.  <train_dir>/model_metrics.txt is the reference's (train.py:137-159).
+
+The reference deletes --train_dir at start (train.py:338-340).  Here a non-empty --train_dir is refused unless --resume
+or --overwrite (delete, as the reference does).  Not carried over: the image summary with drawn boxes and Pascal VOC.
+Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
+"""
+import argparse
+import datetime
+import os
+import shutil
+import sys
+import time
+
+import numpy as np
+
+NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
+RESIDENT_BYTES = 4 << 30       # a dataset whose uint8 images fit this budget lives on the device (BatchReader resident=True)
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--dataset", default="KITTI", help="Currently only support KITTI dataset.")
+    ap.add_argument("--data_path", default="", help="Root directory of data")
+    ap.add_argument("--image_set", default="train", help="Can be train, trainval, val, or test")
+    ap.add_argument("--train_dir", default="/tmp/squeezeDet/train", help="Directory where to write summaries and checkpoints.")
+    ap.add_argument("--max_steps", type=int, default=1000000, help="Maximum number of batches to run.")
+    ap.add_argument("--net", default="squeezeDet", choices=NETS, help="Neural net architecture.")
+    ap.add_argument("--pretrained_model_path", default="", help="Path to the pretrained model (.npz, or the backbone pickle).")
+    ap.add_argument("--summary_step", type=int, default=10, help="Number of steps to save summary (0: never).")
+    ap.add_argument("--checkpoint_step", type=int, default=1000, help="Number of steps to save a checkpoint.")
+    ap.add_argument("--gpu", default="0", help="gpu id.")
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16"], help="fp32: the reference's; fp16: mixed precision")
+    ap.add_argument("--batch_size", type=int, default=0, help="images per GPU per step (default: the config's BATCH_SIZE)")
+    ap.add_argument("--seed", type=int, default=0, help="seeds the batch order, the augmentation, the dropout and --synthetic")
+    ap.add_argument("--resume", action="store_true", help="continue from the newest checkpoint of --train_dir")
+    ap.add_argument("--overwrite", action="store_true", help="delete a non-empty --train_dir first, as the reference does")
+    ap.add_argument("--keep_checkpoints", type=int, default=0, help="keep only the newest N checkpoints (0: all)")
+    ap.add_argument("--no_graph", action="store_true", help="eager steps only (no hipGraph replay)")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N seeded synthetic KITTI-sized images")
+    ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="network input size (default: the net's)")
+    ap.add_argument("--loss_scale", type=float, default=1024.0, help="fp16: the initial loss scale")
+    a = ap.parse_args(argv)
+    assert a.dataset == "KITTI", "Currently only supports KITTI dataset"
+    if a.resume and a.overwrite:
+        ap.error("--resume and --overwrite exclude each other")
+    return a
+
+
+def make_config(net, image_size=None):
+    import squeezedet_amd as S
+    from squeezedet_amd import config
+    if image_size is not None:
+        sized = {"squeezeDet": config.kitti_squeezeDet_config_for_input, "resnet50": config.kitti_res50_config_for_input,
+                 "vgg16": config.kitti_vgg16_config_for_input}
+        if net not in sized:
+            raise SystemExit("--image_size: no sized config for --net %s (squeezeDet, resnet50 and vgg16 have one)" % net)
+        return sized[net](int(image_size[0]), int(image_size[1]))
+    return {"squeezeDet": S.kitti_squeezeDet_config, "squeezeDet+": S.kitti_squeezeDetPlus_config, "resnet50": S.kitti_res50_config,
+            "vgg16": S.kitti_vgg16_config}[net]()
+
+
+def make_trainer(a, mc, local_rank=0):
+    """(model, trainer) of --net in training mode."""
+    import torch
+    from squeezedet_amd import nets
+    from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer, VGG16ConvDetTrainer
+    mc.IS_TRAINING = True
+    mc.LOAD_PRETRAINED_MODEL = False
+    mc.PRETRAINED_MODEL_PATH = a.pretrained_model_path
+    if a.batch_size:
+        mc.BATCH_SIZE = int(a.batch_size)
+    # (SqueezeDetTrainer walks any conv / fire / pool chain: it trains SqueezeDet+ too, tests/test_gpu_train.py)
+    cls, trainer = {"squeezeDet": (nets.SqueezeDet, SqueezeDetTrainer), "squeezeDet+": (nets.SqueezeDetPlus, SqueezeDetTrainer),
+                    "resnet50": (nets.ResNet50ConvDet, ResNet50ConvDetTrainer), "vgg16": (nets.VGG16ConvDet, VGG16ConvDetTrainer)}[a.net]
+    model = cls(mc, gpu_id=str(local_rank), dtype=torch.float16 if a.dtype == "fp16" else torch.float32)
+    return model, trainer
+
+
+def initial_params(a, model):
+    from squeezedet_amd import synthetic, weights
+    p = a.pretrained_model_path
+    if not p:
+        return synthetic.synthetic_params(model, seed=a.seed)
+    if p.endswith(".npz"):
+        return weights.load_params(p)
+    import joblib                       # the reference's ImageNet backbones are joblib pickles (nn_skeleton.py:397-412)
+    return weights.from_caffe_weights(joblib.load(p), model)
+
+
+def load_dataset(a, mc):
+    """(images: list of uint8 BGR arrays, rois)."""
+    if a.synthetic:
+        from squeezedet_amd.synthetic import synthetic_dataset
+        return synthetic_dataset(mc, int(a.synthetic), seed=300 + a.seed)
+    from PIL import Image
+    from squeezedet_amd.kitti_ap import load_kitti
+    data = load_kitti(a.data_path, a.image_set, mc)
+    images = [np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[:, :, ::-1]) for p in data.image_paths]   # BGR, as cv2.imread
+    return images, data.rois
+
+
+def write_model_metrics(path, model):
+    """train.py:137-159."""
+    with open(path, "w") as f:
+        for k, (title, counter) in enumerate((("Number of parameter by layer:", model.model_size_counter),
+                                              ("Activation size by layer:", model.activation_counter),
+                                              ("Number of flops by layer:", model.flop_counter))):
+            f.write(("\n" if k else "") + title + "\n")
+            count = 0
+            for c in counter:
+                f.write("\t{}: {}\n".format(c[0], c[1]))
+                count += c[1]
+            f.write("\ttotal: {}\n".format(count))
+
+
+def prepare_train_dir(a, rank):
+    """The train_dir policy; returns the step to resume from, or None."""
+    from squeezedet_amd import checkpoint
+    used = os.path.isdir(a.train_dir) and bool(os.listdir(a.train_dir))
+    if a.resume:
+        step = checkpoint.latest(a.train_dir) if used else None
+        if step is None:
+            raise SystemExit("--resume: no checkpoint (model.ckpt-<step>.npz with state/step-<step>.npz) in %s" % a.train_dir)
+        return step
+    if used and not a.overwrite:
+        raise SystemExit("%s is not empty: pass --resume to continue its run or --overwrite to delete it" % a.train_dir)
+    if rank == 0:
+        if used:
+            shutil.rmtree(a.train_dir)
+        os.makedirs(a.train_dir, exist_ok=True)
+    return None
+
+
+class Run:
+    """Everything one process of a run holds: config, model, trainer, reader, the graphed stepper and the summaries.
+    ``Run(a)`` builds it (and restores the checkpoint of ``resume_step``); ``step(k)`` is the body of one training step,
+    ``save(k)`` writes the checkpoint pair, ``close()`` settles the trainer and the summaries."""
+
+    def __init__(self, a, rank=0, local_rank=0, world=1, resume_step=None):
+        import torch
+        import squeezedet_amd as S
+        from squeezedet_amd import checkpoint
+        from squeezedet_amd.summary import TrainSummary
+        from squeezedet_amd.train import GraphedStep
+        self.a, self.rank = a, rank
+        self.dev = dev = torch.device("cuda", local_rank)
+        self.mc = mc = make_config(a.net, a.image_size)
+        self.model, trainer_cls = make_trainer(a, mc, local_rank)
+        self.model.load_params(initial_params(a, self.model))
+        self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)
+        images, rois = load_dataset(a, mc)
+        resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
+        self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
+        self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE))
+        self.first = 0
+        if resume_step is not None:
+            saved = checkpoint.read_extra(a.train_dir, resume_step)
+            for key, now in self.extra.items():
+                if saved.get(key) != now:
+                    raise SystemExit("--resume: the checkpoint was trained with %s %r, this run asks for %r" % (key, saved.get(key), now))
+            checkpoint.load(a.train_dir, resume_step, self.model, self.tr, self.reader)
+            self.first = resume_step + 1
+        self.anchors = torch.from_numpy(np.asarray(mc.ANCHOR_BOX, np.float64)).to(dev)
+        self.stepper = None if a.no_graph else GraphedStep(self.tr, self.anchors, mc.CLASSES)
+        self.summary = TrainSummary(self.tr, a.train_dir, write=(rank == 0)) if a.summary_step > 0 else None
+        self._wd_plan = None
+
+    def total_loss(self, out):
+        """loss = the three terms + the weight decay of the 'losses' collection (one statistics call over the flat variables:
+        sumsq per kernel); a synchronisation: print steps only."""
+        from squeezedet_amd.summary import StatsPlan, decode
+        tr = self.tr
+        if self._wd_plan is None:
+            self._wd_plan = StatsPlan([(tr.view[n].data_ptr() - tr.flat_params.data_ptr()) // 4 for n in tr.names],
+                                      [int(tr.view[n].numel()) for n in tr.names], tr.total, self.dev)
+        rec = decode(self._wd_plan.run(tr.flat_params).cpu(), self._wd_plan.n_bins)
+        wd = sum(float(r["sumsq"]) for n, r in zip(tr.names, rec) if n.endswith("/kernels")) * self.mc.WEIGHT_DECAY / 2
+        return float(out["class_loss"]) + float(out["conf_loss"]) + float(out["bbox_loss"]) + wd
+
+    def step(self, step):
+        """train.py:273-325 for one step."""
+        from squeezedet_amd import ops
+        a, tr, mc, summary = self.a, self.tr, self.mc, self.summary
+        start_time = time.time()
+        is_summary = summary is not None and step % a.summary_step == 0
+        lr = tr.learning_rate()
+        b = self.reader.read_batch()
+        if is_summary or self.stepper is None:
+            out = tr.step(b.image_input, *ops.build_labels(self.anchors, b.gt_boxes, b.gt_classes, b.gt_counts, mc.CLASSES)[:4],
+                          keep_activations=is_summary)
+        else:
+            out = self.stepper.step(b.image_input, b.gt_boxes, b.gt_classes, b.gt_counts)
+        if is_summary:
+            summary.record(step, out, lr)
+            if self.rank == 0:
+                print("conf_loss: {}, bbox_loss: {}, class_loss: {}".format(float(out["conf_loss"]), float(out["bbox_loss"]),
+                                                                           float(out["class_loss"])))
+        elif summary is not None:
+            summary.poll()
+        if step % 10 == 0:
+            loss_value = self.total_loss(out)               # (reads the device: the step has finished)
+            duration = time.time() - start_time
+            # the reference asserts on the loss every step (train.py:313); here the trainer raises FloatingPointError on a
+            # non-finite float32 gradient (at the latest at the next step / flush), so the loss is read on print steps only
+            assert not np.isnan(loss_value), \
+                "Model diverged. Total loss: {}, conf_loss: {}, bbox_loss: {}, class_loss: {}".format(
+                    loss_value, float(out["conf_loss"]), float(out["bbox_loss"]), float(out["class_loss"]))
+            if self.rank == 0:
+                print("%s: step %d, loss = %.2f (%.1f images/sec; %.3f sec/batch)" % (
+                    datetime.datetime.now(), step, loss_value, mc.BATCH_SIZE / duration, float(duration)))
+                sys.stdout.flush()
+        return out
+
+    def save(self, step):
+        """(state_dict() flushes the trainer first: a diverged step raises before anything is written)"""
+        from squeezedet_amd import checkpoint
+        if self.rank == 0:
+            return checkpoint.save(self.a.train_dir, step, self.model, self.tr, self.reader, extra=self.extra, keep=self.a.keep_checkpoints)
+        self.tr.flush()
+
+    def close(self):
+        try:
+            self.tr.flush()
+        finally:
+            if self.summary is not None:
+                self.summary.close()
+
+
+def train(a):
+    rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
+    resume_step = prepare_train_dir(a, rank)
+    import torch
+    if world == 1:
+        local_rank = int(a.gpu)
+    torch.cuda.set_device(local_rank)
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+        dist.barrier(device_ids=[local_rank])          # rank 0 has prepared the directory
+    run = Run(a, rank, local_rank, world, resume_step)
+    if rank == 0:
+        if resume_step is not None:
+            print("Resuming from step {} of {}".format(resume_step, a.train_dir))
+        write_model_metrics(os.path.join(a.train_dir, "model_metrics.txt"), run.model)
+        print("Model statistics saved to {}.".format(os.path.join(a.train_dir, "model_metrics.txt")))
+    try:
+        for step in range(run.first, a.max_steps):
+            run.step(step)
+            if (a.checkpoint_step > 0 and step % a.checkpoint_step == 0) or step + 1 == a.max_steps:
+                run.save(step)
+    finally:
+        try:
+            run.close()
+        finally:
+            if world > 1:
+                torch.distributed.destroy_process_group()
+
+
+def main(argv=None):
+    train(parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()

@@ -454,8 +454,9 @@ int sqdet_add_relu(const void* a, const void* b, void* y, size_t count, int dtyp
  * producer could not write its channel range directly.  c, y_cstride, y_coffset multiples of 16 bytes. */
 int sqdet_copy_channels(const void* x, void* y, size_t pixels, int c, int y_cstride, int y_coffset, int dtype,
                         sqdet_stream_t stream);
-/* mask[i] = floor(keep_prob + u_i), u_i ~ U[0,1) from a counter-based generator of (seed, i): the keep mask of
- * tf.nn.dropout (nets/squeezeDet.py:74), to be applied with sqdet_scale_mask(x, mask, 1/keep_prob). */
+/* mask[i] = min(floor(keep_prob + u_i), 1), u_i ~ U[0,1) in 24 bits from a counter-based generator of (seed, i): the keep
+ * mask of tf.nn.dropout (nets/squeezeDet.py:74), every element 0 or 1 (the min only acts at keep_prob = 1, where the float32
+ * sum 1 + (1 - 2^-24) rounds to 2), to be applied with sqdet_scale_mask(x, mask, 1/keep_prob). */
 int sqdet_dropout_mask(void* mask, size_t count, float keep_prob, uint64_t seed, int dtype, sqdet_stream_t stream);
 
 /* Momentum + per-variable clip_by_norm over flat parameter / gradient / momentum buffers.

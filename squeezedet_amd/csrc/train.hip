@@ -173,6 +173,16 @@ __global__ void scale_mask_relu_kernel(const T* __restrict__ x, const T* __restr
   }
 }
 
+// (D)(v * scale), the product formed on its own.  Left to itself hipcc fuses a float32 multiply and the conversion to float16
+// into v_fma_mixlo_f16(v, scale, +0), and (-0) + (+0) = +0: the sign of a zero product was lost -- on two of convert_scale's four
+// lanes (the other two go through v_pk_mul_f32 + v_cvt_pk_f16_f32 and kept it) and in some of the loss kernel's stores.
+template <typename D>
+__device__ __forceinline__ D scaled_to(float v, float scale) {
+  float p = v * scale;
+  asm volatile("" : "+v"(p));
+  return (D)p;
+}
+
 // dst = (D)(src * scale): the float16 <-> float32 hand-offs of mixed-precision training (preds -> loss, dpreds * loss_scale)
 template <typename S, typename D>
 __global__ void convert_scale_kernel(const S* __restrict__ src, D* __restrict__ dst, float scale, size_t n4) {
@@ -182,7 +192,7 @@ __global__ void convert_scale_kernel(const S* __restrict__ src, D* __restrict__ 
     const SV v = reinterpret_cast<const SV*>(src)[i];
     DV o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (D)((float)v[e] * scale);
+    for (int e = 0; e < 4; ++e) o[e] = scaled_to<D>((float)v[e], scale);
     reinterpret_cast<DV*>(dst)[i] = o;
   }
 }
@@ -503,7 +513,7 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
     // float32 dpreds, and -- mixed precision -- its loss-scaled float16 copy (convert_scale_kernel's expression) in the same pass
     auto put = [&](int off, float v) {
       dp[off] = v;
-      if (sizeof(PT) == 2) gp[off] = (f16)(v * a.gscale);
+      if (sizeof(PT) == 2) gp[off] = scaled_to<f16>(v, a.gscale);
     };
     const float m = a.mask[idx];
     // class probabilities (softmax) and their loss (nn_skeleton.py:150-160, 292-299)
@@ -723,7 +733,8 @@ __global__ void dropout_mask_kernel(T* __restrict__ mask, size_t n, float keep_p
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
     const float u = (float)(z >> 40) * (1.0f / 16777216.0f);   // 24 random bits -> [0, 1)
-    mask[i] = (T)floorf(keep_prob + u);
+    // keep_prob = 1 and the top draw u = 1 - 2^-24: the float32 sum 2 - 2^-24 is a tie that rounds to 2.0 -- a keep mask holds 0 or 1
+    mask[i] = (T)fminf(floorf(keep_prob + u), 1.0f);
   }
 }
 

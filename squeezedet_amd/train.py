@@ -62,6 +62,36 @@ def _reject_vgg16(model, trainer):
         raise NotImplementedError("%s does not train VGG16ConvDet: use VGG16ConvDetTrainer" % trainer)
 
 
+class _WgradSession:
+    """The weight gradients of ONE backward.  Every conv's gradient kernel writes its partial slabs into a workspace of its own
+    and one launch at the end sums them all (ops.WgradPlan, kept per `key` -- the input shape of the trainable region); the
+    first backward of a key runs the per-conv two-launch form and records what the plan needs.  The caller issues add()
+    through trainer._wgrad (the side stream); finish() joins it."""
+
+    def __init__(self, trainer, key):
+        self.tr, self.key, self.gs = trainer, key, 1.0 / trainer.loss_scale
+        self.plan, self.items = trainer._wplans.get(key), []
+        if self.plan is not None:
+            trainer._wplans[key] = trainer._wplans.pop(key)            # most recently used last
+
+    def add(self, name, x, dy, k, cin, cout, dw, db, dy_coffset=0):
+        if self.plan is not None:
+            self.plan.partial(name, x, dy, dy_coffset=dy_coffset)
+            return
+        self.items.append((name, (int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), cin, cout, k), dw, db, None, 0.0))
+        ops.conv2d_bwd_filter(x, dy, k, cin, cout, dy_coffset=dy_coffset, dw=dw, db=db, grad_scale=self.gs)
+
+    def finish(self):
+        tr = self.tr
+        tr._join_wgrad()
+        if self.plan is not None:
+            self.plan.reduce(self.gs)
+        elif tr.plan_wgrads:
+            tr._wplans[self.key] = ops.WgradPlan(self.items)
+            while len(tr._wplans) > tr.MAX_WPLANS:
+                del tr._wplans[next(iter(tr._wplans))]
+
+
 class _TrainerBase:
     """Flat float32 parameter / gradient / momentum buffers over the trainable variables of a model built with
     mc.IS_TRAINING = True, the gradient all-reduce and the optimizer step.
@@ -137,12 +167,16 @@ class _TrainerBase:
         model._plan_stale = True
         self.opt = ops.MomentumOptimizer(offs, cnts, decs, self.dev)
         self.found_inf = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._labels_forked = False
+        self._flag_host, self._flag_event = None, None     # lazy_overflow_check's pinned flag + its event, made at the first lazy step
+        self._frozen_packed = {}                           # packed kernels of frozen convs the trainer itself runs: name -> (packed, _version)
+        self._graphed = weakref.WeakSet()                  # the GraphedSteps replaying this trainer (load_state_dict resets them)
         if self.world > 1:      # replicas start from rank 0's variables and momentum: they stay bit-identical from here on
-            torch.distributed.broadcast(self.flat_params, src=torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0, group=self.pg)
-            torch.distributed.broadcast(self.flat_accum, src=torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0, group=self.pg)
+            src0 = torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0
+            torch.distributed.broadcast(self.flat_params, src=src0, group=self.pg)
+            torch.distributed.broadcast(self.flat_accum, src=src0, group=self.pg)
             # ... and from rank 0's FROZEN variables (conv1 of SqueezeDet, conv1 .. res3d and the batch-norm statistics of ResNet50):
             # they are not in the flat buffers, and a replica that loaded other values would compute other gradients for good
-            src0 = torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0
             for n in model.params:
                 if not model.trainable[n]:
                     t = model.params[n].contiguous()
@@ -153,16 +187,24 @@ class _TrainerBase:
 
     MAX_WPLANS = 4
 
-    def _wplan_get(self, key):
-        plan = self._wplans.get(key)
-        if plan is not None:
-            self._wplans[key] = self._wplans.pop(key)            # most recently used last
-        return plan
+    def step(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None, apply_update=True,
+             keep_activations=False, num_objects=None):
+        """One training step.  images [B,H,W,3]; input_mask [B,A] or [B,A,1]; box_delta_input / box_input
+        [B,A,4]; labels [B,A,C] (the reference's placeholders, nn_skeleton.py:81-97).  Returns a dict
+        with loss, class_loss, conf_loss, bbox_loss (device scalars).  keep_activations: also return every stored
+        forward activation as out["activations"] = {name: tensor} (names as the oracles' forward_train `override`),
+        for parity tests of the backward pass."""
+        with torch.cuda.device(self.dev):
+            out = self.forward_backward(images, input_mask, box_delta_input, box_input, labels, dropout_mask, keep_activations, num_objects)
+            self._finish_step(apply_update)
+        return out
 
-    def _wplan_put(self, key, plan):
-        self._wplans[key] = plan
-        while len(self._wplans) > self.MAX_WPLANS:
-            del self._wplans[next(iter(self._wplans))]
+    def _result(self, losses, ious, preds, dpreds, num_objects, acts=None):
+        out = collections.OrderedDict(class_loss=losses[0], conf_loss=losses[1], bbox_loss=losses[2], ious=ious, preds=preds,
+                                      dpreds=dpreds, num_objects=num_objects)
+        if acts is not None:
+            out["activations"] = acts
+        return out
 
     def _wgrad(self, fn, *reads):
         """Runs fn() -- weight-gradient launches writing into the flat gradient bucket -- behind everything issued so far,
@@ -194,7 +236,7 @@ class _TrainerBase:
         return out
 
     def _join_labels(self):
-        if getattr(self, "_labels_forked", False):
+        if self._labels_forked:
             torch.cuda.current_stream().wait_stream(self._wg_stream)
             self._labels_forked = False
 
@@ -235,10 +277,22 @@ class _TrainerBase:
         dm = t(dropout_mask)                           # float32 on the device
         return dm if self.adt == torch.float32 else ops.convert_scale(dm, self.adt)
 
+    def _next_mask_seed(self):
+        """The generator seed of the next dropout mask: this replica's stream, one counter step per mask (state_dict carries both)."""
+        self._mask_calls += 1
+        return (self.seed << 32) + self._mask_calls
+
     def _dropout_mask(self, shape, keep):
         """tf.nn.dropout's keep mask floor(keep_prob + U) from the counter-based HIP generator; a new seed per call."""
-        self._mask_calls += 1
-        return ops.dropout_mask(tuple(shape), keep, (self.seed << 32) + self._mask_calls, self.adt, self.dev)
+        return ops.dropout_mask(tuple(shape), keep, self._next_mask_seed(), self.adt, self.dev)
+
+    def _dropout(self, x, keep, dropout_mask, t, scale=True):
+        """tf.nn.dropout of x with the caller's keep mask, or one drawn here: (x * mask / keep, the mask as a device tensor of
+        the activation dtype).  scale=False: x itself."""
+        if dropout_mask is None:
+            dropout_mask = self._dropout_mask(x.shape, keep)
+        dm = self._mask_tensor(dropout_mask, t)
+        return (ops.scale_mask(x, dm, 1.0 / keep) if scale else x), dm
 
     def _loss(self, preds, mask, delta, box, lab, num_objects):
         """Loss forward + backward in float32; returns (gradient w.r.t. preds in the activation dtype -- times
@@ -273,7 +327,7 @@ class _TrainerBase:
             if not self.lazy_overflow_check:
                 self._account(bool(int(self.found_inf.item())))
             else:
-                if getattr(self, "_flag_host", None) is None:
+                if self._flag_host is None:
                     self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
                     self._flag_event = torch.cuda.Event()
                 self._flag_host.copy_(self.found_inf, non_blocking=True)
@@ -358,45 +412,56 @@ class _TrainerBase:
         # the variables changed under every packed / folded kernel and plan, as after an optimizer step
         self.model._packed.clear()
         self.model._plan_stale = True
-        getattr(self, "_frozen_packed", {}).clear()
-        for g in list(getattr(self, "_graphed", ())):     # captured steps carry the loss scale by value: capture again
+        self._frozen_packed.clear()
+        for g in list(self._graphed):                     # captured steps carry the loss scale by value: capture again
             g.reset()
 
 
+_ConvRec = collections.namedtuple("_ConvRec", "node x y")             # y None: no launch wrote it, or the pool above does not need it
+_PoolRec = collections.namedtuple("_PoolRec", "node x y widx in_hw")   # widx: the window index (then x is not kept); in_hw: (h, w) of x
+_FireRec = collections.namedtuple("_FireRec", "sq e1 e3 x s y")        # s: the squeeze conv's output
+
+
+def _chain_input(n):
+    """The node a chain node reads; a fire module stands in the chain as its concat node, reading what its squeeze conv reads."""
+    return n.inputs[0].inputs[0].inputs[0] if n.op == "concat" else n.inputs[0]
+
+
+def _chain(model):
+    """The graph from the image placeholder to preds as a list in forward order: conv / pool / dropout nodes, and a fire
+    module's concat node (nets/squeezeDet.py:30-106)."""
+    chain, n = [], model.preds
+    while n.op != "placeholder":
+        chain.append(n)
+        n = _chain_input(n)
+    return chain[::-1]
+
+
 class SqueezeDetTrainer(_TrainerBase):
-    """model: a squeezedet_amd.nets.SqueezeDet built with mc.IS_TRAINING = True and dtype float32."""
+    """Training step of a linear chain of conv / pool / fire / dropout layers: SqueezeDet and SqueezeDet+ (model: built with
+    mc.IS_TRAINING = True), from the image placeholder up -- conv1 is frozen, so conv1 + pool1 run as the fused stem launch and
+    the backward stops at fire2.  _chain_forward walks self.region from the value of self.boundary and leaves typed records
+    (_ConvRec / _PoolRec / _FireRec); _chain_backward reads them."""
+
+    # The one difference between the chain nets.  SqueezeDet's dropout follows model.keep_prob, the switch GraphedStep reads:
+    # set to 1.0 on a built training graph, the mask is still drawn (the counter stream advances) but the activation is not
+    # scaled and the gradient not masked.  VGG16's follows its graph node, which only exists below 1.0: it always scales.
+    DROPOUT_FOLLOWS_MODEL = True
 
     def __init__(self, model, process_group=None, **kw):
         _reject_vgg16(model, "SqueezeDetTrainer")
         _TrainerBase.__init__(self, model, process_group, **kw)
-        self.layers = self._layer_list()
-        # every trainable kernel is re-packed (forward order; backward-data order for all but the lowest trainable conv) by
-        # ONE launch at the top of a step instead of 62 (ops.PackPlan); the frozen conv1 is packed once
-        kernels = collections.OrderedDict((n[:-len("/kernels")], self.view[n]) for n in self.names if n.endswith("/kernels"))
-        self.packplan = ops.PackPlan(kernels, self.adt, bwd_names=set(kernels))
-        self._frozen_packed = {}
+        self._set_region(_chain(model))
 
-    # ---- the forward graph as a list (nets/squeezeDet.py:30-79) ----
-    def _layer_list(self):
-        m = self.model
-        seq, node = [], m.preds
-        chain = []
-        # walk back from preds through the graph
-        def walk(n):
-            if n.op == "placeholder":
-                return
-            walk(n.inputs[0] if n.op != "concat" else n.inputs[0].inputs[0].inputs[0])
-            chain.append(n)
-        walk(node)
-        for n in chain:
-            if n.op == "concat":
-                e1, e3 = n.inputs
-                seq.append(("fire", n.name.split("/")[0], e1.inputs[0], e1, e3))
-            elif n.op == "conv":
-                seq.append(("conv", n.name, n))
-            elif n.op == "pool":
-                seq.append(("pool", n.name, n))
-        return seq
+    def _set_region(self, region, no_bwd=()):
+        """region: the chain nodes this trainer runs itself, forward order; no_bwd: names of convs whose backward-data never
+        runs.  Every trainable kernel is re-packed (forward order, and backward-data order unless in no_bwd) by ONE launch at
+        the top of a step instead of 62 (ops.PackPlan); a frozen conv of the region is packed once (_pack)."""
+        self.region, self.boundary = region, _chain_input(region[0])
+        # the conv reading the dropout: its backward is the dropout's too
+        self.drop_conv = next((n.name for n in region if n.op == "conv" and n.inputs[0].op == "dropout"), None)
+        kernels = collections.OrderedDict((n[:-len("/kernels")], self.view[n]) for n in self.names if n.endswith("/kernels"))
+        self.packplan = ops.PackPlan(kernels, self.adt, bwd_names=set(kernels) - set(no_bwd))
 
     def _pack(self, name):
         if name in self.packplan.fwd:
@@ -407,82 +472,88 @@ class SqueezeDetTrainer(_TrainerBase):
             hit = self._frozen_packed[name] = (ops.pack_conv_weights(w, self.adt), w._version)
         return hit[0]
 
-    def step(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None, apply_update=True,
-             keep_activations=False, num_objects=None):
-        """One training step.  images [B,H,W,3]; input_mask [B,A] or [B,A,1]; box_delta_input / box_input
-        [B,A,4]; labels [B,A,C] (the reference's placeholders, nn_skeleton.py:81-97).  Returns a dict
-        with loss, class_loss, conf_loss, bbox_loss (device scalars).  keep_activations: also return every stored
-        forward activation as out["activations"] = {name: tensor} (names as oracle/train_oracle.py forward_train's
-        `override`), for parity tests of the backward pass."""
-        with torch.cuda.device(self.dev):
-            out = self.forward_backward(images, input_mask, box_delta_input, box_input, labels, dropout_mask, keep_activations, num_objects)
-            self._finish_step(apply_update)
-        return out
-
     def forward_backward(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None,
                          keep_activations=False, num_objects=None, num_objects_is_global=False):
         """Forward + loss + backward into the flat gradient bucket: kernel launches and stream-ordered allocations only,
         no host round trip (hipGraph-capturable).  _finish_step (all-reduce + update) completes the step."""
-        m, mc, P = self.model, self.mc, self.model.params
-        acts = {}
+        m = self.model
         self.packplan.run()          # the variables may have changed since the last step (optimizer, load_params): one launch
-        x = m._to_input(images)
-        B = int(x.shape[0])
-        t, mask, delta, box, lab, num_objects = self._labels(B, input_mask, box_delta_input, box_input, labels, num_objects, num_objects_is_global)
-        keep = m.keep_prob
-        # ---------------- forward, keeping what the backward needs ----------------
-        saved = []
-        cur = x
-        drop_in = None
-        skip_pool = None
-        for li, item in enumerate(self.layers):
-            if item[0] == "pool" and item[2] is skip_pool:
+        # the boundary: the image itself, or the last frozen activation on the inference graph (its fused launches, nothing kept)
+        (xb,) = m.run([self.boundary], {m.image_input: images}, use_plan=False)
+        t, mask, delta, box, lab, num_objects = self._labels(int(xb.shape[0]), input_mask, box_delta_input, box_input, labels,
+                                                             num_objects, num_objects_is_global)
+        preds, saved, acts, dm = self._chain_forward(xb, dropout_mask, t, keep_activations)
+        self._join_labels()
+        g, dpreds, ious, losses = self._loss(preds, mask, delta, box, lab, num_objects)
+        self._chain_backward(saved, g, tuple(int(v) for v in xb.shape), self.drop_conv, dm)
+        return self._result(losses, ious, preds, dpreds, num_objects, acts if keep_activations else None)
+
+    def _conv_pool(self, i, x):
+        """Can the conv self.region[i] and the pool after it run as ONE launch on x?  (pooled y, window index or None) if so."""
+        m, P, n = self.model, self.model.params, self.region[i]
+        nxt = self.region[i + 1] if i + 1 < len(self.region) else None
+        if nxt is None or nxt.op != "pool":
+            return None
+        kern, bias, pool = P[n.name + "/kernels"], P[n.name + "/biases"], (nxt.attrs["size"], nxt.attrs["stride"])
+        if (i == 0 and not m.trainable[n.name + "/kernels"] and pool == (3, 2) and n.attrs["stride"] == 2 and n.attrs["relu"]
+                and ops.stem_supported(int(kern.shape[3]), int(kern.shape[0]))):
+            # frozen conv1 + pool1 (nets/squeezeDet.py:40-44): nothing below pool1's output is needed by the backward, so
+            # the fused stem launch serves the training forward too
+            try:
+                return ops.stem_conv_pool(x, self._pack(n.name), bias, n.attrs["padding"], nxt.attrs["padding"]), None
+            except SqdetUnsupported:
+                return None         # e.g. set_option("conv_algo", 1): the separate conv + pool kernels
+        if (pool == (2, 2) and nxt.attrs["padding"] == "SAME" and n.attrs["size"] == 3 and n.attrs["stride"] == 1
+                and n.attrs["padding"] == "SAME"
+                and ops.conv2d_maxpool2_supported(int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]),
+                                                  int(n.shape[3]), self.adt)):
+            # conv + pool + window index in one launch (VGG16's pairs): the conv's output never reaches HBM
+            return ops.conv2d_maxpool2_nhwc_idx(x, self._pack(n.name), bias, n.attrs["relu"])
+        return None
+
+    def _chain_forward(self, xb, dropout_mask, t, keep_activations):
+        """Training-mode forward of self.region from xb, the value of self.boundary, keeping what the backward needs: (preds,
+        the records _chain_backward reads, {name: stored activation}, the dropout's keep mask or None).  keep_activations: no
+        fused conv + pool launch, so that every conv's output exists."""
+        m, P = self.model, self.model.params
+        acts = {} if self.boundary.op == "placeholder" else {self.boundary.name: xb}
+        saved, cur, dm, skip = [], xb, None, None
+        for i, n in enumerate(self.region):
+            if n is skip:
                 continue
-            if item[0] == "conv":
-                node = item[2]
-                nxt = self.layers[li + 1] if li + 1 < len(self.layers) else None
-                if (li == 0 and not keep_activations and not m.trainable[node.name + "/kernels"] and nxt is not None
-                        and nxt[0] == "pool" and nxt[2].attrs["size"] == 3 and nxt[2].attrs["stride"] == 2
-                        and node.attrs["stride"] == 2 and node.attrs["relu"]
-                        and ops.stem_supported(int(P[node.name + "/kernels"].shape[3]), int(P[node.name + "/kernels"].shape[0]))):
-                    # frozen conv1 + pool1 (nets/squeezeDet.py:40-44): nothing below pool1's output is needed by the
-                    # backward, so the fused stem launch serves the training forward too
-                    try:
-                        y = ops.stem_conv_pool(cur, self._pack(node.name), P[node.name + "/biases"], node.attrs["padding"],
-                                               nxt[2].attrs["padding"])
-                    except SqdetUnsupported:
-                        y = None        # e.g. set_option("conv_algo", 1): the separate conv + pool kernels below
-                    if y is not None:
-                        saved.append(("conv", node, cur, None))
-                        saved.append(("pool", nxt[2], None, y, None, None))
-                        acts[nxt[2].name] = y
-                        cur = y
-                        skip_pool = nxt[2]
-                        continue
-                if node.name == "conv12":
-                    drop_in = cur
-                    if dropout_mask is None:
-                        dropout_mask = self._dropout_mask(cur.shape, keep)                           # tf.nn.dropout's mask
-                    dm = self._mask_tensor(dropout_mask, t)
-                    cur = ops.scale_mask(cur, dm, 1.0 / keep) if keep != 1.0 else cur
-                    acts["drop"] = cur
-                y = ops.conv2d_nhwc(cur, self._pack(node.name), P[node.name + "/biases"], node.attrs["stride"],
-                                    node.attrs["padding"], node.attrs["relu"])
-                saved.append(("conv", node, cur, y))
-                acts[node.name] = y
-                cur = y
-            elif item[0] == "pool":
-                node = item[2]
-                if node.attrs["size"] == 3 and node.attrs["stride"] == 2:
-                    # the window index rides along: the backward reads it (+ y, dy) instead of searching x again
-                    y, widx = ops.maxpool_nhwc_idx(cur, 3, 2, node.attrs["padding"])
+            in_hw = tuple(cur.shape[1:3])
+            if n.op == "dropout":
+                keep = m.keep_prob if self.DROPOUT_FOLLOWS_MODEL else n.attrs["keep_prob"]
+                cur, dm = self._dropout(cur, keep, dropout_mask, t, scale=keep != 1.0)
+                dm = dm if keep != 1.0 else None
+                acts["drop"] = cur
+            elif n.op == "conv":
+                fused = None if keep_activations else self._conv_pool(i, cur)
+                if fused is not None:
+                    y, widx = fused
+                    skip = self.region[i + 1]
+                    saved.append(_ConvRec(n, cur, None))
+                    saved.append(_PoolRec(skip, None, y, widx, in_hw))
+                    acts[skip.name] = cur = y
+                    continue
+                y = ops.conv2d_nhwc(cur, self._pack(n.name), P[n.name + "/biases"], n.attrs["stride"], n.attrs["padding"],
+                                    n.attrs["relu"])
+                saved.append(_ConvRec(n, cur, y))
+                acts[n.name] = cur = y
+            elif n.op == "pool":
+                size, stride = n.attrs["size"], n.attrs["stride"]
+                if (size, stride) in ((3, 2), (2, 2)):
+                    # the window index rides along: the backward reads it (+ y, dy) instead of searching x again, and masks
+                    # the ReLU of a conv below with it -- neither the pool's input nor that conv's output is kept
+                    y, widx = ops.maxpool_nhwc_idx(cur, size, stride, n.attrs["padding"])
+                    if saved and isinstance(saved[-1], _ConvRec):
+                        saved[-1] = saved[-1]._replace(y=None)
+                    saved.append(_PoolRec(n, None, y, widx, in_hw))
                 else:
-                    y, widx = ops.maxpool_nhwc(cur, node.attrs["size"], node.attrs["stride"], node.attrs["padding"]), None
-                saved.append(("pool", node, cur, y, widx, tuple(cur.shape[1:3])))
-                acts[node.name] = y
-                cur = y
-            else:
-                _, fname, sq, e1, e3 = item
+                    saved.append(_PoolRec(n, cur, ops.maxpool_nhwc(cur, size, stride, n.attrs["padding"]), None, in_hw))
+                acts[n.name] = cur = saved[-1].y
+            elif n.op == "concat":
+                (e1, e3), sq = n.inputs, n.inputs[0].inputs[0]
                 if self.half:
                     # the module in ONE launch (sqdet_fire_fwd_keep: the fused kernel's squeeze epilogue also writes the
                     # squeeze tensor the backward reads): mixed-precision step 3.40 -> 3.25 ms
@@ -491,82 +562,51 @@ class SqueezeDetTrainer(_TrainerBase):
                 else:
                     # float32: the fused tile kernels spill at this width -- squeeze + the two expand convs are faster (9.92 vs 10.16 ms)
                     s = ops.conv2d_nhwc(cur, self._pack(sq.name), P[sq.name + "/biases"], 1, "SAME", True)
-                    y = torch.empty((B, int(s.shape[1]), int(s.shape[2]), e1.shape[3] + e3.shape[3]), dtype=self.adt, device=self.dev)
+                    y = torch.empty(tuple(s.shape[:3]) + (e1.shape[3] + e3.shape[3],), dtype=self.adt, device=self.dev)
                     ops.conv2d_nhwc(s, self._pack(e1.name), P[e1.name + "/biases"], 1, "SAME", True, out=y, out_coffset=0)
                     ops.conv2d_nhwc(s, self._pack(e3.name), P[e3.name + "/biases"], 1, "SAME", True, out=y, out_coffset=e1.shape[3])
-                saved.append(("fire", (sq, e1, e3), cur, s, y))
-                acts[fname + "/squeeze1x1"], acts[fname] = s, y
+                saved.append(_FireRec(sq, e1, e3, cur, s, y))
+                acts[sq.name], acts[n.name.split("/")[0]] = s, y
                 cur = y
-        preds = cur
-        # ---------------- loss ----------------
-        self._join_labels()
-        g, dpreds, ious, losses = self._loss(preds, mask, delta, box, lab, num_objects)
-        self._chain_backward(saved, g, tuple(int(v) for v in x.shape), "conv12", dm if keep != 1.0 else None)
-        out = collections.OrderedDict(class_loss=losses[0], conf_loss=losses[1], bbox_loss=losses[2], ious=ious, preds=preds,
-                                      dpreds=dpreds, num_objects=num_objects)
-        if keep_activations:
-            out["activations"] = acts
-        return out
+            else:
+                raise SqdetError("%s: unsupported node %s (%s) in the chain" % (type(self).__name__, n.name, n.op))
+        return cur, saved, acts, dm
 
     def _chain_backward(self, saved, g, wkey, drop_name, dm):
-        """Backward of a linear chain of layer records into the flat gradient bucket.  saved: the forward's records in order --
-        ("conv", node, x, y), ("pool", node, x, y, window index or None, (h, w) of x), ("fire", (sq, e1, e3), x, s, y); a conv
-        record's y may be None where a fused launch never wrote it (its gradient is then masked by the pool backward above
-        it).  g: gradient w.r.t. the last record's output; wkey: the WgradPlan key (the input shape); drop_name: the conv
-        reading the dropout, dm its keep mask (None: no dropout)."""
+        """Backward of a linear chain of layer records (_chain_forward's, in forward order) into the flat gradient bucket.  A
+        _ConvRec's y may be None (its gradient is then masked by the pool backward above it).  g: gradient w.r.t. the last
+        record's output; wkey: the WgradPlan key (the input shape); drop_name: the conv reading the dropout, dm its keep mask
+        (None: no dropout)."""
         m, P = self.model, self.model.params
         keep = m.keep_prob
-        # ---------------- backward ----------------
         self.flat_grads.zero_()
-        gs = 1.0 / self.loss_scale      # g: gradient w.r.t. the current layer's OUTPUT (pre-activation mask applied below)
         bwd = lambda name: self.packplan.bwd[name] if name in self.packplan.bwd else ops.PackedConvBwd(P[name + "/kernels"], self.adt)
-        # weight gradients: every conv's gradient kernel writes its partial slabs into a workspace of its own and ONE launch
-        # at the end sums them all (ops.WgradPlan); the first step of an input shape runs the per-conv two-launch form and
-        # records what the plan needs
-        wplan = self._wplan_get(wkey)
-        witems = []
+        ws = _WgradSession(self, wkey)
 
         def wg(name, xt, gt, k, cin, cout, dy_coffset=0):
-            if wplan is not None:
-                wplan.partial(name, xt, gt, dy_coffset=dy_coffset)
-                return
-            witems.append((name, (int(xt.shape[0]), int(xt.shape[1]), int(xt.shape[2]), cin, cout, k),
-                           self.gview[name + "/kernels"], self.gview[name + "/biases"], None, 0.0))
-            ops.conv2d_bwd_filter(xt, gt, k, cin, cout, dy_coffset=dy_coffset, dw=self.gview[name + "/kernels"],
-                                  db=self.gview[name + "/biases"], grad_scale=gs)
-
-        def has_trainable(rec):
-            if rec[0] == "conv":
-                return m.trainable[rec[1].name + "/kernels"]
-            return rec[0] == "fire"
-        first_tr = min(i for i, r in enumerate(saved) if has_trainable(r))
+            ws.add(name, xt, gt, k, cin, cout, self.gview[name + "/kernels"], self.gview[name + "/biases"], dy_coffset)
+        is_conv, is_fire = lambda r: isinstance(r, _ConvRec), lambda r: isinstance(r, _FireRec)
+        first_tr = min(i for i, r in enumerate(saved) if is_fire(r) or (is_conv(r) and m.trainable[r.node.name + "/kernels"]))
         # ReLU backward: every gradient w.r.t. a ReLU output is masked in the epilogue of the kernel that PRODUCES it (the
         # backward-data conv or the max-pool backward above it) -- `masked` says g already carries the mask of the layer
-        # whose output it is the gradient of; the loss gradient of conv12 (no ReLU) and any other case fall back to relu_bwd
+        # whose output it is the gradient of; the loss gradient of the last conv (no ReLU) and any other case fall back to relu_bwd
         masked = False
 
-        def relu_src(rj):
-            """The ReLU output the record below ri produces (= the tensor dx is the gradient of), or None."""
-            r = saved[rj]
-            if r[0] == "fire":
-                return r[4]
-            if r[0] == "conv" and r[1].attrs["relu"] and r[3] is not None:
-                return r[3]
-            return None
+        def relu_src(r):
+            """The ReLU output the record r produces (= the tensor the dx of the record above is the gradient of), or None."""
+            return r.y if is_fire(r) or (is_conv(r) and r.node.attrs["relu"]) else None
 
-        def relu_below(rj):
-            """The record rj ends in a ReLU (a pool backward masks with its own x or, from the window index, with y)."""
-            r = saved[rj]
-            return r[0] == "fire" or (r[0] == "conv" and r[1].attrs["relu"])
+        def relu_below(r):
+            """The record r ends in a ReLU (a pool backward masks with its own x or, from the window index, with y)."""
+            return is_fire(r) or (is_conv(r) and r.node.attrs["relu"])
         for ri in range(len(saved) - 1, first_tr - 1, -1):
             rec = saved[ri]
             need_dx = ri > first_tr     # nothing trainable (and no image gradient) below the first trainable layer
-            below = relu_src(ri - 1) if ri > 0 else None          # x of this layer, when it is a ReLU output
-            if rec[0] == "conv":
-                _, node, xin, y = rec
-                name = node.name
+            below = relu_src(saved[ri - 1]) if ri > 0 else None          # x of this layer, when it is a ReLU output
+            if is_conv(rec):
+                node, xin, name = rec.node, rec.x, rec.node.name
                 if node.attrs["relu"] and not masked:
-                    ops.relu_bwd(y, g)
+                    ops.relu_bwd(rec.y, g)
                 k = node.attrs["size"]
                 cin, cout = int(xin.shape[3]), int(node.shape[3])
                 self._wgrad(lambda xin=xin, g=g, k=k, cin=cin, cout=cout, name=name: wg(name, xin, g, k, cin, cout), g)
@@ -575,23 +615,22 @@ class SqueezeDetTrainer(_TrainerBase):
                     if name == drop_name and dm is not None:
                         g = ops.conv2d_bwd_data(g, bwd(name))
                         g = ops.scale_mask(g, dm, 1.0 / keep, relu_of=below)      # dropout backward (+ the ReLU backward below it)
-                        masked = below is not None
                     else:
                         g = ops.conv2d_bwd_data(g, bwd(name), relu_of=below)
-                        masked = below is not None
-            elif rec[0] == "pool":
-                _, node, xin, y, widx, in_hw = rec
-                relu = ri > 0 and relu_below(ri - 1)
-                if widx is not None:
-                    g = ops.maxpool_bwd_idx(widx, y, g, in_hw, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=relu)
+                    masked = below is not None
+            elif isinstance(rec, _PoolRec):
+                node = rec.node
+                relu = ri > 0 and relu_below(saved[ri - 1])
+                if rec.widx is not None:
+                    g = ops.maxpool_bwd_idx(rec.widx, rec.y, g, rec.in_hw, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=relu)
                 else:
-                    g = ops.maxpool_bwd(xin, g, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=relu)
+                    g = ops.maxpool_bwd(rec.x, g, node.attrs["size"], node.attrs["stride"], node.attrs["padding"], relu=relu)
                 masked = relu
             else:
-                _, (sq, e1, e3), xin, s, y = rec
+                sq, e1, e3, xin, s = rec.sq, rec.e1, rec.e3, rec.x, rec.s
                 ne1, ne3, ns = e1.shape[3], e3.shape[3], sq.shape[3]
                 if not masked:
-                    ops.relu_bwd(y, g)      # both expand convs end in ReLU
+                    ops.relu_bwd(rec.y, g)      # both expand convs end in ReLU
                 def expand_wgrads(s=s, g=g, ns=ns, ne1=ne1, ne3=ne3, e1=e1, e3=e3):
                     wg(e1.name, s, g, 1, ns, ne1, dy_coffset=0)
                     wg(e3.name, s, g, 3, ns, ne3, dy_coffset=ne1)
@@ -603,101 +642,31 @@ class SqueezeDetTrainer(_TrainerBase):
                 if need_dx:
                     g = ops.conv2d_bwd_data(ds, bwd(sq.name), relu_of=below)
                     masked = below is not None
-        self._join_wgrad()
-        if wplan is not None:
-            wplan.reduce(gs)
-        elif self.plan_wgrads:
-            self._wplan_put(wkey, ops.WgradPlan(witems))
+        ws.finish()
 
 
 class VGG16ConvDetTrainer(SqueezeDetTrainer):
-    """Training step of VGG16ConvDet (nets/vgg16_convDet.py:31-90 + nn_skeleton.py:285-361).  conv1_1 .. conv2_2 are frozen
-    (:40-50), so the forward up to pool2 runs on the inference graph (its fused conv + pool launches, nothing kept) and the
-    backward stops at conv3_1: a weight gradient, no input gradient.  The trainable region conv3_1 .. conv6 is a linear chain
-    and takes SqueezeDetTrainer's backward.  Its two conv + 2x2 pool pairs (conv3_3 + pool3, conv4_3 + pool4) run as ONE
-    launch that also writes the pool's window index (sqdet_conv2d_maxpool2_nhwc_fwd_idx) where it covers the shape, else as
-    conv + maxpool_nhwc_idx; either way the pool backward reads the index, so the full-resolution conv output is not kept."""
+    """Training step of VGG16ConvDet (nets/vgg16_convDet.py:31-90 + nn_skeleton.py:285-361): SqueezeDetTrainer's chain forward
+    and backward over another region.  conv1_1 .. conv2_2 are frozen (:40-50), so the boundary is pool2, evaluated on the
+    inference graph, and the backward stops at conv3_1: a weight gradient, no input gradient.  The region conv3_1 .. conv6
+    holds two conv + 2x2 pool pairs (conv3_3 + pool3, conv4_3 + pool4): ONE launch that also writes the pool's window index
+    (sqdet_conv2d_maxpool2_nhwc_fwd_idx) where it covers the shape, else conv + maxpool_nhwc_idx."""
+
+    DROPOUT_FOLLOWS_MODEL = False
 
     def __init__(self, model, process_group=None, **kw):
         from .nets import VGG16ConvDet
         if not isinstance(model, VGG16ConvDet):
             raise SqdetError("VGG16ConvDetTrainer trains VGG16ConvDet")
         _TrainerBase.__init__(self, model, process_group, **kw)
-        m = model
-        chain = []
-        n = m.preds
-        while n.op != "placeholder":
-            chain.append(n)
-            n = n.inputs[0]
-        chain.reverse()
+        m, chain = model, _chain(model)
         first = next(i for i, n in enumerate(chain) if n.op == "conv" and m.trainable[n.name + "/kernels"])
-        self.boundary = chain[first].inputs[0]          # the last frozen activation (pool2)
-        self.region = chain[first:]                     # conv / pool / dropout nodes, forward order
-        for n in self.region:
+        for n in chain[first:]:
             if n.op not in ("conv", "pool", "dropout") or (n.op == "conv" and not m.trainable[n.name + "/kernels"]):
                 raise SqdetError("VGG16ConvDetTrainer: unsupported node %s (%s) in the trainable region" % (n.name, n.op))
             if n.op == "pool" and (n.attrs["size"], n.attrs["stride"]) != (2, 2):
                 raise SqdetError("VGG16ConvDetTrainer: pool %s is not 2x2 / stride 2" % n.name)
-        # the conv reading the dropout: its backward is the dropout's too
-        self.drop_conv = next((n.name for n in self.region if n.op == "conv" and n.inputs[0].op == "dropout"), None)
-        kernels = collections.OrderedDict((n.name, self.view[n.name + "/kernels"]) for n in self.region if n.op == "conv")
-        self.packplan = ops.PackPlan(kernels, self.adt, bwd_names=set(kernels) - {chain[first].name})
-        self._frozen_packed = {}
-
-    def forward_backward(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None,
-                         keep_activations=False, num_objects=None, num_objects_is_global=False):
-        m, P = self.model, self.model.params
-        self.packplan.run()
-        (xb,) = m.run([self.boundary], {m.image_input: images}, use_plan=False)
-        B = int(xb.shape[0])
-        t, mask, delta, box, lab, num_objects = self._labels(B, input_mask, box_delta_input, box_input, labels, num_objects, num_objects_is_global)
-        acts = {self.boundary.name: xb}
-        saved, cur, dm, skip = [], xb, None, None
-        for i, n in enumerate(self.region):
-            if n is skip:
-                continue
-            if n.op == "dropout":
-                keep = n.attrs["keep_prob"]
-                if dropout_mask is None:
-                    dropout_mask = self._dropout_mask(cur.shape, keep)
-                dm = self._mask_tensor(dropout_mask, t)
-                cur = ops.scale_mask(cur, dm, 1.0 / keep)
-                acts["drop"] = cur
-            elif n.op == "conv":
-                nxt = self.region[i + 1] if i + 1 < len(self.region) else None
-                pk, bias = self.packplan.fwd[n.name], P[n.name + "/biases"]
-                if (not keep_activations and nxt is not None and nxt.op == "pool" and nxt.attrs["padding"] == "SAME"
-                        and n.attrs["size"] == 3 and n.attrs["stride"] == 1 and n.attrs["padding"] == "SAME"
-                        and ops.conv2d_maxpool2_supported(B, int(cur.shape[1]), int(cur.shape[2]), int(cur.shape[3]),
-                                                          int(n.shape[3]), self.adt)):
-                    # conv + pool + window index in one launch: the conv's output never reaches HBM
-                    y, widx = ops.conv2d_maxpool2_nhwc_idx(cur, pk, bias, n.attrs["relu"])
-                    saved.append(("conv", n, cur, None))
-                    saved.append(("pool", nxt, None, y, widx, tuple(cur.shape[1:3])))
-                    acts[nxt.name] = y
-                    cur, skip = y, nxt
-                    continue
-                y = ops.conv2d_nhwc(cur, pk, bias, n.attrs["stride"], n.attrs["padding"], n.attrs["relu"])
-                saved.append(("conv", n, cur, y))
-                acts[n.name] = y
-                cur = y
-            else:
-                y, widx = ops.maxpool_nhwc_idx(cur, 2, 2, n.attrs["padding"])
-                # the pool's input is not kept: the backward reads the index, y and dy (and masks the conv's ReLU itself)
-                if saved and saved[-1][0] == "conv":
-                    saved[-1] = saved[-1][:3] + (None,)
-                saved.append(("pool", n, None, y, widx, tuple(cur.shape[1:3])))
-                acts[n.name] = y
-                cur = y
-        preds = cur
-        self._join_labels()
-        g, dpreds, ious, losses = self._loss(preds, mask, delta, box, lab, num_objects)
-        self._chain_backward(saved, g, tuple(int(v) for v in xb.shape), self.drop_conv, dm)
-        out = collections.OrderedDict(class_loss=losses[0], conf_loss=losses[1], bbox_loss=losses[2], ious=ious, preds=preds,
-                                      dpreds=dpreds, num_objects=num_objects)
-        if keep_activations:     # names as the oracle's `override`: the conv layer names, pool2, pool3, pool4, drop
-            out["activations"] = acts
-        return out
+        self._set_region(chain[first:], no_bwd=(chain[first].name,))
 
 
 class ResNet50ConvDetTrainer(_TrainerBase):
@@ -762,13 +731,6 @@ class ResNet50ConvDetTrainer(_TrainerBase):
                                           self.gview[n.name + "/gamma"], self.gview[n.name + "/beta"]) for n in convs if n.op == "conv_bn"], eps)
         self._plans_for = self._bn_pointers()
 
-    def step(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None, apply_update=True,
-             keep_activations=False, num_objects=None):
-        with torch.cuda.device(self.dev):
-            out = self.forward_backward(images, input_mask, box_delta_input, box_input, labels, dropout_mask, keep_activations, num_objects)
-            self._finish_step(apply_update)
-        return out
-
     def forward_backward(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None,
                          keep_activations=False, num_objects=None, num_objects_is_global=False):
         m, mc, P = self.model, self.mc, self.model.params
@@ -799,12 +761,7 @@ class ResNet50ConvDetTrainer(_TrainerBase):
                     val[n] = ops.conv2d_nhwc(val[br.inputs[0]], pk[br.name], pbias[br.name], br.attrs["stride"],
                                              br.attrs["padding"], True, residual=val[sc])
             elif n.op == "dropout":
-                x = val[n.inputs[0]]
-                keep = n.attrs["keep_prob"]
-                if dropout_mask is None:
-                    dropout_mask = self._dropout_mask(x.shape, keep)
-                aux[n] = self._mask_tensor(dropout_mask, t)
-                val[n] = ops.scale_mask(x, aux[n], 1.0 / keep)
+                val[n], aux[n] = self._dropout(val[n.inputs[0]], n.attrs["keep_prob"], dropout_mask, t)
             elif n.op == "conv":
                 x = val[n.inputs[0]]
                 val[n] = ops.conv2d_nhwc(x, pk[n.name], P[n.name + "/biases"], n.attrs["stride"], n.attrs["padding"], n.attrs["relu"])
@@ -816,21 +773,13 @@ class ResNet50ConvDetTrainer(_TrainerBase):
         # ---------------- backward ----------------
         self.flat_grads.zero_()
         g = {m.preds: g0}
-        gs = 1.0 / self.loss_scale
-        # weight gradients: partial slabs per conv, ONE reduction (ops.WgradPlan; the folded gradients of the conv_bn convs
-        # land in self.dwf / self.dbf), then ONE fold backward; the first step of an input shape runs the per-conv
-        # two-launch gradient and records what the plan needs
-        wkey = tuple(int(v) for v in xb.shape)
-        wplan = self._wplan_get(wkey)
-        witems = []
+        # weight gradients (_WgradSession): the folded gradients of the conv_bn convs land in self.dwf / self.dbf, ONE fold
+        # backward turns them into d(kernels), d(gamma), d(beta) at the end
+        ws = _WgradSession(self, tuple(int(v) for v in xb.shape))
 
         def wg(n, xt, gt, k, cin, cout):
             dw, db = (self.dwf[n.name], self.dbf[n.name]) if n.op == "conv_bn" else (self.gview[n.name + "/kernels"], self.gview[n.name + "/biases"])
-            if wplan is not None:
-                wplan.partial(n.name, xt, gt)
-                return
-            witems.append((n.name, (int(xt.shape[0]), int(xt.shape[1]), int(xt.shape[2]), cin, cout, k), dw, db, None, 0.0))
-            ops.conv2d_bwd_filter(xt, gt, k, cin, cout, dw=dw, db=db, grad_scale=gs)
+            ws.add(n.name, xt, gt, k, cin, cout, dw, db)
 
         # ReLU backward without a pass of its own: the launch that delivers the LAST contribution to a ReLU output's gradient
         # also zeroes it where that output is <= 0 (conv2d_bwd_data / scale_mask relu_of) -- the bits of a relu_bwd launch
@@ -895,17 +844,10 @@ class ResNet50ConvDetTrainer(_TrainerBase):
                 self._wgrad(lambda x=x, gy=gy, k=k, cin=cin, cout=cout, n=n: wg(n, x, gy, k, cin, cout), gy, x)
                 if stride == 1:
                     give(n.inputs[0], gy, self.packplan.bwd.get(n.name))
-        self._join_wgrad()
-        if wplan is not None:
-            wplan.reduce(gs)
-        elif self.plan_wgrads:
-            self._wplan_put(wkey, ops.WgradPlan(witems))
+        ws.finish()
         self.foldplan.run()      # d(kernels), d(gamma), d(beta) of every conv_bn conv from its folded gradients: two launches
-        out = collections.OrderedDict(class_loss=losses[0], conf_loss=losses[1], bbox_loss=losses[2], ious=ious, preds=preds,
-                                      dpreds=dpreds, num_objects=num_objects)
-        if keep_activations:     # names as oracle/resnet_oracle.py forward_train's `override`
-            out["activations"] = {n.name: v for n, v in val.items()}
-        return out
+        # (activation names as oracle/resnet_oracle.py forward_train's `override`)
+        return self._result(losses, ious, preds, dpreds, num_objects, {n.name: v for n, v in val.items()} if keep_activations else None)
 
 
 class GraphedStep:
@@ -923,8 +865,7 @@ class GraphedStep:
         self.tr, self.anchors, self.classes = trainer, anchors_f64, int(classes)
         self.graph, self.static, self.out, self.key = None, None, None, None
         self.cache = {}      # (loss scale, input shape) -> (graph, static buffers, outputs): a scale seen before is not re-captured
-        if not hasattr(trainer, "_graphed"):
-            trainer._graphed = weakref.WeakSet()
+        self.eager_nobj = False      # global_num_objects at world > 1 (set by _capture, restored with a cached graph)
         trainer._graphed.add(self)                        # (load_state_dict resets the captured steps of its trainer)
 
     def reset(self):
@@ -983,9 +924,8 @@ class GraphedStep:
             st = self.static
             st["x"].copy_(x); st["gt"].copy_(gt); st["gcls"].copy_(gcls); st["gcnt"].copy_(gcnt)
             if tr.model.keep_prob != 1.0:
-                tr._mask_calls += 1
-                ops.dropout_mask_into(st["mask"], tr.model.keep_prob, (tr.seed << 32) + tr._mask_calls)
-            if getattr(self, "eager_nobj", False):
+                ops.dropout_mask_into(st["mask"], tr.model.keep_prob, tr._next_mask_seed())
+            if self.eager_nobj:
                 mask = ops.build_labels(self.anchors, st["gt"], st["gcls"], st["gcnt"], self.classes)[0]
                 ops.sum_f32(mask, out=st["nobj"])
                 reduce_num_objects(st["nobj"], tr.world, tr.pg)

@@ -1,11 +1,18 @@
 #!/usr/bin/env python
-"""SqueezeDet image demo on MI355X: the py3 / HIP counterpart of the reference's src/demo.py image_demo
-(:160-225) -- same call shape (`sess.run([det_boxes, det_probs, det_class], {image_input: [im]})`,
+"""SqueezeDet demo on MI355X: the py3 / HIP counterpart of the reference's src/demo.py -- image_demo (:160-225) and
+video_demo (:44-158) -- same call shape (`sess.run([det_boxes, det_probs, det_class], {image_input: [im]})`,
 `model.filter_prediction`, PLOT_PROB_THRESH, class colours) with the image preparation (float cast, bilinear
 resize to the network input, BGR mean subtraction, demo.py:186-190) done by sqdet_preprocess_bgr on the GPU.
-cv2 is replaced by PIL for file I/O and drawing.
+cv2 is replaced by PIL for file I/O.
 
-    python demo.py --input_path 'data/*.png' --out_dir out/ [--weights weights.npz] [--demo_net squeezeDet]
+    python demo.py --input_path 'data/*.png' --out_dir out/ [--weights weights.npz] [--demo_net squeezeDet] [--draw gpu]
+    python demo.py --mode video --input_path 'frames/*.png' --out_dir out/ [--crop 500 205 239 439] [--batch 8]
+
+--draw pil (default): boxes and labels are drawn with PIL on a host-resized copy of the image.  --draw gpu: they are drawn on
+the device into the preprocessed network input (squeezedet_amd.viz: one launch, the means added back), in the reference's
+cls2clr colours.  --mode video takes a glob of FRAME FILES, sorted by name -- there is no video decoder here -- crops them
+(--crop TOP BOTTOM LEFT RIGHT rows / columns cut off, the reference's frame[500:-205, 239:-439]), runs them in batches of
+--batch with everything from the mean subtraction to the drawing on the device, and writes <out_dir>/%06d.jpg per frame.
 
 --weights: a {variable name: array} file written by squeezedet_amd.weights.save_params (or converted from a
 reference checkpoint with squeezedet_amd.weights.from_reference_names); without it seeded synthetic weights
@@ -15,9 +22,11 @@ the whole path runs.
 import argparse
 import glob
 import os
+import time
 
 import numpy as np
-import torch
+
+CLS2CLR = {"car": (255, 191, 0), "cyclist": (0, 191, 255), "pedestrian": (255, 0, 191)}      # BGR (demo.py:123-127)
 
 
 def draw_boxes(img_rgb, boxes, labels, cdict):
@@ -32,45 +41,141 @@ def draw_boxes(img_rgb, boxes, labels, cdict):
     return img_rgb
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--input_path", default="./data/sample.png", help="glob of input images")
+    ap.add_argument("--mode", default="image", choices=["image", "video"],
+                    help="video: --input_path is a glob of frame files, sorted by name (there is no video decoder on this platform)")
+    ap.add_argument("--input_path", default="./data/sample.png", help="glob of input images / frames")
     ap.add_argument("--out_dir", default="./data/out/")
     ap.add_argument("--demo_net", default="squeezeDet", choices=["squeezeDet", "squeezeDet+", "resnet50", "vgg16"])
     ap.add_argument("--weights", default="")
     ap.add_argument("--gpu", default="0")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
-    a = ap.parse_args()
-    from PIL import Image
+    ap.add_argument("--draw", default="pil", choices=["pil", "gpu"], help="image mode: draw with PIL on the host, or on the device")
+    ap.add_argument("--crop", type=int, nargs=4, default=[500, 205, 239, 439], metavar=("T", "B", "L", "R"),
+                    help="video: rows cut off the top / bottom and columns off the left / right of every frame")
+    ap.add_argument("--batch", type=int, default=1, help="video: frames per forward pass")
+    a = ap.parse_args(argv)
+    if a.mode == "video":
+        assert a.demo_net in ("squeezeDet", "squeezeDet+"), "Selected nueral net architecture not supported: {}".format(a.demo_net)
+        if a.batch < 1 or min(a.crop) < 0:
+            ap.error("--batch must be positive, --crop non-negative")
+    return a
+
+
+def make_model(a, batch):
+    import torch
     import squeezedet_amd as S
-    from squeezedet_amd import nets, ops, synthetic, weights
-    from squeezedet_amd.nn_skeleton import Session
+    from squeezedet_amd import nets, synthetic, weights
     mc, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
                "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[a.demo_net]
     mc = mc()
-    mc.BATCH_SIZE = 1
+    mc.BATCH_SIZE = int(batch)
     mc.LOAD_PRETRAINED_MODEL = False          # parameters are restored below (demo.py:171-172)
     dtype = torch.float16 if a.dtype == "fp16" else torch.float32
     model = cls(mc, a.gpu, dtype=dtype)
     model.load_params(weights.load_params(a.weights) if a.weights else synthetic.synthetic_params(model, seed=0))
+    return mc, model, dtype
+
+
+def read_bgr(path):
+    """uint8 BGR [H, W, 3], what cv2.imread returns."""
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])
+
+
+def detect_and_draw(model, input_image, n):
+    """The first n images of the network input with their detections above PLOT_PROB_THRESH drawn, all on the device: detect,
+    filter_prediction, the item build (the reference's cls2clr as the per-class table, "<name>: (<prob>)") and one draw launch
+    -> (uint8 RGB [n, H, W, 3] device tensor, counts of drawn boxes [n] device tensor)."""
+    from squeezedet_amd import viz
+    mc = model.mc
+    det_boxes, det_probs, det_class = model.detect(input_image)
+    ob, op, oc, _, cnt = model.filter_prediction_batch(det_boxes[:n].contiguous(), det_probs[:n].contiguous(), det_class[:n].contiguous())
+    items = viz.make_items(ob, oc, cnt, list(mc.CLASS_NAMES), probs=op, plot_thresh=mc.PLOT_PROB_THRESH,
+                           class_colors=[CLS2CLR.get(c, (0, 255, 0)) for c in mc.CLASS_NAMES], label="name: (p)")
+    return viz.draw(input_image[:n].contiguous(), items, bgr_means=mc.BGR_MEANS, order="rgb"), items.counts
+
+
+def image_demo(a):
+    import torch
+    from PIL import Image
+    from squeezedet_amd import ops
+    from squeezedet_amd.nn_skeleton import Session
+    mc, model, dtype = make_model(a, 1)
     os.makedirs(a.out_dir, exist_ok=True)
-    cls2clr = {"car": (255, 191, 0), "cyclist": (0, 191, 255), "pedestrian": (255, 0, 191)}
     with Session() as sess:
         for f in glob.iglob(a.input_path):
-            rgb = np.asarray(Image.open(f).convert("RGB"))
-            bgr = torch.from_numpy(np.ascontiguousarray(rgb[:, :, ::-1])).to(model.device)       # what cv2.imread returns
+            bgr_host = read_bgr(f)
+            bgr = torch.from_numpy(bgr_host).to(model.device)
             input_image = ops.preprocess_bgr(bgr[None], mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, dtype)
-            det_boxes, det_probs, det_class = sess.run([model.det_boxes, model.det_probs, model.det_class],
-                                                       feed_dict={model.image_input: input_image})
-            final_boxes, final_probs, final_class = model.filter_prediction(det_boxes[0], det_probs[0], det_class[0])
-            keep = [i for i in range(len(final_probs)) if final_probs[i] > mc.PLOT_PROB_THRESH]
-            labels = [mc.CLASS_NAMES[final_class[i]] + ": (%.2f)" % final_probs[i] for i in keep]
-            # boxes are in network-input coordinates: draw on the resized image like the reference does
-            im = Image.fromarray(rgb).resize((mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT), Image.BILINEAR)
-            draw_boxes(im, [final_boxes[i] for i in keep], labels, cls2clr)
             out = os.path.join(a.out_dir, "out_" + os.path.split(f)[1])
-            im.save(out)
-            print("Image detection output saved to {} ({} boxes above {:.2f})".format(out, len(keep), mc.PLOT_PROB_THRESH))
+            if a.draw == "gpu":
+                pics, counts = detect_and_draw(model, input_image, 1)
+                Image.fromarray(pics[0].cpu().numpy()).save(out)
+                nbox = int(counts[0])
+            else:
+                det_boxes, det_probs, det_class = sess.run([model.det_boxes, model.det_probs, model.det_class],
+                                                           feed_dict={model.image_input: input_image})
+                final_boxes, final_probs, final_class = model.filter_prediction(det_boxes[0], det_probs[0], det_class[0])
+                keep = [i for i in range(len(final_probs)) if final_probs[i] > mc.PLOT_PROB_THRESH]
+                labels = [mc.CLASS_NAMES[final_class[i]] + ": (%.2f)" % final_probs[i] for i in keep]
+                # boxes are in network-input coordinates: draw on the resized image like the reference does
+                im = Image.fromarray(np.ascontiguousarray(bgr_host[:, :, ::-1])).resize((mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT), Image.BILINEAR)
+                draw_boxes(im, [final_boxes[i] for i in keep], labels, CLS2CLR)
+                im.save(out)
+                nbox = len(keep)
+            print("Image detection output saved to {} ({} boxes above {:.2f})".format(out, nbox, mc.PLOT_PROB_THRESH))
+
+
+def video_demo(a):
+    """video_demo of src/demo.py:44-158 over frame files, --batch frames at a time.  A cropped frame that is not of the network's
+    input size is resized to it by the preprocessing, and the boxes are drawn on that input (the reference feeds the crop as it is)."""
+    import torch
+    from PIL import Image
+    from squeezedet_amd import ops
+    mc, model, dtype = make_model(a, a.batch)
+    os.makedirs(a.out_dir, exist_ok=True)
+    frames = sorted(glob.glob(a.input_path))
+    top, bottom, left, right = a.crop
+    count = 0
+    for i0 in range(0, len(frames), a.batch):
+        t_start = time.time()
+        crops = []
+        for f in frames[i0:i0 + a.batch]:
+            frame = read_bgr(f)
+            frame = frame[top:frame.shape[0] - bottom, left:frame.shape[1] - right, :]
+            assert frame.size, "--crop {} leaves nothing of {} ({} x {})".format(a.crop, f, *read_bgr(f).shape[:2])
+            crops.append(frame)
+        n = len(crops)
+        crops += [crops[-1]] * (a.batch - n)               # the last batch is padded with its last frame
+        batch = torch.from_numpy(np.stack(crops)).to(model.device)
+        input_image = ops.preprocess_bgr(batch, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, dtype)     # mean subtraction on the device
+        torch.cuda.synchronize(model.device)
+        t_reshape = time.time()
+        det = model.detect(input_image)
+        torch.cuda.synchronize(model.device)
+        t_detect = time.time()
+        ob, op, oc, _, cnt = model.filter_prediction_batch(det[0][:n].contiguous(), det[1][:n].contiguous(), det[2][:n].contiguous())
+        torch.cuda.synchronize(model.device)
+        t_filter = time.time()
+        from squeezedet_amd import viz
+        items = viz.make_items(ob, oc, cnt, list(mc.CLASS_NAMES), probs=op, plot_thresh=mc.PLOT_PROB_THRESH,
+                               class_colors=[CLS2CLR.get(c, (0, 255, 0)) for c in mc.CLASS_NAMES], label="name: (p)")
+        pics = viz.draw(input_image[:n].contiguous(), items, bgr_means=mc.BGR_MEANS, order="rgb").cpu().numpy()
+        for im in pics:
+            count += 1
+            Image.fromarray(im).save(os.path.join(a.out_dir, str(count).zfill(6) + ".jpg"))
+        print("Total time: {:.4f}, detection time: {:.4f}, filter time: {:.4f}".format(time.time() - t_start, t_detect - t_reshape,
+                                                                                        t_filter - t_detect))
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    if a.mode == "video":
+        video_demo(a)
+    else:
+        image_demo(a)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,9 @@ filter_prediction, then the rows added to the detection table -- here a whole ba
 (filter_prediction_batch, squeezedet_amd.kitti_ap.KittiEvaluator).  The table is scored by the GPU KITTI evaluator
 (or, with --eval_tool, by an external evaluate_object binary through kitti_eval.evaluate_detections).  Outputs under
 --eval_dir: detection_files_<step>/data/*.txt, the evaluator's stats_<cls>_{ap,detection}.txt, error_analysis/
-det_error_file.txt, and one JSON line per checkpoint in eval_log.jsonl (in place of TF summaries).
+det_error_file.txt, and one JSON line per checkpoint in eval_log.jsonl (in place of TF summaries).  --visualize N: N example
+detections per error type of that file, each drawn on the device over its original image (imdb.visualize_detections) to
+error_analysis/<type>/<i>.png; the rows are chosen by a permutation seeded with --seed.
 
 Checkpoints are .npz files from squeezedet_amd.weights.save_params.  --run_once: --checkpoint_path is that file;
 otherwise it is a directory polled every --eval_interval_secs for the newest '*-<step>.npz'.  Every image is scored
@@ -40,6 +42,9 @@ def parse_args(argv=None):
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16"], help="storage type of the forward pass")
     ap.add_argument("--eval_tool", default="", help="score with this evaluate_object binary instead of the GPU evaluator")
     ap.add_argument("--synthetic_weights", action="store_true", help="seeded synthetic weights instead of a checkpoint")
+    ap.add_argument("--visualize", type=int, default=0, metavar="N",
+                    help="draw N example detections per error type of the error analysis (the reference draws 10; 0: none)")
+    ap.add_argument("--seed", type=int, default=0, help="seeds the choice of the rows --visualize draws")
     return ap.parse_args(argv)
 
 
@@ -92,6 +97,43 @@ def rescale_boxes(det_boxes, scales):
     n = len(scales)
     s = torch.tensor(np.tile(np.asarray(scales, np.float32).reshape(n, 1, 2), (1, 1, 2)), device=det_boxes.device)  # x, y, x, y
     return det_boxes[:n] / s
+
+
+VIS_COLOR = (200, 200, 0)       # RGB (imdb.py:285)
+
+
+def visualize_detections(image_dir, image_format, det_error_file, output_image_dir, num_det_per_type, seed, device):
+    """imdb.visualize_detections (src/dataset/imdb.py:254-305): num_det_per_type rows per error type of det_error_file, each
+    drawn over its original-size image -- rectangle and "<class> (<score>)" at its top-left corner, colour (200, 200, 0) RGB --
+    to <output_image_dir>/<type>/<i>.png.  The image goes to the device as uint8 and is drawn there (squeezedet_amd.viz).  The
+    reference shuffles the lines with random.shuffle; here their order is RandomState(seed).permutation, so that a run can
+    be repeated.  Returns [(error type, i, line number)] of what was drawn."""
+    import shutil
+    import torch
+    from PIL import Image
+    from squeezedet_amd import viz
+    with open(det_error_file) as f:
+        lines = f.read().splitlines()
+    dets_per_type = {}
+    for k in np.random.RandomState(seed).permutation(len(lines)):
+        obj = lines[k].strip().split(" ")
+        dets_per_type.setdefault(obj[1], []).append((int(k), obj))
+    drawn = []
+    for error_type, dets in dets_per_type.items():
+        det_im_dir = os.path.join(output_image_dir, error_type)
+        if os.path.exists(det_im_dir):
+            shutil.rmtree(det_im_dir)
+        os.makedirs(det_im_dir)
+        for i, (k, obj) in enumerate(dets[:num_det_per_type]):
+            rgb = np.asarray(Image.open(os.path.join(image_dir, obj[0] + image_format)).convert("RGB"))
+            bgr = torch.from_numpy(np.ascontiguousarray(rgb[None, :, :, ::-1])).to(device)
+            x0, y0, x1, y1 = (int(float(v)) for v in obj[2:6])
+            label = "{:s} ({:.2f})".format(obj[6], float(obj[7]))
+            items = viz.pack_items([[(x0, y0, x1, y1, VIS_COLOR[::-1], label, "top_left")]], device)
+            pic = viz.draw(bgr, items, order="rgb")
+            Image.fromarray(pic[0].cpu().numpy()).save(os.path.join(det_im_dir, str(i) + image_format))
+            drawn.append((error_type, i, k))
+    return drawn
 
 
 def eval_once(a, model, data, ckpt_path, evaluator):
@@ -157,7 +199,12 @@ def eval_once(a, model, data, ckpt_path, evaluator):
 
     print("Analyzing detections...")
     stats = evaluator.analyze()
-    evaluator.write_error_file(os.path.join(result_dir, "error_analysis", "det_error_file.txt"), data.image_idx)
+    det_error_file = os.path.join(result_dir, "error_analysis", "det_error_file.txt")
+    evaluator.write_error_file(det_error_file, data.image_idx)
+    if a.visualize > 0:
+        drawn = visualize_detections(os.path.dirname(data.image_paths[0]), ".png", det_error_file, os.path.dirname(det_error_file),
+                                     a.visualize, a.seed, model.device)
+        print("Visualized {} detections under {}".format(len(drawn), os.path.dirname(det_error_file)))
     print("Detection Analysis:")
     print("    Number of detections: {}".format(stats["num of detections"]))
     print("    Number of objects: {}".format(stats["num of objects"]))

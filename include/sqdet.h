@@ -664,6 +664,69 @@ int sqdet_tensor_stats_many(const void* base, int64_t base_count, const int64_t*
                             int n_segments, const float* edges_dev, int n_bins, void* records_dev, void* workspace,
                             int dtype, sqdet_stream_t stream);
 
+/* ------------------------------------------------------------ drawing --
+ * Boxes and labels drawn into a batch of images that is already on the device: the reference's _draw_box of the training
+ * image summary (src/train.py:51-99), the rectangle + text of imdb.visualize_detections (src/dataset/imdb.py:254-305) and
+ * of the demos (src/demo.py), which draw with cv2 / PIL on the host, one image at a time.
+ *
+ * An ITEM is SQDET_DRAW_ITEM_BYTES (64) bytes:
+ *   int32 x0, y0, x1, y1   a rectangle, corners in either order, any value (used clamped to +-2^30)
+ *   uint8 b, g, r          its colour, BGR like the images
+ *   uint8 anchor           SQDET_DRAW_BOTTOM_LEFT: the label's text cell has its left column at x0 and its bottom row at y1
+ *                          (where _draw_box puts its text); SQDET_DRAW_TOP_LEFT: the cell starts at (x0, y0) (visualize_detections)
+ *   int32 label_len        0 .. SQDET_DRAW_LABEL_MAX (used clamped to that range)
+ *   char  label[32]        bytes; 8 bytes of padding follow
+ * An item TABLE is [n, cap] items (16-byte aligned) + int32 counts [n]: image i draws its first clamp(counts[i], 0, cap) rows.
+ *
+ * sqdet_draw_items: out uint8 [n,h,w,3] = the images with the items of up to SQDET_DRAW_MAX_TABLES tables drawn over them,
+ * table after table, row after row (painter's order: a later item overwrites an earlier one; an item is its rectangle, then
+ * its label).  ONE launch; every output pixel GATHERS its value from the tables, so the result does not depend on scheduling.
+ *   images  in_type SQDET_F32 / SQDET_F16: the network input [n,h,w,3], mean-subtracted BGR; a pixel is restored as
+ *           rint(float32(x) + float32(host_bgr_means[c])) (half to even), clamped to [0, 255].  SQDET_DRAW_U8: uint8 BGR
+ *           [n,h,w,3], taken as it is (host_bgr_means is not read; out may be the images themselves).
+ *   rgb_out 0: out is BGR; 1: out is RGB (channels reversed, colours with them).
+ *   rectangle: one pixel wide, the set cv2.rectangle(.., 1) paints -- x in {x0, x1} and min(y0,y1) <= y <= max(y0,y1), or
+ *           y in {y0, y1} and min(x0,x1) <= x <= max(x0,x1) -- clipped to the image.
+ *   label:  character k occupies the 6x8 cell k cells to the right of the anchor cell; its 5x7 glyph (sqdet_draw_font5x7) sits
+ *           in columns 1..5 and rows 0..6 of the cell; set glyph bits take the item's colour, everything else keeps what is
+ *           under it.  Bytes outside ASCII 32..126 draw as '?'.  Clipped to the image.
+ * item_tables / item_counts / caps: HOST arrays of n_tables device pointers / capacities.  The capacities together may not
+ * exceed SQDET_DRAW_MAX_ITEMS (256), nor n*h*w 2^31 - 1: SQDET_EUNSUPPORTED.
+ *
+ * sqdet_draw_build_items: item rows from box rows, on the device.  boxes [n,rows,4] float32 (boxes_f64 = 0: the out_boxes of
+ * sqdet_detect_filter / sqdet_filter_prediction) or float64 (1: a ground-truth table); cls int32 [n,rows]; counts int32 [n]
+ * (used clamped to [0, rows]); probs float32 [n,rows] or NULL.  Image i keeps, in order, its rows j < counts[i] with
+ * double(probs[i,j]) > plot_thresh (all of them when probs is NULL; the reference compares a float32 with a Python float,
+ * i.e. in double) and writes them to items [n,cap]; item_counts[i] = their number.
+ *   coordinates  diagonal = 0: int() -- truncation toward zero -- of cx - w/2, cy - h/2, cx + w/2, cy + h/2 (util.bbox_transform)
+ *           computed in the boxes' own precision; diagonal = 1: int() of the four values as they are.  NaN -> 0.
+ *   colour  class_bgr (device uint8 [classes,3], the reference's cdict) where it is given and the class is in range, else
+ *           (b, g, r).
+ *   label   names: device bytes [classes, SQDET_DRAW_NAME_BYTES], NUL-padded ('?' for a class out of range).  label_format
+ *           SQDET_DRAW_LABEL_NAME: "<name>"; _NAME_COLON_PROB: "<name>: (%.2f)"; _NAME_PROB: "<name> (%.2f)" of
+ *           double(float32 prob) with the digits Python's '%' prints (|prob| >= 1e7: "?.??"); cut at SQDET_DRAW_LABEL_MAX bytes.
+ * rows > cap or cap > SQDET_DRAW_MAX_ITEMS: SQDET_EUNSUPPORTED.  Both calls are asynchronous, allocate nothing and validate
+ * their arguments before they touch the device.
+ *
+ * sqdet_draw_font5x7: the font, 95 glyphs (ASCII 32..126) x 7 rows, one byte per row, bit 4 = leftmost column, into
+ * host_out (capacity >= 665 bytes).  The table is this project's own (csrc/font5x7.h). */
+enum { SQDET_DRAW_U8 = 2 };
+enum { SQDET_DRAW_BOTTOM_LEFT = 0, SQDET_DRAW_TOP_LEFT = 1 };
+enum { SQDET_DRAW_LABEL_NAME = 0, SQDET_DRAW_LABEL_NAME_COLON_PROB = 1, SQDET_DRAW_LABEL_NAME_PROB = 2 };
+#define SQDET_DRAW_ITEM_BYTES 64
+#define SQDET_DRAW_MAX_ITEMS 256
+#define SQDET_DRAW_MAX_TABLES 4
+#define SQDET_DRAW_LABEL_MAX 31
+#define SQDET_DRAW_NAME_BYTES 32
+int sqdet_draw_items(const void* images, unsigned char* out, int in_type, int n, int h, int w, const float* host_bgr_means,
+                     int rgb_out, const void* const* item_tables, const int32_t* const* item_counts, const int* caps,
+                     int n_tables, sqdet_stream_t stream);
+int sqdet_draw_build_items(const void* boxes, int boxes_f64, const float* probs, const int32_t* cls, const int32_t* counts,
+                           int n, int rows, int diagonal, double plot_thresh, const unsigned char* names, int classes,
+                           const unsigned char* class_bgr, int b, int g, int r, int label_format, int anchor, void* items,
+                           int32_t* item_counts, int cap, sqdet_stream_t stream);
+int sqdet_draw_font5x7(unsigned char* host_out, size_t capacity);
+
 /* ------------------------------------------------------------ utilities --
  * Device -> pinned-host copy issued as a KERNEL: dst is host memory mapped into the device's address space
  * (hipHostMalloc); nbytes a multiple of 16.  Used by the serving loop to hand the <= 64 filtered rows per image

@@ -55,6 +55,9 @@ SOURCES = [
     ("train.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: sumsq adds the exact float64 square; nothing to contract, and the sums keep the order written)
     ("summary.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the pixel restore rint(x + mean) and bbox_transform's cx - w/2 are single roundings, the label's '%.2f' is
+    # kitti_eval.hip's rounding)
+    ("draw.hip", ["-ffp-contract=off"]),
     ("wgrad.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     # (the calibration loops: hipcc's default AGPR form ROTATES the 16x16x32 loop's accumulators -- a[24:27] = mfma(.., a[22:25]) plus
     # v_accvgpr copies inside the loop -- so consecutive MFMAs depend on each other and the "bare MFMA loop" of rounds 3-4 read half

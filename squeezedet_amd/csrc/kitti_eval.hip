@@ -12,6 +12,7 @@
 // Everything is double precision with -ffp-contract=off (build.py): overlaps, recall steps and the rounding are bitwise
 // those of the host programs.  Counts are integer atomics, so results do not depend on scheduling.
 #include "common.h"
+#include "round_decimal.h"   // '%.2f' / '%.3f' as the detection files carry them
 
 namespace sqdet {
 namespace {
@@ -57,16 +58,6 @@ __device__ __forceinline__ double box_overlap(const double* a, const double* b, 
   if (criterion == 0) return inter / a_area;
   const double b_area = (b[2] - b[0]) * (b[3] - b[1]);
   return inter / (a_area + b_area - inter);
-}
-
-// The double nearest to the decimal that Python's '%.<d>f' prints for v (scale = 10^d): the integer is v * scale rounded
-// half-to-even on the EXACT product (fma gives the product's rounding error, which decides a tie of the rounded product).
-__device__ __forceinline__ double round_decimal(double v, double scale) {
-  const double p = v * scale;
-  const double e = __builtin_fma(v, scale, -p);
-  double k = __builtin_rint(p);
-  if (__builtin_fabs(p - k) == 0.5 && e != 0) k = e > 0 ? __builtin_floor(p) + 1.0 : __builtin_floor(p);
-  return k / scale;
 }
 
 __device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }

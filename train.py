@@ -8,13 +8,14 @@ with on-device summaries.
 
 Per step as the reference (train.py:266-330): a summary step (step % summary_step == 0) runs the eager trainer step with the
 activations kept and hands it to squeezedet_amd.summary.TrainSummary (-> <train_dir>/summaries.jsonl, in place of TF event
-files); every other step is a hipGraph replay (squeezedet_amd.train.GraphedStep) unless --no_graph.  A checkpoint -- written
-at step % checkpoint_step == 0 and at the last step, named by the step -- is the pair model.ckpt-<step>.npz (what eval.py
-polls for and demo.py --weights reads) + state/step-<step>.npz (squeezedet_amd.checkpoint); --resume continues from the
-newest pair bit for bit.  <train_dir>/model_metrics.txt is the reference's (train.py:137-159).
+files) and, with --image_summary N, the first N images of its batch with ground truth and detections drawn on the device to
+squeezedet_amd.viz.ImageSummary (-> <train_dir>/images/step-<step>/<i>.png); every other step is a hipGraph replay
+(squeezedet_amd.train.GraphedStep) unless --no_graph.  A checkpoint -- written at step % checkpoint_step == 0 and at the last
+step, named by the step -- is the pair model.ckpt-<step>.npz (what eval.py polls for and demo.py --weights reads) +
+state/step-<step>.npz (squeezedet_amd.checkpoint); --resume continues from the newest pair bit for bit.  <train_dir>/model_metrics.txt is the reference's (train.py:137-159).
 
 The reference deletes --train_dir at start (train.py:338-340).  Here a non-empty --train_dir is refused unless --resume
-or --overwrite (delete, as the reference does).  Not carried over: the image summary with drawn boxes and Pascal VOC.
+or --overwrite (delete, as the reference does).  Not carried over: Pascal VOC.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
 import argparse
@@ -52,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N seeded synthetic KITTI-sized images")
     ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="network input size (default: the net's)")
     ap.add_argument("--loss_scale", type=float, default=1024.0, help="fp16: the initial loss scale")
+    ap.add_argument("--image_summary", type=int, default=0, metavar="N",
+                    help="at summary steps, write the first N images of the batch with ground truth and detections drawn (0: none)")
     a = ap.parse_args(argv)
     assert a.dataset == "KITTI", "Currently only supports KITTI dataset"
     if a.resume and a.overwrite:
@@ -176,6 +179,11 @@ class Run:
         self.anchors = torch.from_numpy(np.asarray(mc.ANCHOR_BOX, np.float64)).to(dev)
         self.stepper = None if a.no_graph else GraphedStep(self.tr, self.anchors, mc.CLASSES)
         self.summary = TrainSummary(self.tr, a.train_dir, write=(rank == 0)) if a.summary_step > 0 else None
+        # (reads the summary step's batch and preds, nothing of the trainer or the reader: a run with it is bitwise the run without)
+        self.images = None
+        if a.image_summary > 0 and a.summary_step > 0 and rank == 0:
+            from squeezedet_amd.viz import ImageSummary
+            self.images = ImageSummary(mc, a.train_dir, a.image_summary, device=dev)
         self._wd_plan = None
 
     def total_loss(self, out):
@@ -205,11 +213,15 @@ class Run:
             out = self.stepper.step(b.image_input, b.gt_boxes, b.gt_classes, b.gt_counts)
         if is_summary:
             summary.record(step, out, lr)
+            if self.images is not None:
+                self.images.record(step, b, out["preds"])
             if self.rank == 0:
                 print("conf_loss: {}, bbox_loss: {}, class_loss: {}".format(float(out["conf_loss"]), float(out["bbox_loss"]),
                                                                            float(out["class_loss"])))
         elif summary is not None:
             summary.poll()
+            if self.images is not None:
+                self.images.poll()
         if step % 10 == 0:
             loss_value = self.total_loss(out)               # (reads the device: the step has finished)
             duration = time.time() - start_time
@@ -235,8 +247,12 @@ class Run:
         try:
             self.tr.flush()
         finally:
-            if self.summary is not None:
-                self.summary.close()
+            try:
+                if self.summary is not None:
+                    self.summary.close()
+            finally:
+                if self.images is not None:
+                    self.images.close()
 
 
 def train(a):

@@ -4,7 +4,7 @@
 // with x = conv2d(in, W) [+ biases]; mean / var are non-trainable variables (:437-438), so the whole
 // thing is the conv with W[..., c] * inv[c] and bias (biases[c] - mean[c]) * inv[c] + beta[c].
 // A load-time transform: one pass over the kernel, HBM-streaming, one thread per 4 output channels.
-#include "common.h"
+#include "launch.h"
 
 namespace sqdet {
 

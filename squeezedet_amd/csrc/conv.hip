@@ -281,12 +281,6 @@ static int dispatch_mt(ConvArgs& a, int nt, bool gather, hipStream_t st) {
   }
 }
 
-int conv2d_launch_ex(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
-                     int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
-                     int x_cstride, int x_coffset, int accum, hipStream_t st);
-int conv2d_launch_masked(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
-                         int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
-                         int x_cstride, int x_coffset, int accum, const void* relu_of, hipStream_t st);
 int conv2d_launch_res(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
                       int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
                       int x_cstride, int x_coffset, int accum, const void* relu_of, const void* res, hipStream_t st);

@@ -232,7 +232,7 @@ bool conv2d_maxpool2_eligible(int n, int h, int w, int cin, int cout, int dtype)
 }
 
 int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
-                           int relu, int dtype, hipStream_t st, unsigned char* widx = nullptr) {
+                           int relu, int dtype, hipStream_t st, unsigned char* widx) {
   SQDET_REQUIRE(x && w_packed && bias && y, "conv2d_maxpool2: null pointer");
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "conv2d_maxpool2: bad dtype %d", dtype);
   SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && cout > 0, "conv2d_maxpool2: bad dims");

@@ -1,6 +1,7 @@
-// Shared device helpers of the conv kernels (conv.hip, conv3x3.hip).
+// Shared device helpers of the conv kernels (conv.hip, conv3x3.hip); their host-side launchers are declared in launch.h.
 #pragma once
 #include "common.h"
+#include "launch.h"
 
 namespace sqdet {
 
@@ -87,67 +88,5 @@ __device__ __forceinline__ void store_couts(T* dst, const f32x4 (&v)[NT], int nt
       if (t < nt_valid) store4<T>(dst + t * 4, v[t]);
   }
 }
-
-// Which kernel family conv2d_launch may pick: 0 = auto (fast paths when eligible),
-// 1 = generic only (conv_direct / conv_gather).  Set from SQDET_CONV_ALGO=generic (tests, A/B).
-int conv_algo();
-// experiment knobs set through sqdet_set_option (0 = built-in heuristic)
-// fire_fuse: 0 / 1 = a fire module is one fused launch wherever a fused kernel takes it (the default since round 5), 2 = never,
-// 10 = the round-1..4 rule (only maps of <= 100 k pixels); stem_algo: 0 phase kernel (stem4.hip), else persistent strip-lane kernel (stem3.hip), else strip kernel (in-register pool), whichever is eligible first; 3 skips the phase kernel; 2 strip kernel only
-// conv_pool: 1 (the default) = a 3x3 conv followed by a 2x2/s2 SAME max-pool is one launch of conv3x3_tile's POOL2 form wherever it
-// takes the shape (plans and sqdet_conv2d_maxpool2_*), 0 = never
-// g1_wr / g1_mbw / g1_ntw: conv1x1_pipe's wave layout (waves along the pixel blocks: 1, 2, 4), pixel blocks per wave (2, 4, 8) and cout tiles per wave -- tools/g1_sweep.py
-enum { TUNE_C1_WAVES = 0, TUNE_C1_MT = 1, TUNE_C1_MIN_TILES = 2, TUNE_FIRE_FUSE = 3, TUNE_STEM_ALGO = 4, TUNE_DBG = 5, TUNE_G1_WR = 6, TUNE_G1_MBW = 7, TUNE_G1_NTW = 8, TUNE_G1_NS = 9,
-       TUNE_CONV_POOL = 10 };
-int tune(int which);
-
-// fire2.hip: persistent streaming fused fire for the large, few-channel modules
-bool fire_stream_eligible(int cin, int s, int e1, int e3, int dtype);
-// (the *_keep forms also write the module's squeeze tensor: training)
-int fire_stream_launch_keep(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                            const float* b3, void* sq_out, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                            hipStream_t st, bool* handled);
-int fire_fused_launch_keep(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                           const float* b3, void* sq_out, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                           hipStream_t st, bool* handled);
-int fire_stream_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                       const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                       hipStream_t st, bool* handled);
-// pool != 0: fire module + max_pool 3x3/s2/SAME in one launch; y is the pooled tensor
-int fire_stream_launch_ex(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                          const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                          int pool, hipStream_t st, bool* handled);
-// the expand half of a fire module from its squeeze tensor (+ the 3x3/s2 SAME max-pool behind it when pool != 0)
-bool fire_expand_stream_eligible(int s, int e1, int e3, int dtype);
-int fire_expand_stream_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3, void* y,
-                              int n, int h, int w, int s, int e1, int e3, int dtype, int pool, hipStream_t st, bool* handled);
-// whole fire module from x, its concat tensor replaced by the NEXT module's squeeze tensor (fire2 / fire4 of SqueezeDet)
-bool fire_squeeze_next_eligible(int cin, int s, int e1, int e3, int s2, int dtype);
-int fire_squeeze_next_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                             const float* b3, const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int cin,
-                             int s, int e1, int e3, int s2, int dtype, hipStream_t st, bool* handled);
-bool fire_expand_squeeze_next_eligible(int s, int e1, int e3, int s2, int pool, int dtype);
-int fire_expand_squeeze_next_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3,
-                                    const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int s, int e1, int e3,
-                                    int s2, int pool, int dtype, hipStream_t st, bool* handled);
-// fire3.hip: the same launch as a DMA-fed kernel sized for four waves per SIMD (SqueezeDet's four shapes)
-int fire_dma_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3, const void* ws2,
-                    const float* bs2, void* s_out, int n, int h, int w, int s, int e1, int e3, int s2, int pool, int dtype,
-                    hipStream_t st, bool* handled);
-int conv3x3_tile_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled);
-// conv3x3.hip: the same with max_pool 2x2/s2/SAME in the epilogue (y = the pooled tensor); dry = eligibility only
-int conv3x3_pool2_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled, bool dry,
-                         unsigned char* widx = nullptr);
-// conv3x3.hip: both expands of a fire module from ONE staged squeeze tile (the tile kernel's PAIR form)
-bool conv3x3_pair_eligible(int n, int h, int w, int s, int e1, int e3, int dtype);
-int conv3x3_pair_launch(const void* sq_in, const void* w3, const float* b3, const void* w1, const float* b1, void* y, int n, int h, int w,
-                        int s, int e1, int e3, int dtype, hipStream_t st, bool* handled);
-// convdet.hip: the score epilogue's shapes; conv.hip: ConvDet + scores in one launch (sqdet_convdet_fwd)
-bool convdet_score_supported(int cout, int apg, int classes, int dtype);
-int convdet_scored_launch(const void* x, const void* w_packed, const float* bias, void* preds, float* scores, int n, int h, int w,
-                          int cin, int apg, int classes, int dtype, hipStream_t st);
-int conv1x1_stream_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled);
-int conv1x1_tile_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled);   // gemm1x1.hip
-int conv1x1_deepk_launch(const ConvArgs& a, const ConvGeom& g, int dtype, hipStream_t st, bool* handled);  // conv1x1k.hip
 
 }  // namespace sqdet

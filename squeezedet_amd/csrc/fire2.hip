@@ -729,10 +729,6 @@ static bool dispatch_stream(const FireSArgs& a, int nchx, int nts, int nwaves, h
 }
 
 // *handled = false: shape not covered (fire_fused_launch / the three separate convs take over).
-int fire_stream_launch_ex(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                          const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                          int pool, hipStream_t st, bool* handled);
-
 int fire_stream_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
                        const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
                        hipStream_t st, bool* handled) {

@@ -10,60 +10,8 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "launch.h"
 #include "chain.h"
-
-namespace sqdet {
-int conv2d_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
-                  int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
-                  hipStream_t st);
-int conv2d_launch_ex(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
-                     int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
-                     int x_cstride, int x_coffset, int accum, hipStream_t st);
-int convdet_scored_launch(const void* x, const void* w_packed, const float* bias, void* preds, float* scores, int n, int h, int w,
-                          int cin, int apg, int classes, int dtype, hipStream_t st);
-int fold_bn_launch(const float* w, const float* cbias, const float* gamma, const float* beta, const float* mean,
-                   const float* var, float eps, float* wf, float* bf, int k, int cin, int cout, hipStream_t st);
-int maxpool_launch(const void* x, void* y, int n, int h, int w, int c, int k, int stride, int pad_mode, int dtype,
-                   hipStream_t st);
-int stem_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cout, int k,
-                int conv_pad, int pool_pad, int dtype, int y_cstride, int y_coffset, hipStream_t st, bool* handled);
-int stem_squeeze_launch(const void* x, const void* w_packed, const float* bias, const void* ws2_packed, const float* bs2,
-                        void* s_out, int n, int h, int w, int cout, int k, int conv_pad, int pool_pad, int s2, int dtype,
-                        hipStream_t st, bool* handled);
-bool stem_squeeze_eligible(int h, int w, int cout, int k, int conv_pad, int pool_pad, int s2, int dtype, int n);
-int fire_fused_launch_keep(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                           const float* b3, void* sq_out, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                           hipStream_t st, bool* handled);
-int fire_fused_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                      const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                      hipStream_t st, bool* handled);
-bool fire_fused_eligible(int cin, int s, int e1, int e3, int dtype);
-bool fire_stream_eligible(int cin, int s, int e1, int e3, int dtype);
-int fire_stream_launch_ex(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                          const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
-                          int pool, hipStream_t st, bool* handled);
-bool fire_chain_eligible(int s, int e1, int e3, int s2, int dtype);
-bool fire_expand_stream_eligible(int s, int e1, int e3, int dtype);
-bool fire_squeeze_next_eligible(int cin, int s, int e1, int e3, int s2, int dtype);
-bool fire_expand_squeeze_next_eligible(int s, int e1, int e3, int s2, int pool, int dtype);
-int fire_expand_squeeze_next_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3,
-                                    const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int s, int e1, int e3,
-                                    int s2, int pool, int dtype, hipStream_t st, bool* handled);
-int fire_squeeze_next_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
-                             const float* b3, const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int cin,
-                             int s, int e1, int e3, int s2, int dtype, hipStream_t st, bool* handled);
-int fire_expand_stream_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3, void* y,
-                              int n, int h, int w, int s, int e1, int e3, int dtype, int pool, hipStream_t st, bool* handled);
-bool conv3x3_pair_eligible(int n, int h, int w, int s, int e1, int e3, int dtype);
-int conv3x3_pair_launch(const void* sq_in, const void* w3, const float* b3, const void* w1, const float* b1, void* y, int n, int h, int w,
-                        int s, int e1, int e3, int dtype, hipStream_t st, bool* handled);
-bool conv2d_maxpool2_eligible(int n, int h, int w, int cin, int cout, int dtype);
-int conv2d_maxpool2_launch(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin, int cout,
-                           int relu, int dtype, hipStream_t st, unsigned char* widx = nullptr);
-int conv_algo();
-int tune(int which);
-}  // namespace sqdet
 
 using namespace sqdet;
 
@@ -118,6 +66,21 @@ struct Layer {
   int fs2 = 0, kp_s2 = -1, bp_s2 = -1;
   size_t chain_off = 0;
   double flops, bytes;
+
+  // channels per pixel of the tensor the layer reads / writes (NHWC: what a sub-batch's pointer offset counts)
+  int in_channels() const {
+    if (type == L_STEM || type == L_STEMSQ) return 3;
+    return type == L_CHAIN || type == L_EXPAND || type == L_EXPSQ ? fs : cin;
+  }
+  int out_channels() const {
+    switch (type) {
+      case L_STEMSQ: case L_FIRESQ: case L_EXPSQ: return fs2;   // the next module's squeeze tensor
+      case L_CHAIN: return fs2 > 0 ? fs2 : fe1 + fe3;           // the same, or (a run's last launch) the concat tensor
+      case L_EXPAND: return fe1 + fe3;
+      case L_POOL: return cin;
+      default: return y_cstride;
+    }
+  }
 };
 
 struct FireSpec { const char* name; int s, e1, e3; };
@@ -154,6 +117,13 @@ struct sqdet_net {
   // sqdet_net_set_signal: an event recorded right before layer signal_layer's launch
   int signal_layer = -1;
   hipEvent_t signal_event = nullptr;
+
+  // packed kernel of parameter i; float32 bias of parameter i (-1: none) or, for a _conv_bn_layer, its folded bias
+  const void* kernel(int i) const { return param_mem + params[i].offset; }
+  const float* bias(int i, int fold = -1) const {
+    if (fold >= 0) return reinterpret_cast<const float*>(param_mem + folds[fold].fbias_off);
+    return i >= 0 ? reinterpret_cast<const float*>(param_mem + params[i].offset) : nullptr;
+  }
 };
 
 namespace {
@@ -182,41 +152,49 @@ struct Builder {
     if (buf >= 0 && elems > net->buf_elems[buf]) net->buf_elems[buf] = elems;
   }
 
-  // conv reading `in_buf` (dims h,w,cin) writing channels [coff, coff+cout) of out_buf rows of cstride channels
-  void conv(const std::string& name, int in_buf, int out_buf, int cin, int cout, int k, int stride, int pad_mode,
-            int relu, int cstride, int coff) {
+  // A layer reading `in_buf` (dims h, w, cin) and writing channels [coff, coff+cout) of out_buf's rows of cstride channels:
+  // its geometry and the size its output buffer needs.  No parameters, flops or bytes yet.
+  Layer shaped(int type, const std::string& name, int in_buf, int out_buf, int cin, int cout, int k, int stride, int pad_mode,
+               int relu, int cstride, int coff) {
     Layer L;
-    L.type = L_CONV;
+    L.type = type;
     L.name = name;
     L.in_buf = in_buf; L.out_buf = out_buf;
     L.h = h; L.w = w; L.cin = cin; L.cout = cout; L.k = k; L.stride = stride; L.pad_mode = pad_mode; L.relu = relu;
     L.ho = out_size(h, k, stride, pad_mode);
     L.wo = out_size(w, k, stride, pad_mode);
-    L.y_cstride = cstride; L.y_coffset = coff;
+    L.y_cstride = cstride; L.y_coffset = coff; L.kparam = L.bparam = -1;
+    note_buf(out_buf, (size_t)net->batch * L.ho * L.wo * cstride);
+    return L;
+  }
+
+  // Pushes a conv layer with its flops and algorithmic bytes (accum: the output is also read); the caller registers the parameters.
+  Layer& push_conv(const std::string& name, int in_buf, int out_buf, int cin, int cout, int k, int stride, int pad_mode, int relu,
+                   int cstride, int coff, int accum) {
+    Layer L = shaped(L_CONV, name, in_buf, out_buf, cin, cout, k, stride, pad_mode, relu, cstride, coff);
+    L.accum = accum;
+    const double npix = (double)net->batch * L.ho * L.wo;
+    L.flops = 2.0 * k * k * cin * cout * npix;
+    L.bytes = ((double)net->batch * h * w * cin + npix * cout * (accum ? 2.0 : 1.0) + (double)k * k * cin * cout) *
+                  (double)esz + cout * 4.0;
+    net->layers.push_back(L);
+    return net->layers.back();
+  }
+
+  void conv(const std::string& name, int in_buf, int out_buf, int cin, int cout, int k, int stride, int pad_mode,
+            int relu, int cstride, int coff) {
+    Layer& L = push_conv(name, in_buf, out_buf, cin, cout, k, stride, pad_mode, relu, cstride, coff, 0);
     const int kshape[4] = {k, k, cin, cout};
     L.kparam = add_param(name + "/kernels", 4, kshape, sqdet_conv_packed_bytes(k, cin, cout, net->dtype));
     const int bshape[1] = {cout};
     L.bparam = add_param(name + "/biases", 1, bshape, (size_t)cout * 4);
-    const double npix = (double)net->batch * L.ho * L.wo;
-    L.flops = 2.0 * k * k * cin * cout * npix;
-    L.bytes = ((double)net->batch * h * w * cin + npix * cout + (double)k * k * cin * cout) * (double)esz + cout * 4.0;
-    note_buf(out_buf, (size_t)net->batch * L.ho * L.wo * cstride);
-    net->layers.push_back(L);
   }
 
   // _conv_bn_layer (nn_skeleton.py:374-468): variables kernels, [biases], gamma, beta, mean, var in
   // the reference's creation order; executed as one conv with the BN folded in.
   void conv_bn(const std::string& name, int in_buf, int out_buf, int cin, int cout, int k, int stride, int relu,
                bool with_bias, int accum) {
-    Layer L;
-    L.type = L_CONV;
-    L.name = name;
-    L.in_buf = in_buf; L.out_buf = out_buf;
-    L.h = h; L.w = w; L.cin = cin; L.cout = cout; L.k = k; L.stride = stride; L.pad_mode = SQDET_PAD_SAME; L.relu = relu;
-    L.ho = out_size(h, k, stride, SQDET_PAD_SAME);
-    L.wo = out_size(w, k, stride, SQDET_PAD_SAME);
-    L.y_cstride = cout; L.y_coffset = 0;
-    L.accum = accum;
+    Layer& L = push_conv(name, in_buf, out_buf, cin, cout, k, stride, SQDET_PAD_SAME, relu, cout, 0, accum);
     BnFold f;
     f.k = k; f.cin = cin; f.cout = cout; f.dirty = true;
     const int kshape[4] = {k, k, cin, cout};
@@ -233,17 +211,10 @@ struct Builder {
     f.fbias_off = net->param_bytes;
     net->param_bytes = align_up(net->param_bytes + (size_t)cout * 4, 256);
     if (raw_bytes > net->fold_scratch_bytes) net->fold_scratch_bytes = raw_bytes;
-    L.bparam = -1;
     L.fold = (int)net->folds.size();
     for (int pi : {f.kparam, f.cbias, f.gamma, f.beta, f.mean, f.var})
       if (pi >= 0) net->params[pi].fold = L.fold;
     net->folds.push_back(f);
-    const double npix = (double)net->batch * L.ho * L.wo;
-    L.flops = 2.0 * k * k * cin * cout * npix;
-    L.bytes = ((double)net->batch * h * w * cin + npix * cout * (accum ? 2.0 : 1.0) + (double)k * k * cin * cout) *
-                  (double)esz + cout * 4.0;
-    note_buf(out_buf, (size_t)net->batch * L.ho * L.wo * cout);
-    net->layers.push_back(L);
   }
 
   // One bottleneck of ResNet50ConvDet (resnet50_convDet.py:50-118 + _res_branch :134-169):
@@ -275,17 +246,9 @@ struct Builder {
   }
 
   void pool_layer(const std::string& name, int k, int stride, int pad_mode) {
-    Layer L;
-    L.type = L_POOL;
-    L.name = name;
-    L.in_buf = cur; L.out_buf = other(cur);
-    L.h = h; L.w = w; L.cin = c; L.cout = c; L.k = k; L.stride = stride; L.pad_mode = pad_mode; L.relu = 0;
-    L.ho = out_size(h, k, stride, pad_mode);
-    L.wo = out_size(w, k, stride, pad_mode);
-    L.y_cstride = c; L.y_coffset = 0; L.kparam = L.bparam = -1;
+    Layer L = shaped(L_POOL, name, cur, other(cur), c, c, k, stride, pad_mode, 0, c, 0);
     L.flops = 0;
     L.bytes = ((double)net->batch * h * w * c + (double)net->batch * L.ho * L.wo * c) * (double)esz;
-    note_buf(L.out_buf, (size_t)net->batch * L.ho * L.wo * c);
     net->layers.push_back(L);
     h = L.ho; w = L.wo; cur = L.out_buf;
   }
@@ -318,125 +281,95 @@ void* buf_ptr(const sqdet_net* net, int buf, const void* input, void* preds) {
   return net->workspace + net->buf_off[buf];
 }
 
-// Runs layer L on images [n0, n0 + nb) of the batch (activations are NHWC with the image index outermost, so a
-// sub-batch is a pointer offset).
 // riders one fire_chain launch takes: its idle CUs ("dbg" 300 + k caps it at k -- experiments)
 int layer_riders(const sqdet_net* net, const Layer& L) {
   int idle = sqdet::fire_chain_idle_cus(net->batch, L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2, net->dtype);
-  const int d = sqdet::tune(5);
+  const int d = tune(TUNE_DBG);
   if (d >= 300 && d < 400 && idle > d - 300) idle = d - 300;
   return idle;
 }
 
+// The share of the pending post job (sqdet_net_set_post_job) that chain launch L carries, NULL when none: the job's images
+// are dealt over the plan's fire_chain launches from the LAST one backwards (the late launches are the long ones), one image
+// per idle CU and launch.
+const sqdet::ChainRide* deal_riders(const sqdet_net* net, const Layer& L, sqdet::ChainRide* ride) {
+  const int idle = layer_riders(net, L);
+  int later = 0;      // images taken by the chain launches behind this one
+  for (size_t i = net->layers.size(); i-- > 0 && &net->layers[i] != &L;)
+    if (net->layers[i].type == L_CHAIN) later += layer_riders(net, net->layers[i]);
+  const int left = net->job_n - later;
+  if (idle <= 0 || left <= 0) return nullptr;
+  ride->fa = net->job_fa; ride->da = net->job_da;
+  ride->nimg = left < idle ? left : idle;
+  ride->img0 = left - ride->nimg;
+  ride->nriders = ride->nimg;
+  return ride;
+}
+
+// A launcher the plan chose at creation declined the shape at launch time (*handled false): the options changed in between.
+int still_eligible(int rc, bool handled, const char* what) {
+  if (rc != SQDET_OK || handled) return rc;
+  set_error("%s", what);
+  return SQDET_ESTATE;
+}
+
+// Runs layer L on images [n0, n0 + nb) of the batch (activations are NHWC with the image index outermost, so a
+// sub-batch is a pointer offset).
 int run_layer_part(sqdet_net* net, const Layer& L, const void* input, void* preds, int n0, int nb, hipStream_t st) {
   const size_t esz = dtype_size(net->dtype);
-  if (L.type == L_CHAIN) {
-    const size_t px0 = (size_t)n0 * L.h * L.w;
-    const char* sq_in = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + px0 * L.fs * esz;
-    char* out = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) + px0 * (L.fs2 > 0 ? L.fs2 : L.fe1 + L.fe3) * esz;
-    auto pb = [&](int i) { return i >= 0 ? reinterpret_cast<const float*>(net->param_mem + net->params[i].offset) : nullptr; };
-    // riders: the pending job's images are dealt over the plan's fire_chain launches from the LAST one backwards (the late
-    // launches are the long ones), one image per idle CU and launch
-    sqdet::ChainRide ride;
-    const sqdet::ChainRide* rp = nullptr;
-    if (net->job_set && n0 == 0 && nb == net->batch) {
-      const int idle = layer_riders(net, L);
-      int later = 0;      // images taken by the chain launches behind this one
-      for (size_t i = net->layers.size(); i-- > 0 && &net->layers[i] != &L;)
-        if (net->layers[i].type == L_CHAIN) later += layer_riders(net, net->layers[i]);
-      const int left = net->job_n - later;
-      if (idle > 0 && left > 0) {
-        ride.fa = net->job_fa; ride.da = net->job_da;
-        ride.nimg = left < idle ? left : idle;
-        ride.img0 = left - ride.nimg;
-        ride.nriders = ride.nimg;
-        rp = &ride;
-      }
+  const int dt = net->dtype;
+  const void* x = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + (size_t)n0 * L.h * L.w * L.in_channels() * esz;
+  void* y = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) + (size_t)n0 * L.ho * L.wo * L.out_channels() * esz;
+  const sqdet_stream_t cst = reinterpret_cast<sqdet_stream_t>(st);
+  bool handled = false;
+  int rc;
+  switch (L.type) {
+    case L_CONV:
+      if (L.conv_pool)
+        return conv2d_maxpool2_launch(x, net->kernel(L.kparam), net->bias(L.bparam, L.fold), y, nb, L.h, L.w, L.cin, L.cout, L.relu, dt, st);
+      if (net->scores && &L == &net->layers.back())   // (validated by sqdet_net_set_scores)
+        return convdet_scored_launch(x, net->kernel(L.kparam), net->bias(L.bparam, L.fold), y, net->scores + (size_t)n0 * L.h * L.w * net->apg,
+                                     nb, L.h, L.w, L.cin, net->apg, net->classes, dt, st);
+      return conv2d_launch_ex(x, net->kernel(L.kparam), net->bias(L.bparam, L.fold), y, nb, L.h, L.w, L.cin, L.cout, L.k, L.stride, L.pad_mode,
+                              L.relu, dt, L.y_cstride, L.y_coffset, L.cin, 0, L.accum, st);
+    case L_POOL:
+      return maxpool_launch(x, y, nb, L.h, L.w, L.cin, L.k, L.stride, L.pad_mode, dt, st);
+    case L_STEM:
+      rc = stem_launch(x, net->kernel(L.kparam), net->bias(L.bparam, L.fold), y, nb, L.h, L.w, L.cout, L.k, L.pad_mode, L.pool_pad_mode, dt,
+                       L.y_cstride, L.y_coffset, st, &handled);
+      return still_eligible(rc, handled, "net: fused stem no longer eligible (conv_algo changed after net_create?)");
+    case L_STEMSQ:
+      rc = stem_squeeze_launch(x, net->kernel(L.kparam), net->bias(L.bparam), net->kernel(L.kp_s2), net->bias(L.bp_s2), y, nb, L.h, L.w,
+                               L.cout, L.k, L.pad_mode, L.pool_pad_mode, L.fs2, dt, st, &handled);
+      return still_eligible(rc, handled, "net: stem + squeeze launch no longer eligible (options changed after net_create?)");
+    case L_FIRE:
+      rc = L.fire_pool
+          ? fire_stream_launch_ex(x, net->kernel(L.kp_s), net->bias(L.bp_s), net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3),
+                                  net->bias(L.bp_3), y, nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, dt, 1, st, &handled)
+          : fire_fused_launch(x, net->kernel(L.kp_s), net->bias(L.bp_s), net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3),
+                              net->bias(L.bp_3), y, nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, dt, st, &handled);
+      return still_eligible(rc, handled, "net: fused fire no longer eligible (options changed after net_create?)");
+    case L_FIRESQ:
+      return sqdet_fire_squeeze_next_fwd(x, net->kernel(L.kp_s), net->bias(L.bp_s), net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3),
+                                         net->bias(L.bp_3), net->kernel(L.kp_s2), net->bias(L.bp_s2), y, nb, L.h, L.w, L.cin, L.fs, L.fe1,
+                                         L.fe3, L.fs2, dt, cst);
+    case L_EXPSQ:
+      return sqdet_fire_expand_squeeze_next_fwd(x, net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3), net->bias(L.bp_3),
+                                                net->kernel(L.kp_s2), net->bias(L.bp_s2), y, nb, L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2,
+                                                L.fire_pool, dt, cst);
+    case L_EXPAND:
+      return sqdet_fire_expand_fwd(x, net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3), net->bias(L.bp_3), y, nb, L.h, L.w, L.fs,
+                                   L.fe1, L.fe3, L.fire_pool, dt, cst);
+    case L_CHAIN: {
+      sqdet::ChainRide ride;
+      const sqdet::ChainRide* rp = net->job_set && n0 == 0 && nb == net->batch ? deal_riders(net, L, &ride) : nullptr;
+      return sqdet::fire_chain_launch_ride(x, net->param_mem + L.chain_off, net->bias(L.bp_1), net->bias(L.bp_3), net->bias(L.bp_s2),
+                                           L.fs2 > 0 ? nullptr : y, L.fs2 > 0 ? y : nullptr, nb, L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2, dt,
+                                           rp, st);
     }
-    return sqdet::fire_chain_launch_ride(sq_in, net->param_mem + L.chain_off, pb(L.bp_1), pb(L.bp_3), pb(L.bp_s2),
-                                         L.fs2 > 0 ? nullptr : out, L.fs2 > 0 ? out : nullptr, nb, L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2,
-                                         net->dtype, rp, st);
   }
-  if (L.type == L_FIRESQ) {
-    const char* xin = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + (size_t)n0 * L.h * L.w * L.cin * esz;
-    char* out = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) + (size_t)n0 * L.h * L.w * L.fs2 * esz;
-    auto pk = [&](int i) { return (const void*)(net->param_mem + net->params[i].offset); };
-    auto pb = [&](int i) { return reinterpret_cast<const float*>(net->param_mem + net->params[i].offset); };
-    return sqdet_fire_squeeze_next_fwd(xin, pk(L.kp_s), pb(L.bp_s), pk(L.kp_1), pb(L.bp_1), pk(L.kp_3), pb(L.bp_3), pk(L.kp_s2),
-                                       pb(L.bp_s2), out, nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, L.fs2, net->dtype,
-                                       reinterpret_cast<sqdet_stream_t>(st));
-  }
-  if (L.type == L_EXPSQ) {
-    const char* sq_in = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + (size_t)n0 * L.h * L.w * L.fs * esz;
-    char* out = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) + (size_t)n0 * L.ho * L.wo * L.fs2 * esz;
-    auto pk = [&](int i) { return (const void*)(net->param_mem + net->params[i].offset); };
-    auto pb = [&](int i) { return reinterpret_cast<const float*>(net->param_mem + net->params[i].offset); };
-    return sqdet_fire_expand_squeeze_next_fwd(sq_in, pk(L.kp_1), pb(L.bp_1), pk(L.kp_3), pb(L.bp_3), pk(L.kp_s2), pb(L.bp_s2), out, nb,
-                                              L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2, L.fire_pool, net->dtype,
-                                              reinterpret_cast<sqdet_stream_t>(st));
-  }
-  if (L.type == L_EXPAND) {
-    const char* sq_in = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + (size_t)n0 * L.h * L.w * L.fs * esz;
-    char* out = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) + (size_t)n0 * L.ho * L.wo * (L.fe1 + L.fe3) * esz;
-    auto pk = [&](int i) { return (const void*)(net->param_mem + net->params[i].offset); };
-    auto pb = [&](int i) { return reinterpret_cast<const float*>(net->param_mem + net->params[i].offset); };
-    return sqdet_fire_expand_fwd(sq_in, pk(L.kp_1), pb(L.bp_1), pk(L.kp_3), pb(L.bp_3), out, nb, L.h, L.w, L.fs, L.fe1, L.fe3,
-                                 L.fire_pool, net->dtype, reinterpret_cast<sqdet_stream_t>(st));
-  }
-  if (L.type == L_STEMSQ) {
-    const void* x = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + (size_t)n0 * L.h * L.w * 3 * esz;
-    void* so = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) + (size_t)n0 * L.ho * L.wo * L.fs2 * esz;
-    const void* wp = net->param_mem + net->params[L.kparam].offset;
-    const float* b = reinterpret_cast<const float*>(net->param_mem + net->params[L.bparam].offset);
-    const void* ws = net->param_mem + net->params[L.kp_s2].offset;
-    const float* bs = reinterpret_cast<const float*>(net->param_mem + net->params[L.bp_s2].offset);
-    bool handled = false;
-    const int rc = stem_squeeze_launch(x, wp, b, ws, bs, so, nb, L.h, L.w, L.cout, L.k, L.pad_mode, L.pool_pad_mode, L.fs2,
-                                       net->dtype, st, &handled);
-    if (rc != SQDET_OK) return rc;
-    if (!handled) { set_error("net: stem + squeeze launch no longer eligible (options changed after net_create?)"); return SQDET_ESTATE; }
-    return SQDET_OK;
-  }
-  const int in_c = L.type == L_STEM ? 3 : L.cin;
-  const void* x = reinterpret_cast<const char*>(buf_ptr(net, L.in_buf, input, preds)) + (size_t)n0 * L.h * L.w * in_c * esz;
-  void* y = reinterpret_cast<char*>(buf_ptr(net, L.out_buf, input, preds)) +
-            (size_t)n0 * L.ho * L.wo * (L.type == L_POOL ? L.cin : L.y_cstride) * esz;
-  if (L.type == L_CONV) {
-    const void* wp = net->param_mem + net->params[L.kparam].offset;
-    const float* b = reinterpret_cast<const float*>(
-        net->param_mem + (L.fold >= 0 ? net->folds[L.fold].fbias_off : net->params[L.bparam].offset));
-    if (L.conv_pool) return conv2d_maxpool2_launch(x, wp, b, y, nb, L.h, L.w, L.cin, L.cout, L.relu, net->dtype, st);
-    if (net->scores && &L == &net->layers.back())   // (validated by sqdet_net_set_scores)
-      return convdet_scored_launch(x, wp, b, y, net->scores + (size_t)n0 * L.h * L.w * net->apg, nb, L.h, L.w, L.cin, net->apg,
-                                   net->classes, net->dtype, st);
-    return conv2d_launch_ex(x, wp, b, y, nb, L.h, L.w, L.cin, L.cout, L.k, L.stride, L.pad_mode, L.relu,
-                            net->dtype, L.y_cstride, L.y_coffset, L.cin, 0, L.accum, st);
-  }
-  if (L.type == L_STEM) {
-    const void* wp = net->param_mem + net->params[L.kparam].offset;
-    const float* b = reinterpret_cast<const float*>(
-        net->param_mem + (L.fold >= 0 ? net->folds[L.fold].fbias_off : net->params[L.bparam].offset));
-    bool handled = false;
-    const int rc = stem_launch(x, wp, b, y, nb, L.h, L.w, L.cout, L.k, L.pad_mode, L.pool_pad_mode, net->dtype,
-                               L.y_cstride, L.y_coffset, st, &handled);
-    if (rc != SQDET_OK) return rc;
-    if (!handled) { set_error("net: fused stem no longer eligible (conv_algo changed after net_create?)"); return SQDET_ESTATE; }
-    return SQDET_OK;
-  }
-  if (L.type == L_FIRE) {
-    auto pk = [&](int i) { return (const void*)(net->param_mem + net->params[i].offset); };
-    auto pb = [&](int i) { return reinterpret_cast<const float*>(net->param_mem + net->params[i].offset); };
-    bool handled = false;
-    const int rc = L.fire_pool
-        ? fire_stream_launch_ex(x, pk(L.kp_s), pb(L.bp_s), pk(L.kp_1), pb(L.bp_1), pk(L.kp_3), pb(L.bp_3), y, nb, L.h, L.w,
-                                L.cin, L.fs, L.fe1, L.fe3, net->dtype, 1, st, &handled)
-        : fire_fused_launch(x, pk(L.kp_s), pb(L.bp_s), pk(L.kp_1), pb(L.bp_1), pk(L.kp_3), pb(L.bp_3), y,
-                            nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, net->dtype, st, &handled);
-    if (rc != SQDET_OK) return rc;
-    if (!handled) { set_error("net: fused fire no longer eligible (options changed after net_create?)"); return SQDET_ESTATE; }
-    return SQDET_OK;
-  }
-  return maxpool_launch(x, y, nb, L.h, L.w, L.cin, L.k, L.stride, L.pad_mode, net->dtype, st);
+  set_error("net: unknown layer type %d", L.type);
+  return SQDET_ESTATE;
 }
 
 int run_layer(sqdet_net* net, const Layer& L, const void* input, void* preds, hipStream_t st) {
@@ -462,25 +395,80 @@ int refresh_folds(sqdet_net* net, hipStream_t st) {
   return SQDET_OK;
 }
 
+// ---- the fusion passes (sqdet_net_create runs them in the order fuse_stem, fuse_fires, fuse_fire_pools, fuse_chains,
+// fuse_expand_pairs, fuse_stem_squeeze, fuse_conv_pools)
+
+// Rewrites the plan front to back: step(in, i, out) either appends the replacement of the layers starting at in[i] to `out` and
+// returns how many it consumed, or returns 0 -- in[i] is then copied.  `in` is a copy the step may edit behind i (absorb_pool).
+template <class Step>
+void rewrite_layers(sqdet_net* net, Step&& step) {
+  std::vector<Layer> in = net->layers, out;
+  for (size_t i = 0; i < in.size();) {
+    const size_t took = step(in, i, out);
+    if (!took) out.push_back(in[i]);
+    i += took ? took : 1;
+  }
+  net->layers.swap(out);
+}
+
+// in[i] with the max-pool in[i + 1] behind it taken into its own launch: the layer's full-resolution output never reaches HBM.
+// The pooled tensor goes where the layer's own output would have gone -- NOT into the pool's output buffer: that is the
+// ping-pong buffer the layer READS (other workgroups are still reading it).  One ping-pong step disappears, so the two buffers
+// swap roles for every later layer, and either may now hold what the other was sized for.  The caller sets its pool flag.
+Layer absorb_pool(sqdet_net* net, std::vector<Layer>& in, size_t i, size_t esz) {
+  const Layer& p = in[i + 1];
+  Layer f = in[i];
+  f.name = f.name + "+" + p.name;
+  // algorithmic bytes: the POOLED output instead of the full-resolution one
+  f.bytes = f.bytes - (double)net->batch * f.ho * f.wo * f.cout * (double)esz + (double)net->batch * p.ho * p.wo * f.cout * (double)esz;
+  f.ho = p.ho; f.wo = p.wo;
+  for (size_t k = i + 2; k < in.size(); ++k) {
+    auto sw = [](int b) { return b == BUF_A ? BUF_B : (b == BUF_B ? BUF_A : b); };
+    in[k].in_buf = sw(in[k].in_buf);
+    in[k].out_buf = sw(in[k].out_buf);
+  }
+  const size_t m = net->buf_elems[BUF_A] > net->buf_elems[BUF_B] ? net->buf_elems[BUF_A] : net->buf_elems[BUF_B];
+  net->buf_elems[BUF_A] = net->buf_elems[BUF_B] = m;
+  return f;
+}
+
+// flops / algorithmic bytes of the launches of a fire module f over npix pixels (npix_out: after the max-pool it may carry)
+double expand_weights(const Layer& f) { return (double)f.fs * f.fe1 + 9.0 * f.fs * f.fe3; }
+double expand_flops(const Layer& f, double npix) { return (2.0 * f.fs * f.fe1 + 18.0 * f.fs * f.fe3) * npix; }
+// both expands (+ pool) from the squeeze tensor: squeeze tensor in + concat tensor out + the weights
+void cost_expand(Layer& c, const Layer& f, double npix, double npix_out, size_t esz) {
+  c.flops = expand_flops(f, npix);
+  c.bytes = (npix * f.fs + npix_out * (f.fe1 + f.fe3) + expand_weights(f)) * (double)esz + 4.0 * (f.fe1 + f.fe3);
+}
+// the same + the next module's squeeze1x1 (fs2 > 0: its squeeze tensor goes out instead of the concat tensor; 0: the chain's last launch)
+void cost_expand_squeeze(Layer& c, const Layer& f, int fs2, double npix, double npix_out, size_t esz) {
+  c.flops = expand_flops(f, npix) + 2.0 * (f.fe1 + f.fe3) * fs2 * npix_out;
+  c.bytes = (npix * f.fs + npix_out * (fs2 > 0 ? fs2 : f.fe1 + f.fe3) + expand_weights(f) + (double)(f.fe1 + f.fe3) * fs2) * (double)esz +
+            4.0 * (f.fe1 + f.fe3 + fs2);
+}
+// the whole module from x + the next module's squeeze1x1: fire input in + next squeeze tensor out + the four weight sets
+void cost_fire_squeeze(Layer& c, const Layer& f, int fs2, double npix, size_t esz) {
+  c.flops = f.flops + 2.0 * (f.fe1 + f.fe3) * fs2 * npix;
+  c.bytes = (npix * f.cin + npix * fs2 + (double)f.cin * f.fs + expand_weights(f) + (double)(f.fe1 + f.fe3) * fs2) * (double)esz +
+            4.0 * (f.fs + f.fe1 + f.fe3 + fs2);
+}
+
 // squeeze1x1 + expand1x1 + expand3x3 -> one L_FIRE launch (decided at plan creation) wherever a fused kernel takes the
 // module.  (Rounds 1-4 fused maps of <= 100000 pixels only -- tuned on SqueezeDet, whose large maps run the streaming
 // kernels anyway; SqueezeDet+'s 227 k-pixel fire2-4 at batch 8 run 1.5-2 % faster fused, SqueezeDet is level:
 // profiles/r05_fire_fuse_ab.txt.)  "fire_fuse" = 2 disables the fusion, 10 restores the pixel rule.
 void fuse_fires(sqdet_net* net, size_t esz) {
-  if (conv_algo() != 0 || tune(3) == 2) return;
-  std::vector<Layer> out;
-  const std::vector<Layer>& in = net->layers;
-  for (size_t i = 0; i < in.size(); ++i) {
+  const int ff = tune(TUNE_FIRE_FUSE);
+  if (conv_algo() != 0 || ff == 2) return;
+  rewrite_layers(net, [&](std::vector<Layer>& in, size_t i, std::vector<Layer>& out) -> size_t {
     const bool trio = i + 2 < in.size() && in[i].type == L_CONV && in[i + 1].type == L_CONV && in[i + 2].type == L_CONV &&
                       in[i].out_buf == BUF_S && in[i + 1].in_buf == BUF_S && in[i + 2].in_buf == BUF_S && in[i].k == 1 &&
                       in[i + 1].k == 1 && in[i + 2].k == 3 && in[i + 1].out_buf == in[i + 2].out_buf;
     const long pixels = (long)net->batch * in[i].h * in[i].w;
-    const bool streams = trio && tune(3) != 3 && fire_stream_eligible(in[i].cin, in[i].cout, in[i + 1].cout, in[i + 2].cout, net->dtype);
-    if (!trio || !(tune(3) != 10 || pixels <= 100000 || streams) ||
-        !fire_fused_eligible(in[i].cin, in[i].cout, in[i + 1].cout, in[i + 2].cout, net->dtype)) {
-      out.push_back(in[i]);
-      continue;
-    }
+    const bool streams = trio && ff != 3 && fire_stream_eligible(in[i].cin, in[i].cout, in[i + 1].cout, in[i + 2].cout, net->dtype);
+    if (!trio || !(ff != 10 || pixels <= 100000 || streams) ||
+        !fire_fused_eligible(in[i].cin, in[i].cout, in[i + 1].cout, in[i + 2].cout, net->dtype))
+      return 0;
     const Layer &s = in[i], &e1 = in[i + 1], &e3 = in[i + 2];
     Layer f = s;
     f.type = L_FIRE;
@@ -496,61 +484,40 @@ void fuse_fires(sqdet_net* net, size_t esz) {
     f.bytes = (npix * s.cin + npix * f.cout + (double)s.cin * s.cout + (double)s.cout * e1.cout + 9.0 * s.cout * e3.cout) *
                   (double)esz + 4.0 * (s.cout + e1.cout + e3.cout);
     out.push_back(f);
-    i += 2;
-  }
-  net->layers.swap(out);
+    return 3;
+  });
 }
 
 // fire module + the 3x3/s2 SAME max-pool behind it -> one launch of the streaming kernel's POOL form (fire3+pool3,
-// fire5+pool5 of SqueezeDet): the module's full-resolution output never reaches HBM.  "fire_fuse" = 4 keeps them apart.
+// fire5+pool5 of SqueezeDet).  "fire_fuse" = 2 / 3 / 4 keeps them apart.
 void fuse_fire_pools(sqdet_net* net, size_t esz) {
-  if (conv_algo() != 0 || tune(3) == 2 || tune(3) == 3 || tune(3) == 4) return;
-  std::vector<Layer> out;
-  std::vector<Layer> in = net->layers;
-  bool fused_any = false;
-  for (size_t i = 0; i < in.size(); ++i) {
+  const int ff = tune(TUNE_FIRE_FUSE);
+  if (conv_algo() != 0 || ff == 2 || ff == 3 || ff == 4) return;
+  rewrite_layers(net, [&](std::vector<Layer>& in, size_t i, std::vector<Layer>& out) -> size_t {
     const bool ok = i + 1 < in.size() && in[i].type == L_FIRE && in[i + 1].type == L_POOL && in[i + 1].k == 3 &&
                     in[i + 1].stride == 2 && in[i + 1].pad_mode == SQDET_PAD_SAME && in[i + 1].in_buf == in[i].out_buf &&
                     fire_stream_eligible(in[i].cin, in[i].fs, in[i].fe1, in[i].fe3, net->dtype);
-    if (!ok) { out.push_back(in[i]); continue; }
-    const Layer& p = in[i + 1];
-    Layer f = in[i];
-    f.fire_pool = 1;
-    f.name = in[i].name + "+" + p.name;
-    // The pooled tensor goes where the module's own output would have gone -- NOT into the pool's output buffer:
-    // that is the ping-pong buffer the module READS (other workgroups are still reading it).  One ping-pong step
-    // disappears, so the two buffers swap roles for every later layer.
-    f.ho = p.ho; f.wo = p.wo;
-    for (size_t k = i + 2; k < in.size(); ++k) {
-      auto sw = [](int b) { return b == BUF_A ? BUF_B : (b == BUF_B ? BUF_A : b); };
-      in[k].in_buf = sw(in[k].in_buf);
-      in[k].out_buf = sw(in[k].out_buf);
-    }
-    fused_any = true;
-    // algorithmic bytes: fire input + POOLED output + the three weight sets
-    f.bytes = in[i].bytes - (double)net->batch * in[i].h * in[i].w * in[i].cout * (double)esz +
-              (double)net->batch * p.ho * p.wo * in[i].cout * (double)esz;
-    out.push_back(f);
-    ++i;
-  }
-  net->layers.swap(out);
-  if (fused_any) {   // either buffer may now hold what the other was sized for
-    const size_t m = net->buf_elems[BUF_A] > net->buf_elems[BUF_B] ? net->buf_elems[BUF_A] : net->buf_elems[BUF_B];
-    net->buf_elems[BUF_A] = net->buf_elems[BUF_B] = m;
-  }
+    if (!ok) return 0;
+    out.push_back(absorb_pool(net, in, i, esz));
+    out.back().fire_pool = 1;
+    return 2;
+  });
 }
 
 // Runs of consecutive fire modules (SqueezeDet: fire2 .. fire11, nets/squeezeDet.py:46-69): the only reader of a module's
 // concat tensor -- pooled or not -- is the next module's squeeze1x1, so inside a run only 16-96-channel SQUEEZE tensors
 // travel between the launches (float16).  Per member, by what covers its shape:
-//   first module (input x):   one streaming launch, whole module + next squeeze (L_FIRESQ)  |  squeeze conv, then as below
-//   module from its squeeze:  streaming launch expand (+ pool) + next squeeze (L_EXPSQ: one-chunk squeezes)
-//                             |  ring chain launch expand + next squeeze (L_CHAIN; no pool)
-//   last module:              expand + pool from the squeeze tensor (L_EXPAND)  |  chain launch writing the concat tensor
-// "fire_fuse" = 5 keeps one launch per module, 6 chains the late (<= 100000 pixel) maps only, 7 never uses L_FIRESQ,
-// 8 never uses L_EXPSQ (a pooled module then ends its run).
+//   first module (input x):   one streaming launch, whole module + next squeeze (L_FIRESQ; cost_fire_squeeze)
+//                             |  squeeze conv (L_CONV; fuse_stem_squeeze may move it into the stem launch), then as below
+//   module from its squeeze:  streaming launch expand (+ pool) + next squeeze (L_EXPSQ: one-chunk squeezes; cost_expand_squeeze)
+//                             |  ring chain launch expand + next squeeze (L_CHAIN; no pool; cost_expand_squeeze)
+//   last module:              expand + pool from the squeeze tensor (L_EXPAND; cost_expand)
+//                             |  chain launch writing the concat tensor (L_CHAIN, fs2 = 0; cost_expand_squeeze)
+// "fire_fuse" = 2 / 5 keeps one launch per module, 6 chains the late (<= 100000 pixel) maps only, 7 never uses L_FIRESQ,
+// 8 never uses L_EXPSQ (a pooled module then ends its run), 8 / 9 keeps the first module's squeeze out of the stem launch.
 void fuse_chains(sqdet_net* net, size_t esz) {
-  if (conv_algo() != 0 || tune(3) == 2 || tune(3) == 5) return;
+  const int ff = tune(TUNE_FIRE_FUSE);
+  if (conv_algo() != 0 || ff == 2 || ff == 5) return;
   const std::vector<Layer> in = net->layers;
   std::vector<Layer> out;
   const int dt = net->dtype;
@@ -559,14 +526,14 @@ void fuse_chains(sqdet_net* net, size_t esz) {
   // the first module right behind a fused stem: its squeeze1x1 moves INTO the stem launch (fuse_stem_squeeze below) when the
   // module itself can then run from its squeeze tensor ("fire_fuse" = 9: not)
   auto stem_takes_squeeze = [&](const Layer& f, const Layer& nx) {
-    return tune(3) != 9 && tune(3) != 8 && in.size() > 1 && &f == &in[1] && in[0].type == L_STEM && f.in_buf == in[0].out_buf && !f.fire_pool &&
+    return ff != 9 && ff != 8 && in.size() > 1 && &f == &in[1] && in[0].type == L_STEM && f.in_buf == in[0].out_buf && !f.fire_pool &&
            stem_squeeze_eligible(in[0].h, in[0].w, in[0].cout, in[0].k, in[0].pad_mode, in[0].pool_pad_mode, f.fs, dt, net->batch) &&
            fire_expand_squeeze_next_eligible(f.fs, f.fe1, f.fe3, nx.fs, 0, dt);
   };
   auto mid_impl = [&](const Layer& f, const Layer& nx, bool first) -> int {
-    if (first && tune(3) != 7 && !f.fire_pool && !stem_takes_squeeze(f, nx) &&
+    if (first && ff != 7 && !f.fire_pool && !stem_takes_squeeze(f, nx) &&
         fire_squeeze_next_eligible(f.cin, f.fs, f.fe1, f.fe3, nx.fs, dt)) return L_FIRESQ;
-    if (tune(3) != 8 && fire_expand_squeeze_next_eligible(f.fs, f.fe1, f.fe3, nx.fs, f.fire_pool, dt)) return L_EXPSQ;
+    if (ff != 8 && fire_expand_squeeze_next_eligible(f.fs, f.fe1, f.fe3, nx.fs, f.fire_pool, dt)) return L_EXPSQ;
     if (!f.fire_pool && fire_chain_eligible(f.fs, f.fe1, f.fe3, nx.fs, dt)) return L_CHAIN;
     return 0;
   };
@@ -579,7 +546,7 @@ void fuse_chains(sqdet_net* net, size_t esz) {
     // candidate run: consecutive fire modules, each reading its predecessor's (possibly pooled) output
     size_t j = i + 1;
     while (j < in.size() && in[j].type == L_FIRE && in[j].in_buf == in[j - 1].out_buf && in[j].h == in[j - 1].ho && in[j].w == in[j - 1].wo) ++j;
-    if (tune(3) == 6) {   // late maps only
+    if (ff == 6) {   // late maps only
       if ((long)net->batch * in[i].h * in[i].w > 100000) { out.push_back(in[i]); ++i; continue; }
     }
     // longest prefix [i, e) every member of which has an implementation and whose final member is implemented as a LAST one
@@ -611,7 +578,6 @@ void fuse_chains(sqdet_net* net, size_t esz) {
       const int im = impl[k - i];
       const double npix = (double)net->batch * f.h * f.w;
       const double npix_out = (double)net->batch * f.ho * f.wo;
-      const double wexp = (double)f.fs * f.fe1 + 9.0 * f.fs * f.fe3;
       if (k == i && im != L_FIRESQ) {     // the first module's squeeze as a plain conv
         Layer sq = f;
         sq.type = L_CONV;
@@ -638,9 +604,7 @@ void fuse_chains(sqdet_net* net, size_t esz) {
       if (im == L_FIRESQ) {
         c.out_buf = BUF_S;
         c.name = base(f) + nxs;
-        c.flops = f.flops + 2.0 * (f.fe1 + f.fe3) * fs2 * npix;
-        c.bytes = (npix * f.cin + npix * fs2 + (double)f.cin * f.fs + wexp + (double)(f.fe1 + f.fe3) * fs2) * (double)esz +
-                  4.0 * (f.fs + f.fe1 + f.fe3 + fs2);
+        cost_fire_squeeze(c, f, fs2, npix, esz);
         note_s(f, fs2, false);
         out.push_back(c);
         sbuf = BUF_S;
@@ -649,17 +613,13 @@ void fuse_chains(sqdet_net* net, size_t esz) {
       c.in_buf = sbuf;
       if (im == L_EXPAND) {     // (last member with a pool: its pooled concat tensor goes where the fused layer's went)
         c.name = base(f) + "/expand" + pool_s;
-        c.flops = (2.0 * f.fs * f.fe1 + 18.0 * f.fs * f.fe3) * npix;
-        c.bytes = (npix * f.fs + npix_out * (f.fe1 + f.fe3) + wexp) * (double)esz + 4.0 * (f.fe1 + f.fe3);
+        cost_expand(c, f, npix, npix_out, esz);
         out.push_back(c);
         continue;
       }
       c.out_buf = last ? f.out_buf : (sbuf == BUF_S ? BUF_T : BUF_S);
       c.name = base(f) + "/expand" + pool_s + nxs;
-      c.flops = (2.0 * f.fs * f.fe1 + 18.0 * f.fs * f.fe3) * npix + 2.0 * (f.fe1 + f.fe3) * fs2 * npix_out;
-      // algorithmic bytes: squeeze tensor in + (next squeeze tensor | concat tensor) out + the weights
-      c.bytes = (npix * f.fs + npix_out * (last ? f.fe1 + f.fe3 : fs2) + wexp + (double)(f.fe1 + f.fe3) * fs2) * (double)esz +
-                4.0 * (f.fe1 + f.fe3 + fs2);
+      cost_expand_squeeze(c, f, fs2, npix, npix_out, esz);
       if (im == L_CHAIN) {
         c.chain_off = net->param_bytes;
         net->param_bytes = align_up(net->param_bytes + sqdet_fire_chain_stream_bytes(f.fs, f.fe1, f.fe3, fs2, dt), 256);
@@ -677,10 +637,9 @@ void fuse_chains(sqdet_net* net, size_t esz) {
 // chain) -> one L_EXPAND launch of the tile kernel's PAIR form where it covers the shape (conv3x3_pair_eligible): both expands from ONE
 // staged squeeze tile.  "fire_fuse" = 2 / 11: not.
 void fuse_expand_pairs(sqdet_net* net, size_t esz) {
-  if (conv_algo() != 0 || tune(3) == 2 || tune(3) == 11) return;
-  std::vector<Layer> out;
-  const std::vector<Layer>& in = net->layers;
-  for (size_t i = 0; i < in.size(); ++i) {
+  const int ff = tune(TUNE_FIRE_FUSE);
+  if (conv_algo() != 0 || ff == 2 || ff == 11) return;
+  rewrite_layers(net, [&](std::vector<Layer>& in, size_t i, std::vector<Layer>& out) -> size_t {
     const bool pair = i + 1 < in.size() && in[i].type == L_CONV && in[i + 1].type == L_CONV && in[i].k == 1 && in[i + 1].k == 3 &&
                       in[i].in_buf == BUF_S && in[i + 1].in_buf == BUF_S && in[i].out_buf == in[i + 1].out_buf && in[i].stride == 1 &&
                       in[i + 1].stride == 1 && in[i].relu && in[i + 1].relu && in[i].cin == in[i + 1].cin && in[i].y_coffset == 0 &&
@@ -688,7 +647,7 @@ void fuse_expand_pairs(sqdet_net* net, size_t esz) {
                       in[i + 1].y_cstride == in[i].y_cstride && in[i].fold < 0 && in[i + 1].fold < 0 && !in[i].accum && !in[i + 1].accum &&
                       in[i + 1].pad_mode == SQDET_PAD_SAME &&
                       conv3x3_pair_eligible(net->batch, in[i].h, in[i].w, in[i].cin, in[i].cout, in[i + 1].cout, net->dtype);
-    if (!pair) { out.push_back(in[i]); continue; }
+    if (!pair) return 0;
     const Layer &e1 = in[i], &e3 = in[i + 1];
     Layer f = e3;
     f.type = L_EXPAND;
@@ -703,15 +662,15 @@ void fuse_expand_pairs(sqdet_net* net, size_t esz) {
     const double npix = (double)net->batch * e1.h * e1.w;
     f.bytes = (npix * e1.cin + npix * f.cout + 10.0 * e1.cin * e1.cout) * (double)esz + 4.0 * f.cout;
     out.push_back(f);
-    ++i;
-  }
-  net->layers.swap(out);
+    return 2;
+  });
 }
 
 // L_STEM followed by the first chained module's squeeze1x1 (a plain 64 -> 16 conv emitted by fuse_chains) -> one L_STEMSQ
 // launch: pool1's tensor is never written.
 void fuse_stem_squeeze(sqdet_net* net, size_t esz) {
-  if (conv_algo() != 0 || tune(3) == 9 || net->layers.size() < 3) return;
+  const int ff = tune(TUNE_FIRE_FUSE);
+  if (conv_algo() != 0 || ff == 9 || net->layers.size() < 3) return;
   const Layer& st = net->layers[0];
   const Layer& sq = net->layers[1];
   if (st.type != L_STEM || sq.type != L_CONV || sq.k != 1 || sq.stride != 1 || !sq.relu || sq.in_buf != st.out_buf) return;
@@ -733,42 +692,20 @@ void fuse_stem_squeeze(sqdet_net* net, size_t esz) {
 }
 
 // 3x3/s1/SAME conv + the 2x2/s2 SAME max-pool behind it (VGG16's conv1_2+pool1 .. conv4_3+pool4) -> one L_CONV launch of the tile
-// kernel's POOL2 form wherever it takes the shape: the conv's full-resolution output never reaches HBM.  As in fuse_fire_pools the pooled
-// tensor goes where the conv's output would have gone (the pool's output buffer is the one the conv reads), so the ping-pong buffers
-// swap roles for every later layer.  "conv_pool" = 0: not.
+// kernel's POOL2 form wherever it takes the shape.  "conv_pool" = 0: not.
 void fuse_conv_pools(sqdet_net* net, size_t esz) {
-  if (conv_algo() != 0 || tune(10) == 0) return;   // ("conv_pool")
-  std::vector<Layer> out;
-  std::vector<Layer> in = net->layers;
-  bool fused_any = false;
-  for (size_t i = 0; i < in.size(); ++i) {
+  if (conv_algo() != 0 || tune(TUNE_CONV_POOL) == 0) return;
+  rewrite_layers(net, [&](std::vector<Layer>& in, size_t i, std::vector<Layer>& out) -> size_t {
     const Layer& c = in[i];
     const bool ok = i + 1 < in.size() && c.type == L_CONV && c.k == 3 && c.stride == 1 && c.pad_mode == SQDET_PAD_SAME && c.fold < 0 &&
                     !c.accum && c.y_cstride == c.cout && c.y_coffset == 0 && c.out_buf >= 0 && in[i + 1].type == L_POOL &&
                     in[i + 1].k == 2 && in[i + 1].stride == 2 && in[i + 1].pad_mode == SQDET_PAD_SAME && in[i + 1].in_buf == c.out_buf &&
                     conv2d_maxpool2_eligible(net->batch, c.h, c.w, c.cin, c.cout, net->dtype);
-    if (!ok) { out.push_back(c); continue; }
-    const Layer& p = in[i + 1];
-    Layer f = c;
-    f.conv_pool = 1;
-    f.name = c.name + "+" + p.name;
-    f.ho = p.ho; f.wo = p.wo;
-    for (size_t k = i + 2; k < in.size(); ++k) {
-      auto sw = [](int b) { return b == BUF_A ? BUF_B : (b == BUF_B ? BUF_A : b); };
-      in[k].in_buf = sw(in[k].in_buf);
-      in[k].out_buf = sw(in[k].out_buf);
-    }
-    fused_any = true;
-    // algorithmic bytes: conv input + POOLED output + weights + bias
-    f.bytes = c.bytes - (double)net->batch * c.ho * c.wo * c.cout * (double)esz + (double)net->batch * p.ho * p.wo * c.cout * (double)esz;
-    out.push_back(f);
-    ++i;
-  }
-  net->layers.swap(out);
-  if (fused_any) {   // either buffer may now hold what the other was sized for
-    const size_t m = net->buf_elems[BUF_A] > net->buf_elems[BUF_B] ? net->buf_elems[BUF_A] : net->buf_elems[BUF_B];
-    net->buf_elems[BUF_A] = net->buf_elems[BUF_B] = m;
-  }
+    if (!ok) return 0;
+    out.push_back(absorb_pool(net, in, i, esz));
+    out.back().conv_pool = 1;
+    return 2;
+  });
 }
 
 // conv1 + pool1 -> one L_STEM launch when the fused kernel applies (decided at plan creation).
@@ -1136,7 +1073,7 @@ static int fire_fwd_impl(const void* x, const void* w_s, const float* b_s, const
   hipStream_t st = as_stream(stream);
   bool handled = false;
   int rc = SQDET_OK;
-  if (tune(3) != 2) {  // one fused launch when eligible (keep: its squeeze epilogue also writes the squeeze tensor)
+  if (tune(TUNE_FIRE_FUSE) != 2) {  // one fused launch when eligible (keep: its squeeze epilogue also writes the squeeze tensor)
     rc = fire_fused_launch_keep(x, w_s, b_s, w_e1, b_e1, w_e3, b_e3, keep ? sq_scratch : nullptr, y, n, h, w, cin, s1x1, e1x1, e3x3,
                                 dtype, st, &handled);
     if (rc != SQDET_OK || handled) return rc;
@@ -1155,7 +1092,7 @@ extern "C" int sqdet_fire_maxpool_fwd(const void* x, const void* w_s, const floa
                                       sqdet_stream_t stream) {
   SQDET_REQUIRE(fire_scratch && y, "fire_maxpool_fwd: null pointer");
   hipStream_t st = as_stream(stream);
-  const int ff = tune(3);
+  const int ff = tune(TUNE_FIRE_FUSE);
   if (ff != 2 && ff != 3 && ff != 4) {   // one launch when the streaming kernel covers the shape (the scratches stay untouched)
     bool handled = false;
     const int rc = fire_stream_launch_ex(x, w_s, b_s, w_e1, b_e1, w_e3, b_e3, y, n, h, w, cin, s1x1, e1x1, e3x3, dtype, 1, st,

@@ -16,13 +16,6 @@
 
 namespace sqdet {
 
-int conv2d_launch_ex(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
-                     int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
-                     int x_cstride, int x_coffset, int accum, hipStream_t st);
-int conv2d_launch_masked(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w, int cin,
-                         int cout, int k, int stride, int pad_mode, int relu, int dtype, int y_cstride, int y_coffset,
-                         int x_cstride, int x_coffset, int accum, const void* relu_of, hipStream_t st);
-
 // ------------------------------------------------------------------ backward-data weight packing
 // dgrad(dy)[ci] = sum_{tap,co} W[k-1-ty][k-1-tx][ci][co] * dy@tap[co]: a forward conv with
 // kernel W'[ty][tx][co][ci].  Packed in the forward fragment order for a [k,k,cout,cin] kernel.

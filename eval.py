@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""Evaluates SqueezeDet checkpoints on KITTI (the reference's src/eval.py) in batches, scored on the GPU.
+"""Evaluates SqueezeDet checkpoints on KITTI or Pascal VOC (the reference's src/eval.py) in batches, scored on the GPU.
 
     python eval.py --data_path KITTI --image_set val --checkpoint_path ckpt/model-20000.npz --run_once [--net squeezeDet]
+    python eval.py --dataset PASCAL_VOC --data_path VOCdevkit --year 2007 --image_set test --checkpoint_path ... --run_once
 
 The reference's order per image: det_boxes rescaled to the original image size (float32, eval.py:83-84), then
 filter_prediction, then the rows added to the detection table -- here a whole batch at a time on the device
@@ -11,6 +12,12 @@ filter_prediction, then the rows added to the detection table -- here a whole ba
 det_error_file.txt, and one JSON line per checkpoint in eval_log.jsonl (in place of TF summaries).  --visualize N: N example
 detections per error type of that file, each drawn on the device over its original image (imdb.visualize_detections) to
 error_analysis/<type>/<i>.png; the rows are chosen by a permutation seeded with --seed.
+
+--dataset PASCAL_VOC reads <data_path>/VOC<year> (squeezedet_amd.voc.load_voc; any dataset in VOC XML format), runs
+SqueezeDet with the 20-class config at --image_size and scores the table with the GPU VOC evaluator
+(squeezedet_amd.voc.VocEvaluator): it prints '<cls>: AP = ...' and 'Mean AP = ...' as pascal_voc.evaluate_detections does
+and writes detection_files_<step>/<cls>.txt and the eval_log.jsonl line.  --eval_tool, the error analysis and --visualize
+are KITTI-only.  (The net's ConvDet head is padded from 20 to 23 classes, the padding pinned to probability 0: DESIGN.md section 3.9.)
 
 Checkpoints are .npz files from squeezedet_amd.weights.save_params.  --run_once: --checkpoint_path is that file;
 otherwise it is a directory polled every --eval_interval_secs for the newest '*-<step>.npz'.  Every image is scored
@@ -29,9 +36,12 @@ NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--dataset", default="KITTI", help="only KITTI is supported")
-    ap.add_argument("--data_path", default="", help="root directory of the KITTI data")
-    ap.add_argument("--image_set", default="test", help="ImageSets/<image_set>.txt")
+    ap.add_argument("--dataset", default="KITTI", help="KITTI or PASCAL_VOC")
+    ap.add_argument("--data_path", default="", help="root directory of the KITTI data (PASCAL_VOC: the directory that holds VOC<year>)")
+    ap.add_argument("--image_set", default="test", help="ImageSets/<image_set>.txt (PASCAL_VOC: ImageSets/Main/<image_set>.txt)")
+    ap.add_argument("--year", default="2007", help="PASCAL_VOC: the VOC<year> directory; before 2010 the 11-point AP is reported")
+    ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="PASCAL_VOC: network input size (default: 384 1248, SqueezeDet's)")
     ap.add_argument("--eval_dir", default="/tmp/squeezeDet/eval", help="where results are written")
     ap.add_argument("--checkpoint_path", default="/tmp/squeezeDet/train", help="a .npz file (--run_once) or a directory")
     ap.add_argument("--eval_interval_secs", type=int, default=60, help="how often to look for a new checkpoint")
@@ -45,20 +55,38 @@ def parse_args(argv=None):
     ap.add_argument("--visualize", type=int, default=0, metavar="N",
                     help="draw N example detections per error type of the error analysis (the reference draws 10; 0: none)")
     ap.add_argument("--seed", type=int, default=0, help="seeds the choice of the rows --visualize draws")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    assert a.dataset in ("KITTI", "PASCAL_VOC"), "Currently only supports KITTI dataset (and PASCAL_VOC)"
+    return a
 
 
 def make_model(net, gpu, dtype, batch_size=0):
-    import torch
     import squeezedet_amd as S
     from squeezedet_amd import nets
     cfg, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
                 "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[net]
     mc = cfg()
+    return mc, _build(mc, cls, gpu, dtype, batch_size)
+
+
+def make_voc_model(net, gpu, dtype, batch_size=0, image_size=None):
+    """SqueezeDet with the 20-class VOC config (config.voc_squeezeDet_config_for_input) at image_size."""
+    import squeezedet_amd as S
+    from squeezedet_amd import nets
+    if net != "squeezeDet":
+        raise SystemExit("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
+    h, w = image_size or (384, 1248)
+    from squeezedet_amd.config import pad_head_classes
+    mc = pad_head_classes(S.voc_squeezeDet_config_for_input(int(h), int(w)))     # 20 classes -> a head of 23, 3 of them padding
+    return mc, _build(mc, nets.SqueezeDet, gpu, dtype, batch_size)
+
+
+def _build(mc, cls, gpu, dtype, batch_size):
+    import torch
     if batch_size:
         mc.BATCH_SIZE = int(batch_size)
     mc.LOAD_PRETRAINED_MODEL = False
-    return mc, cls(mc, gpu, dtype=torch.float16 if dtype == "fp16" else torch.float32)
+    return cls(mc, gpu, dtype=torch.float16 if dtype == "fp16" else torch.float32)
 
 
 def read_image(path, model):
@@ -136,17 +164,25 @@ def visualize_detections(image_dir, image_format, det_error_file, output_image_d
     return drawn
 
 
-def eval_once(a, model, data, ckpt_path, evaluator):
-    import torch
-    from squeezedet_amd import kitti_eval, weights, synthetic
-    mc = model.mc
+def load_weights(a, model, ckpt_path):
+    """Loads the checkpoint (or the seeded synthetic weights) into the model; returns the global step as text."""
+    from squeezedet_amd import weights, synthetic
+    from squeezedet_amd.config import pin_padding_classes
     if a.synthetic_weights:
-        model.load_params(synthetic.synthetic_params(model, seed=0))
+        model.load_params(pin_padding_classes(model.mc, synthetic.synthetic_params(model, seed=0)))
         global_step = "0"
     else:
         from squeezedet_amd.kitti_ap import parse_checkpoint_step
-        model.load_params(weights.load_params(ckpt_path))
+        model.load_params(pin_padding_classes(model.mc, weights.load_params(ckpt_path)))
         global_step = parse_checkpoint_step(ckpt_path)
+    return global_step
+
+
+def detect_all(model, data, evaluator):
+    """Every image of the set through the detector and the filter into the evaluator's table, a batch at a time.
+    Returns (detections, seconds in detect, seconds in the rest, batches)."""
+    import torch
+    mc = model.mc
     n = len(data.image_idx)
     evaluator.reset()
     t_detect = t_misc = 0.0
@@ -170,6 +206,15 @@ def eval_once(a, model, data, ckpt_path, evaluator):
                                                                          t_misc / (i0 // mc.BATCH_SIZE + 1)))
     num_detection = int(torch.cat(counts).clamp(min=0).sum().item())
     nb = max(1, (n + mc.BATCH_SIZE - 1) // mc.BATCH_SIZE)
+    return num_detection, t_detect, t_misc, nb
+
+
+def eval_once(a, model, data, ckpt_path, evaluator):
+    from squeezedet_amd import kitti_eval
+    mc = model.mc
+    global_step = load_weights(a, model, ckpt_path)
+    n = len(data.image_idx)
+    num_detection, t_detect, t_misc, nb = detect_all(model, data, evaluator)
 
     print("Evaluating detections...")
     t0 = time.time()
@@ -223,6 +268,39 @@ def eval_once(a, model, data, ckpt_path, evaluator):
     return rec
 
 
+def eval_once_voc(a, model, data, ckpt_path, evaluator):
+    """eval_once for Pascal VOC: pascal_voc.evaluate_detections (:81-137) on the device table."""
+    from squeezedet_amd.voc import use_07_metric_for
+    global_step = load_weights(a, model, ckpt_path)
+    n = len(data.image_idx)
+    num_detection, t_detect, t_misc, nb = detect_all(model, data, evaluator)
+
+    print("Evaluating detections...")
+    t0 = time.time()
+    evaluator.write_detection_files(os.path.join(a.eval_dir, "detection_files_{:s}".format(global_step)), data.image_idx)
+    aps, ap_names = evaluator.evaluate(use_07_metric_for(a.year))
+    for cls, ap in zip(ap_names, aps):
+        print("{:s}: AP = {:.4f}".format(cls, ap))
+    print("Mean AP = {:.4f}".format(np.mean(aps)))
+    t_eval = time.time() - t0
+
+    print("Evaluation summary:")
+    print("  Average number of detections per image: {}:".format(num_detection / float(n)))
+    print("  Timing:")
+    print("    detect: {:.3f}s misc: {:.3f}s eval: {:.3f}s".format(t_detect / nb, t_misc / nb, t_eval))
+    print("  Average precisions:")
+    for cls, ap in zip(ap_names, aps):
+        print("    {}: {:.3f}".format(cls, ap))
+    print("    Mean average precision: {:.3f}".format(np.mean(aps)))
+
+    rec = {"global_step": global_step, "checkpoint": ckpt_path, "mAP": float(np.mean(aps)),
+           "APs": dict(zip(ap_names, [float(v) for v in aps])), "num_det_per_image": num_detection / float(n),
+           "timing": {"im_detect": t_detect / nb, "post_proc": t_misc / nb, "eval": t_eval}}
+    with open(os.path.join(a.eval_dir, "eval_log.jsonl"), "a") as f:
+        f.write(json.dumps(rec) + "\n")
+    return rec
+
+
 def latest_checkpoint(directory):
     """The newest '*-<step>.npz' in directory (largest step), or None."""
     from squeezedet_amd.kitti_ap import parse_checkpoint_step
@@ -236,14 +314,26 @@ def latest_checkpoint(directory):
 
 def main(argv=None):
     a = parse_args(argv)
-    assert a.dataset == "KITTI", "Currently only supports KITTI dataset"
-    from squeezedet_amd.kitti_ap import KittiEvaluator, load_kitti
-    mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size)
-    data = load_kitti(a.data_path, a.image_set, mc)
-    evaluator = KittiEvaluator(mc, data.gt, model.device)
+    if a.dataset == "PASCAL_VOC":
+        for flag, given in (("--eval_tool", a.eval_tool), ("--visualize", a.visualize)):
+            if given:
+                raise SystemExit("%s is KITTI-only: the external evaluator and the error analysis have no Pascal VOC form" % flag)
+        from squeezedet_amd.voc import VocEvaluator, load_voc
+        mc, model = make_voc_model(a.net, a.gpu, a.dtype, a.batch_size, a.image_size)
+        data = load_voc(a.data_path, a.year, a.image_set, mc)
+        evaluator = VocEvaluator(mc, data.gt, model.device)
+        once = eval_once_voc
+    else:
+        if a.image_size is not None:
+            raise SystemExit("--image_size is for --dataset PASCAL_VOC (the KITTI nets run at their configs' size)")
+        from squeezedet_amd.kitti_ap import KittiEvaluator, load_kitti
+        mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size)
+        data = load_kitti(a.data_path, a.image_set, mc)
+        evaluator = KittiEvaluator(mc, data.gt, model.device)
+        once = eval_once
     os.makedirs(a.eval_dir, exist_ok=True)
     if a.run_once:
-        return eval_once(a, model, data, a.checkpoint_path, evaluator)
+        return once(a, model, data, a.checkpoint_path, evaluator)
     seen = set()
     while True:
         ckpt = latest_checkpoint(a.checkpoint_path)
@@ -252,7 +342,7 @@ def main(argv=None):
         elif ckpt not in seen:
             seen.add(ckpt)
             print("Evaluating {}...".format(ckpt))
-            eval_once(a, model, data, ckpt, evaluator)
+            once(a, model, data, ckpt, evaluator)
             continue
         print("Wait {:d}s for new checkpoints to be saved ... ".format(a.eval_interval_secs))
         time.sleep(a.eval_interval_secs)

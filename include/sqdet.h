@@ -636,6 +636,56 @@ int sqdet_kitti_analyze(const double* det_box, const double* det_score, const in
                         int num_rois, int32_t* counters, int32_t* rec_count, int32_t* rec_type, int32_t* rec_cls,
                         double* rec_box, double* rec_score, sqdet_stream_t stream);
 
+/* -------------------------------------------------- Pascal VOC evaluation --
+ * Replaces the scoring half of the reference for Pascal VOC -- the per-class detection files of
+ * dataset/pascal_voc.py:98-109 and the VOC AP metric of dataset/voc_eval.py:33-64,124-204 -- with device tables, for every
+ * class at once.  All values are double: exactly what voc_eval reads back with float() from the files the reference writes.
+ *
+ * Detection table (caller-owned, device; the KITTI table's layout, `cap` <= SQDET_VOC_MAX_DETECTIONS rows per image):
+ *   det_box double [num_images,cap,4] (x1,y1,x2,y2, 1-based as the files carry them), det_score double [num_images,cap],
+ *   det_cls int32 [num_images,cap] (0 <= class < classes <= SQDET_VOC_MAX_CLASSES), det_count int32 [num_images] (zero it
+ *   to reset), status int32 [2] (zero it to reset).
+ * Ground truth (device): image i owns rows [gt_offsets[i], gt_offsets[i+1]) (<= SQDET_VOC_MAX_GROUNDTRUTH), gt_box double
+ *   [G,4] (the XML's integers xmin,ymin,xmax,ymax), gt_cls int32 [G] (-1: a name outside the class list, never matched),
+ *   gt_difficult int32 [G].
+ *
+ * TIE RULE (ours): the rows of a class are ordered by descending score, equal scores by image index, then by row index
+ * within the image.  The reference's np.argsort(-confidence) (voc_eval.py:151) is not stable, so its order of equal
+ * scores is unspecified; this one is fixed, and two runs on the same table give bitwise the same results. */
+enum { SQDET_VOC_MAX_DETECTIONS = 512, SQDET_VOC_MAX_GROUNDTRUTH = 128, SQDET_VOC_MAX_CLASSES = 64 };
+
+/* pascal_voc.evaluate_detections' file writer (pascal_voc.py:98-109) into the table: appends n images of filter rows
+ * (sqdet_filter_prediction layout, as sqdet_kitti_ingest) as table images [image_offset, image_offset + n).  Per row, in
+ * float32 as the reference's NumPy does: cx,w /= (float)x_scale and cy,h /= (float)y_scale (scales: double [n,2], NULL = no
+ * division; eval.py:83-84), bbox_transform (cx - w/2, ...; eval.py:91), + 1 (pascal_voc.py:107-108); then each coordinate
+ * is the double nearest to what '{:.1f}' prints for it and the score the double nearest to its '{:.3f}'.  Rows are stored
+ * class-major, filter order within a class: the order of the per-class files.  A count outside [0, max_out] or a class
+ * outside [0, classes) makes the WHOLE call write nothing and marks status; sqdet_voc_evaluate then returns SQDET_EINVAL.
+ * max_out > cap: SQDET_EUNSUPPORTED.  Asynchronous. */
+int sqdet_voc_ingest(const float* boxes, const float* probs, const int32_t* cls, const int32_t* count, const double* scales,
+                     int n, int max_out, int classes, double* det_box, double* det_score, int32_t* det_cls, int32_t* det_count,
+                     int32_t* status, int image_offset, int num_images, int cap, sqdet_stream_t stream);
+
+/* voc_eval (voc_eval.py:124-204) and voc_ap (:33-64) for every class, on the device: per (image, class) the class's
+ * detections by descending score are matched greedily to the image's objects of the class ('+1' overlaps, ovmax > 0.5 in
+ * double, np.argmax's first index; a difficult best match counts as neither, a taken one as false positive, :187-195); the
+ * flags are put in the class's order (TIE RULE above), summed by a prefix sum, rec = tp / npos and
+ * prec = tp / max(tp + fp, DBL_EPSILON); then both APs.
+ * Host outputs, each [classes]: host_ap07 (the 11-point form, thresholds i * 0.1, `ap + p / 11.` in threshold order:
+ * bitwise the reference's), host_ap_area (area under the precision envelope; the terms are summed in a fixed order that is
+ * not NumPy's pairwise one, so it may differ from the reference by n * 2^-53 for n rows), host_npos (non-difficult
+ * objects), host_num_det (rows).  A class without rows has AP 0 (:147-148).  curve_cls >= 0: that class's rec and prec
+ * (host_num_det[curve_cls] values each, the class's order) into the device buffers curve_rec / curve_prec of
+ * num_images * cap doubles; curve_cls < 0: they may be NULL.  workspace: sqdet_voc_eval_workspace_bytes(num_images, cap,
+ * classes) of device scratch.  SYNCHRONISES `stream` once, at the end; the host outputs are untouched on failure.  An image
+ * over the row limits: SQDET_EUNSUPPORTED; a rejected ingest in the table: SQDET_EINVAL. */
+size_t sqdet_voc_eval_workspace_bytes(int num_images, int cap, int classes);
+int sqdet_voc_evaluate(const double* det_box, const double* det_score, const int32_t* det_cls, const int32_t* det_count,
+                       const int32_t* status, int num_images, int cap, int classes, const int32_t* gt_offsets,
+                       const double* gt_box, const int32_t* gt_cls, const int32_t* gt_difficult, int num_gt, void* workspace,
+                       double* host_ap07, double* host_ap_area, int32_t* host_npos, int32_t* host_num_det, int curve_cls,
+                       double* curve_rec, double* curve_prec, sqdet_stream_t stream);
+
 /* ------------------------------------------------------ training summaries --
  * Replaces the per-tensor summary ops of the training graph: tf.summary.histogram of every trainable variable and of its
  * gradient (nn_skeleton.py:353-358) and _activation_summary (nn_skeleton.py:736-755: histogram, tf.nn.zero_fraction,

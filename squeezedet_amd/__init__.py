@@ -3,7 +3,7 @@ interpret_output, filter_prediction, and the training step) as hand-written HIP 
 (gfx950) behind the reference's Python surface.  See DESIGN.md / INTEGRATION.md."""
 from .config import (base_model_config, kitti_res50_config, kitti_res50_config_for_input,  # noqa: F401
                      kitti_squeezeDet_config, kitti_squeezeDet_config_for_input, kitti_squeezeDetPlus_config,
-                     kitti_vgg16_config, kitti_vgg16_config_for_input)
+                     kitti_vgg16_config, kitti_vgg16_config_for_input, voc_squeezeDet_config_for_input)
 from .imdb import Batch, BatchReader  # noqa: F401  (NumPy only at import; the GPU half is used lazily)
 
 

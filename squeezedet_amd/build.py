@@ -52,6 +52,8 @@ SOURCES = [
     ("filter_fast.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: overlaps, recall steps and the '%.2f' / '%.3f' rounding are bitwise those of the host programs)
     ("kitti_eval.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the '+1' overlaps, recall / precision and the '{:.1f}' / '{:.3f}' rounding are bitwise NumPy's)
+    ("voc_eval.hip", ["-ffp-contract=off"]),
     ("train.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: sumsq adds the exact float64 square; nothing to contract, and the sums keep the order written)
     ("summary.hip", ["-ffp-contract=off"]),

@@ -190,3 +190,54 @@ def kitti_vgg16_config_for_input(image_height, image_width):
     for _ in range(4):
         gh, gw = -(-gh // 2), -(-gw // 2)
     return _finish(mc, gh, gw, SQUEEZEDET_ANCHOR_SHAPES)
+
+
+def voc_squeezeDet_config_for_input(image_height, image_width):
+    """SqueezeDet on Pascal VOC's 20 classes at a given input size.  OURS: the reference ships no VOC net config
+    (config/ has KITTI ones only); this is base_model_config("PASCAL_VOC") with the hyperparameters, the grid and the
+    anchor construction of kitti_squeezeDet_config_for_input, so that eval.py and train.py can run on VOC XML datasets.
+    The anchor shapes are KITTI's, not tuned for VOC.
+    A net for it is built on pad_head_classes(mc): 9 * (20 + 5) = 225 ConvDet channels are not a multiple of 4."""
+    mc = base_model_config("PASCAL_VOC")
+    mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT = int(image_width), int(image_height)
+    gh, gw = int(image_height), int(image_width)
+    for _ in range(4):
+        gh, gw = -(-gh // 2), -(-gw // 2)
+    return _finish(_kitti_common(mc), gh, gw, SQUEEZEDET_ANCHOR_SHAPES)
+
+
+PAD_CLASS_BIAS = -1.0e4      # the ConvDet bias of a padding class: exp(-1e4 - max) is exactly 0 in float32 and float16
+
+
+def pad_head_classes(mc):
+    """The config a net is BUILT with when ANCHOR_PER_GRID * (CLASSES + 5) is not a multiple of 4 (the conv kernels store
+    output channels four at a time): a copy of mc whose CLASSES is the next count that is -- 20 -> 23, a ConvDet layer of
+    252 channels -- with HEAD_PAD_CLASSES = the classes added (0: nothing to do).  CLASS_NAMES keeps the real names: class
+    indices >= len(CLASS_NAMES) are padding.  With pin_padding_classes on its parameters a padding class has probability
+    exactly 0, so the net computes what the unpadded one would: softmax over the real classes, no detection of a padding
+    class, and a zero gradient into the padding channels."""
+    mc = type(mc)(mc)
+    c = int(mc.CLASSES)
+    while (mc.ANCHOR_PER_GRID * (c + 1 + 4)) % 4:
+        c += 1
+    mc.HEAD_PAD_CLASSES = c - int(mc.CLASSES)
+    mc.CLASSES = c
+    return mc
+
+
+def pin_padding_classes(mc, params, layer="conv12"):
+    """params ({name: array / tensor}) with the ConvDet layer's padding-class channels pinned: kernels 0, biases
+    PAD_CLASS_BIAS.  The class logits are channels a * CLASSES + c (anchor a, class c; nn_skeleton.py:250-258); c >=
+    len(CLASS_NAMES) is padding.  Returns params itself when mc has no padding."""
+    pad = int(mc.get("HEAD_PAD_CLASSES", 0))
+    if not pad:
+        return params
+    C, real = int(mc.CLASSES), int(mc.CLASSES) - pad
+    ch = np.array([a * C + c for a in range(int(mc.ANCHOR_PER_GRID)) for c in range(real, C)])
+    out = dict(params)
+    host = lambda v: np.array(v.detach().cpu().numpy() if hasattr(v, "detach") else v, np.float32)
+    k, b = host(out[layer + "/kernels"]), host(out[layer + "/biases"])
+    k[..., ch] = 0.0
+    b[ch] = PAD_CLASS_BIAS
+    out[layer + "/kernels"], out[layer + "/biases"] = k, b
+    return out

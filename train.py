@@ -3,6 +3,7 @@
 with on-device summaries.
 
     python train.py --data_path KITTI --image_set train --train_dir logs/train --net squeezeDet [--pretrained_model_path w.npz]
+    python train.py --dataset PASCAL_VOC --data_path VOCdevkit --year 2007 --image_set trainval --train_dir logs/voc
     python train.py --synthetic 40 --train_dir /tmp/run --max_steps 100          # seeded synthetic data, no dataset needed
     python train.py ... --resume                                                  # continue from the newest checkpoint
 
@@ -15,7 +16,9 @@ step, named by the step -- is the pair model.ckpt-<step>.npz (what eval.py polls
 state/step-<step>.npz (squeezedet_amd.checkpoint); --resume continues from the newest pair bit for bit.  <train_dir>/model_metrics.txt is the reference's (train.py:137-159).
 
 The reference deletes --train_dir at start (train.py:338-340).  Here a non-empty --train_dir is refused unless --resume
-or --overwrite (delete, as the reference does).  Not carried over: Pascal VOC.
+or --overwrite (delete, as the reference does).  --dataset PASCAL_VOC trains SqueezeDet with the 20-class config
+(config.voc_squeezeDet_config_for_input, at --image_size or 384 x 1248) on <data_path>/VOC<year>, read by
+squeezedet_amd.voc.load_voc; the images may differ in size.  (Its ConvDet head is padded to 23 classes: DESIGN.md section 3.9.)
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
 import argparse
@@ -33,7 +36,8 @@ RESIDENT_BYTES = 4 << 30       # a dataset whose uint8 images fit this budget li
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--dataset", default="KITTI", help="Currently only support KITTI dataset.")
+    ap.add_argument("--dataset", default="KITTI", help="KITTI or PASCAL_VOC.")
+    ap.add_argument("--year", default="2007", help="PASCAL_VOC: the VOC<year> directory under --data_path")
     ap.add_argument("--data_path", default="", help="Root directory of data")
     ap.add_argument("--image_set", default="train", help="Can be train, trainval, val, or test")
     ap.add_argument("--train_dir", default="/tmp/squeezeDet/train", help="Directory where to write summaries and checkpoints.")
@@ -56,15 +60,20 @@ def parse_args(argv=None):
     ap.add_argument("--image_summary", type=int, default=0, metavar="N",
                     help="at summary steps, write the first N images of the batch with ground truth and detections drawn (0: none)")
     a = ap.parse_args(argv)
-    assert a.dataset == "KITTI", "Currently only supports KITTI dataset"
+    assert a.dataset in ("KITTI", "PASCAL_VOC"), "Currently only supports KITTI dataset (and PASCAL_VOC)"
+    if a.dataset == "PASCAL_VOC" and a.net != "squeezeDet":
+        ap.error("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
     if a.resume and a.overwrite:
         ap.error("--resume and --overwrite exclude each other")
     return a
 
 
-def make_config(net, image_size=None):
+def make_config(net, image_size=None, dataset="KITTI"):
     import squeezedet_amd as S
     from squeezedet_amd import config
+    if dataset == "PASCAL_VOC":
+        h, w = image_size if image_size is not None else (384, 1248)
+        return config.pad_head_classes(config.voc_squeezeDet_config_for_input(int(h), int(w)))
     if image_size is not None:
         sized = {"squeezeDet": config.kitti_squeezeDet_config_for_input, "resnet50": config.kitti_res50_config_for_input,
                  "vgg16": config.kitti_vgg16_config_for_input}
@@ -93,6 +102,16 @@ def make_trainer(a, mc, local_rank=0):
 
 
 def initial_params(a, model):
+    from squeezedet_amd.config import pin_padding_classes
+    params = _initial_params(a, model)
+    if model.mc.get("HEAD_PAD_CLASSES", 0):         # a padded ConvDet head (PASCAL_VOC): its padding classes get probability 0
+        for name in ("conv12/kernels", "conv12/biases"):
+            params.setdefault(name, model.params[name])          # (a backbone pickle does not cover the head)
+        params = pin_padding_classes(model.mc, params)
+    return params
+
+
+def _initial_params(a, model):
     from squeezedet_amd import synthetic, weights
     p = a.pretrained_model_path
     if not p:
@@ -109,8 +128,12 @@ def load_dataset(a, mc):
         from squeezedet_amd.synthetic import synthetic_dataset
         return synthetic_dataset(mc, int(a.synthetic), seed=300 + a.seed)
     from PIL import Image
-    from squeezedet_amd.kitti_ap import load_kitti
-    data = load_kitti(a.data_path, a.image_set, mc)
+    if a.dataset == "PASCAL_VOC":
+        from squeezedet_amd.voc import load_voc
+        data = load_voc(a.data_path, a.year, a.image_set, mc)
+    else:
+        from squeezedet_amd.kitti_ap import load_kitti
+        data = load_kitti(a.data_path, a.image_set, mc)
     images = [np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[:, :, ::-1]) for p in data.image_paths]   # BGR, as cv2.imread
     return images, data.rois
 
@@ -160,7 +183,7 @@ class Run:
         from squeezedet_amd.train import GraphedStep
         self.a, self.rank = a, rank
         self.dev = dev = torch.device("cuda", local_rank)
-        self.mc = mc = make_config(a.net, a.image_size)
+        self.mc = mc = make_config(a.net, a.image_size, a.dataset)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)

@@ -17,7 +17,8 @@ cls2clr colours.  --mode video takes a glob of FRAME FILES, sorted by name -- th
 --weights: a {variable name: array} file written by squeezedet_amd.weights.save_params (or converted from a
 reference checkpoint with squeezedet_amd.weights.from_reference_names); without it seeded synthetic weights
 are used (there is no network access to fetch the reference's checkpoint), so the boxes are meaningless but
-the whole path runs.
+the whole path runs.  --anchor_shapes FILE: the anchor shapes the weights were trained with (tools/fit_anchors.py, train.py
+--anchor_shapes); without the flag an anchor_shapes.json beside --weights is used, else the config's own shapes.
 """
 import argparse
 import glob
@@ -49,6 +50,8 @@ def parse_args(argv=None):
     ap.add_argument("--out_dir", default="./data/out/")
     ap.add_argument("--demo_net", default="squeezeDet", choices=["squeezeDet", "squeezeDet+", "resnet50", "vgg16"])
     ap.add_argument("--weights", default="")
+    ap.add_argument("--anchor_shapes", default="", metavar="FILE",
+                    help="anchor shapes the weights were trained with (default: anchor_shapes.json beside --weights, else the config's)")
     ap.add_argument("--gpu", default="0")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp32"])
     ap.add_argument("--draw", default="pil", choices=["pil", "gpu"], help="image mode: draw with PIL on the host, or on the device")
@@ -66,10 +69,13 @@ def parse_args(argv=None):
 def make_model(a, batch):
     import torch
     import squeezedet_amd as S
-    from squeezedet_amd import nets, synthetic, weights
+    from squeezedet_amd import anchors, config, nets, synthetic, weights
     mc, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
                "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[a.demo_net]
     mc = mc()
+    shapes_file = a.anchor_shapes or (a.weights and anchors.beside_checkpoint(a.weights))
+    if shapes_file:
+        mc = config.with_anchor_shapes(mc, anchors.load_for_driver(shapes_file))
     mc.BATCH_SIZE = int(batch)
     mc.LOAD_PRETRAINED_MODEL = False          # parameters are restored below (demo.py:171-172)
     dtype = torch.float16 if a.dtype == "fp16" else torch.float32

@@ -19,6 +19,9 @@ SqueezeDet with the 20-class config at --image_size and scores the table with th
 and writes detection_files_<step>/<cls>.txt and the eval_log.jsonl line.  --eval_tool, the error analysis and --visualize
 are KITTI-only.  (The net's ConvDet head is padded from 20 to 23 classes, the padding pinned to probability 0: DESIGN.md section 3.9.)
 
+--anchor_shapes FILE: the net's anchors take the shapes of that file (tools/fit_anchors.py, train.py --anchor_shapes); without
+the flag an anchor_shapes.json beside the checkpoint -- train.py leaves one in its --train_dir -- is used, else the config's own.
+
 Checkpoints are .npz files from squeezedet_amd.weights.save_params.  --run_once: --checkpoint_path is that file;
 otherwise it is a directory polled every --eval_interval_secs for the newest '*-<step>.npz'.  Every image is scored
 once (the last batch is padded; the reference's reader wraps around instead).
@@ -55,29 +58,47 @@ def parse_args(argv=None):
     ap.add_argument("--visualize", type=int, default=0, metavar="N",
                     help="draw N example detections per error type of the error analysis (the reference draws 10; 0: none)")
     ap.add_argument("--seed", type=int, default=0, help="seeds the choice of the rows --visualize draws")
+    ap.add_argument("--anchor_shapes", default="", metavar="FILE",
+                    help="anchor shapes the checkpoint was trained with (default: anchor_shapes.json beside the checkpoint, else the config's)")
     a = ap.parse_args(argv)
     assert a.dataset in ("KITTI", "PASCAL_VOC"), "Currently only supports KITTI dataset (and PASCAL_VOC)"
     return a
 
 
-def make_model(net, gpu, dtype, batch_size=0):
+def anchor_shapes_for(a):
+    """[k,2] from --anchor_shapes, else from an anchor_shapes.json beside the checkpoint, else None (the config's shapes)."""
+    from squeezedet_amd import anchors
+    path = a.anchor_shapes or anchors.beside_checkpoint(a.checkpoint_path)
+    if not path:
+        return None
+    print("Anchor shapes from {}".format(path))
+    return anchors.load_for_driver(path)
+
+
+def make_model(net, gpu, dtype, batch_size=0, anchor_shapes=None):
     import squeezedet_amd as S
     from squeezedet_amd import nets
+    from squeezedet_amd.config import with_anchor_shapes
     cfg, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
                 "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[net]
     mc = cfg()
+    if anchor_shapes is not None:
+        mc = with_anchor_shapes(mc, anchor_shapes)
     return mc, _build(mc, cls, gpu, dtype, batch_size)
 
 
-def make_voc_model(net, gpu, dtype, batch_size=0, image_size=None):
+def make_voc_model(net, gpu, dtype, batch_size=0, image_size=None, anchor_shapes=None):
     """SqueezeDet with the 20-class VOC config (config.voc_squeezeDet_config_for_input) at image_size."""
     import squeezedet_amd as S
     from squeezedet_amd import nets
     if net != "squeezeDet":
         raise SystemExit("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
     h, w = image_size or (384, 1248)
-    from squeezedet_amd.config import pad_head_classes
-    mc = pad_head_classes(S.voc_squeezeDet_config_for_input(int(h), int(w)))     # 20 classes -> a head of 23, 3 of them padding
+    from squeezedet_amd.config import pad_head_classes, with_anchor_shapes
+    mc = S.voc_squeezeDet_config_for_input(int(h), int(w))
+    if anchor_shapes is not None:
+        mc = with_anchor_shapes(mc, anchor_shapes)                                # (before the padding, which depends on the count)
+    mc = pad_head_classes(mc)                                                     # 20 classes -> a head of 23, 3 of them padding
     return mc, _build(mc, nets.SqueezeDet, gpu, dtype, batch_size)
 
 
@@ -319,7 +340,7 @@ def main(argv=None):
             if given:
                 raise SystemExit("%s is KITTI-only: the external evaluator and the error analysis have no Pascal VOC form" % flag)
         from squeezedet_amd.voc import VocEvaluator, load_voc
-        mc, model = make_voc_model(a.net, a.gpu, a.dtype, a.batch_size, a.image_size)
+        mc, model = make_voc_model(a.net, a.gpu, a.dtype, a.batch_size, a.image_size, anchor_shapes_for(a))
         data = load_voc(a.data_path, a.year, a.image_set, mc)
         evaluator = VocEvaluator(mc, data.gt, model.device)
         once = eval_once_voc
@@ -327,7 +348,7 @@ def main(argv=None):
         if a.image_size is not None:
             raise SystemExit("--image_size is for --dataset PASCAL_VOC (the KITTI nets run at their configs' size)")
         from squeezedet_amd.kitti_ap import KittiEvaluator, load_kitti
-        mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size)
+        mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, anchor_shapes_for(a))
         data = load_kitti(a.data_path, a.image_set, mc)
         evaluator = KittiEvaluator(mc, data.gt, model.device)
         once = eval_once

@@ -565,6 +565,47 @@ int sqdet_build_labels(const double* anchors_f64, const double* gt_boxes_f64, co
                        int* anchor_index, int batch, int num_anchors, int max_objects, int classes,
                        sqdet_stream_t stream);
 
+/* --------------------------------------------------------- anchor shapes --
+ * OURS for the fitting: the reference ships fixed anchor shapes (config/kitti_squeezeDet_config.py:45-79, the nine k-means
+ * shapes of KITTI's objects) and no way to get them for another dataset.
+ *
+ * sqdet_anchor_kmeans: Lloyd's k-means over box shapes under the IoU distance, `restarts` independent runs at once.
+ * The distance of two shapes is 1 - IoU of the two boxes on a common centre, in double, in exactly this order:
+ *   inter = min(w, cw) * min(h, ch);   iou = inter / (w*h + cw*ch - inter)
+ * wh: device double [n,2] (w, h; finite and > 0 -- the caller checks, squeezedet_amd.anchors does).  centroids: device double
+ * [restarts,k,2], the initial centroids on entry, the final ones on exit.  Iteration it = 0 .. max_iter - 1: every box goes
+ * to the centroid of highest IoU (the lowest index on a tie, np.argmax); then every centroid becomes the arithmetic mean of
+ * its members' (w, h) -- sum over count, in double -- and one without members keeps its value.  Outputs (device, per restart):
+ *   assign   int32  [restarts,n]  the assignment of the last iteration
+ *   counts   int32  [restarts,k]  its member counts
+ *   mean_iou double [restarts]    mean over the boxes of IoU(box, final centroid of assign[box])
+ *   iters    int32  [restarts]    the first iteration (counted from 0) whose assignment changed no box, max_iter if none did
+ * All max_iter iterations are enqueued -- past convergence one reproduces the fixed point bit for bit -- so nothing returns to
+ * the host inside the loop and the call does not synchronise.  Every floating-point sum has a fixed order that depends on n
+ * alone (per-workgroup partials in `workspace`, no float atomics): two calls on the same input are bitwise equal.
+ * workspace: sqdet_anchor_kmeans_workspace_bytes(n, k, restarts) bytes of device scratch, 8-byte aligned (0: bad arguments).
+ * n < 1, k < 1, restarts < 1, max_iter < 1 or a null pointer: SQDET_EINVAL; k > SQDET_ANCHOR_KMEANS_MAX_K or restarts >
+ * SQDET_ANCHOR_KMEANS_MAX_RESTARTS: SQDET_EUNSUPPORTED; nothing is launched and no output touched on either. */
+enum { SQDET_ANCHOR_KMEANS_MAX_K = 64, SQDET_ANCHOR_KMEANS_MAX_RESTARTS = 64 };
+size_t sqdet_anchor_kmeans_workspace_bytes(int n, int k, int restarts);
+int sqdet_anchor_kmeans(const double* wh, double* centroids, int* assign, int* counts, double* mean_iou, int* iters,
+                        void* workspace, int n, int k, int restarts, int max_iter, sqdet_stream_t stream);
+
+/* sqdet_anchor_coverage: how the anchor grid covers a set of ground-truth boxes.  Replaces the IoU statistics of the
+ * mc.DEBUG_MODE branch of imdb.read_batch (dataset/imdb.py:135-139, 203-215, 241-246), per object: from claimed_iou the
+ * caller gets its max / min / avg iou and its count of objects with 0 iou.  anchors_f64 [num_anchors,4] = mc.ANCHOR_BOX;
+ * gt_boxes_f64 [batch,max_objects,4] and gt_counts [batch] in sqdet_build_labels' padded layout; anchor_index int32
+ * [batch,max_objects] as sqdet_build_labels writes it, or NULL.  Outputs (device, [batch,max_objects], fully written):
+ *   best_iou    double  the maximum over all anchors of util.batch_iou's expression (utils/util.py:42-54) in double, in the
+ *                       reference's operation order
+ *   best_index  int32   the first anchor that attains it (np.argmax; 0 when nothing overlaps)
+ *   claimed_iou double  the IoU with anchor anchor_index[b,i]; 0 where anchor_index is NULL, -1 or out of range
+ * Entries at or beyond gt_counts[b] get 0 / -1 / 0.  One workgroup per entry, one reduction over the anchors (any count).
+ * Asynchronous.  batch * max_objects > 2^31 - 1: SQDET_EUNSUPPORTED. */
+int sqdet_anchor_coverage(const double* anchors_f64, const double* gt_boxes_f64, const int* gt_counts, const int* anchor_index,
+                          double* best_iou, int* best_index, double* claimed_iou, int batch, int num_anchors, int max_objects,
+                          sqdet_stream_t stream);
+
 /* -------------------------------------------------------- pre-processing --
  * Replaces the caller-side image preparation of demo.py:186-190 / imdb.py:101-118:
  *   im = cv2.imread(f).astype(float32); im = cv2.resize(im, (dst_w, dst_h)); input = im - BGR_MEANS

@@ -116,6 +116,9 @@ SIGNATURES = {
     "sqdet_net_set_probe": (ci, [vp, ci, ci]),
     "sqdet_net_read_probe": (ci, [vp, C.POINTER(cf), ci, C.POINTER(ci)]),
     "sqdet_build_labels": (ci, [vp] * 9 + [ci] * 4 + [vp]),
+    "sqdet_anchor_kmeans_workspace_bytes": (sz, [ci, ci, ci]),
+    "sqdet_anchor_kmeans": (ci, [vp] * 7 + [ci] * 4 + [vp]),
+    "sqdet_anchor_coverage": (ci, [vp] * 7 + [ci] * 3 + [vp]),
     "sqdet_preprocess_bgr": (ci, [vp, vp] + [ci] * 5 + [cf, cf, cf, ci, vp]),
     "sqdet_augment_bgr": (ci, [vp, sz, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, vp]),
     "sqdet_kitti_ingest": (ci, [vp] * 5 + [ci, ci] + [vp] * 5 + [ci, ci, ci, vp]),

@@ -48,6 +48,9 @@ SOURCES = [
     ("preproc.hip", ["-ffp-contract=off"]),
     ("augment.hip", ["-ffp-contract=off"]),
     ("labels.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the IoU expressions are the float64 NumPy ones operation for operation -- assignments and argmax indices
+    # are compared bit for bit -- and the sums keep the order written)
+    ("anchors.hip", ["-ffp-contract=off"]),
     ("postproc.hip", ["-ffp-contract=off"]),
     ("filter_fast.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: overlaps, recall steps and the '%.2f' / '%.3f' rounding are bitwise those of the host programs)

@@ -206,6 +206,48 @@ def voc_squeezeDet_config_for_input(image_height, image_width):
     return _finish(_kitti_common(mc), gh, gw, SQUEEZEDET_ANCHOR_SHAPES)
 
 
+def anchor_grid(mc):
+    """(H, W) of the grid mc.ANCHOR_BOX was built on, read back from its centres (set_anchors' closed form)."""
+    ab = np.asarray(mc.ANCHOR_BOX, np.float64).reshape(-1, int(mc.ANCHOR_PER_GRID), 4)
+    W = len(np.unique(ab[:, 0, 0]))
+    H = len(np.unique(ab[:, 0, 1]))
+    if H * W != len(ab):
+        raise ValueError("anchor_grid: mc.ANCHOR_BOX is not a grid of %d anchors per cell" % int(mc.ANCHOR_PER_GRID))
+    return H, W
+
+
+def check_anchor_shapes(shapes):
+    """float64 [k,2] of finite, strictly positive (w, h); ValueError otherwise."""
+    a = np.array(shapes, np.float64)
+    if a.ndim != 2 or a.shape[1] != 2 or len(a) < 1:
+        raise ValueError("anchor shapes must be [k,2] (w, h) with k >= 1, got an array of shape %s" % (a.shape,))
+    if not np.isfinite(a).all() or not (a > 0).all():
+        raise ValueError("anchor shapes must be finite and strictly positive, got %s" % a.tolist())
+    return a
+
+
+def with_anchor_shapes(mc, shapes):
+    """A copy of mc whose ANCHOR_BOX, ANCHORS and ANCHOR_PER_GRID are rebuilt for `shapes` ([k,2] of (w, h) in network-input
+    pixels, e.g. anchors.fit_anchor_shapes' result) on mc's own grid through set_anchors:
+    ANCHOR_BOX[(h*W+w)*k+j] = [(w+1)*IMG_W/(W+1), (h+1)*IMG_H/(H+1), shapes[j,0], shapes[j,1]].  OURS: the reference's shapes are
+    literals in its configs.  Apply it BEFORE pad_head_classes, which depends on ANCHOR_PER_GRID; a config that is already
+    padded is refused."""
+    if int(mc.get("HEAD_PAD_CLASSES", 0)):
+        raise ValueError("with_anchor_shapes: apply it before pad_head_classes (the padding depends on ANCHOR_PER_GRID)")
+    shapes = check_anchor_shapes(shapes)
+    H, W = anchor_grid(mc)
+    mc = type(mc)(mc)
+    mc.ANCHOR_BOX = set_anchors(mc, H, W, shapes)
+    mc.ANCHORS = len(mc.ANCHOR_BOX)
+    mc.ANCHOR_PER_GRID = len(shapes)
+    return mc
+
+
+def anchor_shapes_of(mc):
+    """The [ANCHOR_PER_GRID, 2] shapes mc.ANCHOR_BOX carries (its first cell's)."""
+    return np.array(np.asarray(mc.ANCHOR_BOX, np.float64)[:int(mc.ANCHOR_PER_GRID), 2:4])
+
+
 PAD_CLASS_BIAS = -1.0e4      # the ConvDet bias of a padding class: exp(-1e4 - max) is exactly 0 in float32 and float16
 
 

@@ -14,8 +14,9 @@ drifts and the flips are the reference's.
 Divergences from the reference, on purpose:
   * an image with no boxes draws its drift from the full [-DRIFT, DRIFT] range; the reference crashes on it (``min()`` of
     an empty sequence, imdb.py:158-159);
-  * ``mc.DEBUG_MODE``'s IoU statistics are not printed, and the anchor assignment (imdb.py:195-239) is not done here --
-    ``ops.build_labels`` / the trainers do it on the GPU from ``gt_boxes`` / ``gt_classes`` / ``gt_counts``.
+  * the anchor assignment (imdb.py:195-239) is not done here -- ``ops.build_labels`` / the trainers do it on the GPU from
+    ``gt_boxes`` / ``gt_classes`` / ``gt_counts`` -- and ``mc.DEBUG_MODE``'s IoU statistics come from ``anchors.coverage`` /
+    ``anchors.dataset_coverage`` (``train.py --anchor_report``), for a whole dataset instead of per batch.
 
 Kept on purpose, as in the reference: the shuffled branch reshuffles as soon as ``cur + BATCH_SIZE >= len`` (imdb.py:
 121-123), so the last full batch of every epoch is never served and each epoch serves ``ceil(len / B) - 1`` batches.

@@ -864,6 +864,63 @@ def build_labels(anchor_box, gt_boxes, gt_classes, gt_counts, classes, device=No
     return mask, delta, box, lab, aidx
 
 
+ANCHOR_KMEANS_MAX_K = 64             # SQDET_ANCHOR_KMEANS_MAX_K / _MAX_RESTARTS (include/sqdet.h)
+ANCHOR_KMEANS_MAX_RESTARTS = 64
+
+
+def anchor_kmeans(wh, centroids, max_iter, out=None):
+    """sqdet_anchor_kmeans: Lloyd's k-means over box shapes under the IoU distance, all restarts at once.  wh: device float64
+    [n,2]; centroids: device float64 [R,k,2], the initial centroids, UPDATED IN PLACE.  Returns (assign int32 [R,n], counts
+    int32 [R,k], mean_iou float64 [R], iters int32 [R]) on the device (`out`: the same four, preallocated).  Enqueues
+    2 * max_iter + 2 launches on the current stream and does not synchronise.  The shapes are NOT validated here (the kernel
+    cannot reject device data): squeezedet_amd.anchors.kmeans does that on the host first."""
+    if not isinstance(wh, torch.Tensor) or not isinstance(centroids, torch.Tensor) or wh.dim() != 2 or centroids.dim() != 3 \
+            or wh.shape[1] != 2 or centroids.shape[2] != 2:
+        raise _lib.SqdetError("anchor_kmeans: wh must be a tensor [n,2] and centroids a tensor [R,k,2]")
+    n, R, k = int(wh.shape[0]), int(centroids.shape[0]), int(centroids.shape[1])
+    dev = centroids.device
+    if out is None:
+        out = (torch.empty((R, n), dtype=torch.int32, device=dev), torch.empty((R, k), dtype=torch.int32, device=dev),
+               torch.empty((R,), dtype=torch.float64, device=dev), torch.empty((R,), dtype=torch.int32, device=dev))
+    assign, counts, mean_iou, iters = out
+    for t, shape, name in ((assign, (R, n), "assign"), (counts, (R, k), "counts"), (mean_iou, (R,), "mean_iou"), (iters, (R,), "iters")):
+        if tuple(t.shape) != shape:
+            raise _lib.SqdetError("anchor_kmeans: %s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    ws = torch.empty(max(8, int(lib().sqdet_anchor_kmeans_workspace_bytes(n, k, R))), dtype=torch.uint8, device=dev)
+    check(lib().sqdet_anchor_kmeans(_dev(wh, "wh", torch.float64), _dev(centroids, "centroids", torch.float64),
+                                    _dev(assign, "assign", torch.int32), _dev(counts, "counts", torch.int32),
+                                    _dev(mean_iou, "mean_iou", torch.float64), _dev(iters, "iters", torch.int32), _dev(ws, "workspace"),
+                                    n, k, R, int(max_iter), stream_ptr()), "sqdet_anchor_kmeans")
+    return assign, counts, mean_iou, iters
+
+
+def anchor_coverage(anchor_box, gt_boxes, gt_counts, anchor_index=None, device=None):
+    """sqdet_anchor_coverage: per ground-truth box its best IoU over all anchors, the first anchor that attains it, and the IoU
+    with the anchor build_labels gave it (imdb.py's DEBUG_MODE statistics, per object).  anchor_box: mc.ANCHOR_BOX [A,4]
+    float64; gt_boxes [B,M,4] float64, gt_counts [B] (build_labels' padded layout); anchor_index [B,M] int32 or None.
+    Returns (best_iou float64, best_index int32, claimed_iou float64), each [B,M] on the device; entries at or beyond
+    gt_counts are 0 / -1 / 0."""
+    dev = torch.device(device) if device is not None else (gt_boxes.device if isinstance(gt_boxes, torch.Tensor) else torch.device("cuda", torch.cuda.current_device()))
+    to = lambda v, dt: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(dev, dt).contiguous()
+    anc, gt, cnt = to(anchor_box, torch.float64), to(gt_boxes, torch.float64), to(gt_counts, torch.int32)
+    if anc.dim() != 2 or anc.shape[1] != 4 or gt.dim() != 3 or gt.shape[2] != 4 or tuple(cnt.shape) != (gt.shape[0],):
+        raise _lib.SqdetError("anchor_coverage: anchors [A,4], gt_boxes [B,M,4] and gt_counts [B] expected")
+    B, M, A = int(gt.shape[0]), int(gt.shape[1]), int(anc.shape[0])
+    aidx = None
+    if anchor_index is not None:
+        aidx = to(anchor_index, torch.int32)
+        if tuple(aidx.shape) != (B, M):
+            raise _lib.SqdetError("anchor_coverage: anchor_index must be [%d,%d], got %s" % (B, M, tuple(aidx.shape)))
+    best = torch.empty((B, M), dtype=torch.float64, device=dev)
+    bidx = torch.empty((B, M), dtype=torch.int32, device=dev)
+    claimed = torch.empty((B, M), dtype=torch.float64, device=dev)
+    check(lib().sqdet_anchor_coverage(_dev(anc, "anchors"), _dev(gt, "gt_boxes"), _dev(cnt, "gt_counts"),
+                                      _dev(aidx, "anchor_index") if aidx is not None else None, _dev(best, "best_iou"),
+                                      _dev(bidx, "best_index"), _dev(claimed, "claimed_iou"), B, A, M, stream_ptr()),
+          "sqdet_anchor_coverage")
+    return best, bidx, claimed
+
+
 def preprocess_bgr(images_u8, dst_h, dst_w, bgr_means, dtype=torch.float32):
     """uint8 BGR [N,H,W,3] (device) -> resized (cv2 INTER_LINEAR), mean-subtracted NHWC network input
     (demo.py:186-190) in `dtype`."""

@@ -6,6 +6,7 @@ with on-device summaries.
     python train.py --dataset PASCAL_VOC --data_path VOCdevkit --year 2007 --image_set trainval --train_dir logs/voc
     python train.py --synthetic 40 --train_dir /tmp/run --max_steps 100          # seeded synthetic data, no dataset needed
     python train.py ... --resume                                                  # continue from the newest checkpoint
+    python train.py ... --anchor_shapes anchors.json --anchor_report             # shapes from tools/fit_anchors.py; coverage report
 
 Per step as the reference (train.py:266-330): a summary step (step % summary_step == 0) runs the eager trainer step with the
 activations kept and hands it to squeezedet_amd.summary.TrainSummary (-> <train_dir>/summaries.jsonl, in place of TF event
@@ -19,6 +20,10 @@ The reference deletes --train_dir at start (train.py:338-340).  Here a non-empty
 or --overwrite (delete, as the reference does).  --dataset PASCAL_VOC trains SqueezeDet with the 20-class config
 (config.voc_squeezeDet_config_for_input, at --image_size or 384 x 1248) on <data_path>/VOC<year>, read by
 squeezedet_amd.voc.load_voc; the images may differ in size.  (Its ConvDet head is padded to 23 classes: DESIGN.md section 3.9.)
+--anchor_shapes FILE (tools/fit_anchors.py writes it) replaces the config's anchor shapes (config.with_anchor_shapes, before the
+head is padded); the file is copied to <train_dir>/anchor_shapes.json, where eval.py and demo.py find it, and the shapes are
+recorded in every checkpoint: --resume refuses other shapes and, without the flag, uses the recorded ones.  --anchor_report writes
+<train_dir>/anchor_coverage.json (squeezedet_amd.anchors.dataset_coverage of the training set) once, before the first step.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
 import argparse
@@ -59,6 +64,9 @@ def parse_args(argv=None):
     ap.add_argument("--loss_scale", type=float, default=1024.0, help="fp16: the initial loss scale")
     ap.add_argument("--image_summary", type=int, default=0, metavar="N",
                     help="at summary steps, write the first N images of the batch with ground truth and detections drawn (0: none)")
+    ap.add_argument("--anchor_shapes", default="", metavar="FILE", help="anchor shapes fitted by tools/fit_anchors.py (default: the config's)")
+    ap.add_argument("--anchor_report", action="store_true",
+                    help="write <train_dir>/anchor_coverage.json, how the anchors cover the training set, before the first step")
     a = ap.parse_args(argv)
     assert a.dataset in ("KITTI", "PASCAL_VOC"), "Currently only supports KITTI dataset (and PASCAL_VOC)"
     if a.dataset == "PASCAL_VOC" and a.net != "squeezeDet":
@@ -68,12 +76,21 @@ def parse_args(argv=None):
     return a
 
 
-def make_config(net, image_size=None, dataset="KITTI"):
+def make_config(net, image_size=None, dataset="KITTI", anchor_shapes=None):
+    """The config of --net; anchor_shapes ([k,2], None: the config's own) go in before the head is padded."""
+    from squeezedet_amd import config
+    mc = base_config(net, image_size, dataset)
+    if anchor_shapes is not None:
+        mc = config.with_anchor_shapes(mc, anchor_shapes)
+    return config.pad_head_classes(mc) if dataset == "PASCAL_VOC" else mc
+
+
+def base_config(net, image_size, dataset):
     import squeezedet_amd as S
     from squeezedet_amd import config
     if dataset == "PASCAL_VOC":
         h, w = image_size if image_size is not None else (384, 1248)
-        return config.pad_head_classes(config.voc_squeezeDet_config_for_input(int(h), int(w)))
+        return config.voc_squeezeDet_config_for_input(int(h), int(w))
     if image_size is not None:
         sized = {"squeezeDet": config.kitti_squeezeDet_config_for_input, "resnet50": config.kitti_res50_config_for_input,
                  "vgg16": config.kitti_vgg16_config_for_input}
@@ -152,6 +169,33 @@ def write_model_metrics(path, model):
             f.write("\ttotal: {}\n".format(count))
 
 
+def resolve_anchor_shapes(a, resume_step=None):
+    """The anchor shapes of this run, [k,2] or None (the config's): --anchor_shapes, checked against what the checkpoint to resume
+    from records; without the flag, what it records."""
+    from squeezedet_amd import anchors, checkpoint
+    shapes = anchors.load_for_driver(a.anchor_shapes) if a.anchor_shapes else None
+    if resume_step is not None:
+        rec = checkpoint.read_extra(a.train_dir, resume_step).get("anchor_shapes")
+        if shapes is not None and (rec is None or not anchors.same_shapes(rec, shapes)):
+            raise SystemExit("--resume: the checkpoint was trained with anchor shapes %s, --anchor_shapes %s gives %s"
+                             % ("of its config" if rec is None else rec, a.anchor_shapes, shapes.tolist()))
+        if shapes is None and rec is not None:
+            shapes = np.array(rec, np.float64)
+    return shapes
+
+
+def write_anchor_report(path, mc, reader, device):
+    """--anchor_report: how mc's anchors cover the training set (no augmentation), as JSON."""
+    import json
+    from squeezedet_amd import anchors, config
+    rep = anchors.dataset_coverage(mc, reader.rois, reader.sizes, device=device)
+    with open(path, "w") as f:
+        json.dump(dict(rep.summary(), anchor_shapes=config.anchor_shapes_of(mc).tolist(),
+                       image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)]), f, indent=1)
+        f.write("\n")
+    return rep
+
+
 def prepare_train_dir(a, rank):
     """The train_dir policy; returns the step to resume from, or None."""
     from squeezedet_amd import checkpoint
@@ -183,14 +227,16 @@ class Run:
         from squeezedet_amd.train import GraphedStep
         self.a, self.rank = a, rank
         self.dev = dev = torch.device("cuda", local_rank)
-        self.mc = mc = make_config(a.net, a.image_size, a.dataset)
+        self.anchor_shapes = resolve_anchor_shapes(a, resume_step)
+        self.mc = mc = make_config(a.net, a.image_size, a.dataset, self.anchor_shapes)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)
         images, rois = load_dataset(a, mc)
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
-        self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE))
+        self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE),
+                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist())
         self.first = 0
         if resume_step is not None:
             saved = checkpoint.read_extra(a.train_dir, resume_step)
@@ -296,6 +342,13 @@ def train(a):
             print("Resuming from step {} of {}".format(resume_step, a.train_dir))
         write_model_metrics(os.path.join(a.train_dir, "model_metrics.txt"), run.model)
         print("Model statistics saved to {}.".format(os.path.join(a.train_dir, "model_metrics.txt")))
+        beside = os.path.join(a.train_dir, "anchor_shapes.json")
+        if a.anchor_shapes and os.path.abspath(a.anchor_shapes) != os.path.abspath(beside):
+            shutil.copyfile(a.anchor_shapes, beside)
+        if a.anchor_report and resume_step is None:
+            rep = write_anchor_report(os.path.join(a.train_dir, "anchor_coverage.json"), run.mc, run.reader, run.dev)
+            print("Anchor coverage of the training set ({}):".format(os.path.join(a.train_dir, "anchor_coverage.json")))
+            print("\n".join("  {}: {}".format(k, v) for k, v in rep.lines()))
     try:
         for step in range(run.first, a.max_steps):
             run.step(step)

@@ -230,39 +230,25 @@ def detect_all(model, data, evaluator):
     return num_detection, t_detect, t_misc, nb
 
 
-def eval_once(a, model, data, ckpt_path, evaluator):
+def score_kitti(a, model, data, evaluator, result_dir, global_step):
+    """The detection files, then the GPU evaluator and its stats files (or --eval_tool on the files) -> (aps, names)."""
     from squeezedet_amd import kitti_eval
     mc = model.mc
-    global_step = load_weights(a, model, ckpt_path)
-    n = len(data.image_idx)
-    num_detection, t_detect, t_misc, nb = detect_all(model, data, evaluator)
-
-    print("Evaluating detections...")
-    t0 = time.time()
-    result_dir = os.path.join(a.eval_dir, "detection_files_{:s}".format(global_step))
-    det_file_dir = os.path.join(result_dir, "data")
-    evaluator.write_detection_files(det_file_dir, data.image_idx)
+    evaluator.write_detection_files(os.path.join(result_dir, "data"), data.image_idx)
     if a.eval_tool:
-        all_boxes = kitti_eval.new_all_boxes(len(mc.CLASS_NAMES), n)
+        all_boxes = kitti_eval.new_all_boxes(len(mc.CLASS_NAMES), len(data.image_idx))
         for i, rows in enumerate(evaluator.tables()):
             for c, x1, y1, x2, y2, s in rows:
                 all_boxes[c][i].append([x1, y1, x2, y2, s])
-        aps, ap_names = kitti_eval.evaluate_detections(a.eval_tool, a.data_path, a.image_set, a.eval_dir, global_step,
-                                                       data.image_idx, mc.CLASS_NAMES, all_boxes)
-    else:
-        aps, ap_names, _ = evaluator.evaluate()
-        evaluator.write_stats(result_dir)
-    t_eval = time.time() - t0
+        return kitti_eval.evaluate_detections(a.eval_tool, a.data_path, a.image_set, a.eval_dir, global_step, data.image_idx,
+                                              mc.CLASS_NAMES, all_boxes)
+    aps, ap_names, _ = evaluator.evaluate()
+    evaluator.write_stats(result_dir)
+    return aps, ap_names
 
-    print("Evaluation summary:")
-    print("  Average number of detections per image: {}:".format(num_detection / float(n)))
-    print("  Timing:")
-    print("    detect: {:.3f}s misc: {:.3f}s eval: {:.3f}s".format(t_detect / nb, t_misc / nb, t_eval))
-    print("  Average precisions:")
-    for cls, ap in zip(ap_names, aps):
-        print("    {}: {:.3f}".format(cls, ap))
-    print("    Mean average precision: {:.3f}".format(np.mean(aps)))
 
+def analyze_kitti(a, model, data, evaluator, result_dir):
+    """kitti.analyze_detections: det_error_file.txt, --visualize and the printed analysis -> the stats dict."""
     print("Analyzing detections...")
     stats = evaluator.analyze()
     det_error_file = os.path.join(result_dir, "error_analysis", "det_error_file.txt")
@@ -280,29 +266,32 @@ def eval_once(a, model, data, ckpt_path, evaluator):
     print("    Percentage of background error: {}".format(stats["% background error"]))
     print("    Percentage of repeated detections: {}".format(stats["% repeated error"]))
     print("    Recall: {}".format(stats["% recall"]))
-
-    rec = {"global_step": global_step, "checkpoint": ckpt_path, "mAP": float(np.mean(aps)),
-           "APs": dict(zip(ap_names, [float(v) for v in aps])), "num_det_per_image": num_detection / float(n),
-           "timing": {"im_detect": t_detect / nb, "post_proc": t_misc / nb, "eval": t_eval}, "analysis": stats}
-    with open(os.path.join(a.eval_dir, "eval_log.jsonl"), "a") as f:
-        f.write(json.dumps(rec) + "\n")
-    return rec
+    return stats
 
 
-def eval_once_voc(a, model, data, ckpt_path, evaluator):
-    """eval_once for Pascal VOC: pascal_voc.evaluate_detections (:81-137) on the device table."""
+def score_voc(a, model, data, evaluator, result_dir, global_step):
+    """pascal_voc.evaluate_detections (:81-137) on the device table: the per-class files and the 'AP =' lines -> (aps, names)."""
     from squeezedet_amd.voc import use_07_metric_for
+    evaluator.write_detection_files(result_dir, data.image_idx)
+    aps, ap_names = evaluator.evaluate(use_07_metric_for(a.year))
+    for cls, ap in zip(ap_names, aps):
+        print("{:s}: AP = {:.4f}".format(cls, ap))
+    print("Mean AP = {:.4f}".format(np.mean(aps)))
+    return aps, ap_names
+
+
+def eval_once(a, model, data, ckpt_path, evaluator):
+    """One checkpoint: its weights, every image into the evaluator's table, the dataset's scoring (score_kitti and
+    analyze_kitti, or score_voc), the summary and the eval_log.jsonl record (KITTI's carries "analysis")."""
+    voc = a.dataset == "PASCAL_VOC"
     global_step = load_weights(a, model, ckpt_path)
     n = len(data.image_idx)
     num_detection, t_detect, t_misc, nb = detect_all(model, data, evaluator)
 
     print("Evaluating detections...")
     t0 = time.time()
-    evaluator.write_detection_files(os.path.join(a.eval_dir, "detection_files_{:s}".format(global_step)), data.image_idx)
-    aps, ap_names = evaluator.evaluate(use_07_metric_for(a.year))
-    for cls, ap in zip(ap_names, aps):
-        print("{:s}: AP = {:.4f}".format(cls, ap))
-    print("Mean AP = {:.4f}".format(np.mean(aps)))
+    result_dir = os.path.join(a.eval_dir, "detection_files_{:s}".format(global_step))
+    aps, ap_names = (score_voc if voc else score_kitti)(a, model, data, evaluator, result_dir, global_step)
     t_eval = time.time() - t0
 
     print("Evaluation summary:")
@@ -317,6 +306,8 @@ def eval_once_voc(a, model, data, ckpt_path, evaluator):
     rec = {"global_step": global_step, "checkpoint": ckpt_path, "mAP": float(np.mean(aps)),
            "APs": dict(zip(ap_names, [float(v) for v in aps])), "num_det_per_image": num_detection / float(n),
            "timing": {"im_detect": t_detect / nb, "post_proc": t_misc / nb, "eval": t_eval}}
+    if not voc:
+        rec["analysis"] = analyze_kitti(a, model, data, evaluator, result_dir)
     with open(os.path.join(a.eval_dir, "eval_log.jsonl"), "a") as f:
         f.write(json.dumps(rec) + "\n")
     return rec
@@ -343,7 +334,6 @@ def main(argv=None):
         mc, model = make_voc_model(a.net, a.gpu, a.dtype, a.batch_size, a.image_size, anchor_shapes_for(a))
         data = load_voc(a.data_path, a.year, a.image_set, mc)
         evaluator = VocEvaluator(mc, data.gt, model.device)
-        once = eval_once_voc
     else:
         if a.image_size is not None:
             raise SystemExit("--image_size is for --dataset PASCAL_VOC (the KITTI nets run at their configs' size)")
@@ -351,10 +341,9 @@ def main(argv=None):
         mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, anchor_shapes_for(a))
         data = load_kitti(a.data_path, a.image_set, mc)
         evaluator = KittiEvaluator(mc, data.gt, model.device)
-        once = eval_once
     os.makedirs(a.eval_dir, exist_ok=True)
     if a.run_once:
-        return once(a, model, data, a.checkpoint_path, evaluator)
+        return eval_once(a, model, data, a.checkpoint_path, evaluator)
     seen = set()
     while True:
         ckpt = latest_checkpoint(a.checkpoint_path)
@@ -363,7 +352,7 @@ def main(argv=None):
         elif ckpt not in seen:
             seen.add(ckpt)
             print("Evaluating {}...".format(ckpt))
-            once(a, model, data, ckpt, evaluator)
+            eval_once(a, model, data, ckpt, evaluator)
             continue
         print("Wait {:d}s for new checkpoints to be saved ... ".format(a.eval_interval_secs))
         time.sleep(a.eval_interval_secs)

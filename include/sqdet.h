@@ -628,14 +628,20 @@ int sqdet_preprocess_bgr(const uint8_t* src_bgr_u8, void* dst, int n, int src_h,
 int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom, void* dst, int n,
                       int dst_h, int dst_w, double mean_b, double mean_g, double mean_r, int dtype, sqdet_stream_t stream);
 
-/* ------------------------------------------------------- KITTI evaluation --
+/* -------------------------------------------------------- detection table --
+ * What the KITTI and the Pascal VOC evaluation below score: ONE layout, filled by sqdet_kitti_ingest / sqdet_voc_ingest
+ * with the values of the respective dataset's detection files (or by the caller).  Caller-owned, device; `cap` rows per image
+ * (<= SQDET_KITTI_MAX_DETECTIONS = SQDET_VOC_MAX_DETECTIONS), num_images images:
+ *   det_box double [num_images,cap,4] (x1,y1,x2,y2), det_score double [num_images,cap], det_cls int32 [num_images,cap]
+ *   (0 <= class < the dataset's class count), det_count int32 [num_images] (rows of the image, class-major; zero it to
+ *   reset), status int32 [2] (a rejected ingest, sticky; zero it to reset).
+ *
+ * ------------------------------------------------------- KITTI evaluation --
  * Replaces the scoring half of src/eval.py (:69-101) -- the detection files of dataset/kitti.py:100-127, the KITTI C++
  * evaluator's 2D box metric (dataset/kitti-eval/cpp/evaluate_object.cpp) and kitti.analyze_detections (:182-296) -- with
  * device tables.  All values are double: exactly what the evaluator reads back from the files the reference writes.
  *
- * Detection table (caller-owned, device; `cap` <= SQDET_KITTI_MAX_DETECTIONS rows per image, num_images images):
- *   det_box double [num_images,cap,4] (x1,y1,x2,y2), det_score double [num_images,cap], det_cls int32 [num_images,cap]
- *   (0 car, 1 pedestrian, 2 cyclist), det_count int32 [num_images] (zero it to reset), status int32 [2] (zero it to reset).
+ * Detection table: see above; det_cls 0 car, 1 pedestrian, 2 cyclist.
  * Ground truth (device): image i owns rows [gt_offsets[i], gt_offsets[i+1]) (<= SQDET_KITTI_MAX_GROUNDTRUTH), gt_box double
  *   [G,4] (x1,y1,x2,y2), gt_truncation double [G], gt_occlusion int32 [G], gt_type int32 [G] (SQDET_KITTI_* type codes). */
 enum { SQDET_KITTI_MAX_DETECTIONS = 512, SQDET_KITTI_MAX_GROUNDTRUTH = 128, SQDET_KITTI_ANALYSIS_COUNTERS = 8 };
@@ -682,10 +688,7 @@ int sqdet_kitti_analyze(const double* det_box, const double* det_score, const in
  * dataset/pascal_voc.py:98-109 and the VOC AP metric of dataset/voc_eval.py:33-64,124-204 -- with device tables, for every
  * class at once.  All values are double: exactly what voc_eval reads back with float() from the files the reference writes.
  *
- * Detection table (caller-owned, device; the KITTI table's layout, `cap` <= SQDET_VOC_MAX_DETECTIONS rows per image):
- *   det_box double [num_images,cap,4] (x1,y1,x2,y2, 1-based as the files carry them), det_score double [num_images,cap],
- *   det_cls int32 [num_images,cap] (0 <= class < classes <= SQDET_VOC_MAX_CLASSES), det_count int32 [num_images] (zero it
- *   to reset), status int32 [2] (zero it to reset).
+ * Detection table: see above; det_box 1-based as the files carry them, det_cls 0 <= class < classes <= SQDET_VOC_MAX_CLASSES.
  * Ground truth (device): image i owns rows [gt_offsets[i], gt_offsets[i+1]) (<= SQDET_VOC_MAX_GROUNDTRUTH), gt_box double
  *   [G,4] (the XML's integers xmin,ymin,xmax,ymax), gt_cls int32 [G] (-1: a name outside the class list, never matched),
  *   gt_difficult int32 [G].

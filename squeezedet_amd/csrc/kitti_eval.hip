@@ -1,9 +1,9 @@
 // KITTI 2D detection scoring on the GPU: the reference's eval path after the detector (src/eval.py:69-101,
 // src/dataset/kitti.py:100-296) without text files or an external evaluator.
 //
-//   ingest    filter_prediction rows -> the device detection table, each value exactly the double the evaluator's
-//             fscanf("%lf") reads back from the detection file kitti_eval.write_detection_files writes (coordinates
-//             rounded as '%.2f', scores as '%.3f');
+//   ingest    filter_prediction rows -> the device detection table (det_table.h, KittiRow), each value exactly the double the
+//             evaluator's fscanf("%lf") reads back from the detection file kitti_eval.write_detection_files writes
+//             (coordinates rounded as '%.2f', scores as '%.3f');
 //   evaluate  the KITTI 2D box metric (easy / moderate / hard AP of car, pedestrian, cyclist): per (class, difficulty) a
 //             recall pass that collects the scores of the true positives, threshold selection at 41 recall steps, a
 //             precision pass with one lane per threshold, then precision = tp / (tp + fp) and its running maximum;
@@ -11,14 +11,14 @@
 //
 // Everything is double precision with -ffp-contract=off (build.py): overlaps, recall steps and the rounding are bitwise
 // those of the host programs.  Counts are integer atomics, so results do not depend on scheduling.
-#include "common.h"
-#include "round_decimal.h"   // '%.2f' / '%.3f' as the detection files carry them
+#include "det_table.h"   // the table, its ingest ('%.2f' / '%.3f' as the detection files carry them) and the shared helpers
 
 namespace sqdet {
 namespace {
 
-constexpr int KMAXD = SQDET_KITTI_MAX_DETECTIONS;   // detection rows per image
-constexpr int KMAXG = SQDET_KITTI_MAX_GROUNDTRUTH;  // ground-truth rows per image
+constexpr int KMAXD = DT_MAX_ROWS;                  // detection rows per image
+constexpr int KMAXG = DT_MAX_GT;                    // ground-truth rows per image
+constexpr int NCLASS = 3;                           // car, pedestrian, cyclist
 constexpr int NCOMBO = 9;                           // 3 classes x 3 difficulties, combo = class * 3 + difficulty
 constexpr int NPTS = 41;                            // recall sample points
 constexpr int MAXTHR = 64;                          // threshold slots (<= 41 are ever used; one lane each)
@@ -60,66 +60,6 @@ __device__ __forceinline__ double box_overlap(const double* a, const double* b, 
   return inter / (a_area + b_area - inter);
 }
 
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
-// ------------------------------------------------------------------------------------------------------ ingest
-// One block: is every count of this call in [0, max_out] and every class of its rows in [0, 3)?  status[1] = this call's
-// verdict (the write kernel reads it); a bad call also sets status[0] (sticky until the table is reset).
-__global__ void __launch_bounds__(256) ingest_check_kernel(const int32_t* __restrict__ cls, const int32_t* __restrict__ count,
-                                                           int n, int max_out, int32_t* status) {
-  __shared__ int bad;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  int b = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int c = count[i];
-    if (c < 0 || c > max_out) b = 1;
-  }
-  for (size_t r = threadIdx.x; r < (size_t)n * max_out; r += blockDim.x) {
-    const int i = (int)(r / max_out), j = (int)(r % max_out);
-    const int c = count[i];
-    if (j < c && c <= max_out && (cls[r] < 0 || cls[r] >= 3)) b = 1;
-  }
-  if (b) atomicOr(&bad, 1);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    status[1] = bad;
-    if (bad) status[0] = SQDET_EINVAL;
-  }
-}
-
-// One wave per image: rows in file order (class-major, then filter order), each value as the detection file carries it.
-__global__ void __launch_bounds__(64) ingest_kernel(const float* __restrict__ boxes, const float* __restrict__ probs,
-                                                    const int32_t* __restrict__ cls, const int32_t* __restrict__ count,
-                                                    const double* __restrict__ scales, int max_out, int image_offset, int cap,
-                                                    double* __restrict__ det_box, double* __restrict__ det_score,
-                                                    int32_t* __restrict__ det_cls, int32_t* __restrict__ det_count,
-                                                    const int32_t* __restrict__ status) {
-  if (status[1]) return;
-  const int i = blockIdx.x;
-  const int n = count[i];
-  const size_t src = (size_t)i * max_out, dst = (size_t)(image_offset + i) * cap;
-  const double sx = scales ? scales[2 * i] : 1.0, sy = scales ? scales[2 * i + 1] : 1.0;
-  for (int j = threadIdx.x; j < n; j += 64) {
-    const int c = cls[src + j];
-    int pos = 0;  // rows of smaller classes, then rows of the same class before j
-    for (int k = 0; k < n; ++k) {
-      const int ck = cls[src + k];
-      pos += (ck < c) || (ck == c && k < j);
-    }
-    const float* b = boxes + (src + j) * 4;
-    const double cx = (double)b[0] / sx, cy = (double)b[1] / sy, w = (double)b[2] / sx, h = (double)b[3] / sy;
-    double* o = det_box + (dst + pos) * 4;
-    o[0] = round_decimal(cx - w / 2, 100.0);
-    o[1] = round_decimal(cy - h / 2, 100.0);
-    o[2] = round_decimal(cx + w / 2, 100.0);
-    o[3] = round_decimal(cy + h / 2, 100.0);
-    det_score[dst + pos] = round_decimal((double)probs[src + j], 1000.0);
-    det_cls[dst + pos] = c;
-  }
-  if (threadIdx.x == 0) det_count[image_offset + i] = n;
-}
-
 // ---------------------------------------------------------------------------------------------------- evaluate
 __global__ void __launch_bounds__(64) eval_zero_kernel(int* p, int n) {
   for (int i = threadIdx.x; i < n; i += 64) p[i] = 0;
@@ -135,45 +75,36 @@ struct ImageLds {
   int ngt, nd;
 };
 
+// The evaluator's ground truth (sqdet.h): image i owns rows [off[i], off[i + 1]).
+struct KittiGt {
+  const int32_t* off;
+  const double* box;
+  const double* trunc;
+  const int32_t* occ;
+  const int32_t* type;
+};
+
 // Loads image `img` for class `c`, difficulty `d`.  Returns false (and flags the error) when a row count is over the limits.
-__device__ bool load_image(ImageLds& s, int img, int c, int d, int cap, const double* __restrict__ det_box,
-                           const double* __restrict__ det_score, const int32_t* __restrict__ det_cls,
-                           const int32_t* __restrict__ det_count, const int32_t* __restrict__ gt_off,
-                           const double* __restrict__ gt_box, const double* __restrict__ gt_trunc,
-                           const int32_t* __restrict__ gt_occ, const int32_t* __restrict__ gt_type, int* error) {
+__device__ bool load_image(ImageLds& s, int img, int c, int d, const DetTable& t, const KittiGt& gt, int* error) {
   const int lane = threadIdx.x;
-  const int g0 = gt_off[img], ngt = gt_off[img + 1] - g0, nrow = det_count[img];
-  if (ngt < 0 || ngt > KMAXG || nrow < 0 || nrow > cap) {
+  const int g0 = gt.off[img], ngt = gt.off[img + 1] - g0, nrow = t.count[img];
+  if (!rows_ok(ngt, nrow, t.cap)) {
     if (lane == 0) atomicOr(error, 1);
     return false;
   }
   for (int k = lane; k < ngt; k += 64) {
-    const double* g = gt_box + (size_t)(g0 + k) * 4;
+    const double* g = gt.box + (size_t)(g0 + k) * 4;
     for (int q = 0; q < 4; ++q) s.gt[k][q] = g[q];
-    const int t = gt_type[g0 + k];
+    const int type = gt.type[g0 + k];
     int valid = -1;
-    if (t == c) valid = 1;
-    else if ((c == SQDET_KITTI_PEDESTRIAN && t == SQDET_KITTI_PERSON_SITTING) || (c == SQDET_KITTI_CAR && t == SQDET_KITTI_VAN)) valid = 0;
+    if (type == c) valid = 1;
+    else if ((c == SQDET_KITTI_PEDESTRIAN && type == SQDET_KITTI_PERSON_SITTING) || (c == SQDET_KITTI_CAR && type == SQDET_KITTI_VAN)) valid = 0;
     const double height = g[3] - g[1];
-    const bool ignore = gt_occ[g0 + k] > kMaxOcclusion[d] || gt_trunc[g0 + k] > kMaxTruncation[d] || height < kMinHeight[d];
+    const bool ignore = gt.occ[g0 + k] > kMaxOcclusion[d] || gt.trunc[g0 + k] > kMaxTruncation[d] || height < kMinHeight[d];
     s.ig[k] = (valid == 1 && !ignore) ? 0 : ((valid == 0 || (ignore && valid == 1)) ? 1 : -1);
-    s.dc[k] = t == SQDET_KITTI_DONTCARE;
+    s.dc[k] = type == SQDET_KITTI_DONTCARE;
   }
-  // the class's rows, order kept (ballot compaction)
-  const size_t r0 = (size_t)img * cap;
-  int nd = 0;
-  for (int j0 = 0; j0 < nrow; j0 += 64) {
-    const int j = j0 + lane;
-    const bool mine = j < nrow && det_cls[r0 + j] == c;
-    const uint64_t m = __ballot(mine);
-    if (mine) {
-      const int p = nd + __popcll(m & lanes_below());
-      const double* b = det_box + (r0 + j) * 4;
-      for (int q = 0; q < 4; ++q) s.det[p][q] = b[q];
-      s.score[p] = det_score[r0 + j];
-    }
-    nd += __popcll(m);
-  }
+  const int nd = gather_class_rows(t, img, c, nrow, s.det, s.score);
   if (lane == 0) {
     s.ngt = ngt;
     s.nd = nd;
@@ -184,18 +115,12 @@ __device__ bool load_image(ImageLds& s, int img, int c, int d, int cap, const do
 
 // Recall pass (the evaluator's computeStatistics without false positives), one wave per (image, combo): each ground truth
 // in order takes the highest-scoring unassigned detection of overlap > MIN_OVERLAP (first index on equal scores).
-__global__ void __launch_bounds__(64) eval_recall_kernel(const double* __restrict__ det_box, const double* __restrict__ det_score,
-                                                         const int32_t* __restrict__ det_cls, const int32_t* __restrict__ det_count,
-                                                         int cap, const int32_t* __restrict__ gt_off, const double* __restrict__ gt_box,
-                                                         const double* __restrict__ gt_trunc, const int32_t* __restrict__ gt_occ,
-                                                         const int32_t* __restrict__ gt_type, int num_gt, EvalHeader* h,
-                                                         double* __restrict__ v) {
+__global__ void __launch_bounds__(64) eval_recall_kernel(DetTable t, KittiGt gt, int num_gt, EvalHeader* h, double* __restrict__ v) {
   __shared__ ImageLds s;
   __shared__ uint32_t assigned[KMAXD / 32];
   __shared__ double tp_score[KMAXG];
   const int img = blockIdx.x, combo = blockIdx.y, c = combo / 3, d = combo % 3, lane = threadIdx.x;
-  if (!load_image(s, img, c, d, cap, det_box, det_score, det_cls, det_count, gt_off, gt_box, gt_trunc, gt_occ, gt_type, &h->error))
-    return;
+  if (!load_image(s, img, c, d, t, gt, &h->error)) return;
   const int ngt = s.ngt, nd = s.nd;
   if (lane < KMAXD / 32) assigned[lane] = 0;
   if (lane == 0 && nd > 0) atomicOr(&h->evaluated[c], 1);
@@ -216,14 +141,7 @@ __global__ void __launch_bounds__(64) eval_recall_kernel(const double* __restric
         idx = j;
       }
     }
-    for (int off = 32; off > 0; off >>= 1) {  // highest score, lowest index on ties
-      const double ob = __shfl_xor(best, off);
-      const int oi = __shfl_xor(idx, off);
-      if (oi >= 0 && (idx < 0 || ob > best || (ob == best && oi < idx))) {
-        best = ob;
-        idx = oi;
-      }
-    }
+    wave_best_lowest_index(best, idx);  // highest score, lowest index on ties
     if (idx >= 0) {
       if (lane == 0) {
         assigned[idx >> 5] |= 1u << (idx & 31);
@@ -277,48 +195,31 @@ __global__ void __launch_bounds__(64) eval_select_kernel(EvalHeader* h) {
 
 // The selected order statistics of the scores (descending): element e sits at sorted positions [#(v > e), #(v >= e)); the
 // first copy of a value writes the thresholds that fall there.
-__global__ void __launch_bounds__(256) eval_rank_kernel(EvalHeader* h, const double* __restrict__ v, int num_gt) {
-  __shared__ double tile[256];
+__global__ void __launch_bounds__(DT_RANK) eval_rank_kernel(EvalHeader* h, const double* __restrict__ v, int num_gt) {
+  __shared__ double tile[DT_RANK];
   const int combo = blockIdx.y, n = h->n_tp[combo], nthr = h->n_thr[combo];
-  const int e_idx = blockIdx.x * 256 + threadIdx.x;
-  if ((int)(blockIdx.x * 256) >= n) return;
+  const int e_idx = blockIdx.x * DT_RANK + threadIdx.x;
+  if ((int)(blockIdx.x * DT_RANK) >= n) return;
   const double* vc = v + (size_t)combo * num_gt;
   const double e = e_idx < n ? vc[e_idx] : 0.0;
-  int greater = 0, equal_before = 0, equal = 0;
-  for (int t0 = 0; t0 < n; t0 += 256) {
-    __syncthreads();
-    if (t0 + (int)threadIdx.x < n) tile[threadIdx.x] = vc[t0 + threadIdx.x];
-    __syncthreads();
-    const int m = n - t0 < 256 ? n - t0 : 256;
-    for (int q = 0; q < m; ++q) {
-      const double x = tile[q];
-      greater += x > e;
-      equal += x == e;
-      equal_before += x == e && t0 + q < e_idx;
-    }
-  }
-  if (e_idx >= n || equal_before) return;
+  const Before b = count_before(vc, n, e, e_idx, tile);
+  if (e_idx >= n || b.equal_before) return;
   for (int k = 0; k < nthr; ++k) {
     const int p = h->thr_idx[combo][k];
-    if (p >= greater && p < greater + equal) h->thr[combo][k] = e;
+    if (p >= b.greater && p < b.greater + b.equal) h->thr[combo][k] = e;
   }
 }
 
 // Precision pass (computeStatistics with false positives), one wave per (image, combo), lane t = threshold t: detections
 // scoring below the threshold are left out, each ground truth takes the unassigned detection of greatest overlap, the rest
 // are false positives unless their own area lies in a DontCare region by more than MIN_OVERLAP.
-__global__ void __launch_bounds__(64) eval_precision_kernel(const double* __restrict__ det_box, const double* __restrict__ det_score,
-                                                            const int32_t* __restrict__ det_cls, const int32_t* __restrict__ det_count,
-                                                            int cap, const int32_t* __restrict__ gt_off, const double* __restrict__ gt_box,
-                                                            const double* __restrict__ gt_trunc, const int32_t* __restrict__ gt_occ,
-                                                            const int32_t* __restrict__ gt_type, EvalHeader* h) {
+__global__ void __launch_bounds__(64) eval_precision_kernel(DetTable tab, KittiGt gt, EvalHeader* h) {
   __shared__ ImageLds s;
   __shared__ uint32_t assigned[MAXTHR][KMAXD / 32 + 1];
   const int img = blockIdx.x, combo = blockIdx.y, c = combo / 3, d = combo % 3, t = threadIdx.x;
   const int nthr = h->n_thr[combo];
   if (nthr == 0) return;
-  if (!load_image(s, img, c, d, cap, det_box, det_score, det_cls, det_count, gt_off, gt_box, gt_trunc, gt_occ, gt_type, &h->error))
-    return;
+  if (!load_image(s, img, c, d, tab, gt, &h->error)) return;
   if (t >= nthr) return;
   const int ngt = s.ngt, nd = s.nd;
   uint32_t* a = assigned[t];
@@ -403,9 +304,7 @@ __global__ void __launch_bounds__(64) eval_finish_kernel(EvalHeader* h) {
 // ----------------------------------------------------------------------------------------------------- analyze
 // kitti.analyze_detections, one wave per image: detections in descending score (stable), the first len(gt) of them
 // judged against the image's ground-truth rois by batch_iou (cx, cy, w, h with bbox_transform_inv's +1).
-__global__ void __launch_bounds__(64) analyze_kernel(const double* __restrict__ det_box, const double* __restrict__ det_score,
-                                                     const int32_t* __restrict__ det_cls, const int32_t* __restrict__ det_count,
-                                                     int cap, const int32_t* __restrict__ roi_off, const double* __restrict__ roi_box,
+__global__ void __launch_bounds__(64) analyze_kernel(DetTable t, const int32_t* __restrict__ roi_off, const double* __restrict__ roi_box,
                                                      const int32_t* __restrict__ roi_cls, int32_t* __restrict__ counters,
                                                      int32_t* __restrict__ rec_count, int32_t* __restrict__ rec_type,
                                                      int32_t* __restrict__ rec_cls, double* __restrict__ rec_box,
@@ -416,34 +315,27 @@ __global__ void __launch_bounds__(64) analyze_kernel(const double* __restrict__ 
   __shared__ int order[KMAXD];
   __shared__ uint8_t detected[KMAXG];
   const int img = blockIdx.x, lane = threadIdx.x;
-  const int g0 = roi_off[img], ngt = roi_off[img + 1] - g0, nd = det_count[img];
-  if (ngt < 0 || ngt > KMAXG || nd < 0 || nd > cap) {
+  const int g0 = roi_off[img], ngt = roi_off[img + 1] - g0, nd = t.count[img];
+  if (!rows_ok(ngt, nd, t.cap)) {
     if (lane == 0) {
       atomicOr(&counters[SQDET_KITTI_ANALYSIS_COUNTERS], 1);
       rec_count[img] = 0;
     }
     return;
   }
-  const size_t r0 = (size_t)img * cap;
+  const size_t r0 = (size_t)img * t.cap;
   for (int j = lane; j < nd; j += 64) {
-    const double* b = det_box + (r0 + j) * 4;
+    const double* b = t.box + (r0 + j) * 4;
     const double w = b[2] - b[0] + 1.0, hh = b[3] - b[1] + 1.0;
     det[j][0] = b[0] + 0.5 * w;
     det[j][1] = b[1] + 0.5 * hh;
     det[j][2] = w;
     det[j][3] = hh;
-    score[j] = det_score[r0 + j];
-    dcls[j] = det_cls[r0 + j];
-    order[j] = j;  // (a NaN score has no rank: its slot keeps an in-range index)
+    score[j] = t.score[r0 + j];
+    dcls[j] = t.cls[r0 + j];
   }
   for (int k = lane; k < ngt; k += 64) detected[k] = 0;
-  __syncthreads();
-  for (int j = lane; j < nd; j += 64) {  // stable descending rank
-    int r = 0;
-    for (int k = 0; k < nd; ++k) r += score[k] > score[j] || (score[k] == score[j] && k < j);
-    order[r] = j;
-  }
-  __syncthreads();
+  stable_rank_desc(score, order, nd);
   if (lane != 0) return;
   const size_t rbase = 2 * (size_t)g0;
   int nrec = 0;
@@ -521,19 +413,8 @@ extern "C" int sqdet_kitti_ingest(const float* boxes, const float* probs, const 
                                   int32_t* det_count, int32_t* status, int image_offset, int num_images, int cap,
                                   sqdet_stream_t stream) {
   using namespace sqdet;
-  SQDET_REQUIRE(boxes && probs && cls && count && det_box && det_score && det_cls && det_count && status, "kitti_ingest: null pointer");
-  SQDET_REQUIRE(n >= 0 && max_out > 0 && cap > 0 && num_images >= 0, "kitti_ingest: bad dims");
-  SQDET_UNSUPPORTED(cap > SQDET_KITTI_MAX_DETECTIONS, "kitti_ingest: %d rows per image (limit %d)", cap, SQDET_KITTI_MAX_DETECTIONS);
-  SQDET_UNSUPPORTED(max_out > cap, "kitti_ingest: %d filter rows per image, the table holds %d", max_out, cap);
-  SQDET_REQUIRE(image_offset >= 0 && (long long)image_offset + n <= num_images,
-                "kitti_ingest: images [%d, %lld) outside the table's %d", image_offset, (long long)image_offset + n, num_images);
-  if (n == 0) return SQDET_OK;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(ingest_check_kernel, dim3(1), dim3(256), 0, st, cls, count, n, max_out, status);
-  hipLaunchKernelGGL(ingest_kernel, dim3((unsigned)n), dim3(64), 0, st, boxes, probs, cls, count, scales, max_out, image_offset, cap,
-                     det_box, det_score, det_cls, det_count, status);
-  SQDET_CHECK_HIP(hipGetLastError());
-  return SQDET_OK;
+  return ingest_rows<KittiRow>("kitti_ingest", boxes, probs, cls, count, scales, n, max_out, NCLASS, NCLASS,
+                               DetTable{det_box, det_score, det_cls, det_count, status, num_images, cap}, image_offset, stream);
 }
 
 extern "C" size_t sqdet_kitti_eval_workspace_bytes(int num_gt) {
@@ -553,28 +434,21 @@ extern "C" int sqdet_kitti_evaluate(const double* det_box, const double* det_sco
   SQDET_REQUIRE(num_gt == 0 || (gt_box && gt_truncation && gt_occlusion && gt_type), "kitti_evaluate: null ground-truth pointer");
   SQDET_UNSUPPORTED(cap > SQDET_KITTI_MAX_DETECTIONS, "kitti_evaluate: %d rows per image (limit %d)", cap, SQDET_KITTI_MAX_DETECTIONS);
   hipStream_t st = as_stream(stream);
+  const DetTable t = read_only_table(det_box, det_score, det_cls, det_count, status, num_images, cap);
+  const KittiGt gt = {gt_offsets, gt_box, gt_truncation, gt_occlusion, gt_type};
   EvalHeader* h = reinterpret_cast<EvalHeader*>(workspace);
   double* v = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + ((sizeof(EvalHeader) + 255) & ~(size_t)255));
   const int ng = num_gt > 0 ? num_gt : 1;
   hipLaunchKernelGGL(eval_zero_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<int*>(h),
                      (int)(offsetof(EvalHeader, thr) / sizeof(int)));
-  hipLaunchKernelGGL(eval_recall_kernel, dim3((unsigned)num_images, NCOMBO), dim3(64), 0, st, det_box, det_score, det_cls, det_count, cap,
-                     gt_offsets, gt_box, gt_truncation, gt_occlusion, gt_type, ng, h, v);
+  hipLaunchKernelGGL(eval_recall_kernel, dim3((unsigned)num_images, NCOMBO), dim3(64), 0, st, t, gt, ng, h, v);
   hipLaunchKernelGGL(eval_select_kernel, dim3(NCOMBO), dim3(64), 0, st, h);
-  hipLaunchKernelGGL(eval_rank_kernel, dim3((unsigned)((ng + 255) / 256), NCOMBO), dim3(256), 0, st, h, v, ng);
-  hipLaunchKernelGGL(eval_precision_kernel, dim3((unsigned)num_images, NCOMBO), dim3(64), 0, st, det_box, det_score, det_cls, det_count,
-                     cap, gt_offsets, gt_box, gt_truncation, gt_occlusion, gt_type, h);
+  hipLaunchKernelGGL(eval_rank_kernel, dim3((unsigned)((ng + DT_RANK - 1) / DT_RANK), NCOMBO), dim3(DT_RANK), 0, st, h, v, ng);
+  hipLaunchKernelGGL(eval_precision_kernel, dim3((unsigned)num_images, NCOMBO), dim3(64), 0, st, t, gt, h);
   hipLaunchKernelGGL(eval_finish_kernel, dim3(NCOMBO), dim3(64), 0, st, h);
   SQDET_CHECK_HIP(hipGetLastError());
   EvalHeader host;
-  int32_t st_host[2] = {0, 0};
-  SQDET_CHECK_HIP(hipMemcpyAsync(&host, h, sizeof(EvalHeader), hipMemcpyDeviceToHost, st));
-  if (status) SQDET_CHECK_HIP(hipMemcpyAsync(st_host, status, sizeof(st_host), hipMemcpyDeviceToHost, st));
-  SQDET_CHECK_HIP(hipStreamSynchronize(st));
-  SQDET_REQUIRE(st_host[0] == 0, "kitti_evaluate: the detection table holds a rejected ingest (negative or over-capacity count, "
-                "or a class outside 0..2); reset it");
-  SQDET_UNSUPPORTED(host.error & 1, "kitti_evaluate: an image has more than %d ground-truth or %d detection rows",
-                    SQDET_KITTI_MAX_GROUNDTRUTH, cap);
+  if (const int rc = read_back("kitti_evaluate", h, t, NCLASS, st, &host)) return rc;
   SQDET_REQUIRE(!(host.error & 2), "kitti_evaluate: more than 41 recall thresholds");
   for (int c = 0; c < NCOMBO; ++c) {
     for (int i = 0; i < NPTS; ++i) host_precision[c * NPTS + i] = host.precision[c][i];
@@ -596,8 +470,9 @@ extern "C" int sqdet_kitti_analyze(const double* det_box, const double* det_scor
   SQDET_UNSUPPORTED(cap > SQDET_KITTI_MAX_DETECTIONS, "kitti_analyze: %d rows per image (limit %d)", cap, SQDET_KITTI_MAX_DETECTIONS);
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(eval_zero_kernel, dim3(1), dim3(64), 0, st, counters, SQDET_KITTI_ANALYSIS_COUNTERS + 1);
-  hipLaunchKernelGGL(analyze_kernel, dim3((unsigned)num_images), dim3(64), 0, st, det_box, det_score, det_cls, det_count, cap,
-                     roi_offsets, roi_box, roi_cls, counters, rec_count, rec_type, rec_cls, rec_box, rec_score);
+  hipLaunchKernelGGL(analyze_kernel, dim3((unsigned)num_images), dim3(64), 0, st,
+                     read_only_table(det_box, det_score, det_cls, det_count, nullptr, num_images, cap), roi_offsets, roi_box, roi_cls,
+                     counters, rec_count, rec_type, rec_cls, rec_box, rec_score);
   SQDET_CHECK_HIP(hipGetLastError());
   return SQDET_OK;
 }

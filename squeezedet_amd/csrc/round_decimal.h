@@ -1,5 +1,5 @@
 // Decimal rounding as Python's '%.<d>f' does it, for the kernels whose output is compared with text a host program prints
-// (kitti_eval.hip: the detection files' '%.2f' / '%.3f'; draw.hip: the '%.2f' of a label).  Build with -ffp-contract=off.
+// (det_table.h: the detection files' '%.2f' / '{:.1f}' / '%.3f'; draw.hip: the '%.2f' of a label).  Build with -ffp-contract=off.
 #pragma once
 #include "common.h"
 

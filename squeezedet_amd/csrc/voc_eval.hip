@@ -1,9 +1,9 @@
 // Pascal VOC detection scoring on the GPU: the reference's VOC path after the detector (src/dataset/pascal_voc.py:81-137,
 // src/dataset/voc_eval.py) without text files, for every class at once.
 //
-//   ingest    filter_prediction rows -> the device detection table, each value exactly the double float() reads back from
-//             the per-class files pascal_voc.evaluate_detections writes (coordinates + 1 in float32, rounded as '{:.1f}',
-//             scores as '{:.3f}');
+//   ingest    filter_prediction rows -> the device detection table (det_table.h, VocRow), each value exactly the double
+//             float() reads back from the per-class files pascal_voc.evaluate_detections writes (coordinates + 1 in
+//             float32, rounded as '{:.1f}', scores as '{:.3f}');
 //   evaluate  voc_eval for all classes: count (rows and non-difficult objects per image and class), scan (where each
 //             (image, class) segment starts in its class's list), match (one wave per (image, class): the greedy walk of
 //             voc_eval.py:161-195), rank (each row's position in its class's order), prefix (cumulative tp / fp) and
@@ -13,16 +13,15 @@
 // bitwise those of NumPy.  Counts are integers and every sum has a fixed order, so results do not depend on scheduling.
 #include <float.h>
 
-#include "common.h"
-#include "round_decimal.h"   // '{:.1f}' / '{:.3f}' as the detection files carry them
+#include "det_table.h"   // the table, its ingest ('{:.1f}' / '{:.3f}' as the detection files carry them) and the shared helpers
 
 namespace sqdet {
 namespace {
 
-constexpr int VMAXD = SQDET_VOC_MAX_DETECTIONS;   // detection rows per image
-constexpr int VMAXG = SQDET_VOC_MAX_GROUNDTRUTH;  // ground-truth rows per image
+constexpr int VMAXD = DT_MAX_ROWS;                // detection rows per image
+constexpr int VMAXG = DT_MAX_GT;                  // ground-truth rows per image
 constexpr int VMAXC = SQDET_VOC_MAX_CLASSES;
-constexpr int SCAN = 256;                         // threads of the scan / rank / ap blocks: a class longer than this loops
+constexpr int SCAN = DT_RANK;                     // threads of the scan / rank / ap blocks: a class longer than this loops
 constexpr int NT07 = 11;                          // thresholds of the 11-point metric
 enum { FLAG_NONE = 0, FLAG_TP = 1, FLAG_FP = 2 };
 
@@ -68,88 +67,25 @@ VocWorkspace carve(void* p, int num_images, int cap, int classes) {
   return w;
 }
 
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
 __device__ __forceinline__ int class_offset(const VocHeader* h, int c) {
   int o = 0;
   for (int k = 0; k < c; ++k) o += h->ndet[k];
   return o;
 }
 
-// ------------------------------------------------------------------------------------------------------ ingest
-// One block: is every count of this call in [0, max_out] and every class of its rows in [0, classes)?  status[1] = this
-// call's verdict (the write kernel reads it); a bad call also sets status[0] (sticky until the table is reset).
-__global__ void __launch_bounds__(256) voc_ingest_check_kernel(const int32_t* __restrict__ cls, const int32_t* __restrict__ count,
-                                                               int n, int max_out, int classes, int32_t* status) {
-  __shared__ int bad;
-  if (threadIdx.x == 0) bad = 0;
-  __syncthreads();
-  int b = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int c = count[i];
-    if (c < 0 || c > max_out) b = 1;
-  }
-  for (size_t r = threadIdx.x; r < (size_t)n * max_out; r += blockDim.x) {
-    const int i = (int)(r / max_out), j = (int)(r % max_out);
-    const int c = count[i];
-    if (j < c && c <= max_out && (cls[r] < 0 || cls[r] >= classes)) b = 1;
-  }
-  if (b) atomicOr(&bad, 1);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    status[1] = bad;
-    if (bad) status[0] = SQDET_EINVAL;
-  }
-}
-
-// One wave per image: rows in file order (class-major, then filter order), each value as the detection files carry it.
-// The arithmetic up to the '+ 1' is float32, as NumPy's on the float32 rows (eval.py:83-91, pascal_voc.py:107-108).
-__global__ void __launch_bounds__(64) voc_ingest_kernel(const float* __restrict__ boxes, const float* __restrict__ probs,
-                                                        const int32_t* __restrict__ cls, const int32_t* __restrict__ count,
-                                                        const double* __restrict__ scales, int max_out, int image_offset, int cap,
-                                                        double* __restrict__ det_box, double* __restrict__ det_score,
-                                                        int32_t* __restrict__ det_cls, int32_t* __restrict__ det_count,
-                                                        const int32_t* __restrict__ status) {
-  if (status[1]) return;
-  const int i = blockIdx.x;
-  const int n = count[i];
-  const size_t src = (size_t)i * max_out, dst = (size_t)(image_offset + i) * cap;
-  const float sx = scales ? (float)scales[2 * i] : 1.0f, sy = scales ? (float)scales[2 * i + 1] : 1.0f;
-  for (int j = threadIdx.x; j < n; j += 64) {
-    const int c = cls[src + j];
-    int pos = 0;  // rows of smaller classes, then rows of the same class before j
-    for (int k = 0; k < n; ++k) {
-      const int ck = cls[src + k];
-      pos += (ck < c) || (ck == c && k < j);
-    }
-    const float* b = boxes + (src + j) * 4;
-    const float cx = b[0] / sx, cy = b[1] / sy, w = b[2] / sx, h = b[3] / sy;
-    const float x1 = cx - w / 2.0f, y1 = cy - h / 2.0f, x2 = cx + w / 2.0f, y2 = cy + h / 2.0f;
-    double* o = det_box + (dst + pos) * 4;
-    o[0] = round_decimal((double)(x1 + 1.0f), 10.0);
-    o[1] = round_decimal((double)(y1 + 1.0f), 10.0);
-    o[2] = round_decimal((double)(x2 + 1.0f), 10.0);
-    o[3] = round_decimal((double)(y2 + 1.0f), 10.0);
-    det_score[dst + pos] = round_decimal((double)probs[src + j], 1000.0);
-    det_cls[dst + pos] = c;
-  }
-  if (threadIdx.x == 0) det_count[image_offset + i] = n;
-}
-
 // ---------------------------------------------------------------------------------------------------- evaluate
 // Are the image's row counts within the limits (and its ground-truth rows inside the arrays)?  An image that is not is
 // scored as empty by every kernel, so that every offset stays inside the workspace; the call then fails.
-__device__ __forceinline__ bool image_ok(int img, int cap, int num_gt, const int32_t* __restrict__ det_count,
-                                         const int32_t* __restrict__ gt_off, int* g0, int* ngt, int* nrow) {
+__device__ __forceinline__ bool image_ok(int img, const DetTable& t, int num_gt, const int32_t* __restrict__ gt_off, int* g0, int* ngt,
+                                         int* nrow) {
   *g0 = gt_off[img];
   *ngt = gt_off[img + 1] - *g0;
-  *nrow = det_count[img];
-  return *g0 >= 0 && *ngt >= 0 && *ngt <= VMAXG && (long long)*g0 + *ngt <= num_gt && *nrow >= 0 && *nrow <= cap;
+  *nrow = t.count[img];
+  return rows_ok(*ngt, *nrow, t.cap) && *g0 >= 0 && (long long)*g0 + *ngt <= num_gt;
 }
 
 // One wave per image: rows and non-difficult objects of every class (voc_eval.py:127-132).
-__global__ void __launch_bounds__(64) voc_count_kernel(const int32_t* __restrict__ det_cls, const int32_t* __restrict__ det_count,
-                                                       int num_images, int cap, int classes, const int32_t* __restrict__ gt_off,
+__global__ void __launch_bounds__(64) voc_count_kernel(DetTable t, int classes, const int32_t* __restrict__ gt_off,
                                                        const int32_t* __restrict__ gt_cls, const int32_t* __restrict__ gt_difficult,
                                                        int num_gt, VocHeader* h, int* __restrict__ cnt_det, int* __restrict__ cnt_pos) {
   __shared__ int nd[VMAXC], np[VMAXC];
@@ -157,10 +93,10 @@ __global__ void __launch_bounds__(64) voc_count_kernel(const int32_t* __restrict
   for (int c = lane; c < classes; c += 64) nd[c] = np[c] = 0;
   __syncthreads();
   int g0, ngt, nrow;
-  if (image_ok(img, cap, num_gt, det_count, gt_off, &g0, &ngt, &nrow)) {
-    const size_t r0 = (size_t)img * cap;
+  if (image_ok(img, t, num_gt, gt_off, &g0, &ngt, &nrow)) {
+    const size_t r0 = (size_t)img * t.cap;
     for (int j = lane; j < nrow; j += 64) {
-      const int c = det_cls[r0 + j];
+      const int c = t.cls[r0 + j];
       if (c >= 0 && c < classes) atomicAdd(&nd[c], 1);
     }
     for (int k = lane; k < ngt; k += 64) {
@@ -172,8 +108,8 @@ __global__ void __launch_bounds__(64) voc_count_kernel(const int32_t* __restrict
   }
   __syncthreads();
   for (int c = lane; c < classes; c += 64) {
-    cnt_det[(size_t)c * num_images + img] = nd[c];
-    cnt_pos[(size_t)c * num_images + img] = np[c];
+    cnt_det[(size_t)c * t.num_images + img] = nd[c];
+    cnt_pos[(size_t)c * t.num_images + img] = np[c];
   }
 }
 
@@ -222,9 +158,7 @@ __global__ void __launch_bounds__(SCAN) voc_scan_kernel(int num_images, VocHeade
 // order), each against the image's objects of the class -- lanes compute the overlaps, the wave takes the maximum with the
 // first index winning (np.argmax) -- then the tp / fp / neither decision.  Writes the rows' scores and flags into the
 // class's list.
-__global__ void __launch_bounds__(64) voc_match_kernel(const double* __restrict__ det_box, const double* __restrict__ det_score,
-                                                       const int32_t* __restrict__ det_cls, const int32_t* __restrict__ det_count,
-                                                       int num_images, int cap, const int32_t* __restrict__ gt_off,
+__global__ void __launch_bounds__(64) voc_match_kernel(DetTable t, const int32_t* __restrict__ gt_off,
                                                        const double* __restrict__ gt_box, const int32_t* __restrict__ gt_cls,
                                                        const int32_t* __restrict__ gt_difficult, int num_gt, const VocHeader* h,
                                                        const int* __restrict__ cnt_det, const int* __restrict__ base,
@@ -238,46 +172,19 @@ __global__ void __launch_bounds__(64) voc_match_kernel(const double* __restrict_
   __shared__ int dflag[VMAXD];
   const int img = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
   int g0, ngt, nrow;
-  if (!image_ok(img, cap, num_gt, det_count, gt_off, &g0, &ngt, &nrow)) return;
-  if (cnt_det[(size_t)c * num_images + img] == 0) return;
-  // the image's objects and rows of the class, order kept (ballot compaction)
-  int ng = 0;
-  for (int k0 = 0; k0 < ngt; k0 += 64) {
-    const int k = k0 + lane;
-    const bool mine = k < ngt && gt_cls[g0 + k] == c;
-    const uint64_t m = __ballot(mine);
-    if (mine) {
-      const int p = ng + __popcll(m & lanes_below());
-      const double* g = gt_box + (size_t)(g0 + k) * 4;
-      for (int q = 0; q < 4; ++q) gbox[p][q] = g[q];
-      gdiff[p] = gt_difficult[g0 + k] != 0;
-      gtaken[p] = 0;
-    }
-    ng += __popcll(m);
-  }
-  const size_t r0 = (size_t)img * cap;
-  int nd = 0;
-  for (int j0 = 0; j0 < nrow; j0 += 64) {
-    const int j = j0 + lane;
-    const bool mine = j < nrow && det_cls[r0 + j] == c;
-    const uint64_t m = __ballot(mine);
-    if (mine) {
-      const int p = nd + __popcll(m & lanes_below());
-      const double* b = det_box + (r0 + j) * 4;
-      for (int q = 0; q < 4; ++q) dbox[p][q] = b[q];
-      dscore[p] = det_score[r0 + j];
-      order[p] = p;  // (a NaN score has no rank: its slot keeps an in-range index)
-    }
-    nd += __popcll(m);
-  }
-  __syncthreads();
-  for (int j = lane; j < nd; j += 64) {  // stable descending rank
-    const double s = dscore[j];
-    int r = 0;
-    for (int k = 0; k < nd; ++k) r += dscore[k] > s || (dscore[k] == s && k < j);
-    if (s == s) order[r] = j;
-  }
-  __syncthreads();
+  if (!image_ok(img, t, num_gt, gt_off, &g0, &ngt, &nrow)) return;
+  if (cnt_det[(size_t)c * t.num_images + img] == 0) return;
+  // the image's objects and rows of the class, order kept
+  const int ng = wave_compact(
+      ngt, [&](int k) { return gt_cls[g0 + k] == c; },
+      [&](int k, int p) {
+        const double* g = gt_box + (size_t)(g0 + k) * 4;
+        for (int q = 0; q < 4; ++q) gbox[p][q] = g[q];
+        gdiff[p] = gt_difficult[g0 + k] != 0;
+        gtaken[p] = 0;
+      });
+  const int nd = gather_class_rows(t, img, c, nrow, dbox, dscore);
+  stable_rank_desc(dscore, order, nd);
   for (int r = 0; r < nd; ++r) {
     const int j = order[r];
     const double b0 = dbox[j][0], b1 = dbox[j][1], b2 = dbox[j][2], b3 = dbox[j][3];
@@ -295,14 +202,7 @@ __global__ void __launch_bounds__(64) voc_match_kernel(const double* __restrict_
         bi = k;
       }
     }
-    for (int off = 32; off > 0; off >>= 1) {  // greatest overlap, lowest index on ties
-      const double ob = __shfl_xor(best, off);
-      const int oi = __shfl_xor(bi, off);
-      if (oi >= 0 && (bi < 0 || ob > best || (ob == best && oi < bi))) {
-        best = ob;
-        bi = oi;
-      }
-    }
+    wave_best_lowest_index(best, bi);  // greatest overlap, lowest index on ties
     int f = FLAG_FP;  // no object of the class in the image (ovmax = -inf), or ovmax <= ovthresh
     if (bi >= 0 && best > 0.5) {
       if (gdiff[bi]) f = FLAG_NONE;
@@ -315,7 +215,7 @@ __global__ void __launch_bounds__(64) voc_match_kernel(const double* __restrict_
     }
     __syncthreads();
   }
-  const size_t out = (size_t)class_offset(h, c) + base[(size_t)c * num_images + img];
+  const size_t out = (size_t)class_offset(h, c) + base[(size_t)c * t.num_images + img];
   for (int j = lane; j < nd; j += 64) {
     cscore[out + j] = dscore[j];
     cflag[out + j] = dflag[j];
@@ -332,17 +232,8 @@ __global__ void __launch_bounds__(SCAN) voc_rank_kernel(const VocHeader* h, cons
   const size_t off = class_offset(h, c);
   const int e_idx = blockIdx.x * SCAN + threadIdx.x;
   const double e = e_idx < n ? cscore[off + e_idx] : 0.0;
-  int before = 0;
-  for (int t0 = 0; t0 < n; t0 += SCAN) {
-    __syncthreads();
-    if (t0 + (int)threadIdx.x < n) tile[threadIdx.x] = cscore[off + t0 + threadIdx.x];
-    __syncthreads();
-    const int m = n - t0 < SCAN ? n - t0 : SCAN;
-    for (int q = 0; q < m; ++q) {
-      const double x = tile[q];
-      before += x > e || (x == e && t0 + q < e_idx);
-    }
-  }
+  const Before b = count_before(cscore + off, n, e, e_idx, tile);
+  const int before = b.greater + b.equal_before;
   if (e_idx >= n || !(e == e)) return;
   const int f = cflag[off + e_idx];
   stp[off + before] = f == FLAG_TP;
@@ -470,20 +361,8 @@ extern "C" int sqdet_voc_ingest(const float* boxes, const float* probs, const in
                                 int n, int max_out, int classes, double* det_box, double* det_score, int32_t* det_cls,
                                 int32_t* det_count, int32_t* status, int image_offset, int num_images, int cap, sqdet_stream_t stream) {
   using namespace sqdet;
-  SQDET_REQUIRE(boxes && probs && cls && count && det_box && det_score && det_cls && det_count && status, "voc_ingest: null pointer");
-  SQDET_REQUIRE(n >= 0 && max_out > 0 && cap > 0 && num_images >= 0 && classes > 0, "voc_ingest: bad dims");
-  SQDET_UNSUPPORTED(classes > SQDET_VOC_MAX_CLASSES, "voc_ingest: %d classes (limit %d)", classes, SQDET_VOC_MAX_CLASSES);
-  SQDET_UNSUPPORTED(cap > SQDET_VOC_MAX_DETECTIONS, "voc_ingest: %d rows per image (limit %d)", cap, SQDET_VOC_MAX_DETECTIONS);
-  SQDET_UNSUPPORTED(max_out > cap, "voc_ingest: %d filter rows per image, the table holds %d", max_out, cap);
-  SQDET_REQUIRE(image_offset >= 0 && (long long)image_offset + n <= num_images,
-                "voc_ingest: images [%d, %lld) outside the table's %d", image_offset, (long long)image_offset + n, num_images);
-  if (n == 0) return SQDET_OK;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(voc_ingest_check_kernel, dim3(1), dim3(256), 0, st, cls, count, n, max_out, classes, status);
-  hipLaunchKernelGGL(voc_ingest_kernel, dim3((unsigned)n), dim3(64), 0, st, boxes, probs, cls, count, scales, max_out, image_offset, cap,
-                     det_box, det_score, det_cls, det_count, status);
-  SQDET_CHECK_HIP(hipGetLastError());
-  return SQDET_OK;
+  return ingest_rows<VocRow>("voc_ingest", boxes, probs, cls, count, scales, n, max_out, classes, SQDET_VOC_MAX_CLASSES,
+                             DetTable{det_box, det_score, det_cls, det_count, status, num_images, cap}, image_offset, stream);
 }
 
 extern "C" size_t sqdet_voc_eval_workspace_bytes(int num_images, int cap, int classes) {
@@ -506,29 +385,23 @@ extern "C" int sqdet_voc_evaluate(const double* det_box, const double* det_score
   SQDET_UNSUPPORTED(cap > SQDET_VOC_MAX_DETECTIONS, "voc_evaluate: %d rows per image (limit %d)", cap, SQDET_VOC_MAX_DETECTIONS);
   SQDET_UNSUPPORTED((long long)num_images * cap > 0x7fffffffLL, "voc_evaluate: %d images of %d rows: more than 2^31 table rows", num_images, cap);
   hipStream_t st = as_stream(stream);
+  const DetTable t = read_only_table(det_box, det_score, det_cls, det_count, status, num_images, cap);
   const VocWorkspace w = carve(workspace, num_images, cap, classes);
   const size_t T = (size_t)num_images * cap;
   const unsigned C = (unsigned)classes, N = (unsigned)num_images;
   SQDET_CHECK_HIP(hipMemsetAsync(w.h, 0, sizeof(VocHeader), st));
   SQDET_CHECK_HIP(hipMemsetAsync(w.stp, 0, 2 * T * sizeof(int), st));   // stp and sfp are adjacent
-  hipLaunchKernelGGL(voc_count_kernel, dim3(N), dim3(64), 0, st, det_cls, det_count, num_images, cap, classes, gt_offsets, gt_cls,
-                     gt_difficult, num_gt, w.h, w.cnt_det, w.cnt_pos);
+  hipLaunchKernelGGL(voc_count_kernel, dim3(N), dim3(64), 0, st, t, classes, gt_offsets, gt_cls, gt_difficult, num_gt, w.h, w.cnt_det,
+                     w.cnt_pos);
   hipLaunchKernelGGL(voc_scan_kernel, dim3(C), dim3(SCAN), 0, st, num_images, w.h, w.cnt_det, w.cnt_pos, w.base);
-  hipLaunchKernelGGL(voc_match_kernel, dim3(N, C), dim3(64), 0, st, det_box, det_score, det_cls, det_count, num_images, cap, gt_offsets,
-                     gt_box, gt_cls, gt_difficult, num_gt, w.h, w.cnt_det, w.base, w.cscore, w.cflag);
+  hipLaunchKernelGGL(voc_match_kernel, dim3(N, C), dim3(64), 0, st, t, gt_offsets, gt_box, gt_cls, gt_difficult, num_gt, w.h, w.cnt_det,
+                     w.base, w.cscore, w.cflag);
   hipLaunchKernelGGL(voc_rank_kernel, dim3((unsigned)((T + SCAN - 1) / SCAN), C), dim3(SCAN), 0, st, w.h, w.cscore, w.cflag, w.stp, w.sfp);
   hipLaunchKernelGGL(voc_prefix_kernel, dim3(C), dim3(SCAN), 0, st, w.h, w.stp, w.sfp);
   hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(SCAN), 0, st, w.h, w.stp, w.sfp, w.mpre, curve_cls, curve_rec, curve_prec);
   SQDET_CHECK_HIP(hipGetLastError());
   VocHeader host;
-  int32_t st_host[2] = {0, 0};
-  SQDET_CHECK_HIP(hipMemcpyAsync(&host, w.h, sizeof(VocHeader), hipMemcpyDeviceToHost, st));
-  if (status) SQDET_CHECK_HIP(hipMemcpyAsync(st_host, status, sizeof(st_host), hipMemcpyDeviceToHost, st));
-  SQDET_CHECK_HIP(hipStreamSynchronize(st));
-  SQDET_REQUIRE(st_host[0] == 0, "voc_evaluate: the detection table holds a rejected ingest (negative or over-capacity count, "
-                "or a class outside 0..%d); reset it", classes - 1);
-  SQDET_UNSUPPORTED(host.error & 1, "voc_evaluate: an image has more than %d ground-truth or %d detection rows",
-                    SQDET_VOC_MAX_GROUNDTRUTH, cap);
+  if (const int rc = read_back("voc_evaluate", w.h, t, classes, st, &host)) return rc;
   for (int c = 0; c < classes; ++c) {
     host_ap07[c] = host.ap07[c];
     host_ap_area[c] = host.ap_area[c];

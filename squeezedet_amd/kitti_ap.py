@@ -1,5 +1,5 @@
-"""KITTI 2D average precision on the GPU (include/sqdet.h, csrc/kitti_eval.hip): the scoring half of the reference's
-src/eval.py without detection files or an external evaluator.
+"""KITTI 2D average precision on the GPU (include/sqdet.h, csrc/kitti_eval.hip; the table: det_table.py): the scoring half
+of the reference's src/eval.py without detection files or an external evaluator.
 
   load_kitti(data_path, image_set, mc)     the dataset reader of dataset/kitti.py:14-90: image paths, the `rois` lists
                                            (BatchReader / analysis) and the evaluator's raw ground truth
@@ -20,13 +20,13 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, stream_ptr
+from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, ptr as _ptr, row_offsets  # noqa: F401
 from .util import bbox_transform_inv
 
 CLASS_NAMES = ("car", "pedestrian", "cyclist")                  # the evaluator's classes (= kitti.py:22)
 # the evaluator's type names, compared case-insensitively (strcasecmp); anything else is "other"
 TYPE_CODES = {"car": 0, "pedestrian": 1, "cyclist": 2, "van": 3, "person_sitting": 4, "dontcare": 5}
 TYPE_OTHER = 6
-MAX_DETECTIONS, MAX_GROUNDTRUTH = 512, 128                       # per image (SQDET_KITTI_MAX_*)
 DIFFICULTIES = ("easy", "medium", "hard")
 ERROR_TYPES = ("loc", "cls", "bg", "missed")                     # SQDET_KITTI_ERR_*
 ANALYSIS_KEYS = ("num of detections", "num of objects", "% correct detections", "% localization error",
@@ -109,19 +109,14 @@ class GroundTruth:
     def __init__(self, raw, rois):
         if len(raw) != len(rois):
             raise ValueError("GroundTruth: %d label lists for %d roi lists" % (len(raw), len(rois)))
-        for name, per in (("ground-truth", raw), ("roi", rois)):
-            big = [i for i, r in enumerate(per) if len(r) > MAX_GROUNDTRUTH]
-            if big:
-                raise _lib.SqdetUnsupported("KITTI evaluation: image %d has %d %s rows (limit %d)"
-                                            % (big[0], len(per[big[0]]), name, MAX_GROUNDTRUTH))
         self.num_images = len(raw)
-        self.offsets = np.concatenate([[0], np.cumsum([len(r) for r in raw])]).astype(np.int32)
+        self.offsets = row_offsets(raw, "KITTI evaluation: image %d has %d ground-truth rows (limit %d)")
+        self.roi_offsets = row_offsets(rois, "KITTI evaluation: image %d has %d roi rows (limit %d)")
         flat = [row for r in raw for row in r]
         self.box = np.array([row[1:5] for row in flat], np.float64).reshape(-1, 4)
         self.truncation = np.array([row[5] for row in flat], np.float64)
         self.occlusion = np.array([row[6] for row in flat], np.int32)
         self.type = np.array([row[0] for row in flat], np.int32)
-        self.roi_offsets = np.concatenate([[0], np.cumsum([len(r) for r in rois])]).astype(np.int32)
         rflat = [row for r in rois for row in r]
         self.roi_box = np.array([row[:4] for row in rflat], np.float64).reshape(-1, 4)
         self.roi_cls = np.array([int(row[4]) for row in rflat], np.int32)
@@ -175,68 +170,27 @@ def parse_checkpoint_step(path):
     return name.split("-")[-1]
 
 
-def _ptr(t):
-    return _lib.C.c_void_p(t.data_ptr())
-
-
-class KittiEvaluator:
+class KittiEvaluator(DetectionTable):
     """Device detection table for one image set + the scoring calls.  gt: a GroundTruth (load_kitti(...).gt).
     max_detections: rows per image the table holds (>= the filter's max_out; default mc.TOP_N_DETECTION, else 512)."""
 
     def __init__(self, mc, gt, device="cuda:0", max_detections=None):
         if tuple(c.lower() for c in mc.CLASS_NAMES) != CLASS_NAMES:
             raise _lib.SqdetError("KittiEvaluator: the KITTI classes %s are required, got %s" % (CLASS_NAMES, mc.CLASS_NAMES))
-        self.mc, self.gt = mc, gt
-        self.device = torch.device(device)
-        cap = int(max_detections or (mc.TOP_N_DETECTION if mc.TOP_N_DETECTION > 0 else MAX_DETECTIONS))
-        if not 0 < cap <= MAX_DETECTIONS:
-            raise _lib.SqdetUnsupported("KittiEvaluator: %d detections per image (limit %d)" % (cap, MAX_DETECTIONS))
-        self.cap, n = cap, gt.num_images
-        dev = self.device
-        self.det_box = torch.zeros((n, cap, 4), dtype=torch.float64, device=dev)
-        self.det_score = torch.zeros((n, cap), dtype=torch.float64, device=dev)
-        self.det_cls = torch.zeros((n, cap), dtype=torch.int32, device=dev)
-        self.det_count = torch.zeros((n,), dtype=torch.int32, device=dev)
-        self.status = torch.zeros((2,), dtype=torch.int32, device=dev)
-
-        def up(a, dt):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a).to(dev) if a.size else torch.zeros((1,), dtype=dt, device=dev)
+        super().__init__(mc, gt, device, max_detections)
+        up = self.up
         self.gt_offsets = up(gt.offsets, torch.int32)
         self.gt_box, self.gt_trunc = up(gt.box, torch.float64), up(gt.truncation, torch.float64)
         self.gt_occ, self.gt_type = up(gt.occlusion, torch.int32), up(gt.type, torch.int32)
         self.num_gt = int(gt.offsets[-1])
         self.roi_offsets, self.roi_box, self.roi_cls = up(gt.roi_offsets, torch.int32), up(gt.roi_box, torch.float64), up(gt.roi_cls, torch.int32)
         self.num_rois = int(gt.roi_offsets[-1])
-        self.workspace = torch.empty((lib().sqdet_kitti_eval_workspace_bytes(self.num_gt),), dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty((lib().sqdet_kitti_eval_workspace_bytes(self.num_gt),), dtype=torch.uint8, device=self.device)
         self.precision = self.aps_raw = self.evaluated = self.analysis = None
         self._records = None
 
-    def reset(self):
-        """Empties the table (stream-ordered)."""
-        self.det_count.zero_()
-        self.status.zero_()
-
-    def add_rows(self, boxes, probs, cls, count, image_offset, scales=None):
-        """filter_prediction_batch rows of images [image_offset, image_offset + n) -> the table, stream-ordered, no host
-        sync.  scales: per-image (x_scale, y_scale) the boxes are divided by (None = 1).  A negative count (the filter's
-        overflow report) makes the call write nothing; evaluate() then raises."""
-        n, max_out = int(probs.shape[0]), int(probs.shape[1])
-        for t, name, dt in ((boxes, "boxes", torch.float32), (probs, "probs", torch.float32), (cls, "cls", torch.int32),
-                            (count, "count", torch.int32)):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
-                raise _lib.SqdetError("add_rows: %s must be a contiguous %s tensor on %s" % (name, dt, self.device))
-        if tuple(boxes.shape) != (n, max_out, 4) or tuple(cls.shape) != (n, max_out) or tuple(count.shape) != (n,):
-            raise _lib.SqdetError("add_rows: shapes %s %s %s %s" % (tuple(boxes.shape), tuple(probs.shape), tuple(cls.shape), tuple(count.shape)))
-        sc = None
-        if scales is not None:
-            sc = torch.as_tensor(np.ascontiguousarray(np.asarray(scales, np.float64).reshape(n, 2))).to(self.device, non_blocking=True)
-        check(lib().sqdet_kitti_ingest(_ptr(boxes), _ptr(probs), _ptr(cls), _ptr(count), _ptr(sc) if sc is not None else None,
-                                       n, max_out, _ptr(self.det_box), _ptr(self.det_score), _ptr(self.det_cls), _ptr(self.det_count),
-                                       _ptr(self.status), int(image_offset), self.gt.num_images, self.cap, stream_ptr()),
-              "sqdet_kitti_ingest")
-        if sc is not None:
-            sc.record_stream(torch.cuda.current_stream(self.device))
+    def _ingest(self, src, dst):
+        check(lib().sqdet_kitti_ingest(*src, *dst), "sqdet_kitti_ingest")
 
     def evaluate(self):
         """-> (aps, names, precision): aps / names exactly as kitti_eval.evaluate_detections returns them (an AP read back
@@ -246,8 +200,7 @@ class KittiEvaluator:
         ap = np.zeros(9, np.float64)
         ev = np.zeros(3, np.int32)
         P = lambda a: a.ctypes.data_as(_lib.C.c_void_p)
-        check(lib().sqdet_kitti_evaluate(_ptr(self.det_box), _ptr(self.det_score), _ptr(self.det_cls), _ptr(self.det_count),
-                                         _ptr(self.status), self.gt.num_images, self.cap, _ptr(self.gt_offsets), _ptr(self.gt_box),
+        check(lib().sqdet_kitti_evaluate(*self.table_args(), _ptr(self.status), self.gt.num_images, self.cap, _ptr(self.gt_offsets), _ptr(self.gt_box),
                                          _ptr(self.gt_trunc), _ptr(self.gt_occ), _ptr(self.gt_type), self.num_gt,
                                          _ptr(self.workspace), P(prec), P(ap), P(ev), stream_ptr()), "sqdet_kitti_evaluate")
         self.precision, self.aps_raw, self.evaluated = prec, ap, ev
@@ -284,7 +237,7 @@ class KittiEvaluator:
         rec_cls = torch.empty((2 * R,), dtype=torch.int32, device=dev)
         rec_box = torch.empty((2 * R, 4), dtype=torch.float64, device=dev)
         rec_score = torch.empty((2 * R,), dtype=torch.float64, device=dev)
-        check(lib().sqdet_kitti_analyze(_ptr(self.det_box), _ptr(self.det_score), _ptr(self.det_cls), _ptr(self.det_count), n, self.cap,
+        check(lib().sqdet_kitti_analyze(*self.table_args(), n, self.cap,
                                         _ptr(self.roi_offsets), _ptr(self.roi_box), _ptr(self.roi_cls), self.num_rois, _ptr(counters),
                                         _ptr(rec_count), _ptr(rec_type), _ptr(rec_cls), _ptr(rec_box), _ptr(rec_score), stream_ptr()),
               "sqdet_kitti_analyze")
@@ -323,13 +276,6 @@ class KittiEvaluator:
                 f.write("{:s} {:s} {:.1f} {:.1f} {:.1f} {:.1f} {:s} {:.3f}\n".format(
                     image_idx[i], t, cx - w / 2., cy - h / 2., cx + w / 2., cy + h / 2., self.mc.CLASS_NAMES[c], s))
 
-    def tables(self):
-        """The table on the host: per image a list of (class index, x1, y1, x2, y2, score), file order."""
-        cnt = self.det_count.cpu().numpy()
-        box, score, cls = self.det_box.cpu().numpy(), self.det_score.cpu().numpy(), self.det_cls.cpu().numpy()
-        return [[(int(cls[i, j]),) + tuple(float(v) for v in box[i, j]) + (float(score[i, j]),) for j in range(max(0, int(cnt[i])))]
-                for i in range(len(cnt))]
-
     def write_detection_files(self, det_file_dir, image_idx):
         """The detection files of kitti_eval.write_detection_files, from the table (each value is the double nearest to the
         text it came from, so formatting it again gives that text)."""
@@ -339,28 +285,6 @@ class KittiEvaluator:
                 for c, x1, y1, x2, y2, s in rows:
                     f.write("{:s} -1 -1 0.0 {:.2f} {:.2f} {:.2f} {:.2f} 0.0 0.0 0.0 0.0 0.0 0.0 0.0 {:.3f}\n".format(
                         CLASS_NAMES[c], x1, y1, x2, y2, s))
-
-    def load_rows(self, rows):
-        """Fills the table from host rows (per image a list of (class index, x1, y1, x2, y2, score), file order)."""
-        n = self.gt.num_images
-        if len(rows) != n:
-            raise _lib.SqdetError("load_rows: %d images for a table of %d" % (len(rows), n))
-        big = [i for i, r in enumerate(rows) if len(r) > self.cap]
-        if big:
-            raise _lib.SqdetUnsupported("load_rows: image %d has %d detections (table holds %d)" % (big[0], len(rows[big[0]]), self.cap))
-        box = np.zeros((n, self.cap, 4), np.float64)
-        score = np.zeros((n, self.cap), np.float64)
-        cls = np.zeros((n, self.cap), np.int32)
-        cnt = np.zeros(n, np.int32)
-        for i, r in enumerate(rows):
-            cnt[i] = len(r)
-            for j, (c, x1, y1, x2, y2, s) in enumerate(r):
-                cls[i, j], box[i, j], score[i, j] = c, (x1, y1, x2, y2), s
-        self.det_box.copy_(torch.from_numpy(box))
-        self.det_score.copy_(torch.from_numpy(score))
-        self.det_cls.copy_(torch.from_numpy(cls))
-        self.det_count.copy_(torch.from_numpy(cnt))
-        self.status.zero_()
 
 
 def parse_detection_file(path):
@@ -392,11 +316,7 @@ def evaluate_detection_files(data_root_path, image_set, det_dir, mc=None, device
     label_dir = os.path.join(data_root_path, "training", "label_2")
     raw = [parse_label_file(os.path.join(label_dir, i + ".txt")) for i in idx]
     rows = [parse_detection_file(os.path.join(det_dir, "data", i + ".txt")) for i in idx]
-    cap = max([1] + [len(r) for r in rows])
-    if cap > MAX_DETECTIONS:
-        raise _lib.SqdetUnsupported("evaluate_detection_files: %d detections in one image (limit %d)" % (cap, MAX_DETECTIONS))
-    ev = KittiEvaluator(mc, GroundTruth(raw, [[] for _ in idx]), device, max_detections=cap)
-    ev.load_rows(rows)
+    ev = KittiEvaluator.from_rows(mc, GroundTruth(raw, [[] for _ in idx]), rows, device)
     aps, names, _ = ev.evaluate()
     ev.write_stats(det_dir)
     return aps, names

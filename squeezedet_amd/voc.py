@@ -1,5 +1,5 @@
 """Pascal VOC: the dataset reader of the reference's src/dataset/pascal_voc.py and its VOC average precision
-(src/dataset/voc_eval.py) on the GPU (include/sqdet.h, csrc/voc_eval.hip), without detection files.
+(src/dataset/voc_eval.py) on the GPU (include/sqdet.h, csrc/voc_eval.hip; the table: det_table.py), without detection files.
 
   load_voc(data_path, year, image_set, mc)   the reader of pascal_voc.py:36-79: image paths, the `rois` lists (BatchReader)
                                              and the ground truth voc_eval.parse_rec reads from the same XML files
@@ -20,9 +20,10 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, stream_ptr
+from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, ptr as _ptr, row_offsets  # noqa: F401
 from .util import bbox_transform_inv
 
-MAX_DETECTIONS, MAX_GROUNDTRUTH, MAX_CLASSES = 512, 128, 64      # SQDET_VOC_MAX_*
+MAX_CLASSES = 64                                                 # SQDET_VOC_MAX_CLASSES
 
 VocSet = namedtuple("VocSet", "image_idx image_paths rois gt")
 
@@ -81,11 +82,8 @@ class GroundTruth:
     XML's integers), cls int32 [G] (-1: not in the class list), difficult int32 [G]."""
 
     def __init__(self, raw):
-        big = [i for i, r in enumerate(raw) if len(r) > MAX_GROUNDTRUTH]
-        if big:
-            raise _lib.SqdetUnsupported("VOC evaluation: image %d has %d objects (limit %d)" % (big[0], len(raw[big[0]]), MAX_GROUNDTRUTH))
         self.num_images = len(raw)
-        self.offsets = np.concatenate([[0], np.cumsum([len(r) for r in raw])]).astype(np.int32)
+        self.offsets = row_offsets(raw, "VOC evaluation: image %d has %d objects (limit %d)")
         flat = [row for r in raw for row in r]
         self.cls = np.array([row[0] for row in flat], np.int32)
         self.box = np.array([row[1:5] for row in flat], np.float64).reshape(-1, 4)
@@ -108,70 +106,25 @@ def load_voc(data_path, year, image_set, mc):
     return VocSet(idx, [os.path.join(voc, "JPEGImages", i + ".jpg") for i in idx], rois, GroundTruth(raw))
 
 
-def _ptr(t):
-    return _lib.C.c_void_p(t.data_ptr())
-
-
-class VocEvaluator:
+class VocEvaluator(DetectionTable):
     """Device detection table for one image set + the scoring call.  gt: a GroundTruth (load_voc(...).gt).
     max_detections: rows per image the table holds (>= the filter's max_out; default mc.TOP_N_DETECTION, else 512)."""
 
     def __init__(self, mc, gt, device="cuda:0", max_detections=None):
         self.class_names = tuple(mc.CLASS_NAMES)
-        self.classes = len(self.class_names)
-        if not 0 < self.classes <= MAX_CLASSES:
-            raise _lib.SqdetUnsupported("VocEvaluator: %d classes (limit %d)" % (self.classes, MAX_CLASSES))
-        self.mc, self.gt = mc, gt
-        self.device = torch.device(device)
-        top_n = mc.get("TOP_N_DETECTION", 0)
-        cap = int(max_detections or (top_n if top_n > 0 else MAX_DETECTIONS))
-        if not 0 < cap <= MAX_DETECTIONS:
-            raise _lib.SqdetUnsupported("VocEvaluator: %d detections per image (limit %d)" % (cap, MAX_DETECTIONS))
-        self.cap, n = cap, gt.num_images
-        dev = self.device
-        self.det_box = torch.zeros((n, cap, 4), dtype=torch.float64, device=dev)
-        self.det_score = torch.zeros((n, cap), dtype=torch.float64, device=dev)
-        self.det_cls = torch.zeros((n, cap), dtype=torch.int32, device=dev)
-        self.det_count = torch.zeros((n,), dtype=torch.int32, device=dev)
-        self.status = torch.zeros((2,), dtype=torch.int32, device=dev)
-
-        def up(a, dt):
-            a = np.ascontiguousarray(a)
-            return torch.from_numpy(a).to(dev) if a.size else torch.zeros((1,), dtype=dt, device=dev)
-        self.gt_offsets = up(gt.offsets, torch.int32)
-        self.gt_box, self.gt_cls, self.gt_difficult = up(gt.box, torch.float64), up(gt.cls, torch.int32), up(gt.difficult, torch.int32)
+        if not 0 < len(self.class_names) <= MAX_CLASSES:
+            raise _lib.SqdetUnsupported("VocEvaluator: %d classes (limit %d)" % (len(self.class_names), MAX_CLASSES))
+        super().__init__(mc, gt, device, max_detections, classes=len(self.class_names))
+        self.gt_offsets = self.up(gt.offsets, torch.int32)
+        self.gt_box, self.gt_cls, self.gt_difficult = self.up(gt.box, torch.float64), self.up(gt.cls, torch.int32), self.up(gt.difficult, torch.int32)
         self.num_gt = int(gt.offsets[-1])
-        self.workspace = torch.empty((max(1, lib().sqdet_voc_eval_workspace_bytes(n, cap, self.classes)),), dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty((max(1, lib().sqdet_voc_eval_workspace_bytes(gt.num_images, self.cap, self.classes)),),
+                                     dtype=torch.uint8, device=self.device)
         self._curve_rec = self._curve_prec = None
         self.ap07 = self.ap_area = self.npos = self.num_det = None
 
-    def reset(self):
-        """Empties the table (stream-ordered)."""
-        self.det_count.zero_()
-        self.status.zero_()
-
-    def add_rows(self, boxes, probs, cls, count, image_offset, scales=None):
-        """filter_prediction_batch rows of images [image_offset, image_offset + n) -> the table, stream-ordered, no host
-        sync.  scales: per-image (x_scale, y_scale) the boxes are divided by (None = 1).  A negative count (the filter's
-        overflow report) makes the call write nothing; evaluate() then raises."""
-        n, max_out = int(probs.shape[0]), int(probs.shape[1])
-        for t, name, dt in ((boxes, "boxes", torch.float32), (probs, "probs", torch.float32), (cls, "cls", torch.int32),
-                            (count, "count", torch.int32)):
-            if t.device != self.device or t.dtype != dt or not t.is_contiguous():
-                raise _lib.SqdetError("add_rows: %s must be a contiguous %s tensor on %s" % (name, dt, self.device))
-        if tuple(boxes.shape) != (n, max_out, 4) or tuple(cls.shape) != (n, max_out) or tuple(count.shape) != (n,):
-            raise _lib.SqdetError("add_rows: shapes %s %s %s %s" % (tuple(boxes.shape), tuple(probs.shape), tuple(cls.shape), tuple(count.shape)))
-        if n == 0:
-            return
-        sc = None
-        if scales is not None:
-            sc = torch.as_tensor(np.ascontiguousarray(np.asarray(scales, np.float64).reshape(n, 2))).to(self.device, non_blocking=True)
-        check(lib().sqdet_voc_ingest(_ptr(boxes), _ptr(probs), _ptr(cls), _ptr(count), _ptr(sc) if sc is not None else None,
-                                     n, max_out, self.classes, _ptr(self.det_box), _ptr(self.det_score), _ptr(self.det_cls),
-                                     _ptr(self.det_count), _ptr(self.status), int(image_offset), self.gt.num_images, self.cap,
-                                     stream_ptr()), "sqdet_voc_ingest")
-        if sc is not None:
-            sc.record_stream(torch.cuda.current_stream(self.device))
+    def _ingest(self, src, dst):
+        check(lib().sqdet_voc_ingest(*src, self.classes, *dst), "sqdet_voc_ingest")
 
     def _evaluate(self, curve_cls=-1):
         C = self.classes
@@ -181,8 +134,7 @@ class VocEvaluator:
             self._curve_rec = torch.empty((self.gt.num_images * self.cap,), dtype=torch.float64, device=self.device)
             self._curve_prec = torch.empty_like(self._curve_rec)
         P = lambda a: a.ctypes.data_as(_lib.C.c_void_p)
-        check(lib().sqdet_voc_evaluate(_ptr(self.det_box), _ptr(self.det_score), _ptr(self.det_cls), _ptr(self.det_count),
-                                       _ptr(self.status), self.gt.num_images, self.cap, C, _ptr(self.gt_offsets), _ptr(self.gt_box),
+        check(lib().sqdet_voc_evaluate(*self.table_args(), _ptr(self.status), self.gt.num_images, self.cap, C, _ptr(self.gt_offsets), _ptr(self.gt_box),
                                        _ptr(self.gt_cls), _ptr(self.gt_difficult), self.num_gt, _ptr(self.workspace), P(ap07),
                                        P(ap_area), P(npos), P(ndet), int(curve_cls),
                                        _ptr(self._curve_rec) if curve_cls >= 0 else None,
@@ -207,41 +159,10 @@ class VocEvaluator:
         n = int(self.num_det[cls])
         return self._curve_rec[:n].cpu().numpy(), self._curve_prec[:n].cpu().numpy()
 
-    def tables(self):
-        """The table on the host: per image a list of (class index, x1, y1, x2, y2, score), file order."""
-        cnt = self.det_count.cpu().numpy()
-        box, score, cls = self.det_box.cpu().numpy(), self.det_score.cpu().numpy(), self.det_cls.cpu().numpy()
-        return [[(int(cls[i, j]),) + tuple(float(v) for v in box[i, j]) + (float(score[i, j]),) for j in range(max(0, int(cnt[i])))]
-                for i in range(len(cnt))]
-
     def write_detection_files(self, det_file_dir, image_idx):
         """<det_file_dir>/<cls>.txt of every class, as pascal_voc.evaluate_detections writes them (:98-109), from the table
         (each value is the double nearest to the text it came from, so formatting it again gives that text)."""
         write_detection_files(det_file_dir, self.class_names, image_idx, self.tables())
-
-    def load_rows(self, rows):
-        """Fills the table from host rows (per image a list of (class index, x1, y1, x2, y2, score), class-major)."""
-        n = self.gt.num_images
-        if len(rows) != n:
-            raise _lib.SqdetError("load_rows: %d images for a table of %d" % (len(rows), n))
-        big = [i for i, r in enumerate(rows) if len(r) > self.cap]
-        if big:
-            raise _lib.SqdetUnsupported("load_rows: image %d has %d detections (table holds %d)" % (big[0], len(rows[big[0]]), self.cap))
-        box = np.zeros((n, self.cap, 4), np.float64)
-        score = np.zeros((n, self.cap), np.float64)
-        cls = np.zeros((n, self.cap), np.int32)
-        cnt = np.zeros(n, np.int32)
-        for i, r in enumerate(rows):
-            cnt[i] = len(r)
-            for j, (c, x1, y1, x2, y2, s) in enumerate(r):
-                if not 0 <= c < self.classes:
-                    raise _lib.SqdetError("load_rows: image %d row %d has class %d of %d" % (i, j, c, self.classes))
-                cls[i, j], box[i, j], score[i, j] = c, (x1, y1, x2, y2), s
-        self.det_box.copy_(torch.from_numpy(box))
-        self.det_score.copy_(torch.from_numpy(score))
-        self.det_cls.copy_(torch.from_numpy(cls))
-        self.det_count.copy_(torch.from_numpy(cnt))
-        self.status.zero_()
 
 
 def write_detection_files(det_file_dir, class_names, image_idx, tables):
@@ -281,10 +202,5 @@ def evaluate_detection_files(data_root_path, year, image_set, det_dir, mc, devic
             continue
         for index, s, x1, y1, x2, y2 in parse_detection_file(fn):
             rows[where[index]].append((c, x1, y1, x2, y2, s))
-    cap = max([1] + [len(r) for r in rows])
-    if cap > MAX_DETECTIONS:
-        raise _lib.SqdetUnsupported("evaluate_detection_files: %d detections in one image (limit %d)" % (cap, MAX_DETECTIONS))
     gt = GroundTruth([parse_rec(os.path.join(voc, "Annotations", i + ".xml"), names) for i in idx])
-    ev = VocEvaluator(mc, gt, device, max_detections=cap)
-    ev.load_rows(rows)
-    return ev.evaluate(use_07_metric_for(year))
+    return VocEvaluator.from_rows(mc, gt, rows, device).evaluate(use_07_metric_for(year))

@@ -32,7 +32,7 @@ def _reference_stats(name, root, result_dir, n, golden_dir):
     return {str(fn): str(g["%s:%s" % (name, fn)]) for fn in g[name + "_files"]}
 
 
-@pytest.mark.parametrize("name", ["mixed", "all", "few", "large"])
+@pytest.mark.parametrize("name", ["mixed", "all", "few", "large", "wave"])
 def test_stats_files_byte_identical_to_reference(name, tmp_path, golden_dir):
     from squeezedet_amd import kitti_ap as KA
     from tests.golden import kitti_ap_cases as KC

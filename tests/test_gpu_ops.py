@@ -74,6 +74,7 @@ CONV_CASES = [
     ("e3_multitile_96_384", 1, 17, 30, 96, 384, 3, 1, "SAME", True),
     ("convdet_full_24x78", 1, 24, 78, 768, 72, 3, 1, "SAME", False),
     ("plus_convdet_22x76", 1, 22, 76, 512, 72, 3, 1, "SAME", False),
+    ("voc_convdet_512_252", 2, 7, 13, 512, 252, 3, 1, "SAME", False),    # the Pascal VOC head: 9 x (23 + 5) channels
     # odd tile counts per group (8-byte-aligned rows only) and shallow-K 72-cout 3x3
     ("c1_k64_n48", 1, 12, 20, 64, 48, 1, 1, "SAME", True),
     ("c1_k32_n80", 2, 9, 21, 32, 80, 1, 1, "SAME", False),

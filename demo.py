@@ -27,6 +27,8 @@ import time
 
 import numpy as np
 
+from squeezedet_amd import drivers
+
 CLS2CLR = {"car": (255, 191, 0), "cyclist": (0, 191, 255), "pedestrian": (255, 0, 191)}      # BGR (demo.py:123-127)
 
 
@@ -48,7 +50,7 @@ def parse_args(argv=None):
                     help="video: --input_path is a glob of frame files, sorted by name (there is no video decoder on this platform)")
     ap.add_argument("--input_path", default="./data/sample.png", help="glob of input images / frames")
     ap.add_argument("--out_dir", default="./data/out/")
-    ap.add_argument("--demo_net", default="squeezeDet", choices=["squeezeDet", "squeezeDet+", "resnet50", "vgg16"])
+    ap.add_argument("--demo_net", default="squeezeDet", choices=drivers.NETS)
     ap.add_argument("--weights", default="")
     ap.add_argument("--anchor_shapes", default="", metavar="FILE",
                     help="anchor shapes the weights were trained with (default: anchor_shapes.json beside --weights, else the config's)")
@@ -67,27 +69,11 @@ def parse_args(argv=None):
 
 
 def make_model(a, batch):
-    import torch
-    import squeezedet_amd as S
-    from squeezedet_amd import anchors, config, nets, synthetic, weights
-    mc, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
-               "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[a.demo_net]
-    mc = mc()
-    shapes_file = a.anchor_shapes or (a.weights and anchors.beside_checkpoint(a.weights))
-    if shapes_file:
-        mc = config.with_anchor_shapes(mc, anchors.load_for_driver(shapes_file))
-    mc.BATCH_SIZE = int(batch)
-    mc.LOAD_PRETRAINED_MODEL = False          # parameters are restored below (demo.py:171-172)
-    dtype = torch.float16 if a.dtype == "fp16" else torch.float32
-    model = cls(mc, a.gpu, dtype=dtype)
+    from squeezedet_amd import synthetic, weights
+    mc = drivers.make_config(a.demo_net, anchor_shapes=drivers.driver_anchor_shapes(a.anchor_shapes, a.weights))
+    model = drivers.build_model(mc, a.demo_net, a.gpu, a.dtype, batch)     # parameters are restored below (demo.py:171-172)
     model.load_params(weights.load_params(a.weights) if a.weights else synthetic.synthetic_params(model, seed=0))
-    return mc, model, dtype
-
-
-def read_bgr(path):
-    """uint8 BGR [H, W, 3], what cv2.imread returns."""
-    from PIL import Image
-    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])
+    return mc, model, drivers.torch_dtype(a.dtype)
 
 
 def detect_and_draw(model, input_image, n):
@@ -112,7 +98,7 @@ def image_demo(a):
     os.makedirs(a.out_dir, exist_ok=True)
     with Session() as sess:
         for f in glob.iglob(a.input_path):
-            bgr_host = read_bgr(f)
+            bgr_host = drivers.read_bgr(f)
             bgr = torch.from_numpy(bgr_host).to(model.device)
             input_image = ops.preprocess_bgr(bgr[None], mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, dtype)
             out = os.path.join(a.out_dir, "out_" + os.path.split(f)[1])
@@ -149,9 +135,9 @@ def video_demo(a):
         t_start = time.time()
         crops = []
         for f in frames[i0:i0 + a.batch]:
-            frame = read_bgr(f)
+            frame = drivers.read_bgr(f)
             frame = frame[top:frame.shape[0] - bottom, left:frame.shape[1] - right, :]
-            assert frame.size, "--crop {} leaves nothing of {} ({} x {})".format(a.crop, f, *read_bgr(f).shape[:2])
+            assert frame.size, "--crop {} leaves nothing of {} ({} x {})".format(a.crop, f, *drivers.read_bgr(f).shape[:2])
             crops.append(frame)
         n = len(crops)
         crops += [crops[-1]] * (a.batch - n)               # the last batch is padded with its last frame

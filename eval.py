@@ -34,25 +34,18 @@ import time
 
 import numpy as np
 
-NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
+from squeezedet_amd import drivers
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--dataset", default="KITTI", help="KITTI or PASCAL_VOC")
-    ap.add_argument("--data_path", default="", help="root directory of the KITTI data (PASCAL_VOC: the directory that holds VOC<year>)")
-    ap.add_argument("--image_set", default="test", help="ImageSets/<image_set>.txt (PASCAL_VOC: ImageSets/Main/<image_set>.txt)")
-    ap.add_argument("--year", default="2007", help="PASCAL_VOC: the VOC<year> directory; before 2010 the 11-point AP is reported")
-    ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"),
-                    help="PASCAL_VOC: network input size (default: 384 1248, SqueezeDet's)")
+    drivers.add_dataset_args(ap, image_set_default="test")
+    drivers.add_model_args(ap, dtype_default="fp32")       # (--image_size: PASCAL_VOC only, main refuses it for KITTI)
     ap.add_argument("--eval_dir", default="/tmp/squeezeDet/eval", help="where results are written")
     ap.add_argument("--checkpoint_path", default="/tmp/squeezeDet/train", help="a .npz file (--run_once) or a directory")
     ap.add_argument("--eval_interval_secs", type=int, default=60, help="how often to look for a new checkpoint")
     ap.add_argument("--run_once", action="store_true", help="evaluate --checkpoint_path once and exit")
-    ap.add_argument("--net", default="squeezeDet", choices=NETS)
-    ap.add_argument("--gpu", default="0", help="gpu id")
     ap.add_argument("--batch_size", type=int, default=0, help="images per forward pass (default: the config's)")
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16"], help="storage type of the forward pass")
     ap.add_argument("--eval_tool", default="", help="score with this evaluate_object binary instead of the GPU evaluator")
     ap.add_argument("--synthetic_weights", action="store_true", help="seeded synthetic weights instead of a checkpoint")
     ap.add_argument("--visualize", type=int, default=0, metavar="N",
@@ -61,65 +54,24 @@ def parse_args(argv=None):
     ap.add_argument("--anchor_shapes", default="", metavar="FILE",
                     help="anchor shapes the checkpoint was trained with (default: anchor_shapes.json beside the checkpoint, else the config's)")
     a = ap.parse_args(argv)
-    assert a.dataset in ("KITTI", "PASCAL_VOC"), "Currently only supports KITTI dataset (and PASCAL_VOC)"
+    drivers.check_dataset_args(ap, a)
     return a
 
 
-def anchor_shapes_for(a):
-    """[k,2] from --anchor_shapes, else from an anchor_shapes.json beside the checkpoint, else None (the config's shapes)."""
-    from squeezedet_amd import anchors
-    path = a.anchor_shapes or anchors.beside_checkpoint(a.checkpoint_path)
-    if not path:
-        return None
-    print("Anchor shapes from {}".format(path))
-    return anchors.load_for_driver(path)
-
-
-def make_model(net, gpu, dtype, batch_size=0, anchor_shapes=None):
-    import squeezedet_amd as S
-    from squeezedet_amd import nets
-    from squeezedet_amd.config import with_anchor_shapes
-    cfg, cls = {"squeezeDet": (S.kitti_squeezeDet_config, nets.SqueezeDet), "squeezeDet+": (S.kitti_squeezeDetPlus_config, nets.SqueezeDetPlus),
-                "resnet50": (S.kitti_res50_config, nets.ResNet50ConvDet), "vgg16": (S.kitti_vgg16_config, nets.VGG16ConvDet)}[net]
-    mc = cfg()
-    if anchor_shapes is not None:
-        mc = with_anchor_shapes(mc, anchor_shapes)
-    return mc, _build(mc, cls, gpu, dtype, batch_size)
-
-
-def make_voc_model(net, gpu, dtype, batch_size=0, image_size=None, anchor_shapes=None):
-    """SqueezeDet with the 20-class VOC config (config.voc_squeezeDet_config_for_input) at image_size."""
-    import squeezedet_amd as S
-    from squeezedet_amd import nets
-    if net != "squeezeDet":
-        raise SystemExit("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
-    h, w = image_size or (384, 1248)
-    from squeezedet_amd.config import pad_head_classes, with_anchor_shapes
-    mc = S.voc_squeezeDet_config_for_input(int(h), int(w))
-    if anchor_shapes is not None:
-        mc = with_anchor_shapes(mc, anchor_shapes)                                # (before the padding, which depends on the count)
-    mc = pad_head_classes(mc)                                                     # 20 classes -> a head of 23, 3 of them padding
-    return mc, _build(mc, nets.SqueezeDet, gpu, dtype, batch_size)
-
-
-def _build(mc, cls, gpu, dtype, batch_size):
-    import torch
-    if batch_size:
-        mc.BATCH_SIZE = int(batch_size)
-    mc.LOAD_PRETRAINED_MODEL = False
-    return cls(mc, gpu, dtype=torch.float16 if dtype == "fp16" else torch.float32)
+def make_model(net, gpu, dtype, batch_size=0, anchor_shapes=None, image_size=None, dataset="KITTI"):
+    """(config, model) of --net for the dataset: drivers.make_config, then the nets class on it."""
+    mc = drivers.make_config(net, image_size, dataset, anchor_shapes)
+    return mc, drivers.build_model(mc, net, gpu, dtype, batch_size)
 
 
 def read_image(path, model):
     """PIL -> BGR uint8 (what cv2.imread returns) -> ops.preprocess_bgr: network input [1,H,W,3] and (x_scale, y_scale)
     = network size / original size (imdb.read_image_batch)."""
     import torch
-    from PIL import Image
     from squeezedet_amd import ops
     mc = model.mc
-    rgb = np.asarray(Image.open(path).convert("RGB"))
-    bgr = torch.from_numpy(np.ascontiguousarray(rgb[:, :, ::-1])).to(model.device)
-    orig_h, orig_w = float(rgb.shape[0]), float(rgb.shape[1])
+    bgr = torch.from_numpy(drivers.read_bgr(path)).to(model.device)
+    orig_h, orig_w = float(bgr.shape[0]), float(bgr.shape[1])
     x = ops.preprocess_bgr(bgr[None], mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, model.dtype)
     return x, (mc.IMAGE_WIDTH / orig_w, mc.IMAGE_HEIGHT / orig_h)
 
@@ -174,8 +126,7 @@ def visualize_detections(image_dir, image_format, det_error_file, output_image_d
             shutil.rmtree(det_im_dir)
         os.makedirs(det_im_dir)
         for i, (k, obj) in enumerate(dets[:num_det_per_type]):
-            rgb = np.asarray(Image.open(os.path.join(image_dir, obj[0] + image_format)).convert("RGB"))
-            bgr = torch.from_numpy(np.ascontiguousarray(rgb[None, :, :, ::-1])).to(device)
+            bgr = torch.from_numpy(drivers.read_bgr(os.path.join(image_dir, obj[0] + image_format))[None]).to(device)
             x0, y0, x1, y1 = (int(float(v)) for v in obj[2:6])
             label = "{:s} ({:.2f})".format(obj[6], float(obj[7]))
             items = viz.pack_items([[(x0, y0, x1, y1, VIS_COLOR[::-1], label, "top_left")]], device)
@@ -330,17 +281,15 @@ def main(argv=None):
         for flag, given in (("--eval_tool", a.eval_tool), ("--visualize", a.visualize)):
             if given:
                 raise SystemExit("%s is KITTI-only: the external evaluator and the error analysis have no Pascal VOC form" % flag)
-        from squeezedet_amd.voc import VocEvaluator, load_voc
-        mc, model = make_voc_model(a.net, a.gpu, a.dtype, a.batch_size, a.image_size, anchor_shapes_for(a))
-        data = load_voc(a.data_path, a.year, a.image_set, mc)
-        evaluator = VocEvaluator(mc, data.gt, model.device)
+        from squeezedet_amd.voc import VocEvaluator as Evaluator
     else:
         if a.image_size is not None:
             raise SystemExit("--image_size is for --dataset PASCAL_VOC (the KITTI nets run at their configs' size)")
-        from squeezedet_amd.kitti_ap import KittiEvaluator, load_kitti
-        mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, anchor_shapes_for(a))
-        data = load_kitti(a.data_path, a.image_set, mc)
-        evaluator = KittiEvaluator(mc, data.gt, model.device)
+        from squeezedet_amd.kitti_ap import KittiEvaluator as Evaluator
+    shapes = drivers.driver_anchor_shapes(a.anchor_shapes, a.checkpoint_path)
+    mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, shapes, a.image_size, a.dataset)
+    data = drivers.load_index(a.dataset, a.data_path, a.year, a.image_set, mc)
+    evaluator = Evaluator(mc, data.gt, model.device)
     os.makedirs(a.eval_dir, exist_ok=True)
     if a.run_once:
         return eval_once(a, model, data, a.checkpoint_path, evaluator)

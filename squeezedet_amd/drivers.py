@@ -1,0 +1,119 @@
+"""What train.py, eval.py, demo.py and tools/fit_anchors.py decide the same way, once: the table of nets, the order in which a
+config is built, the model constructor call, the image read, the dataset choice, the anchor-shape lookup and the shared flags.
+Importing this needs neither torch nor a GPU; the nets and trainer classes are looked up when asked for."""
+import numpy as np
+
+from . import config
+
+NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
+DATASETS = ("KITTI", "PASCAL_VOC")
+VOC_IMAGE_SIZE = (384, 1248)        # PASCAL_VOC without --image_size: SqueezeDet's KITTI input
+
+# net -> (default config, config for an input size or None, class in squeezedet_amd.nets, class in squeezedet_amd.train)
+# (SqueezeDetTrainer walks any conv / fire / pool chain: it trains SqueezeDet+ too, tests/test_gpu_train.py)
+NET_TABLE = {
+    "squeezeDet": (config.kitti_squeezeDet_config, config.kitti_squeezeDet_config_for_input, "SqueezeDet", "SqueezeDetTrainer"),
+    "squeezeDet+": (config.kitti_squeezeDetPlus_config, None, "SqueezeDetPlus", "SqueezeDetTrainer"),
+    "resnet50": (config.kitti_res50_config, config.kitti_res50_config_for_input, "ResNet50ConvDet", "ResNet50ConvDetTrainer"),
+    "vgg16": (config.kitti_vgg16_config, config.kitti_vgg16_config_for_input, "VGG16ConvDet", "VGG16ConvDetTrainer"),
+}
+
+
+def model_class(net):
+    from . import nets
+    return getattr(nets, NET_TABLE[net][2])
+
+
+def trainer_class(net):
+    """(looked up here, not in the table: eval.py and demo.py never import squeezedet_amd.train)"""
+    from . import train
+    return getattr(train, NET_TABLE[net][3])
+
+
+def torch_dtype(name):
+    import torch
+    return torch.float16 if name == "fp16" else torch.float32
+
+
+def base_config(net, image_size=None, dataset="KITTI"):
+    """The config of --net at --image_size (None: the net's own size), its head not padded: the classes are the real ones."""
+    default, sized = NET_TABLE[net][:2]
+    if dataset == "PASCAL_VOC":
+        h, w = image_size if image_size is not None else VOC_IMAGE_SIZE
+        return config.voc_squeezeDet_config_for_input(int(h), int(w))
+    if image_size is None:
+        return default()
+    if sized is None:
+        raise SystemExit("--image_size: no sized config for --net %s (squeezeDet, resnet50 and vgg16 have one)" % net)
+    return sized(int(image_size[0]), int(image_size[1]))
+
+
+def make_config(net, image_size=None, dataset="KITTI", anchor_shapes=None):
+    """The config a driver runs: anchor_shapes ([k,2], None: the config's own) go in before the head is padded, because the
+    padding depends on their count (PASCAL_VOC: 20 classes -> a head of 23, 3 of them padding)."""
+    mc = base_config(net, image_size, dataset)
+    if anchor_shapes is not None:
+        mc = config.with_anchor_shapes(mc, anchor_shapes)
+    return config.pad_head_classes(mc) if dataset == "PASCAL_VOC" else mc
+
+
+def build_model(mc, net, gpu, dtype, batch_size=0):
+    """The nets class of --net on mc; its parameters are loaded by the caller."""
+    if batch_size:
+        mc.BATCH_SIZE = int(batch_size)
+    mc.LOAD_PRETRAINED_MODEL = False
+    return model_class(net)(mc, gpu, dtype=torch_dtype(dtype))
+
+
+def read_bgr(path):
+    """uint8 BGR [H, W, 3], what cv2.imread returns."""
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1])
+
+
+def load_index(dataset, data_path, year, image_set, mc):
+    """The image paths, rois and ground truth of the set: what voc.load_voc / kitti_ap.load_kitti return."""
+    if dataset == "PASCAL_VOC":
+        from .voc import load_voc
+        return load_voc(data_path, year, image_set, mc)
+    from .kitti_ap import load_kitti
+    return load_kitti(data_path, image_set, mc)
+
+
+def synthetic_data(mc, n, seed):
+    """--synthetic N --seed S: (images, rois), the same for every driver."""
+    from .synthetic import synthetic_dataset
+    return synthetic_dataset(mc, int(n), seed=300 + seed)
+
+
+def driver_anchor_shapes(flag_path, checkpoint_path):
+    """[k,2] from --anchor_shapes, else from an anchor_shapes.json beside the checkpoint, else None (the config's shapes)."""
+    from . import anchors
+    path = flag_path or (checkpoint_path and anchors.beside_checkpoint(checkpoint_path))
+    if not path:
+        return None
+    print("Anchor shapes from {}".format(path))
+    return anchors.load_for_driver(path)
+
+
+def add_dataset_args(ap, image_set_default):
+    ap.add_argument("--dataset", default="KITTI", help="KITTI or PASCAL_VOC")
+    ap.add_argument("--year", default="2007", help="PASCAL_VOC: the VOC<year> directory under --data_path; before 2010 the 11-point AP is reported")
+    ap.add_argument("--data_path", default="", help="root directory of the KITTI data (PASCAL_VOC: the directory that holds VOC<year>)")
+    ap.add_argument("--image_set", default=image_set_default, help="ImageSets/<image_set>.txt (PASCAL_VOC: ImageSets/Main/<image_set>.txt)")
+
+
+def add_model_args(ap, dtype_default):
+    """--net, --image_size, --gpu and, unless dtype_default is None, --dtype."""
+    ap.add_argument("--net", default="squeezeDet", choices=NETS, help="neural net architecture")
+    ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="network input size (default: the net's; PASCAL_VOC: %d %d)" % VOC_IMAGE_SIZE)
+    ap.add_argument("--gpu", default="0", help="gpu id")
+    if dtype_default:
+        ap.add_argument("--dtype", default=dtype_default, choices=["fp32", "fp16"], help="fp32: the reference's; fp16: half-precision storage")
+
+
+def check_dataset_args(ap, a):
+    assert a.dataset in DATASETS, "Currently only supports KITTI dataset (and PASCAL_VOC)"
+    if a.dataset == "PASCAL_VOC" and a.net != "squeezeDet":
+        ap.error("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import squeezedet_amd as S
-from squeezedet_amd import anchors, config
+from squeezedet_amd import anchors, config, drivers
 from squeezedet_amd._lib import SqdetError
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +31,11 @@ def _closed_form(mc, H, W, shapes):
                 out[(h * W + w) * B + k] = [(w + 1) * float(mc.IMAGE_WIDTH) / (W + 1), (h + 1) * float(mc.IMAGE_HEIGHT) / (H + 1),
                                             shapes[k][0], shapes[k][1]]
     return out
+
+
+def _shapes_for(a):
+    """what eval.py's main asks for"""
+    return drivers.driver_anchor_shapes(a.anchor_shapes, a.checkpoint_path)
 
 
 SHAPES9 = np.array([[20.5, 31.], [44., 40.], [61., 120.25], [90., 70.], [130., 95.], [150., 210.], [240., 130.], [300., 260.], [410., 300.]])
@@ -199,11 +204,11 @@ def test_driver_arguments(tmp_path):
         with pytest.raises(SystemExit):
             F.parse_args(bad)
     # make_config: the shapes go in before the head is padded; without them the configs are today's
-    mc = T.make_config("squeezeDet", (128, 256), "PASCAL_VOC", SHAPES9)
+    mc = drivers.make_config("squeezeDet", (128, 256), "PASCAL_VOC", SHAPES9)
     assert mc.CLASSES == 23 and np.array_equal(config.anchor_shapes_of(mc), SHAPES9)
-    assert np.array_equal(T.make_config("squeezeDet", (128, 256), "PASCAL_VOC").ANCHOR_BOX,
+    assert np.array_equal(drivers.make_config("squeezeDet", (128, 256), "PASCAL_VOC").ANCHOR_BOX,
                           config.pad_head_classes(S.voc_squeezeDet_config_for_input(128, 256)).ANCHOR_BOX)
-    assert np.array_equal(T.make_config("squeezeDet+").ANCHOR_BOX, S.kitti_squeezeDetPlus_config().ANCHOR_BOX)
+    assert np.array_equal(drivers.make_config("squeezeDet+").ANCHOR_BOX, S.kitti_squeezeDetPlus_config().ANCHOR_BOX)
     # the drivers refuse a count the nets are not built for, by name, before building anything
     p = str(tmp_path / "six.json")
     anchors.save_anchor_shapes(p, SHAPES9[:6], S.kitti_squeezeDet_config())
@@ -218,8 +223,8 @@ def test_driver_arguments(tmp_path):
     assert np.array_equal(T.resolve_anchor_shapes(T.parse_args(["--anchor_shapes", p9])), SHAPES9)
     assert T.resolve_anchor_shapes(T.parse_args([])) is None
     # eval.py: the flag, else the file beside the checkpoint, else nothing
-    assert E.anchor_shapes_for(E.parse_args(["--checkpoint_path", str(tmp_path / "none" / "model.ckpt-1.npz")])) is None
+    assert _shapes_for(E.parse_args(["--checkpoint_path", str(tmp_path / "none" / "model.ckpt-1.npz")])) is None
     os.makedirs(str(tmp_path / "run"))
     anchors.save_anchor_shapes(str(tmp_path / "run" / "anchor_shapes.json"), SHAPES9[::-1], S.kitti_squeezeDet_config())
-    assert np.array_equal(E.anchor_shapes_for(E.parse_args(["--checkpoint_path", str(tmp_path / "run" / "model.ckpt-1.npz")])), SHAPES9[::-1])
-    assert np.array_equal(E.anchor_shapes_for(E.parse_args(["--checkpoint_path", str(tmp_path / "run"), "--anchor_shapes", p9])), SHAPES9)
+    assert np.array_equal(_shapes_for(E.parse_args(["--checkpoint_path", str(tmp_path / "run" / "model.ckpt-1.npz")])), SHAPES9[::-1])
+    assert np.array_equal(_shapes_for(E.parse_args(["--checkpoint_path", str(tmp_path / "run"), "--anchor_shapes", p9])), SHAPES9)

@@ -18,7 +18,7 @@ import pytest
 import torch
 
 import squeezedet_amd as S
-from squeezedet_amd import anchors, config, ops
+from squeezedet_amd import anchors, config, drivers, ops
 from squeezedet_amd._lib import SqdetError, SqdetUnsupported
 
 pytestmark = pytest.mark.gpu
@@ -380,7 +380,7 @@ def test_drivers_end_to_end(tmp_path):
     assert cov["num_objects"] == rec["coverage_fitted"]["num_objects"] and cov["avg_iou"] == rec["coverage_fitted"]["avg_iou"]
     # eval.py on that directory, without the flag: the anchors are with_anchor_shapes' closed form for those shapes
     a = E.parse_args(["--checkpoint_path", d])
-    found = E.anchor_shapes_for(a)
+    found = drivers.driver_anchor_shapes(a.anchor_shapes, a.checkpoint_path)
     assert anchors.same_shapes(found, shapes)
     mc, model = E.make_model(a.net, a.gpu, a.dtype, 1, found)
     plain = S.kitti_squeezeDet_config()
@@ -390,7 +390,7 @@ def test_drivers_end_to_end(tmp_path):
     del model
     # no flag and no file: the config's own anchors, as before
     b = E.parse_args(["--checkpoint_path", str(tmp_path / "elsewhere" / "model.ckpt-1.npz")])
-    assert E.anchor_shapes_for(b) is None
+    assert drivers.driver_anchor_shapes(b.anchor_shapes, b.checkpoint_path) is None
     assert np.array_equal(E.make_model(b.net, b.gpu, b.dtype, 1, None)[0].ANCHOR_BOX, plain.ANCHOR_BOX)
     # --resume with other shapes is refused; without the flag it runs on the recorded ones
     other = str(tmp_path / "other.json")

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from squeezedet_amd import ops, viz
+from squeezedet_amd import drivers, ops, viz
 from tests import draw_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -263,7 +263,7 @@ def test_demo_draw_gpu(tmp_path):
     got = np.asarray(Image.open(tmp_path / "out_sample.png"))
     a = D.parse_args(["--dtype", "fp32"])
     mc, model, dtype = D.make_model(a, 1)
-    x = ops.preprocess_bgr(torch.from_numpy(D.read_bgr(src)).to(model.device)[None], mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, dtype)
+    x = ops.preprocess_bgr(torch.from_numpy(drivers.read_bgr(src)).to(model.device)[None], mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, dtype)
     boxes, probs, cls = model.filter_prediction(*[t[0].cpu().numpy() for t in model.detect(x)])
     items = [R.box_item(b, D.CLS2CLR[mc.CLASS_NAMES[c]], "%s: (%.2f)" % (mc.CLASS_NAMES[c], float(p)))
              for b, p, c in zip(boxes, probs, cls) if float(p) > mc.PLOT_PROB_THRESH]

@@ -273,7 +273,7 @@ def test_eval_py_pascal_voc_run_once(voc_tree, tmp_path, capsys):
     assert not os.path.exists(os.path.join(det_dir, "error_analysis"))
     # the same rows into a second table
     a = E.parse_args(EVAL_ARGS + ["--data_path", voc_tree, "--eval_dir", out, "--synthetic_weights"])
-    mc, model = E.make_voc_model(a.net, a.gpu, a.dtype, a.batch_size, a.image_size)
+    mc, model = E.make_model(a.net, a.gpu, a.dtype, a.batch_size, None, a.image_size, a.dataset)
     assert tuple(mc.CLASS_NAMES) == VC.VOC20 and (mc.CLASSES, mc.HEAD_PAD_CLASSES) == (23, 3)
     data = V.load_voc(voc_tree, "2007", "trainval", mc)
     ev = V.VocEvaluator(mc, data.gt, model.device)

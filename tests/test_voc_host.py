@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import squeezedet_amd as S
-from squeezedet_amd import _lib, voc as V
+from squeezedet_amd import _lib, drivers, voc as V
 from squeezedet_amd import build as sqbuild
 from tests.golden import voc_ap_cases as VC
 
@@ -149,10 +149,10 @@ def test_drivers_accept_pascal_voc_and_refuse_other_datasets():
                 mod.parse_args(["--dataset", bad])
     with pytest.raises(SystemExit):
         T.parse_args(["--dataset", "PASCAL_VOC", "--net", "vgg16"])
-    tc = T.make_config("squeezeDet", [128, 256], "PASCAL_VOC")
+    tc = drivers.make_config("squeezeDet", [128, 256], "PASCAL_VOC")
     assert len(tc.CLASS_NAMES) == 20 and (tc.CLASSES, tc.HEAD_PAD_CLASSES) == (23, 3)        # the padded head (config.pad_head_classes)
-    assert T.make_config("squeezeDet", None, "PASCAL_VOC").ANCHORS == 24 * 78 * 9
-    assert T.make_config("squeezeDet", [128, 256]).CLASSES == 3
+    assert drivers.make_config("squeezeDet", None, "PASCAL_VOC").ANCHORS == 24 * 78 * 9
+    assert drivers.make_config("squeezeDet", [128, 256]).CLASSES == 3
     # --eval_tool / --visualize are KITTI-only: refused before anything is loaded
     for extra in (["--eval_tool", "/bin/true"], ["--visualize", "3"]):
         with pytest.raises(SystemExit, match="KITTI-only"):

@@ -13,61 +13,39 @@ printed twice, side by side: for the config's current shapes and for the fitted 
 train.py / eval.py / demo.py --anchor_shapes read: shapes, input size, dataset, image set, k, seed, mean IoU.
 """
 import argparse
-import importlib.util
 import os
 import sys
 
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from squeezedet_amd import drivers  # noqa: E402
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--dataset", default="KITTI", help="KITTI or PASCAL_VOC.")
-    ap.add_argument("--year", default="2007", help="PASCAL_VOC: the VOC<year> directory under --data_path")
-    ap.add_argument("--data_path", default="", help="Root directory of data")
-    ap.add_argument("--image_set", default="train", help="Can be train, trainval, val, or test")
-    ap.add_argument("--net", default="squeezeDet", choices=NETS, help="Neural net architecture (its config gives the input size and the grid).")
-    ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="network input size (default: the net's)")
+    drivers.add_dataset_args(ap, image_set_default="train")
+    drivers.add_model_args(ap, dtype_default=None)         # (--net: its config gives the input size and the grid)
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="the N seeded synthetic images of train.py --synthetic N")
     ap.add_argument("--k", type=int, default=9, help="anchor shapes per grid cell (the nets are built for 9)")
     ap.add_argument("--seed", type=int, default=0, help="seeds the initial centroids (and --synthetic, as train.py --seed does)")
     ap.add_argument("--restarts", type=int, default=8, help="independent k-means runs; the one of highest mean IoU wins")
     ap.add_argument("--max_iter", type=int, default=100, help="iterations per run")
-    ap.add_argument("--gpu", default="0", help="gpu id.")
     ap.add_argument("--out", default="anchors.json", help="the JSON file to write")
     a = ap.parse_args(argv)
-    if a.dataset not in ("KITTI", "PASCAL_VOC"):
+    if a.dataset not in drivers.DATASETS:           # (a usage error here; train.py and eval.py keep the reference's assert)
         ap.error("--dataset must be KITTI or PASCAL_VOC")
-    if a.dataset == "PASCAL_VOC" and a.net != "squeezeDet":
-        ap.error("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
+    drivers.check_dataset_args(ap, a)
     if a.k < 1 or a.restarts < 1 or a.max_iter < 1:
         ap.error("--k, --restarts and --max_iter must be positive")
     return a
 
 
-def _train_module():
-    spec = importlib.util.spec_from_file_location("_root_train", os.path.join(ROOT, "train.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def load_annotations(a, mc):
     """(rois, sizes [(height, width)], dataset label): annotations and image headers only."""
     if a.synthetic:
-        from squeezedet_amd.synthetic import synthetic_dataset
-        images, rois = synthetic_dataset(mc, int(a.synthetic), seed=300 + a.seed)       # train.py's load_dataset
+        images, rois = drivers.synthetic_data(mc, a.synthetic, a.seed)
         return rois, [im.shape[:2] for im in images], "synthetic-%d" % a.synthetic
     from PIL import Image
-    if a.dataset == "PASCAL_VOC":
-        from squeezedet_amd.voc import load_voc
-        data = load_voc(a.data_path, a.year, a.image_set, mc)
-    else:
-        from squeezedet_amd.kitti_ap import load_kitti
-        data = load_kitti(a.data_path, a.image_set, mc)
+    data = drivers.load_index(a.dataset, a.data_path, a.year, a.image_set, mc)
     sizes = []
     for p in data.image_paths:
         with Image.open(p) as im:                    # reads the header; the pixels are never decoded
@@ -79,7 +57,7 @@ def main(argv=None):
     a = parse_args(argv)
     import torch
     from squeezedet_amd import anchors, config
-    mc = _train_module().base_config(a.net, a.image_size, a.dataset)       # (before any head padding: the classes are the real ones)
+    mc = drivers.base_config(a.net, a.image_size, a.dataset)       # (before any head padding: the classes are the real ones)
     rois, sizes, label = load_annotations(a, mc)
     device = torch.device("cuda", int(a.gpu))
     wh = anchors.dataset_shapes(rois, sizes, mc)

@@ -35,24 +35,20 @@ import time
 
 import numpy as np
 
-NETS = ("squeezeDet", "squeezeDet+", "resnet50", "vgg16")
+from squeezedet_amd import drivers
+
 RESIDENT_BYTES = 4 << 30       # a dataset whose uint8 images fit this budget lives on the device (BatchReader resident=True)
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--dataset", default="KITTI", help="KITTI or PASCAL_VOC.")
-    ap.add_argument("--year", default="2007", help="PASCAL_VOC: the VOC<year> directory under --data_path")
-    ap.add_argument("--data_path", default="", help="Root directory of data")
-    ap.add_argument("--image_set", default="train", help="Can be train, trainval, val, or test")
+    drivers.add_dataset_args(ap, image_set_default="train")
+    drivers.add_model_args(ap, dtype_default="fp32")
     ap.add_argument("--train_dir", default="/tmp/squeezeDet/train", help="Directory where to write summaries and checkpoints.")
     ap.add_argument("--max_steps", type=int, default=1000000, help="Maximum number of batches to run.")
-    ap.add_argument("--net", default="squeezeDet", choices=NETS, help="Neural net architecture.")
     ap.add_argument("--pretrained_model_path", default="", help="Path to the pretrained model (.npz, or the backbone pickle).")
     ap.add_argument("--summary_step", type=int, default=10, help="Number of steps to save summary (0: never).")
     ap.add_argument("--checkpoint_step", type=int, default=1000, help="Number of steps to save a checkpoint.")
-    ap.add_argument("--gpu", default="0", help="gpu id.")
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "fp16"], help="fp32: the reference's; fp16: mixed precision")
     ap.add_argument("--batch_size", type=int, default=0, help="images per GPU per step (default: the config's BATCH_SIZE)")
     ap.add_argument("--seed", type=int, default=0, help="seeds the batch order, the augmentation, the dropout and --synthetic")
     ap.add_argument("--resume", action="store_true", help="continue from the newest checkpoint of --train_dir")
@@ -60,7 +56,6 @@ def parse_args(argv=None):
     ap.add_argument("--keep_checkpoints", type=int, default=0, help="keep only the newest N checkpoints (0: all)")
     ap.add_argument("--no_graph", action="store_true", help="eager steps only (no hipGraph replay)")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="train on N seeded synthetic KITTI-sized images")
-    ap.add_argument("--image_size", type=int, nargs=2, default=None, metavar=("H", "W"), help="network input size (default: the net's)")
     ap.add_argument("--loss_scale", type=float, default=1024.0, help="fp16: the initial loss scale")
     ap.add_argument("--image_summary", type=int, default=0, metavar="N",
                     help="at summary steps, write the first N images of the batch with ground truth and detections drawn (0: none)")
@@ -68,54 +63,17 @@ def parse_args(argv=None):
     ap.add_argument("--anchor_report", action="store_true",
                     help="write <train_dir>/anchor_coverage.json, how the anchors cover the training set, before the first step")
     a = ap.parse_args(argv)
-    assert a.dataset in ("KITTI", "PASCAL_VOC"), "Currently only supports KITTI dataset (and PASCAL_VOC)"
-    if a.dataset == "PASCAL_VOC" and a.net != "squeezeDet":
-        ap.error("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
+    drivers.check_dataset_args(ap, a)
     if a.resume and a.overwrite:
         ap.error("--resume and --overwrite exclude each other")
     return a
 
 
-def make_config(net, image_size=None, dataset="KITTI", anchor_shapes=None):
-    """The config of --net; anchor_shapes ([k,2], None: the config's own) go in before the head is padded."""
-    from squeezedet_amd import config
-    mc = base_config(net, image_size, dataset)
-    if anchor_shapes is not None:
-        mc = config.with_anchor_shapes(mc, anchor_shapes)
-    return config.pad_head_classes(mc) if dataset == "PASCAL_VOC" else mc
-
-
-def base_config(net, image_size, dataset):
-    import squeezedet_amd as S
-    from squeezedet_amd import config
-    if dataset == "PASCAL_VOC":
-        h, w = image_size if image_size is not None else (384, 1248)
-        return config.voc_squeezeDet_config_for_input(int(h), int(w))
-    if image_size is not None:
-        sized = {"squeezeDet": config.kitti_squeezeDet_config_for_input, "resnet50": config.kitti_res50_config_for_input,
-                 "vgg16": config.kitti_vgg16_config_for_input}
-        if net not in sized:
-            raise SystemExit("--image_size: no sized config for --net %s (squeezeDet, resnet50 and vgg16 have one)" % net)
-        return sized[net](int(image_size[0]), int(image_size[1]))
-    return {"squeezeDet": S.kitti_squeezeDet_config, "squeezeDet+": S.kitti_squeezeDetPlus_config, "resnet50": S.kitti_res50_config,
-            "vgg16": S.kitti_vgg16_config}[net]()
-
-
 def make_trainer(a, mc, local_rank=0):
     """(model, trainer) of --net in training mode."""
-    import torch
-    from squeezedet_amd import nets
-    from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer, VGG16ConvDetTrainer
     mc.IS_TRAINING = True
-    mc.LOAD_PRETRAINED_MODEL = False
     mc.PRETRAINED_MODEL_PATH = a.pretrained_model_path
-    if a.batch_size:
-        mc.BATCH_SIZE = int(a.batch_size)
-    # (SqueezeDetTrainer walks any conv / fire / pool chain: it trains SqueezeDet+ too, tests/test_gpu_train.py)
-    cls, trainer = {"squeezeDet": (nets.SqueezeDet, SqueezeDetTrainer), "squeezeDet+": (nets.SqueezeDetPlus, SqueezeDetTrainer),
-                    "resnet50": (nets.ResNet50ConvDet, ResNet50ConvDetTrainer), "vgg16": (nets.VGG16ConvDet, VGG16ConvDetTrainer)}[a.net]
-    model = cls(mc, gpu_id=str(local_rank), dtype=torch.float16 if a.dtype == "fp16" else torch.float32)
-    return model, trainer
+    return drivers.build_model(mc, a.net, str(local_rank), a.dtype, a.batch_size), drivers.trainer_class(a.net)
 
 
 def initial_params(a, model):
@@ -142,17 +100,9 @@ def _initial_params(a, model):
 def load_dataset(a, mc):
     """(images: list of uint8 BGR arrays, rois)."""
     if a.synthetic:
-        from squeezedet_amd.synthetic import synthetic_dataset
-        return synthetic_dataset(mc, int(a.synthetic), seed=300 + a.seed)
-    from PIL import Image
-    if a.dataset == "PASCAL_VOC":
-        from squeezedet_amd.voc import load_voc
-        data = load_voc(a.data_path, a.year, a.image_set, mc)
-    else:
-        from squeezedet_amd.kitti_ap import load_kitti
-        data = load_kitti(a.data_path, a.image_set, mc)
-    images = [np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[:, :, ::-1]) for p in data.image_paths]   # BGR, as cv2.imread
-    return images, data.rois
+        return drivers.synthetic_data(mc, a.synthetic, a.seed)
+    data = drivers.load_index(a.dataset, a.data_path, a.year, a.image_set, mc)
+    return [drivers.read_bgr(p) for p in data.image_paths], data.rois
 
 
 def write_model_metrics(path, model):
@@ -228,7 +178,7 @@ class Run:
         self.a, self.rank = a, rank
         self.dev = dev = torch.device("cuda", local_rank)
         self.anchor_shapes = resolve_anchor_shapes(a, resume_step)
-        self.mc = mc = make_config(a.net, a.image_size, a.dataset, self.anchor_shapes)
+        self.mc = mc = drivers.make_config(a.net, a.image_size, a.dataset, self.anchor_shapes)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)

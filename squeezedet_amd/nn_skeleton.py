@@ -8,13 +8,13 @@ executes them on the GPU.  There is no CPU execution path.
 """
 import collections
 import contextlib
-import os
 
 import numpy as np
 import torch
 
 from . import ops
 from ._lib import SqdetError
+from .serving import Serving
 
 
 class Node:
@@ -103,7 +103,7 @@ class ModelSkeleton:
         # serving lanes of detect_filter_pipelined(defer=True): BATCHES IN FLIGHT (see its docstring: the completion contract of a
         # deferred call depends on it).  None = SQDET_SERVE_LANES from the environment, default 2; the `lanes` argument overrides.
         self.serve_lanes = None
-        self._lanes, self._lane_next, self._lanes_checked, self._lane_check = None, 0, False, None
+        self.serving = Serving()                  # (pipes, lanes, the warm_up_lanes report: serving.py; allocates nothing)
         # measurement hook (bench.py's latency_ms_per_batch): a list -> every detect_filter_pipelined call appends
         # (lane, (event before the call's device work, event behind it)) on the stream the call runs on
         self._latency_probe = None
@@ -470,342 +470,25 @@ class ModelSkeleton:
                               use_plan=use_plan))
 
     def detect_filter_pipelined(self, images, to_host=False, defer=False, lanes=None):
-        """One step of the serving loop as a two-stage pipeline: the network forward runs on the caller's stream,
-        interpret_output + filter_prediction (a few dozen microseconds of latency-bound work on 32 workgroups)
-        run on a side HIP stream behind an event, so the NEXT batch's forward starts while this batch's boxes
-        are being decoded and suppressed.  Returns filter_prediction_batch's tuple; the tensors are complete once
-        flush_pipeline() has been called and the caller's stream (or the device) is synchronised.
-
-        Models with a native plan run it on TWO static sets of buffers (preds, det_*, outputs) used alternately, with
-        explicit events in both directions -- no allocation per step.  (Per-step torch allocations were the first
-        version: preds had to be record_stream'ed for the side stream, so the caching allocator could not reuse a
-        block until its event had completed; a host running a hundred steps ahead then asked for a hundred preds
-        buffers, i.e. hipMalloc inside the serving loop -- the same binary measured 0.77 or 1.0-1.2 ms per step from
-        one run to the next.)  The returned tensors are those of the slot: valid until the second-next call of the lane.
-        to_host=True: the filtered rows (<= TOP_N per image: boxes, probs, classes, anchor indices, counts) are also copied
-        to the slot's PINNED host buffers on the side stream -- what sess.run + filter_prediction hand the reference's
-        caller -- and those host tensors are returned.
-
-        defer=True (plans with the score epilogue and fire_chain launches: float16 SqueezeDet): the decode + filter of this
-        call is carried out BY THE NEXT CALL's forward (or by flush_pipeline()): it is handed to the plan as a post job
-        (sqdet_net_set_post_job) and runs in rider workgroups of that forward's fire_chain launches, one image per
-        otherwise idle CU, writing the rows straight into the slot's pinned host buffer -- no side stream, no events, no
-        extra launch.  Every launch of the forward fills the chip exactly once (persistent kernels with a static share of
-        tiles per workgroup), so side work on another stream costs a whole round of whatever it lands beside, and every
-        event ordering the two streams drains the forward's queue: measured 35 us per 0.49 ms step wherever the filter
-        launch was placed (side stream, same stream, with or without the score kernel, beside the stem or beside the
-        fire_chain launches) -- whereas the six fire_chain launches occupy 240 of the 256 CUs at batch 32.
-        (SQDET_POST_DEFER=signal: the previous form -- the side stream's launch gated on a mid-forward event.)
-
-        lanes (deferred calls on native plans; None = the model attribute `serve_lanes`, whose default is 2, or the environment's
-        SQDET_SERVE_LANES): the number of BATCHES IN FLIGHT.  Consecutive calls alternate between `lanes` serving lanes -- each its
-        own plan (workspace), HIP stream and pipeline slots, nothing ordering the lanes against each other -- so one lane's launch
-        ramps and tails are filled by the other lanes' launches (throughput +20 % at batch 32 with two; three pay at batch 1).
-        THE COMPLETION CONTRACT DEPENDS ON IT: the rows a deferred call returns are complete after the next call OF ITS LANE, i.e.
-        after `lanes` further calls -- or after flush_pipeline() -- plus a synchronisation of the caller's stream behind that
-        call; lanes=1 is the single-stream behaviour (complete after the NEXT call).  The result latency of a steady serving
-        loop is therefore `lanes` step times (bench.py reports it as latency_ms_per_batch)."""
-        with torch.cuda.device(self.device):
-            lane_set = self._serving_lanes(defer, lanes)
-            probe = self._latency_probe
-            if lane_set is None:
-                if probe is None:
-                    return self._detect_filter_pipelined(images, to_host, defer)
-                evs = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                evs[0].record()
-                out = self._detect_filter_pipelined(images, to_host, defer)
-                evs[1].record()
-                probe.append((0, evs))
-                return out
-            # A lane starts behind the caller's stream (the input may have been produced there).
-            if not self._lanes_checked:
-                self.warm_up_lanes(images, lanes=len(lane_set))
-            lane = lane_set[self._lane_next % len(lane_set)]
-            self._lane_next = (self._lane_next + 1) % len(lane_set)
-            cur = torch.cuda.current_stream()
-            lane["in_ev"].record(cur)
-            with torch.cuda.stream(lane["stream"]), self._lane_state(lane):
-                lane["stream"].wait_event(lane["in_ev"])
-                if probe is not None:
-                    evs = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    evs[0].record()
-                out = self._detect_filter_pipelined(images, to_host, defer)
-                if probe is not None:
-                    evs[1].record()
-                    probe.append((lane["which"], evs))
-                if isinstance(images, torch.Tensor) and images.is_cuda:
-                    images.record_stream(lane["stream"])
-            return out
+        """One step of the serving loop as a two-stage pipeline: the forward, then decode + filter of the batch on a side stream or
+        carried by the next call's forward.  The slots, `defer`, `lanes` and THE COMPLETION CONTRACT: serving.Serving.step."""
+        return self.serving.step(self, images, to_host, defer, lanes)
 
     def warm_up_lanes(self, images, lanes=None):
-        """Builds the serving lanes' plans for this batch and makes sure their HIP streams really run CONCURRENTLY; called by the
-        first deferred detect_filter_pipelined of a lane set (a caller that must not pay ~20-40 ms inside its first serving call,
-        or that captures streams, calls it ahead of time).  Which hardware queue a HIP stream lands on is the runtime's business,
-        and two streams that share one serialise -- measured on this stack: of ten streams of torch's pool, the pairs containing
-        one particular stream gave 0.468 ms per forward (= one stream) where every other pair gave 0.371.  For every lane k >= 1:
-        16 forwards alternating between lane 0's stream and lane k's are timed with HIP events against 16 on lane 0's stream
-        alone (median of three repetitions each, plans built and warmed on the lane streams first); a pair that gains less than
-        6 % has lane k's stream replaced (up to four candidates, the best kept).  Result: self._lane_check."""
-        with torch.cuda.device(self.device):
-            lane_set = self._serving_lanes(True, lanes)
-            self._lanes_checked = True
-            if lane_set is None or os.environ.get("SQDET_LANE_CHECK", "1") == "0":
-                return None
-            x = self._to_input(images)
-            B = int(x.shape[0])
-            cur = torch.cuda.current_stream()
-            plans, pre = [], []
-            for lane in lane_set:
-                lane["stream"].wait_stream(cur)
-                with torch.cuda.stream(lane["stream"]):
-                    plans.append(self._native_plan(B, lane["which"]))
-                    pre.append(torch.empty((B, plans[0].gh, plans[0].gw, plans[0].out_ch), dtype=self.dtype, device=self.device))
-            NF, REPS = 16, 3
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-            def timed(k, sb):
-                """ms per forward: NF forwards alternating between lane 0 (plan 0, its stream) and lane k's plan on stream sb"""
-                sa = lane_set[0]["stream"]
-                ts = []
-                for rep in range(REPS + 1):               # (first repetition: warm-up of streams / plans)
-                    torch.cuda.synchronize(self.device)
-                    e0.record(sa)
-                    if sb is not sa:
-                        sb.wait_event(e0)
-                    for i in range(NF):
-                        j, st = (0, sa) if i % 2 == 0 else (k, sb)
-                        with torch.cuda.stream(st):
-                            plans[j].forward(x, pre[j])
-                    if sb is not sa:
-                        sa.wait_stream(sb)
-                    e1.record(sa)
-                    e1.synchronize()
-                    ts.append(e0.elapsed_time(e1) / NF)
-                return float(np.median(ts[1:]))
-
-            single = timed(0, lane_set[0]["stream"])
-            report = dict(single_ms=single, forwards_per_sample=NF, repetitions=REPS, pairs=[])
-            for k in range(1, len(lane_set)):
-                best, best_t, cand = None, None, lane_set[k]["stream"]
-                for attempt in range(4):
-                    t = timed(k, cand)
-                    if best_t is None or t < best_t:
-                        best, best_t = cand, t
-                    if t < 0.94 * single:
-                        break
-                    cand = torch.cuda.Stream(device=self.device)
-                lane_set[k]["stream"] = best
-                report["pairs"].append(dict(lane=k, pair_ms=best_t, attempts=attempt + 1))
-            report["pair_ms"] = max(p["pair_ms"] for p in report["pairs"])
-            report["attempts"] = max(p["attempts"] for p in report["pairs"])
-            cur.wait_stream(lane_set[0]["stream"])
-            self._lane_check = report
-            return report
-
-    @contextlib.contextmanager
-    def _lane_state(self, lane):
-        """The pipeline state (_pipe, post_stream, _post_event, which plan) of `lane` installed for the duration of a call."""
-        saved = (getattr(self, "_pipe", None), getattr(self, "post_stream", None), getattr(self, "_post_event", None))
-        self._pipe, self.post_stream, self._post_event = lane["pipe"], lane["post_stream"], lane["post_event"]
-        self._lane_plan = lane["which"]
-        try:
-            yield
-        finally:
-            lane["pipe"], lane["post_stream"], lane["post_event"] = self._pipe, self.post_stream, self._post_event
-            self._lane_plan = 0
-            self._pipe, self.post_stream, self._post_event = saved
-
-    def _serving_lanes(self, defer, lanes=None):
-        """The serving lanes of detect_filter_pipelined (None: single-lane operation).  Used for deferred steps on native plans.
-        Count: the `lanes` argument, else the attribute serve_lanes (None = SQDET_SERVE_LANES from the environment, default 2).
-        At batch 32 three lanes are no better than two (0.396 against 0.390 ms per step); at batch 1, where a forward leaves most of
-        the chip idle, three give 11.1-11.8 k img/s against 8.3 k with two and four fall back to 8.4 k (bench.py's sqdet_sample_b1
-        config asks for three); SqueezeDet+ at batch 8 loses 11 % with three (1.147 against 1.018 ms).  A change of the count
-        flushes the old lanes first; the new set's streams are checked again at its first use (warm_up_lanes)."""
-        n = lanes if lanes is not None else self.serve_lanes
-        if n is None:
-            n = int(os.environ.get("SQDET_SERVE_LANES", "2"))
-        n = int(n)
-        if n < 1:
-            raise SqdetError("detect_filter_pipelined: lanes must be >= 1, got %r" % (n,))
-        if not defer or self.NATIVE_ARCH is None or n < 2:
-            if self._lanes is not None and defer and any(l["pipe"] is not None and l["pipe"].get("pending") is not None for l in self._lanes):
-                # the lane set holds pending rows of earlier multi-lane calls: carried out ONCE, ahead of the first single-lane call (the
-                # set is kept).  The single-lane pipe's own pending job is left alone -- it rides in this call's forward as ever.
-                with torch.cuda.device(self.device):
-                    self._flush_lane_set(torch.cuda.current_stream())
-            return None
-        if self._lanes is None or len(self._lanes) != n:
-            if self._lanes is not None:
-                self.flush_pipeline()
-            self._lanes = [dict(which=k, stream=torch.cuda.Stream(device=self.device), in_ev=torch.cuda.Event(), pipe=None,
-                                post_stream=None, post_event=None) for k in range(n)]
-            self._lane_next = 0
-            self._lanes_checked = False
-            self._lane_check = None
-        return self._lanes
+        """Builds the serving lanes' plans and checks that their HIP streams run concurrently (serving.Serving.warm_up)."""
+        return self.serving.warm_up(self, images, lanes)
 
     def flush_pipeline(self):
-        """Enqueues the side work of the last call(s) now (nothing to overlap it with) and makes the CALLER's stream wait for all of
-        it: every serving lane's stream AND every post-processing side stream (a lane's own, and the single-lane one).  After
-        flush_pipeline() a synchronisation of the caller's stream alone (torch.cuda.current_stream().synchronize()) is enough to
-        read every returned row, device or pinned host."""
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream()
-            self._flush_lane_set(cur)
-            self._flush_pipe(getattr(self, "_pipe", None))
-            if getattr(self, "post_stream", None) is not None:
-                cur.wait_stream(self.post_stream)
+        """Enqueues all pending side work and makes the CALLER's stream wait for it (serving.Serving.flush)."""
+        self.serving.flush(self)
 
-    def _flush_lane_set(self, cur):
-        """The serving lanes' half of flush_pipeline: every lane's pending side work enqueued on its own stream, `cur` waits for it."""
-        if self._lanes is None:
-            return
-        for lane in self._lanes:
-            with torch.cuda.stream(lane["stream"]), self._lane_state(lane):
-                self._flush_pipe(self._pipe)
-            cur.wait_stream(lane["stream"])
-            if lane["post_stream"] is not None:
-                cur.wait_stream(lane["post_stream"])
+    def _serving_lanes(self, defer, lanes=None):
+        return self.serving.lanes_for(self, defer, lanes)
 
-    def _flush_pipe(self, pipe):
-        if pipe is not None and pipe.get("pending") is not None:
-            s = pipe["pending"]
-            if s.get("ride"):       # same stream as the forward: stream order is all the synchronisation there is
-                cur = torch.cuda.current_stream()
-                s["fwd_done"].record(cur)
-                self._enqueue_post(s, None, stream=cur)
-            else:
-                self._enqueue_post(s, None)
-            pipe["pending"] = None
-
-    def _enqueue_post(self, s, gate, stream=None):
-        """Decode + filter + row copy of slot s on the side stream, behind its forward (and `gate`, an event of a later forward)."""
-        mc = self.mc
-        pstream = stream if stream is not None else (torch.cuda.current_stream() if os.environ.get("SQDET_POST_INLINE") == "1" else self.post_stream)
-        with torch.cuda.stream(pstream):
-            pstream.wait_event(s["fwd_done"])
-            if gate is not None:
-                pstream.wait_event(gate)
-            if s["fused_post"]:
-                # decode + top-N + NMS in one call (score kernel unless scored + filter kernel): boxes / classes are decoded for the selected anchors only
-                ops.detect_filter(s["preds"], self.anchors_f32(), mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT,
-                                  mc.EXP_THRESH, mc.TOP_N_DETECTION, mc.NMS_THRESH, scratch=s["det"][1], out=s["out"],
-                                  scores_ready=s["scored"], max_workgroups=s["post_wgs"] if gate is not None else 0)
-            else:
-                ops.interpret_output(s["preds"], self.anchors_f32(), mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH,
-                                     mc.IMAGE_HEIGHT, mc.EXP_THRESH, out=s["det"])
-                ops.filter_prediction(s["det"][0], s["det"][1], s["det"][2], mc.CLASSES, mc.TOP_N_DETECTION, mc.NMS_THRESH,
-                                      mc.PROB_THRESH, out=s["out"])
-            if s["to_host"]:
-                if s["host"] is None:
-                    s["host_flat"] = torch.empty(s["flat"].shape, dtype=torch.uint8).pin_memory()
-                    s["host"] = self._out_views(s["host_flat"])
-                ops.copy_to_pinned_host(s["flat"], s["host_flat"])      # all five outputs in one launch (never blocks the host)
-            s["post_done"].record(pstream)
-
-    def _detect_filter_pipelined(self, images, to_host, defer=False):
-        mc = self.mc
-        if getattr(self, "post_stream", None) is None:
-            # high priority: the two small post-processing kernels are dispatched as soon as CUs free up at a kernel
-            # boundary of the forward instead of waiting for its queue to drain
-            self.post_stream = torch.cuda.Stream(device=self.device, priority=int(os.environ.get("SQDET_POST_PRIORITY", "-1")))
-            self._post_event = torch.cuda.Event()
-            self._pipe = None
-        cur = torch.cuda.current_stream()
-        if self.NATIVE_ARCH is not None:
-            x = self._to_input(images)
-            B = int(x.shape[0])
-            plan = self._native_plan(B, getattr(self, "_lane_plan", 0))
-            if self._pipe is None or self._pipe["batch"] != B:
-                self.flush_pipeline()
-                A = mc.ANCHORS
-                M = mc.TOP_N_DETECTION if 0 < mc.TOP_N_DETECTION < A else min(A, 1024)
-                f32, dev = torch.float32, self.device
-                def out_views(flat):
-                    """(boxes [B,M,4] f32, probs [B,M] f32, cls [B,M] i32, anchor index [B,M] i32, count [B] i32) as views of ONE
-                    byte buffer, so the filtered rows leave the device in a single copy"""
-                    o, views = 0, []
-                    for shape, dt in (((B, M, 4), f32), ((B, M), f32), ((B, M), torch.int32), ((B, M), torch.int32), ((B,), torch.int32)):
-                        nb = int(np.prod(shape)) * 4
-                        views.append(flat[o:o + nb].view(dt).view(shape))
-                        o += (nb + 255) // 256 * 256
-                    return tuple(views)
-                out_bytes = sum((int(np.prod(sh)) * 4 + 255) // 256 * 256 for sh in ((B, M, 4), (B, M), (B, M), (B, M), (B,)))
-
-                def mk():
-                    flat = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
-                    sig = torch.cuda.Event()
-                    sig.record(cur)                    # (creates the handle sqdet_net_set_signal is given)
-                    return dict(preds=torch.empty((B, plan.gh, plan.gw, plan.out_ch), dtype=self.dtype, device=dev),
-                                det=(torch.empty((B, A, 4), dtype=f32, device=dev), torch.empty((B, A), dtype=f32, device=dev),
-                                     torch.empty((B, A), dtype=torch.int64, device=dev)),
-                                flat=flat, out=out_views(flat), host_flat=None, host=None,
-                                fwd_done=torch.cuda.Event(), post_done=torch.cuda.Event(), sig=sig, used=False)
-                self._out_views = out_views
-                self._pipe = dict(batch=B, slots=[mk(), mk()], k=0, pending=None)
-            pipe = self._pipe
-            s = pipe["slots"][pipe["k"] & 1]
-            pipe["k"] += 1
-            if s["used"]:
-                cur.wait_event(s["post_done"])          # the side stream has finished reading this slot's preds
-            fused_post = ops.detect_filter_supported(mc.ANCHORS, mc.TOP_N_DETECTION) and os.environ.get("SQDET_SPLIT_POST") != "1"
-            # the score half of interpret_output rides in the ConvDet launch's epilogue where the plan has it (float16
-            # SqueezeDet head): what is left for the side stream is ONE filter launch + the row copy
-            # (SQDET_SCORE_EPILOGUE=0: the stand-alone score kernel on the side stream, for A/B)
-            scored = fused_post and plan.scores_supported() and os.environ.get("SQDET_SCORE_EPILOGUE") != "0"
-            mode = os.environ.get("SQDET_POST_DEFER", "ride")
-            ride = bool(defer and scored and mode == "ride" and plan.rider_capacity() >= B)
-            ov = plan.overlap_layer() if (defer and scored and mode == "signal") else -1
-            deferred = ov >= 0
-            s.update(fused_post=fused_post, scored=scored, to_host=to_host, ride=ride,
-                     post_wgs=int(os.environ.get("SQDET_POST_WGS", "16")) if B > 16 else 0)
-            if to_host and s["host"] is None:
-                s["host_flat"] = torch.empty(s["flat"].shape, dtype=torch.uint8).pin_memory()
-                s["host"] = self._out_views(s["host_flat"])
-            prev = pipe["pending"]
-            if ride:
-                # everything on the caller's stream: the previous call's decode + filter rides in this forward's fire_chain
-                # launches and writes its rows where the caller reads them (no post_done wait above either: a slot's preds /
-                # scores are next overwritten by the ConvDet launch of the second-next forward, behind its riders in stream order)
-                if prev is not None:
-                    if prev.get("ride"):
-                        plan.set_post_job(prev["preds"], prev["det"][1], self.anchors_f32(), prev["host"] if prev["to_host"] else prev["out"],
-                                          mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT, mc.EXP_THRESH,
-                                          mc.TOP_N_DETECTION, mc.NMS_THRESH)
-                    else:
-                        self._enqueue_post(prev, None)
-                plan.set_signal(-1, None)
-                plan.forward(x, s["preds"], scores=s["det"][1])
-                pipe["pending"] = s
-                s["used"] = False                       # (no side-stream reader to wait for)
-                return s["host"] if to_host else s["out"]
-            plan.set_signal(ov, s["sig"] if (deferred and prev is not None) else None)
-            plan.forward(x, s["preds"], scores=s["det"][1] if scored else None)
-            s["fwd_done"].record(cur)
-            if prev is not None:                        # the previous call's side work: beside THIS forward's fire_chain launches
-                if prev.get("ride"):
-                    self._enqueue_post(prev, None, stream=cur)
-                else:
-                    self._enqueue_post(prev, s["sig"] if deferred else None)
-                pipe["pending"] = None
-            if deferred:
-                pipe["pending"] = s
-            else:
-                self._enqueue_post(s, None)
-            s["used"] = True
-            return s["host"] if to_host else s["out"]
-        (preds,) = self.run([self.preds], {self.image_input: images})
-        self._post_event.record(cur)
-        with torch.cuda.stream(self.post_stream):
-            self.post_stream.wait_event(self._post_event)
-            boxes, probs, cls = ops.interpret_output(preds, self.anchors_f32(), mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH,
-                                                     mc.IMAGE_HEIGHT, mc.EXP_THRESH)[:3]
-            out = self.filter_prediction_batch(boxes, probs, cls)
-            preds.record_stream(self.post_stream)      # the allocator must not hand preds' memory out before the side stream is done
-            if to_host:
-                out = tuple(t_.to("cpu", non_blocking=True) for t_ in out)
-        return out
+    # read-only views of the serving state: the lane set, warm_up_lanes' report (bench.py), the single-lane pipe's side stream
+    _lanes = property(lambda self: self.serving.lanes)
+    _lane_check = property(lambda self: self.serving.lane_check)
+    post_stream = property(lambda self: self.serving.pipe.post_stream)
 
     # ------------------------------------------------------------------ filter_prediction
     def filter_prediction_batch(self, det_boxes, det_probs, det_class, max_out=None):

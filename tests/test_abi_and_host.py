@@ -329,26 +329,115 @@ def test_bench_rocprof_launch_ms_reads_only_a_fingerprinted_profile(tmp_path, mo
     assert bench.rocprof_launch_ms("missing.json", "conv12") is None
 
 
-def test_serving_lane_state_is_swapped_and_restored():
-    """ModelSkeleton._lane_state (the two-batches-in-flight serving loop): the pipeline state of a lane is installed for the duration
-    of a call and written back, the single-lane state is restored afterwards -- also when the call raises."""
-    from squeezedet_amd.nn_skeleton import ModelSkeleton
+@pytest.mark.parametrize("B,M", [(1, 64), (5, 64), (32, 1024)])
+def test_serving_out_layout(B, M):
+    """serving.out_layout: the five filtered-row tensors as views of one byte buffer -- shapes and dtypes, 256-byte-aligned offsets,
+    no two views sharing a byte, and as many bytes as the sum of the fields' sizes each rounded up to 256."""
+    from squeezedet_amd import serving
+    nbytes, views = serving.out_layout(B, M)
+    want = [((B, M, 4), torch.float32), ((B, M), torch.float32), ((B, M), torch.int32), ((B, M), torch.int32), ((B,), torch.int32)]
+    assert nbytes == sum((int(np.prod(sh)) * 4 + 255) // 256 * 256 for sh, _ in want)
+    flat = torch.zeros(nbytes, dtype=torch.uint8)
+    vs = views(flat)
+    assert [(tuple(v.shape), v.dtype) for v in vs] == want
+    spans = [(v.data_ptr() - flat.data_ptr(), v.data_ptr() - flat.data_ptr() + v.numel() * 4) for v in vs]
+    assert all(a % 256 == 0 for a, _ in spans) and spans[0][0] == 0 and spans[-1][1] <= nbytes
+    assert all(e0 <= a1 for (_, e0), (a1, _) in zip(spans, spans[1:]))
+    for k, v in enumerate(vs):                                  # views of `flat` itself: a write lands in the buffer, in that view only
+        v.fill_(k + 1)
+    assert all(bool((v == k + 1).all()) for k, v in enumerate(vs))
+    assert int((flat != 0).sum()) >= sum(v.numel() for v in vs)
 
-    class M(ModelSkeleton):
-        def __init__(self):          # (no device, no graph: only the attributes _lane_state touches)
-            self._pipe, self.post_stream, self._post_event = "P0", "S0", "E0"
-    m = M()
-    lane = dict(which=1, pipe=None, post_stream=None, post_event=None)
-    with m._lane_state(lane):
-        assert (m._pipe, m.post_stream, m._post_event, m._lane_plan) == (None, None, None, 1)
-        m._pipe, m.post_stream, m._post_event = "P1", "S1", "E1"           # what the first call of a lane creates
-    assert (lane["pipe"], lane["post_stream"], lane["post_event"]) == ("P1", "S1", "E1")
-    assert (m._pipe, m.post_stream, m._post_event, m._lane_plan) == ("P0", "S0", "E0", 0)
-    with pytest.raises(RuntimeError):
-        with m._lane_state(lane):
-            m._pipe = "P2"
-            raise RuntimeError("boom")
-    assert lane["pipe"] == "P2" and m._pipe == "P0" and m._lane_plan == 0
+
+class _FakeHandle:
+    """Stands in for torch.cuda.Stream / Event where a serving object is exercised without a device: records what is called."""
+    log = []
+
+    def __init__(self, *a, **kw):
+        _FakeHandle.log.append(("new", self))
+
+    def record(self, *a):
+        _FakeHandle.log.append(("record", self))
+
+
+def test_serving_state_is_per_pipe_and_off_the_model(monkeypatch):
+    """What replaced the swap of pipeline state through model attributes: every pipe (the single-lane one, each lane's) holds its own
+    state, no serving object refers to the model (it is passed to each call, nothing is written to it), and a lane set leaves the
+    single-lane pipe alone."""
+    import types
+    from squeezedet_amd import serving
+    sv = serving.Serving()
+    assert sv.lanes is None and sv.lane_check is None and not sv.lanes_checked and sv.lane_next == 0
+    a, b = serving.Pipe(0), serving.Pipe(1)
+    a.pending, a.batch, a.post_stream, a.k = "S", 4, "stream-a", 3
+    assert (b.which, b.pending, b.batch, b.post_stream, b.post_event, b.slots, b.k) == (1, None, None, None, None, None, 0)
+    assert (a.which, sv.pipe.which, sv.pipe.pending, sv.pipe.post_stream) == (0, 0, None, None)
+    # a lane set (streams and events faked: no device here)
+    monkeypatch.setattr(torch.cuda, "Stream", _FakeHandle)
+    monkeypatch.setattr(torch.cuda, "Event", _FakeHandle)
+    monkeypatch.delenv("SQDET_SERVE_LANES", raising=False)
+    model = types.SimpleNamespace(serve_lanes=None, NATIVE_ARCH=0, device=torch.device("cpu"))
+    before = dict(vars(model))
+    single = sv.pipe
+    assert sv.lanes_for(model, False) is None and sv.lanes_for(model, True, 1) is None and sv.lanes is None     # single-lane operation: no lane set
+    lanes = sv.lanes_for(model, True)                           # (the default count: 2)
+    assert len(lanes) == 2 and sv.lanes_for(model, True, 2) is lanes and [ln.which for ln in lanes] == [0, 1]
+    assert all(ln["stream"] is ln.stream and ln.pipe.which == ln.which for ln in lanes)
+    assert len({id(p) for p in [single] + [ln.pipe for ln in lanes]}) == 3 and lanes[0].stream is not lanes[1].stream
+    lanes[1].pipe.post_stream, lanes[1].pipe.batch = "stream-1", 32
+    assert (lanes[0].pipe.post_stream, lanes[0].pipe.batch, single.post_stream, single.batch) == (None, None, None, None)
+    assert sv.pipe is single and vars(model) == before
+    for obj in [sv, single] + lanes + [ln.pipe for ln in lanes]:            # no reference back to the model: no cycle through it
+        state = vars(obj).values() if hasattr(obj, "__dict__") else [getattr(obj, n) for n in obj.__slots__]
+        assert all(v is not model for v in state)
+
+
+def test_serving_rejects_a_lane_count_below_one_before_creating_streams(monkeypatch):
+    import types
+    from squeezedet_amd import serving
+
+    def no_stream(*a, **kw):
+        raise AssertionError("a stream was created")
+    monkeypatch.setattr(torch.cuda, "Stream", no_stream)
+    monkeypatch.setenv("SQDET_SERVE_LANES", "0")
+    for serve_lanes, lanes in ((None, 0), (0, None), (None, None), (2, -1)):
+        sv = serving.Serving()
+        with pytest.raises(_lib.SqdetError, match="lanes must be >= 1"):
+            sv.lanes_for(types.SimpleNamespace(serve_lanes=serve_lanes, NATIVE_ARCH=0, device=torch.device("cpu")), True, lanes)
+        assert sv.lanes is None
+
+
+def test_serving_knobs_are_listed_and_read_at_every_use(monkeypatch):
+    from squeezedet_amd import serving
+    assert len(serving.KNOBS) == 8
+    for name, default in serving.KNOBS.items():
+        monkeypatch.delenv(name, raising=False)
+        assert serving.knob(name) == default
+        monkeypatch.setenv(name, "7")
+        assert serving.knob(name) == "7"                        # (not cached)
+    with pytest.raises(KeyError):                               # a knob that is not in the table cannot be read
+        serving.knob("SQDET_NO_SUCH_KNOB")
+
+
+def test_serving_latency_probe_entries(monkeypatch):
+    """model._latency_probe as bench.py's batch_latency reads it: one (lane index, (event before, event after)) per call, both events
+    recorded around the call; without a probe list the call is made and nothing else."""
+    from squeezedet_amd import serving
+    monkeypatch.setattr(torch.cuda, "Event", _FakeHandle)
+    monkeypatch.setattr(_FakeHandle, "log", [])
+
+    def call(a, b):
+        _FakeHandle.log.append(("call", (a, b)))
+        return a + b
+    assert serving._probed(None, 0, call, 1, 2) == 3 and _FakeHandle.log == [("call", (1, 2))]
+    del _FakeHandle.log[:]
+    probe = []
+    assert serving._probed(probe, 2, call, 3, 4) == 7
+    (which, evs), = probe
+    assert which == 2 and isinstance(evs, tuple) and len(evs) == 2 and evs[0] is not evs[1]
+    assert _FakeHandle.log[-3:] == [("record", evs[0]), ("call", (3, 4)), ("record", evs[1])]
+    for i, (w, e) in enumerate(probe):                          # (the loop of bench.batch_latency)
+        assert [e2 for (w2, e2) in probe[i + 1:] if w2 == w] == []
 
 
 def test_tools_and_scripts_parse():

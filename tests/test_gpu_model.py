@@ -300,6 +300,73 @@ def test_deferred_pipelined_step_equals_sequential(mode, batch, lanes, monkeypat
                 assert torch.equal(got[t][i, :n[i]], want[t][i, :n[i]].cpu())
 
 
+def test_deferred_step_across_lane_count_and_batch_changes(monkeypatch):
+    """The transitions bench.py performs between its passes, in ONE sequence in which the test never synchronises the device
+    (warm_up_lanes does, inside the first call of the two-lane and of the three-lane set, ahead of that call's work): serve_lanes 2 -> 1
+    (the two-lane set's pending rows are carried out once, ahead of the first one-lane call), 1 -> lanes=3 (a new lane set: everything
+    pending is flushed first), then a batch-1 call inside a lane of the three (that lane flushes every lane), then flush_pipeline().
+    Every call's rows are read where the completion contract says they are complete -- a steady multi-lane call after the next call
+    of its lane + a synchronisation of THAT LANE's stream; a call ahead of a switch after the first call behind it, a one-lane call
+    after the next call, the last ones after the flush: + a synchronisation of the caller's stream -- and must equal
+    detect -> filter_prediction_batch bitwise."""
+    for name in ("SQDET_POST_DEFER", "SQDET_SERVE_LANES", "SQDET_LANE_CHECK"):     # the default path: riders, the lane stream check
+        monkeypatch.delenv(name, raising=False)
+    m, mc, params, storage = _model("squeezeDet", torch.float16, 2, (375, 1242))
+    xs = [O.synthetic_images(2, 375, 1242, seed=s, storage=storage).to(DEV, torch.float16) for s in (31, 32, 33)]
+    x1 = xs[1][:1].contiguous()
+
+    def sequential(x):
+        b, p, c = m.detect(x)
+        return [t.clone() for t in m.filter_prediction_batch(b, p, c)]
+    want1 = sequential(x1)
+    seq = [sequential(x) for x in xs]
+    torch.cuda.synchronize()
+    plan = m._native_plan(2)
+    assert plan.scores_supported() and plan.rider_capacity() >= 2
+    hist, got = [], {}
+
+    def call(x, **kw):
+        hist.append(m.detect_filter_pipelined(x, to_host=True, defer=True, **kw))
+
+    def read(*calls):
+        for k in calls:
+            got[k] = [t.clone() for t in hist[k]]
+
+    def lane_stream(k, n):
+        return m._serving_lanes(True, n)[k]["stream"]
+
+    cur = torch.cuda.current_stream()
+    m.serve_lanes = 2
+    for i in range(3):                                          # calls 0-2: lanes 0, 1, 0
+        call(xs[i % 3])
+    lane_stream(0, 2).synchronize()
+    read(0)                                                     # carried by call 2, the next of lane 0
+    m.serve_lanes = 1
+    for i in range(3, 6):                                       # calls 3-5 on the caller's stream
+        call(xs[i % 3])
+        cur.synchronize()
+        read(*((1, 2) if i == 3 else (i - 1,)))                 # call 3 flushed the two lanes ahead of itself; then: the previous call
+    for i in range(6, 10):                                      # calls 6-9: lanes 0, 1, 2, 0 of a NEW set of three
+        call(xs[i % 3], lanes=3)
+        if i == 6:
+            cur.synchronize()
+            read(5)                                             # the one-lane pipe's pending rows: flushed with the old set
+    lane_stream(0, 3).synchronize()
+    read(6)                                                     # carried by call 9
+    call(x1, lanes=3)                                           # call 10: lane 1 at batch 1 -- rebuilds its pipe, flushes every lane
+    m.flush_pipeline()
+    cur.synchronize()
+    read(7, 8, 9, 10)
+    assert sorted(got) == list(range(11))
+    for k in range(11):
+        want, batch = (want1, 1) if k == 10 else (seq[k % 3], 2)
+        n = want[4].cpu().numpy()
+        assert np.array_equal(got[k][4].numpy(), n) and (n >= 1).all(), "call %d" % k
+        for i in range(batch):
+            for t in range(4):
+                assert torch.equal(got[k][t][i, :n[i]], want[t][i, :n[i]].cpu()), "call %d image %d output %d" % (k, i, t)
+
+
 @pytest.mark.parametrize("arch,dtype,batch", [("squeezeDet", torch.float32, 3), ("squeezeDet+", torch.float16, 8)], ids=["sqdet-fp32", "plus-fp16-b8"])
 def test_deferred_step_on_plans_without_riders_is_complete_after_flush(arch, dtype, batch):
     """Plans that cannot carry riders (float32 SqueezeDet; SqueezeDet+, which has no fire_chain launches -- BASELINE configs[3],
@@ -318,7 +385,7 @@ def test_deferred_step_on_plans_without_riders_is_complete_after_flush(arch, dty
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):                               # a caller on its own stream
         hist = [m.detect_filter_pipelined(x, to_host=True, defer=True) for x in xs]        # (default lane count: 2)
-        assert m._lanes is not None and len(m._lanes) == 2 and all(ln["post_stream"] is not None for ln in m._lanes)
+        assert m._lanes is not None and len(m._lanes) == 2 and all(ln.pipe.post_stream is not None for ln in m._lanes)
         m.flush_pipeline()
         side.synchronize()                                      # NOT a device-wide synchronize
         outs = [[t.clone() for t in out] for out in hist[-2:]]  # (slot reuse: the rows of the last `lanes` x 2 calls are live)
@@ -361,13 +428,13 @@ def test_pipelined_default_path_preds_vs_oracle_random_weights():
     plain = m.run([m.preds], {m.image_input: xd})[0]
     torch.cuda.synchronize()
     for lane in m._lanes:
-        used = [s for s in lane["pipe"]["slots"] if s.get("ride")]
+        used = [s for s in lane.pipe.slots if s.ride]
         assert len(used) == 1
-        preds = used[0]["preds"]
+        preds = used[0].preds
         assert torch.equal(preds, plain)
         for i in (0, 17):
             ref = O.forward("squeezeDet", params, x[i:i + 1], "fp16")
-            _check_layers(preds[i:i + 1], ref, torch.float16, "preds[%d] (pipelined, lane %d)" % (i, lane["which"]))
+            _check_layers(preds[i:i + 1], ref, torch.float16, "preds[%d] (pipelined, lane %d)" % (i, lane.which))
 
 
 def test_post_job_riders_equal_the_filter_launch():

@@ -47,6 +47,9 @@ const char* sqdet_last_error(void);
  * fuse, 3 = no streaming kernel, 4 = fire modules and the pools behind them stay apart, 5 = no fire-module chains, 6 = chains on
  * the late (small) maps only, 7 = a run's first module as squeeze conv + chain launch instead of one streaming launch,
  * 8 = no streaming expand + next-squeeze launches (a pooled module then ends its run).
+ * "stem_algo": which kernel runs the fused conv1 + pool1 launch: 0 = the fastest that takes the shape (default), 2 = the strip
+ * kernel only (no stem + squeeze launch), 3 = the persistent strip-lane kernel, then the strip kernel (propagates NaN / Inf pixels
+ * like conv -> pool).  Any other value: SQDET_EINVAL, the option keeps its value.
  * "conv_pool": 1 = a 3x3 conv and the 2x2/s2 SAME max-pool behind it are one launch wherever the tile kernel takes the shape
  * (default), 0 = never (plans created afterwards and sqdet_conv2d_maxpool2_*). */
 int sqdet_set_option(const char* name, int value);

@@ -446,6 +446,9 @@ extern "C" int sqdet_set_option(const char* name, int value) {
     set_conv_algo(value);
     return SQDET_OK;
   }
+  if (!strcmp(name, "stem_algo")) {
+    SQDET_REQUIRE(value == 0 || value == 2 || value == 3, "set_option: stem_algo must be 0 (auto), 2 (strip kernel only) or 3 (persistent, then strip kernel)");
+  }
   for (int i = 0; i < kNumTune; ++i) {
     if (!strcmp(name, kTuneNames[i])) {
       g_tune[i] = value;

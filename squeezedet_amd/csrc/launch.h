@@ -16,7 +16,9 @@ struct ConvArgs;  // conv_common.h
 int conv_algo();
 // experiment knobs set through sqdet_set_option (0 = built-in heuristic)
 // fire_fuse: 0 / 1 = a fire module is one fused launch wherever a fused kernel takes it (the default since round 5), 2 = never,
-// 10 = the round-1..4 rule (only maps of <= 100 k pixels); stem_algo: 0 phase kernel (stem4.hip), else persistent strip-lane kernel (stem3.hip), else strip kernel (in-register pool), whichever is eligible first; 3 skips the phase kernel; 2 strip kernel only
+// 10 = the round-1..4 rule (only maps of <= 100 k pixels)
+// stem_algo (0, 2 or 3; sqdet_set_option rejects anything else): 0 = the first eligible of phase kernel (stem4.hip), persistent strip-lane
+// kernel (stem3.hip), 7x7 kernel (stem5.hip), strip kernel (stem2.hip); 3 = persistent, then strip kernel only; 2 = strip kernel only
 // conv_pool: 1 (the default) = a 3x3 conv followed by a 2x2/s2 SAME max-pool is one launch of conv3x3_tile's POOL2 form wherever it
 // takes the shape (plans and sqdet_conv2d_maxpool2_*), 0 = never
 // g1_wr / g1_mbw / g1_ntw: conv1x1_pipe's wave layout (waves along the pixel blocks: 1, 2, 4), pixel blocks per wave (2, 4, 8) and cout tiles per wave -- tools/g1_sweep.py

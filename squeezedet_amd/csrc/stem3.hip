@@ -38,13 +38,11 @@
 namespace sqdet {
 namespace {
 
-constexpr int QPR = 4;                    // pooled rows per tile
-constexpr int QSP = 7;                    // pooled columns per wave strip
+// (QPR = 4 pooled rows per tile, QSP = 7 pooled columns per wave strip, QRP = 44 16-byte pieces fetched per row: stem.h)
 constexpr int QCR = 2 * QPR + 1;          // conv rows under the tile (13)
 constexpr int QCC = 4 * 2 * QSP + 2;      // conv columns under the tile (58)
 constexpr int QTR = 2 * (QCR - 1) + 3;    // staged input rows (27)
 constexpr int QPB = 196 * 4;              // LDS row pitch in bytes
-constexpr int QRP = 44;                   // 16-byte pieces fetched per row (704 B >= 117 * 3 * 2)
 constexpr int QPCS = QTR * QRP;           // pieces per tile (1188)
 constexpr int QNIT = (QPCS + 255) / 256;  // fetch rounds per thread (5)
 constexpr int QBIAS = QTR * QPB;          // LDS offset of the 64 float32 biases
@@ -313,18 +311,13 @@ __global__ __launch_bounds__(256, 4) void stem_pers(StemArgs a, int ntiles, int 
 
 }  // namespace
 
-// fp16, 3x3 / 64 couts, even W and even left pad (dword-aligned patch rows), one image below 2 GiB.
+// The shapes of stem_pers_shape (stem.hip), at least two 44-piece patches wide.
 int stem_pers_launch(StemArgs a, int k, int dtype, hipStream_t st, bool* handled) {
   *handled = false;
-  if (dtype != SQDET_F16 || k != 3 || a.Cout != 64) return SQDET_OK;
-  if (a.W % 2 != 0 || a.plc % 2 != 0 || a.y_cstride % 8 != 0 || a.y_coffset % 8 != 0) return SQDET_OK;
-  if ((size_t)a.H * a.W * 6 >= (1ull << 31) || a.W * 6 < 2 * QRP * 16) return SQDET_OK;
-  if ((size_t)a.N * a.Hp * a.Wp * a.y_cstride * 2 >= (1ull << 31)) return SQDET_OK;
+  if (!stem_pers_shape(a, k, dtype, QRP, QPR, 4 * QSP)) return SQDET_OK;
   a.tiles_x = (a.Wp + 4 * QSP - 1) / (4 * QSP);
   a.tiles_y = (a.Hp + QPR - 1) / QPR;
-  const long nt = (long)a.N * a.tiles_x * a.tiles_y;
-  if (nt >= (1l << 30)) return SQDET_OK;
-  const int ntiles = (int)nt;
+  const int ntiles = a.N * a.tiles_x * a.tiles_y;
   const int per_xcd = (ntiles + 7) / 8;
   int grid = 1024;                                                   // 4 workgroups per CU, a multiple of 8
   if (per_xcd < grid / 8) grid = per_xcd * 8;

@@ -49,6 +49,73 @@ def test_argument_validation_returns_codes(lib):
     assert lib.sqdet_conv_packed_bytes(0, 3, 3, 1) == 0
 
 
+def test_stem_algo_option_takes_three_values(lib):
+    """sqdet_set_option("stem_algo", v): 0 (automatic), 2 (strip kernel only) and 3 (persistent, then strip kernel) are accepted;
+    every other value is an invalid argument with a message and leaves the stored value alone."""
+    try:
+        for v in (0, 2, 3):
+            assert lib.sqdet_set_option(b"stem_algo", v) == 0
+        assert lib.sqdet_set_option(b"stem_algo", 2) == 0
+        shape = (375, 1242, 64, 3, 0, 0, 16, _lib.F16, 1)
+        for v in (-1, 1, 4, 5, 6, 7, 8, 9):
+            assert lib.sqdet_set_option(b"stem_algo", v) == -1, v
+            assert b"stem_algo" in lib.sqdet_last_error()
+            assert lib.sqdet_stem_conv_pool_squeeze_supported(*shape) == 0      # still 2: no stem + squeeze launch
+        assert lib.sqdet_set_option(b"stem_algo", 0) == 0
+        assert lib.sqdet_stem_conv_pool_squeeze_supported(*shape) == 1
+    finally:
+        lib.sqdet_set_option(b"stem_algo", 0)
+
+
+# (h, w, cout, k, conv_pad, pool_pad, next_s, dtype, n) -> the answer under "stem_algo" 0, 2, 3.  SAME = 0, VALID = 1; F16 = 1, F32 = 0.
+STEM_SQUEEZE_SUPPORTED = [
+    ((375, 234, 64, 3, 0, 0, 16, 1, 1), (0, 0, 0)),          # below stem_pers's two patches (235)
+    ((375, 234, 64, 3, 1, 0, 16, 1, 1), (0, 0, 0)),
+    ((375, 235, 64, 3, 0, 0, 16, 1, 1), (0, 0, 0)),          # odd width (SAME: odd left pad too)
+    ((375, 235, 64, 3, 1, 0, 16, 1, 1), (0, 0, 0)),
+    ((375, 236, 64, 3, 0, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 236, 64, 3, 1, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 522, 64, 3, 0, 0, 16, 1, 1), (1, 0, 1)),          # around the phase kernel's bound (523): stem_pers takes it
+    ((375, 522, 64, 3, 1, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 523, 64, 3, 0, 0, 16, 1, 1), (0, 0, 0)),
+    ((375, 523, 64, 3, 1, 0, 16, 1, 1), (0, 0, 0)),
+    ((375, 524, 64, 3, 0, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 524, 64, 3, 1, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 1241, 64, 3, 0, 0, 16, 1, 1), (0, 0, 0)),
+    ((375, 1241, 64, 3, 1, 0, 16, 1, 1), (0, 0, 0)),
+    ((375, 1242, 64, 3, 0, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 1242, 64, 3, 1, 0, 16, 1, 1), (1, 0, 1)),
+    ((375, 1242, 64, 3, 0, 1, 16, 1, 1), (1, 0, 1)),
+    ((375, 1242, 64, 3, 1, 1, 16, 1, 32), (1, 0, 1)),
+    ((375, 1242, 64, 3, 0, 0, 32, 1, 1), (0, 0, 0)),         # next_s 32
+    ((375, 1242, 96, 3, 0, 0, 16, 1, 1), (0, 0, 0)),         # 96 couts
+    ((375, 1242, 64, 7, 0, 0, 16, 1, 1), (0, 0, 0)),         # 7x7
+    ((375, 1242, 96, 7, 1, 1, 16, 1, 1), (0, 0, 0)),
+    ((375, 1242, 64, 3, 0, 0, 16, 0, 1), (0, 0, 0)),         # float32
+    ((375, 1242, 64, 3, 0, 0, 16, 1, 573), (1, 0, 1)),       # 94 x 311 x 64 halves per image: 2 GiB of output at n = 573.9
+    ((375, 1242, 64, 3, 0, 0, 16, 1, 574), (0, 0, 0)),
+    ((375, 236, 64, 3, 0, 0, 16, 1, 3025), (1, 0, 1)),       # 94 x 59 x 64: at n = 3025.1
+    ((375, 236, 64, 3, 0, 0, 16, 1, 3026), (0, 0, 0)),
+    ((288000, 1242, 64, 3, 0, 0, 16, 1, 1), (0, 0, 0)),      # one image beyond 2 GiB
+    ((3, 236, 64, 3, 1, 1, 16, 1, 1), (0, 0, 0)),            # nothing left after the VALID pool
+    ((19, 786, 64, 3, 0, 0, 16, 1, 2), (1, 0, 1)),
+    ((200, 2050, 64, 3, 0, 0, 16, 1, 2), (1, 0, 1)),
+]
+
+
+def test_stem_squeeze_supported_table(lib):
+    """sqdet_stem_conv_pool_squeeze_supported decides at plan creation whether stem + squeeze become one layer; the launchers must
+    agree with it at every forward.  The answers were recorded from the commit before the launchers' shape conditions were merged
+    into one gate (its library built and asked on the host, no device), so the table passes unchanged before and after."""
+    try:
+        for col, algo in enumerate((0, 2, 3)):
+            assert lib.sqdet_set_option(b"stem_algo", algo) == 0
+            got = [lib.sqdet_stem_conv_pool_squeeze_supported(*args) for args, _ in STEM_SQUEEZE_SUPPORTED]
+            assert got == [want[col] for _, want in STEM_SQUEEZE_SUPPORTED], algo
+    finally:
+        lib.sqdet_set_option(b"stem_algo", 0)
+
+
 def test_many_table_builders_are_host_side(lib):
     """The `*_prepare` halves of the one-launch-for-many entry points (weight-gradient slab reduction, packing with the batch norm
     folded, fold backward) are host functions: table sizes, block ranges and argument validation without a device."""

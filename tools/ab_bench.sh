@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of the headline step: alternates `bench.py --full --opt X` over the given option strings, N rounds, prints ms_per_step of each run.
-#   gpurun -- 'bash tools/ab_bench.sh 3 dbg=70 dbg=0'      (an option string may hold several knobs: "stem_algo=6,dbg=70")
+#   bash tools/ab_bench.sh 3 dbg=70 dbg=0      (an option string may hold several knobs: "stem_algo=3,dbg=70")
 N=${1:-3}; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for i in $(seq 1 $N); do

@@ -19,6 +19,11 @@ SqueezeDet with the 20-class config at --image_size and scores the table with th
 and writes detection_files_<step>/<cls>.txt and the eval_log.jsonl line.  --eval_tool, the error analysis and --visualize
 are KITTI-only.  (The net's ConvDet head is padded from 20 to 23 classes, the padding pinned to probability 0: DESIGN.md section 3.9.)
 
+--coco_metrics (either dataset): the same filter rows also fill a squeezedet_amd.coco.CocoEvaluator, and after the dataset's
+own scoring the COCO-style AP over IoU 0.50:0.95 / AR at 1, 10, 100 detections are printed (twelve lines), added to the
+eval_log.jsonl record as "coco" and the table written to detection_files_<step>/coco_results.json.  For KITTI this is a
+localisation metric over KITTI's boxes, not KITTI's protocol (CocoGroundTruth.from_kitti).
+
 --anchor_shapes FILE: the net's anchors take the shapes of that file (tools/fit_anchors.py, train.py --anchor_shapes); without
 the flag an anchor_shapes.json beside the checkpoint -- train.py leaves one in its --train_dir -- is used, else the config's own.
 
@@ -37,6 +42,12 @@ import numpy as np
 from squeezedet_amd import drivers
 
 
+class EvalArgs(argparse.Namespace):
+    """parse_args' result.  --coco_metrics is off through this class attribute, not through an argparse default, so vars() of
+    a run without the flag holds exactly the options it held before the flag existed; with the flag it is an instance attribute."""
+    coco_metrics = False
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[1], formatter_class=argparse.RawDescriptionHelpFormatter)
     drivers.add_dataset_args(ap, image_set_default="test")
@@ -53,7 +64,9 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seeds the choice of the rows --visualize draws")
     ap.add_argument("--anchor_shapes", default="", metavar="FILE",
                     help="anchor shapes the checkpoint was trained with (default: anchor_shapes.json beside the checkpoint, else the config's)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--coco_metrics", action="store_true", default=argparse.SUPPRESS,
+                    help="also score the detections COCO-style: AP over IoU 0.50:0.95 by object size, AR at 1 / 10 / 100 detections")
+    a = ap.parse_args(argv, namespace=EvalArgs())
     drivers.check_dataset_args(ap, a)
     return a
 
@@ -150,13 +163,15 @@ def load_weights(a, model, ckpt_path):
     return global_step
 
 
-def detect_all(model, data, evaluator):
-    """Every image of the set through the detector and the filter into the evaluator's table, a batch at a time.
-    Returns (detections, seconds in detect, seconds in the rest, batches)."""
+def detect_all(model, data, evaluator, coco=None):
+    """Every image of the set through the detector and the filter into the evaluator's table, a batch at a time (coco: a second
+    table that receives the same rows).  Returns (detections, seconds in detect, seconds in the rest, batches)."""
     import torch
     mc = model.mc
     n = len(data.image_idx)
     evaluator.reset()
+    if coco is not None:
+        coco.reset()
     t_detect = t_misc = 0.0
     counts = []
     for i0 in range(0, n, mc.BATCH_SIZE):
@@ -169,6 +184,8 @@ def detect_all(model, data, evaluator):
         boxes = rescale_boxes(det_boxes, scales)
         ob, op, oc, oi, cnt = model.filter_prediction_batch(boxes, det_probs[:k].contiguous(), det_class[:k].contiguous())
         evaluator.add_rows(ob, op, oc, cnt, i0)
+        if coco is not None:
+            coco.add_rows(ob, op, oc, cnt, i0)
         counts.append(cnt)
         torch.cuda.synchronize(model.device)
         t2 = time.time()
@@ -231,13 +248,25 @@ def score_voc(a, model, data, evaluator, result_dir, global_step):
     return aps, ap_names
 
 
-def eval_once(a, model, data, ckpt_path, evaluator):
+def score_coco(coco, result_dir):
+    """--coco_metrics: the twelve lines and coco_results.json -> the record's "coco" entry."""
+    stats = coco.evaluate()
+    print("COCO-style metrics:")
+    for line in coco.summarize():
+        print(line)
+    os.makedirs(result_dir, exist_ok=True)
+    coco.write_results_json(os.path.join(result_dir, "coco_results.json"))
+    return {"stats": [float(v) for v in stats], "per_class_ap": coco.per_class_ap}
+
+
+def eval_once(a, model, data, ckpt_path, evaluator, coco=None):
     """One checkpoint: its weights, every image into the evaluator's table, the dataset's scoring (score_kitti and
-    analyze_kitti, or score_voc), the summary and the eval_log.jsonl record (KITTI's carries "analysis")."""
+    analyze_kitti, or score_voc), the summary and the eval_log.jsonl record (KITTI's carries "analysis"; with coco, a
+    CocoEvaluator, also "coco")."""
     voc = a.dataset == "PASCAL_VOC"
     global_step = load_weights(a, model, ckpt_path)
     n = len(data.image_idx)
-    num_detection, t_detect, t_misc, nb = detect_all(model, data, evaluator)
+    num_detection, t_detect, t_misc, nb = detect_all(model, data, evaluator, coco)
 
     print("Evaluating detections...")
     t0 = time.time()
@@ -259,6 +288,8 @@ def eval_once(a, model, data, ckpt_path, evaluator):
            "timing": {"im_detect": t_detect / nb, "post_proc": t_misc / nb, "eval": t_eval}}
     if not voc:
         rec["analysis"] = analyze_kitti(a, model, data, evaluator, result_dir)
+    if coco is not None:
+        rec["coco"] = score_coco(coco, result_dir)
     with open(os.path.join(a.eval_dir, "eval_log.jsonl"), "a") as f:
         f.write(json.dumps(rec) + "\n")
     return rec
@@ -290,9 +321,14 @@ def main(argv=None):
     mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, shapes, a.image_size, a.dataset)
     data = drivers.load_index(a.dataset, a.data_path, a.year, a.image_set, mc)
     evaluator = Evaluator(mc, data.gt, model.device)
+    coco = None
+    if a.coco_metrics:
+        from squeezedet_amd.coco import CocoEvaluator, CocoGroundTruth
+        cgt = CocoGroundTruth.from_voc(data.gt, mc.CLASS_NAMES) if a.dataset == "PASCAL_VOC" else CocoGroundTruth.from_kitti(data.gt, mc)
+        coco = CocoEvaluator(mc, cgt, model.device)
     os.makedirs(a.eval_dir, exist_ok=True)
     if a.run_once:
-        return eval_once(a, model, data, a.checkpoint_path, evaluator)
+        return eval_once(a, model, data, a.checkpoint_path, evaluator, coco)
     seen = set()
     while True:
         ckpt = latest_checkpoint(a.checkpoint_path)
@@ -301,7 +337,7 @@ def main(argv=None):
         elif ckpt not in seen:
             seen.add(ckpt)
             print("Evaluating {}...".format(ckpt))
-            eval_once(a, model, data, ckpt, evaluator)
+            eval_once(a, model, data, ckpt, evaluator, coco)
             continue
         print("Wait {:d}s for new checkpoints to be saved ... ".format(a.eval_interval_secs))
         time.sleep(a.eval_interval_secs)

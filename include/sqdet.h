@@ -632,10 +632,11 @@ int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_o
                       int dst_h, int dst_w, double mean_b, double mean_g, double mean_r, int dtype, sqdet_stream_t stream);
 
 /* -------------------------------------------------------- detection table --
- * What the KITTI and the Pascal VOC evaluation below score: ONE layout, filled by sqdet_kitti_ingest / sqdet_voc_ingest
- * with the values of the respective dataset's detection files (or by the caller).  Caller-owned, device; `cap` rows per image
- * (<= SQDET_KITTI_MAX_DETECTIONS = SQDET_VOC_MAX_DETECTIONS), num_images images:
- *   det_box double [num_images,cap,4] (x1,y1,x2,y2), det_score double [num_images,cap], det_cls int32 [num_images,cap]
+ * What the KITTI, the Pascal VOC and the COCO-style evaluation below score: ONE layout, filled by sqdet_kitti_ingest /
+ * sqdet_voc_ingest with the values of the respective dataset's detection files, by sqdet_coco_ingest with unrounded x,y,w,h
+ * (or by the caller).  Caller-owned, device; `cap` rows per image
+ * (<= SQDET_KITTI_MAX_DETECTIONS = SQDET_VOC_MAX_DETECTIONS = SQDET_COCO_MAX_DETECTIONS), num_images images:
+ *   det_box double [num_images,cap,4] (x1,y1,x2,y2; COCO: x,y,w,h), det_score double [num_images,cap], det_cls int32 [num_images,cap]
  *   (0 <= class < the dataset's class count), det_count int32 [num_images] (rows of the image, class-major; zero it to
  *   reset), status int32 [2] (a rejected ingest, sticky; zero it to reset).
  *
@@ -732,6 +733,67 @@ int sqdet_voc_evaluate(const double* det_box, const double* det_score, const int
                        const double* gt_box, const int32_t* gt_cls, const int32_t* gt_difficult, int num_gt, void* workspace,
                        double* host_ap07, double* host_ap_area, int32_t* host_npos, int32_t* host_num_det, int curve_cls,
                        double* curve_rec, double* curve_prec, sqdet_stream_t stream);
+
+/* ---------------------------------------------------- COCO-style evaluation --
+ * The published COCOeval bbox protocol on the detection table: average precision over a list of IoU thresholds (0.50:0.05:0.95),
+ * by object area, and average recall at a list of detection limits (1 / 10 / 100), for every class at once.  It has no
+ * counterpart in the reference; it scores the same tables as the two evaluators above with a metric that moves when boxes
+ * get tighter or looser.  All values are double.
+ *
+ * Detection table: see above; det_box holds (x, y, w, h) -- the top-left corner and the size, as COCO results files carry them.
+ * Ground truth (device): image i owns rows [gt_offsets[i], gt_offsets[i+1]) (<= SQDET_COCO_MAX_GROUNDTRUTH), gt_box double
+ *   [G,4] (x, y, w, h), gt_cls int32 [G] (outside [0, classes): never matched, never counted), gt_area double [G],
+ *   gt_ignore int32 [G]: bit 0 = ignore, bit 1 = iscrowd.
+ *
+ * TIE RULE: the rows of a class are ordered by descending score, equal scores by image index, then by rank in the image
+ * (where equal scores keep the row order).  That is the order a stable sort gives the per-image lists put one after
+ * another, which is what COCOeval does (mergesort), so the rule is the protocol's own. */
+enum { SQDET_COCO_MAX_DETECTIONS = 512, SQDET_COCO_MAX_GROUNDTRUTH = 128, SQDET_COCO_MAX_CLASSES = 128,
+       SQDET_COCO_MAX_IOU_THRESHOLDS = 10, SQDET_COCO_MAX_RECALL_THRESHOLDS = 128, SQDET_COCO_MAX_AREA_RANGES = 4,
+       SQDET_COCO_MAX_DET_LIMITS = 3, SQDET_COCO_MAX_KEPT = 128 };
+
+/* A results file's rows into the table (step "load results"): appends n images of filter rows (sqdet_filter_prediction
+ * layout, as sqdet_kitti_ingest) as table images [image_offset, image_offset + n).  Per row, in double: cx,w /= x_scale and
+ * cy,h /= y_scale (scales: double [n,2], NULL = 1), then (cx - w/2, cy - h/2, w, h); the score is the float32 widened.
+ * Nothing is rounded and nothing is added.  Rows are stored class-major, filter order within a class.  A count outside
+ * [0, max_out] or a class outside [0, classes) makes the WHOLE call write nothing and marks status; sqdet_coco_evaluate then
+ * returns SQDET_EINVAL.  max_out > cap or classes > SQDET_COCO_MAX_CLASSES: SQDET_EUNSUPPORTED.  Asynchronous. */
+int sqdet_coco_ingest(const float* boxes, const float* probs, const int32_t* cls, const int32_t* count, const double* scales,
+                      int n, int max_out, int classes, double* det_box, double* det_score, int32_t* det_cls, int32_t* det_count,
+                      int32_t* status, int image_offset, int num_images, int cap, sqdet_stream_t stream);
+
+/* COCOeval's evaluateImg and accumulate for every (class, area range, detection limit, IoU threshold), on the device.
+ * Host inputs, used as they are (np.linspace's values; nothing is recomputed on the device): iou_thrs double [num_iou],
+ * rec_thrs double [num_rec], area_ranges double [num_area,2] (lo, hi, both inclusive), max_dets int32 [num_max_dets]
+ * (positive, ascending).
+ * Step "IoU": iw = min(dx+dw, gx+gw) - max(dx, gx), ih likewise; 0 unless both are positive; else iw*ih over
+ *   dw*dh + gw*gh - iw*ih, or over dw*dh for a crowd.
+ * Step "evaluateImg", per (image, class): the class's rows by descending score (stable), the first max_dets[last] kept; an
+ *   object is ignored in an area range by its ignore or crowd bit or an area outside the range; per threshold t the rows in
+ *   rank order each take, with best = min(t, 1 - 1e-10), the object of largest IoU >= best among the non-ignored ones not yet
+ *   taken at t, the later one of equals -- and only if there is none, likewise among the ignored ones (a crowd can be taken
+ *   again).  A matched row is ignored when its object is, an unmatched one when its own w*h lies outside the range.
+ * Step "accumulate", per (class, area range a, limit m, threshold t): the rows of rank < max_dets[m] in the class's order
+ *   (TIE RULE), tp = matched & !ignored, fp = !matched & !ignored, integer prefix sums, rc = tp / npig,
+ *   pr = tp / (fp + tp + 2.220446049250313e-16), pr's suffix maximum, recall = rc[last] (0 without rows), and
+ *   precision[r] = pr at the first row with rc >= rec_thrs[r] (0 past the end).  npig (the class's non-ignored objects in
+ *   the range) == 0 leaves the whole entry at -1.
+ * Device outputs, the per-row results in the class's order (class c's rows start at the sum of host_num_det[< c]):
+ *   row_rank int32 [num_images * cap] (the row's rank in its image) and row_word int32 [num_area, num_images * cap] (bit t:
+ *   matched at threshold t; bit num_iou + t: ignored at it).
+ * Host outputs: host_precision double [num_iou, num_rec, classes, num_area, num_max_dets], host_recall double [num_iou,
+ *   classes, num_area, num_max_dets], host_npig int32 [classes, num_area], host_num_det int32 [classes] (kept rows).
+ * workspace: sqdet_coco_eval_workspace_bytes(num_images, cap, classes) of device scratch (sized for the largest lists).
+ * One stream; SYNCHRONISES it once, at the end; the host outputs are untouched on failure.  Over a limit above (or an image
+ * over the row limits): SQDET_EUNSUPPORTED; a rejected ingest in the table: SQDET_EINVAL. */
+size_t sqdet_coco_eval_workspace_bytes(int num_images, int cap, int classes);
+int sqdet_coco_evaluate(const double* det_box, const double* det_score, const int32_t* det_cls, const int32_t* det_count,
+                        const int32_t* status, int num_images, int cap, int classes, const int32_t* gt_offsets,
+                        const double* gt_box, const int32_t* gt_cls, const double* gt_area, const int32_t* gt_ignore, int num_gt,
+                        const double* iou_thrs, int num_iou, const double* rec_thrs, int num_rec, const double* area_ranges,
+                        int num_area, const int32_t* max_dets, int num_max_dets, void* workspace, int32_t* row_rank,
+                        int32_t* row_word, double* host_precision, double* host_recall, int32_t* host_npig, int32_t* host_num_det,
+                        sqdet_stream_t stream);
 
 /* ------------------------------------------------------ training summaries --
  * Replaces the per-tensor summary ops of the training graph: tf.summary.histogram of every trainable variable and of its

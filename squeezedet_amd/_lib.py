@@ -128,6 +128,9 @@ SIGNATURES = {
     "sqdet_voc_ingest": (ci, [vp] * 5 + [ci, ci, ci] + [vp] * 5 + [ci, ci, ci, vp]),
     "sqdet_voc_eval_workspace_bytes": (sz, [ci, ci, ci]),
     "sqdet_voc_evaluate": (ci, [vp] * 5 + [ci, ci, ci] + [vp] * 4 + [ci] + [vp] * 5 + [ci, vp, vp, vp]),
+    "sqdet_coco_ingest": (ci, [vp] * 5 + [ci, ci, ci] + [vp] * 5 + [ci, ci, ci, vp]),
+    "sqdet_coco_eval_workspace_bytes": (sz, [ci, ci, ci]),
+    "sqdet_coco_evaluate": (ci, [vp] * 5 + [ci, ci, ci] + [vp] * 5 + [ci] + [vp, ci] * 4 + [vp] * 7 + [vp]),
     "sqdet_tensor_stats_record_bytes": (sz, [ci]),
     "sqdet_tensor_stats_workspace_bytes": (sz, [ci, ci]),
     "sqdet_tensor_stats_many": (ci, [vp, C.c_int64, vp, vp, ci, vp, ci, vp, vp, ci, vp]),

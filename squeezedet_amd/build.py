@@ -57,6 +57,8 @@ SOURCES = [
     ("kitti_eval.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: the '+1' overlaps, recall / precision and the '{:.1f}' / '{:.3f}' rounding are bitwise NumPy's)
     ("voc_eval.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the IoU, recall and precision expressions are single IEEE operations, compared bit for bit with NumPy's)
+    ("coco_eval.hip", ["-ffp-contract=off"]),
     ("train.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: sumsq adds the exact float64 square; nothing to contract, and the sums keep the order written)
     ("summary.hip", ["-ffp-contract=off"]),

@@ -1,5 +1,5 @@
-// The device detection table of the evaluators (include/sqdet.h, "Detection table") and what kitti_eval.hip and
-// voc_eval.hip both do with it: the ingest of filter rows, the per-image row gather, the wave and block helpers of their
+// The device detection table of the evaluators (include/sqdet.h, "Detection table") and what kitti_eval.hip,
+// voc_eval.hip and coco_eval.hip do with it: the ingest of filter rows, the per-image row gather, the wave and block helpers of their
 // matchers and rank kernels, and the host tails of their entry points.  Build with -ffp-contract=off: the row formats'
 // arithmetic is compared bit for bit with what the host programs print.
 #pragma once
@@ -13,6 +13,7 @@ constexpr int DT_MAX_ROWS = SQDET_KITTI_MAX_DETECTIONS;  // detection rows per i
 constexpr int DT_MAX_GT = SQDET_KITTI_MAX_GROUNDTRUTH;   // ground-truth rows per image
 constexpr int DT_RANK = 256;                             // threads of a count_before block
 static_assert(DT_MAX_ROWS == SQDET_VOC_MAX_DETECTIONS && DT_MAX_GT == SQDET_VOC_MAX_GROUNDTRUTH, "one table, one set of limits");
+static_assert(DT_MAX_ROWS == SQDET_COCO_MAX_DETECTIONS && DT_MAX_GT == SQDET_COCO_MAX_GROUNDTRUTH, "one table, one set of limits");
 
 struct DetTable {
   double* box;       // [num_images, cap, 4] x1, y1, x2, y2
@@ -40,6 +41,7 @@ struct KittiRow {  // double arithmetic, rounded as '%.2f'
     o[2] = round_decimal(cx + w / 2, 100.0);
     o[3] = round_decimal(cy + h / 2, 100.0);
   }
+  __device__ __forceinline__ double score(float p) const { return round_decimal((double)p, 1000.0); }  // '%.3f'
 };
 
 // float32 arithmetic up to the '+ 1', as NumPy's on the float32 rows (eval.py:83-91, pascal_voc.py:107-108), rounded as '{:.1f}'
@@ -53,6 +55,19 @@ struct VocRow {
     o[2] = round_decimal((double)(x2 + 1.0f), 10.0);
     o[3] = round_decimal((double)(y2 + 1.0f), 10.0);
   }
+  __device__ __forceinline__ double score(float p) const { return round_decimal((double)p, 1000.0); }  // '{:.3f}'
+};
+
+// COCO results carry x, y, w, h: double arithmetic, nothing rounded (coco_eval.hip), the score widened as it is
+struct CocoRow {
+  __device__ __forceinline__ void operator()(const float* b, double sx, double sy, double* o) const {
+    const double cx = (double)b[0] / sx, cy = (double)b[1] / sy, w = (double)b[2] / sx, h = (double)b[3] / sy;
+    o[0] = cx - w / 2;
+    o[1] = cy - h / 2;
+    o[2] = w;
+    o[3] = h;
+  }
+  __device__ __forceinline__ double score(float p) const { return (double)p; }
 };
 
 // One block: is every count of this call in [0, max_out] and every class of its rows in [0, classes)?  status[1] = this
@@ -81,7 +96,7 @@ __global__ void __launch_bounds__(256) ingest_check_kernel(const int32_t* __rest
 }
 
 // One wave per image: rows in file order (class-major, then filter order), each value as the detection files carry it
-// (Row: the coordinates; the score as '%.3f').
+// (Row: the coordinates and the score).
 template <class Row>
 __global__ void __launch_bounds__(64) ingest_kernel(const float* __restrict__ boxes, const float* __restrict__ probs,
                                                     const int32_t* __restrict__ cls, const int32_t* __restrict__ count,
@@ -99,7 +114,7 @@ __global__ void __launch_bounds__(64) ingest_kernel(const float* __restrict__ bo
       pos += (ck < c) || (ck == c && k < j);
     }
     Row()(boxes + (src + j) * 4, sx, sy, t.box + (dst + pos) * 4);
-    t.score[dst + pos] = round_decimal((double)probs[src + j], 1000.0);
+    t.score[dst + pos] = Row().score(probs[src + j]);
     t.cls[dst + pos] = c;
   }
   if (threadIdx.x == 0) t.count[image_offset + i] = n;
@@ -143,6 +158,16 @@ int read_back(const char* who, const Header* header, const DetTable& t, int clas
 // Are an image's row counts within what the kernels' LDS arrays and the table hold?
 __device__ __forceinline__ bool rows_ok(int ngt, int nrow, int cap) { return ngt >= 0 && ngt <= DT_MAX_GT && nrow >= 0 && nrow <= cap; }
 
+// Are the image's row counts within the limits (and its ground-truth rows inside the arrays)?  An image that is not is
+// scored as empty by every kernel, so that every offset stays inside the workspace; the call then fails.
+__device__ __forceinline__ bool image_ok(int img, const DetTable& t, int num_gt, const int32_t* __restrict__ gt_off, int* g0, int* ngt,
+                                         int* nrow) {
+  *g0 = gt_off[img];
+  *ngt = gt_off[img + 1] - *g0;
+  *nrow = t.count[img];
+  return rows_ok(*ngt, *nrow, t.cap) && *g0 >= 0 && (long long)*g0 + *ngt <= num_gt;
+}
+
 __device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
 
 // Ballot compaction, order kept: put(j, p) for every j in [0, n) with keep(j), p = the number of kept rows before j.
@@ -185,6 +210,18 @@ __device__ __forceinline__ void wave_best_lowest_index(double& best, int& idx) {
   }
 }
 
+// Its sibling: the one of greatest `best`, the HIGHEST index among equals (a walk that takes `>=` ends on the last one).
+__device__ __forceinline__ void wave_best_highest_index(double& best, int& idx) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ob = __shfl_xor(best, off);
+    const int oi = __shfl_xor(idx, off);
+    if (oi >= 0 && (idx < 0 || ob > best || (ob == best && oi > idx))) {
+      best = ob;
+      idx = oi;
+    }
+  }
+}
+
 // order[r] = the row of rank r by descending score, equal scores in row order (LDS arrays, n rows).  A NaN score has no
 // rank: it writes nothing, and the slots no row claims keep the in-range index they start with.  Synchronises the block
 // before (the scores must be written) and after.
@@ -203,6 +240,21 @@ __device__ __forceinline__ void stable_rank_desc(const double* score, int* order
 // ------------------------------------------------------------------------------------------ rank, blocks of DT_RANK
 // Against all n values of v (read through the LDS tile, DT_RANK at a time): how many are greater than e, equal to it, and
 // equal to it at an index below e_idx.  Every thread of the block calls it.
+// Inclusive sum over the block's DT_RANK threads (Hillis-Steele in LDS); buf[DT_RANK - 1] is the total until the next call.
+__device__ __forceinline__ int block_scan_incl(int v, int* buf) {
+  const int t = threadIdx.x;
+  __syncthreads();
+  buf[t] = v;
+  __syncthreads();
+  for (int off = 1; off < DT_RANK; off <<= 1) {
+    const int x = t >= off ? buf[t - off] : 0;
+    __syncthreads();
+    buf[t] += x;
+    __syncthreads();
+  }
+  return buf[t];
+}
+
 struct Before {
   int greater, equal, equal_before;
 };

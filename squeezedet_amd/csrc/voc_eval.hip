@@ -74,16 +74,6 @@ __device__ __forceinline__ int class_offset(const VocHeader* h, int c) {
 }
 
 // ---------------------------------------------------------------------------------------------------- evaluate
-// Are the image's row counts within the limits (and its ground-truth rows inside the arrays)?  An image that is not is
-// scored as empty by every kernel, so that every offset stays inside the workspace; the call then fails.
-__device__ __forceinline__ bool image_ok(int img, const DetTable& t, int num_gt, const int32_t* __restrict__ gt_off, int* g0, int* ngt,
-                                         int* nrow) {
-  *g0 = gt_off[img];
-  *ngt = gt_off[img + 1] - *g0;
-  *nrow = t.count[img];
-  return rows_ok(*ngt, *nrow, t.cap) && *g0 >= 0 && (long long)*g0 + *ngt <= num_gt;
-}
-
 // One wave per image: rows and non-difficult objects of every class (voc_eval.py:127-132).
 __global__ void __launch_bounds__(64) voc_count_kernel(DetTable t, int classes, const int32_t* __restrict__ gt_off,
                                                        const int32_t* __restrict__ gt_cls, const int32_t* __restrict__ gt_difficult,
@@ -111,21 +101,6 @@ __global__ void __launch_bounds__(64) voc_count_kernel(DetTable t, int classes, 
     cnt_det[(size_t)c * t.num_images + img] = nd[c];
     cnt_pos[(size_t)c * t.num_images + img] = np[c];
   }
-}
-
-// Inclusive sum over the block's SCAN threads (Hillis-Steele in LDS); buf[SCAN - 1] is the total until the next call.
-__device__ __forceinline__ int block_scan_incl(int v, int* buf) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  buf[t] = v;
-  __syncthreads();
-  for (int off = 1; off < SCAN; off <<= 1) {
-    const int x = t >= off ? buf[t - off] : 0;
-    __syncthreads();
-    buf[t] += x;
-    __syncthreads();
-  }
-  return buf[t];
 }
 
 // One block per class: where each image's segment starts in the class's list, and the class's totals.

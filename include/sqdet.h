@@ -631,6 +631,26 @@ int sqdet_preprocess_bgr(const uint8_t* src_bgr_u8, void* dst, int n, int src_h,
 int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom, void* dst, int n,
                       int dst_h, int dst_w, double mean_b, double mean_g, double mean_r, int dtype, sqdet_stream_t stream);
 
+/* sqdet_augment_bgr with a free WINDOW in place of the drift and an optional colour matrix: per image i, in this order
+ *   colour (only when color != NULL): the bytes (b, g, r) of every source pixel as float32,
+ *     c_k = ((M[k][0]*b + M[k][1]*g) + M[k][2]*r) + M[k][3];  c_k = fminf(fmaxf(c_k, 0.f), 255.f)   (M = color[i], row-major 3x4)
+ *   mean:   v_k = (float)((double)c_k - mean_k)
+ *   window: D[y, x] = v[y + y0, x + x0] inside the image, exactly 0.0f outside; D is ch x cw.  The window may lie inside the
+ *           image (a crop), contain it (zoom-out onto a canvas of the mean colour) or straddle it; neither the matrix nor its
+ *           offset touches the padding
+ *   flip:   D[y, x] = D[y, cw - 1 - x]
+ *   dst[i] = cv2.resize(D, (dst_w, dst_h)) as sqdet_augment_bgr: the bilinear taps clamp at the WINDOW's border, so a crop never
+ *           uses an image pixel outside its window
+ * geom: device int32 [n,7] = (src_h, src_w, x0, y0, cw, ch, flip); color: device float32 [n,12] or NULL; the rest as
+ * sqdet_augment_bgr.  The window (dx, dy, src_w - dx, src_h - dy) with color == NULL gives sqdet_augment_bgr's output bit for bit.
+ * As there, THIS CALL CANNOT VALIDATE geom: the caller must reject |x0| or |y0| > 65535, cw or ch outside [1, 65535] (a larger
+ * cw is valid only where x0 + cw == src_w, a larger ch only where y0 + ch == src_h: the window of a drift sqdet_augment_bgr accepts),
+ * flip not 0/1 and an image that ends past src_bytes (ops.augment_bgr_window does).  An image that breaks these rules anyway is left unwritten;
+ * no load ever leaves [src, src + src_bytes). */
+int sqdet_augment_bgr_window(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
+                             const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g,
+                             double mean_r, int dtype, sqdet_stream_t stream);
+
 /* -------------------------------------------------------- detection table --
  * What the KITTI, the Pascal VOC and the COCO-style evaluation below score: ONE layout, filled by sqdet_kitti_ingest /
  * sqdet_voc_ingest with the values of the respective dataset's detection files, by sqdet_coco_ingest with unrounded x,y,w,h

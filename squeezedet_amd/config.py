@@ -67,6 +67,17 @@ def base_model_config(dataset="PASCAL_VOC"):
     cfg.DATA_AUGMENTATION = False
     cfg.DRIFT_X = 0
     cfg.DRIFT_Y = 0
+    # BatchReader's augmentation beyond the reference's drift / flip (imdb.py; all off by default)
+    cfg.AUG_GEOMETRY = "drift"                  # "drift": the reference's; "ssd": zoom-out + IoU-constrained crop windows
+    cfg.AUG_ZOOM_OUT_MAX = 1.0                  # "ssd": canvas ratio U[1, max] with probability 1/2 (1.0: never)
+    cfg.AUG_CROP_MIN_SCALE = 0.3                # "ssd": a trial window's width and height, U[min, 1] of the canvas
+    cfg.AUG_CROP_ASPECT = (0.5, 2.0)            # "ssd": the aspect ratio a trial window must keep
+    cfg.AUG_CROP_TRIALS = 50
+    cfg.AUG_COLOR = False
+    cfg.AUG_BRIGHTNESS = 32.0                   # offset U[-b, b]
+    cfg.AUG_CONTRAST = (0.5, 1.5)               # gain
+    cfg.AUG_SATURATION = (0.5, 1.5)             # about the BT.601 luma
+    cfg.AUG_HUE_DEGREES = 18.0                  # rotation U[-h, h] in YIQ
     cfg.EXCLUDE_HARD_EXAMPLES = True
     cfg.BATCH_NORM_EPSILON = 1e-5
     cfg.NUM_THREAD = 4

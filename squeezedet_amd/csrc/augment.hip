@@ -5,6 +5,11 @@
 //   out = cv2.resize(D, (dst_w, dst_h))                              (INTER_LINEAR, float32, coordinates as preproc.hip)
 // -> one launch for a batch of images of different sizes, each at its own byte offset of one flat uint8 buffer.
 //
+// sqdet_augment_bgr_window generalises the drift to a WINDOW (x0, y0, cw, ch) in original-image coordinates -- inside the image
+// (a crop), around it (zoom-out: the padding is 0.0f, the mean colour) or across an edge -- and can apply a 3x4 colour matrix
+// to the bytes of every source pixel, clamped to [0, 255], before the mean is subtracted.  The drift is the window
+// (dx, dy, w - dx, h - dy) without a matrix; both entry points instantiate the one kernel body below.
+//
 // Unlike sqdet_preprocess_bgr (demo.py's order: resize, then subtract the mean) the mean is subtracted BEFORE the
 // interpolation, so the kernel interpolates the float32 mean-subtracted values and the zero padding stays exactly 0.0f.
 // Built with -ffp-contract=off: the same float32 operations in the same order as the CPU restatement.
@@ -17,6 +22,7 @@ namespace sqdet {
 // unaligned 8-byte load (reversed when mirrored) wherever both pixels lie inside the image.
 constexpr int APX = 4;   // destination pixels per thread
 
+// dx, dy: the window's corner in the original image; the window D is Hs x Ws
 struct AugGeom {
   int h, w, dx, dy, flip;
 };
@@ -26,20 +32,46 @@ __device__ __forceinline__ float sub_mean(unsigned long long q, int k, int c, do
   return (float)((double)(unsigned)((q >> (24 * k + 8 * c)) & 255) - mean);
 }
 
-template <typename T>
+// the same after the colour matrix M (row c of a row-major 3x4: three gains on b, g, r and an offset), clamped to [0, 255]
+__device__ __forceinline__ float color_sub_mean(unsigned long long q, int k, int c, const float* M, double mean) {
+  const float b = (float)(unsigned)((q >> (24 * k)) & 255), g = (float)(unsigned)((q >> (24 * k + 8)) & 255);
+  const float r = (float)(unsigned)((q >> (24 * k + 16)) & 255);
+  float v = ((M[4 * c] * b + M[4 * c + 1] * g) + M[4 * c + 2] * r) + M[4 * c + 3];
+  v = fminf(fmaxf(v, 0.f), 255.f);
+  return (float)((double)v - mean);
+}
+
+// WINDOW: geom is [n,7] (src_h, src_w, x0, y0, cw, ch, flip), else [n,5] (src_h, src_w, dx, dy, flip); COLOR: color is [n,12]
+template <typename T, bool WINDOW, bool COLOR>
 __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __restrict__ src, size_t src_bytes,
                                                      const int64_t* __restrict__ offsets, const int32_t* __restrict__ geom,
-                                                     T* __restrict__ dst, int Hd, int Wd, double m0, double m1, double m2) {
+                                                     const float* __restrict__ color, T* __restrict__ dst, int Hd, int Wd,
+                                                     double m0, double m1, double m2) {
   const int row = blockIdx.y;                     // n * Hd + y
   const int n = row / Hd, y = row - n * Hd;
-  const AugGeom g{geom[5 * n], geom[5 * n + 1], geom[5 * n + 2], geom[5 * n + 3], geom[5 * n + 4]};
+  constexpr int GS = WINDOW ? 7 : 5;
+  const AugGeom g{geom[GS * n], geom[GS * n + 1], geom[GS * n + 2], geom[GS * n + 3], geom[GS * n + GS - 1]};
   const int64_t off = offsets[n];
+  int Hs, Ws;                                      // the window D: the drifted image, or (ch, cw)
   // the host wrapper rejects all of these before the launch; an image that gets here anyway is left unwritten
-  if (g.h <= 0 || g.w <= 0 || g.dx >= g.w || g.dy >= g.h || g.dx < -65535 || g.dx > 65535 || g.dy < -65535 ||
-      g.dy > 65535 || (g.flip & ~1) || off < 0 || (size_t)off > src_bytes ||
-      (size_t)g.h * g.w * 3 > src_bytes - (size_t)off)
+  if (g.h <= 0 || g.w <= 0 || g.dx < -65535 || g.dx > 65535 || g.dy < -65535 || g.dy > 65535 || (g.flip & ~1) || off < 0 ||
+      (size_t)off > src_bytes || (size_t)g.h * g.w * 3 > src_bytes - (size_t)off)
     return;
-  const int Hs = g.h - g.dy, Ws = g.w - g.dx;     // the drifted image D
+  if constexpr (WINDOW) {
+    Ws = geom[GS * n + 4];
+    Hs = geom[GS * n + 5];
+    // (above 65535 only the drift's own window, which ends at the image's far edge: what sqdet_augment_bgr accepts)
+    if (Ws < 1 || (Ws > 65535 && (long)g.dx + Ws != g.w) || Hs < 1 || (Hs > 65535 && (long)g.dy + Hs != g.h)) return;
+  } else {
+    if (g.dx >= g.w || g.dy >= g.h) return;
+    Hs = g.h - g.dy;
+    Ws = g.w - g.dx;
+  }
+  float M[COLOR ? 12 : 1];
+  if constexpr (COLOR) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) M[k] = color[12 * n + k];
+  }
   const double scale_x = (double)Ws / (double)Wd, scale_y = (double)Hs / (double)Hd;
   float fy = (float)((y + 0.5) * scale_y - 0.5);
   int sy = (int)floorf(fy);
@@ -96,8 +128,14 @@ __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __rest
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float s00 = ok00 ? sub_mean(q0, 0, c, mean[c]) : 0.f, s01 = ok01 ? sub_mean(q0, 1, c, mean[c]) : 0.f;
-      const float s10 = ok10 ? sub_mean(q1, 0, c, mean[c]) : 0.f, s11 = ok11 ? sub_mean(q1, 1, c, mean[c]) : 0.f;
+      float s00, s01, s10, s11;                      // padding stays 0.0f: neither the matrix nor the mean touches it
+      if constexpr (COLOR) {
+        s00 = ok00 ? color_sub_mean(q0, 0, c, M, mean[c]) : 0.f, s01 = ok01 ? color_sub_mean(q0, 1, c, M, mean[c]) : 0.f;
+        s10 = ok10 ? color_sub_mean(q1, 0, c, M, mean[c]) : 0.f, s11 = ok11 ? color_sub_mean(q1, 1, c, M, mean[c]) : 0.f;
+      } else {
+        s00 = ok00 ? sub_mean(q0, 0, c, mean[c]) : 0.f, s01 = ok01 ? sub_mean(q0, 1, c, mean[c]) : 0.f;
+        s10 = ok10 ? sub_mean(q1, 0, c, mean[c]) : 0.f, s11 = ok11 ? sub_mean(q1, 1, c, mean[c]) : 0.f;
+      }
       const float h0 = s00 * ax0 + s01 * fx;
       const float h1 = s10 * ax0 + s11 * fx;
       out[p * 3 + c] = h0 * ay0 + h1 * fy;
@@ -125,24 +163,39 @@ __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __rest
   }
 }
 
+template <bool WINDOW, bool COLOR>
+static int launch_augment(const char* name, const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
+                          const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g, double mean_r,
+                          int dtype, sqdet_stream_t stream) {
+  SQDET_REQUIRE(src && src_offsets && geom && dst, "%s: null pointer", name);
+  SQDET_REQUIRE(n > 0 && dst_h > 0 && dst_w > 0 && src_bytes > 0, "%s: bad dims", name);
+  SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "%s: bad dtype %d", name, dtype);
+  SQDET_REQUIRE((long)n * dst_h <= 0x7fffffffL / 4, "%s: too many rows", name);
+  const dim3 grid((unsigned)((dst_w + 64 * APX - 1) / (64 * APX)), (unsigned)(n * dst_h));
+  SQDET_REQUIRE(grid.y <= 65535u * 1024u, "%s: too many rows", name);
+  if (dtype == SQDET_F16)
+    hipLaunchKernelGGL((augment_kernel<f16, WINDOW, COLOR>), grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets,
+                       geom, color, (f16*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
+  else
+    hipLaunchKernelGGL((augment_kernel<float, WINDOW, COLOR>), grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets,
+                       geom, color, (float*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
+  SQDET_CHECK_HIP(hipGetLastError());
+  return SQDET_OK;
+}
+
 }  // namespace sqdet
 
 extern "C" int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
                                  void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g, double mean_r,
                                  int dtype, sqdet_stream_t stream) {
-  using namespace sqdet;
-  SQDET_REQUIRE(src && src_offsets && geom && dst, "augment_bgr: null pointer");
-  SQDET_REQUIRE(n > 0 && dst_h > 0 && dst_w > 0 && src_bytes > 0, "augment_bgr: bad dims");
-  SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "augment_bgr: bad dtype %d", dtype);
-  SQDET_REQUIRE((long)n * dst_h <= 0x7fffffffL / 4, "augment_bgr: too many rows");
-  const dim3 grid((unsigned)((dst_w + 64 * APX - 1) / (64 * APX)), (unsigned)(n * dst_h));
-  SQDET_REQUIRE(grid.y <= 65535u * 1024u, "augment_bgr: too many rows");
-  if (dtype == SQDET_F16)
-    hipLaunchKernelGGL(augment_kernel<f16>, grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets, geom,
-                       (f16*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
-  else
-    hipLaunchKernelGGL(augment_kernel<float>, grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets, geom,
-                       (float*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
-  SQDET_CHECK_HIP(hipGetLastError());
-  return SQDET_OK;
+  return sqdet::launch_augment<false, false>("augment_bgr", src, src_bytes, src_offsets, geom, nullptr, dst, n, dst_h, dst_w, mean_b,
+                                             mean_g, mean_r, dtype, stream);
+}
+
+extern "C" int sqdet_augment_bgr_window(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
+                                        const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g,
+                                        double mean_r, int dtype, sqdet_stream_t stream) {
+  const auto launch = color ? sqdet::launch_augment<true, true> : sqdet::launch_augment<true, false>;
+  return launch("augment_bgr_window", src, src_bytes, src_offsets, geom, color, dst, n, dst_h, dst_w, mean_b, mean_g, mean_r, dtype,
+                stream);
 }

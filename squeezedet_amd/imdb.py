@@ -18,6 +18,13 @@ Divergences from the reference, on purpose:
     ``gt_boxes`` / ``gt_classes`` / ``gt_counts`` -- and ``mc.DEBUG_MODE``'s IoU statistics come from ``anchors.coverage`` /
     ``anchors.dataset_coverage`` (``train.py --anchor_report``), for a whole dataset instead of per batch.
 
+Beyond the reference (all off by default; with ``mc.AUG_GEOMETRY == "drift"`` and ``mc.AUG_COLOR`` false -- or a config without
+these fields -- the reader draws the reference's numbers and launches ``sqdet_augment_bgr`` as before):
+  * ``mc.AUG_GEOMETRY = "ssd"``: per image a zoom-out canvas and an IoU-constrained crop window in it (``ssd_window``), the boxes
+    cut to the window (``window_boxes``);
+  * ``mc.AUG_COLOR``: per image a 3x4 colour matrix (``draw_color_matrix`` / ``color_matrix``).
+Both are a few float64 scalars per image on the host and still ONE launch per batch: ``sqdet_augment_bgr_window``.
+
 Kept on purpose, as in the reference: the shuffled branch reshuffles as soon as ``cur + BATCH_SIZE >= len`` (imdb.py:
 121-123), so the last full batch of every epoch is never served and each epoch serves ``ceil(len / B) - 1`` batches.
 """
@@ -26,15 +33,165 @@ from collections import namedtuple
 import numpy as np
 
 Batch = namedtuple("Batch", ["image_input", "gt_boxes", "gt_classes", "gt_counts", "aug", "bbox_per_batch",
-                             "label_per_batch", "batch_idx"])
+                             "label_per_batch", "batch_idx", "window", "mode", "color"], defaults=(None, None, None))
 Batch.__doc__ = """One training batch.  image_input: device [B, IMAGE_HEIGHT, IMAGE_WIDTH, 3] in the reader's dtype;
 gt_boxes float64 [B, M, 4] (cx, cy, w, h in network-input pixels), gt_classes int32 [B, M], gt_counts int32 [B]: device
 tensors padded to M = the dataset's largest object count, ready for ops.build_labels / trainer.step / GraphedStep.step;
 aug: host int32 [B, 3] = (dx, dy, flip) per image; bbox_per_batch / label_per_batch: host lists as the reference returns
-them; batch_idx: the dataset indices of the batch."""
+them; batch_idx: the dataset indices of the batch; window / mode / color: as in Plan (None with the new options off)."""
 
-# the plan of one batch, all host side: dataset indices, per-image (dx, dy, flip), the reference's box / label lists
-Plan = namedtuple("Plan", ["batch_idx", "aug", "bbox_per_batch", "label_per_batch"])
+# the plan of one batch, all host side: dataset indices, per-image (dx, dy, flip), the reference's box / label lists.  With
+# AUG_GEOMETRY "ssd" or AUG_COLOR also: window int64 [B, 4] = (x0, y0, cw, ch) in original-image pixels (aug[:, :2] is its corner),
+# canvas int64 [B, 4] = the zoom-out canvas the window was drawn in, mode = per image "whole" | 0.1 .. 0.9 | "any" | "drift",
+# trial int64 [B] = the 1-based trial that was accepted (0: none was made, or all failed and the window is the whole canvas),
+# color float32 [B, 12] = the row-major 3x4 colour matrices, or None without AUG_COLOR
+Plan = namedtuple("Plan", ["batch_idx", "aug", "bbox_per_batch", "label_per_batch", "window", "mode", "color", "canvas", "trial"],
+                  defaults=(None, None, None, None, None))
+
+CROP_MODES = ("whole", 0.1, 0.3, 0.5, 0.7, 0.9, "any")
+BT601_BGR = np.array([0.114, 0.587, 0.299])                      # luma weights of (b, g, r)
+RGB_TO_YIQ = np.array([[0.299, 0.587, 0.114], [0.596, -0.274, -0.322], [0.211, -0.523, 0.312]])
+YIQ_TO_RGB = np.linalg.inv(RGB_TO_YIQ)
+
+
+def _cfg(mc, key, default):
+    """A config written before these fields existed means "off"."""
+    return mc.get(key, default) if hasattr(mc, "get") else getattr(mc, key, default)
+
+
+def window_iou(win, boxes):
+    """IoU of the window (x0, y0, cw, ch), as the box of its pixel centres [x0, x0 + cw - 1] x [y0, y0 + ch - 1], with each
+    [cx, cy, w, h] box; float64 [n]."""
+    x0, y0, cw, ch = [float(v) for v in win]
+    wx1, wy1, wx2, wy2 = x0, y0, x0 + cw - 1.0, y0 + ch - 1.0
+    bx1, by1 = boxes[:, 0] - boxes[:, 2] / 2.0, boxes[:, 1] - boxes[:, 3] / 2.0
+    bx2, by2 = boxes[:, 0] + boxes[:, 2] / 2.0, boxes[:, 1] + boxes[:, 3] / 2.0
+    iw = np.maximum(np.minimum(wx2, bx2) - np.maximum(wx1, bx1), 0.0)
+    ih = np.maximum(np.minimum(wy2, by2) - np.maximum(wy1, by1), 0.0)
+    inter = iw * ih
+    union = (wx2 - wx1) * (wy2 - wy1) + (bx2 - bx1) * (by2 - by1) - inter
+    return np.where(union > 0, inter / np.where(union > 0, union, 1.0), 0.0)
+
+
+def centres_inside(win, boxes):
+    """[n] bool: the box centres on the window's pixels, x0 <= cx <= x0 + cw - 1 (and y alike)."""
+    x0, y0, cw, ch = [float(v) for v in win]
+    return (boxes[:, 0] >= x0) & (boxes[:, 0] <= x0 + cw - 1.0) & (boxes[:, 1] >= y0) & (boxes[:, 1] <= y0 + ch - 1.0)
+
+
+def ssd_window(rs, mc, w, h, boxes, mode=None):
+    """The "ssd" geometry of one w x h image with [n, 4] boxes (cx, cy, w, h in its pixels): (window, canvas, mode, trial), both
+    rectangles as (x0, y0, width, height) in original-image pixels.  Draws from rs in this order:
+      zoom-out, when AUG_ZOOM_OUT_MAX > 1: randint(2); if 1, the ratio r ~ U[1, max], the canvas int(r w) x int(r h), and the
+        image's integer offset in it, randint(0, Wc - w + 1) then randint(0, Hc - h + 1);
+      the mode, randint(7) into CROP_MODES (not drawn when `mode` is given);
+      for a mode other than "whole", up to AUG_CROP_TRIALS trials: the width and the height as U[AUG_CROP_MIN_SCALE, 1] of the
+        canvas, truncated to pixels; a trial whose aspect is outside AUG_CROP_ASPECT is dropped without a position; else
+        randint(0, Wc - cw + 1), randint(0, Hc - ch + 1).  Accepted: at least one box centre inside and max IoU >= mode ("any":
+        the centre only; no boxes: always).  When every trial fails the window is the whole canvas.
+    The aspect of a trial is (cw / Wc) / (ch / Hc), RELATIVE to the canvas: the window is stretched to the fixed network input
+    whatever its shape, so this is the factor by which the resize distorts the objects (KITTI's 3.3 : 1 images could hardly
+    ever hold a window whose pixel aspect is below 2)."""
+    w, h = int(w), int(h)
+    cx0, cy0, Wc, Hc = 0, 0, w, h
+    zoom = float(_cfg(mc, "AUG_ZOOM_OUT_MAX", 1.0))
+    if zoom > 1.0 and rs.randint(2) > 0.5:
+        r = rs.uniform(1.0, zoom)
+        Wc, Hc = max(int(r * w), w), max(int(r * h), h)
+        cx0 = -int(rs.randint(0, Wc - w + 1))
+        cy0 = -int(rs.randint(0, Hc - h + 1))
+    canvas = (cx0, cy0, Wc, Hc)
+    if mode is None:
+        mode = CROP_MODES[rs.randint(len(CROP_MODES))]
+    if mode == "whole":
+        return canvas, canvas, mode, 0
+    lo = float(_cfg(mc, "AUG_CROP_MIN_SCALE", 0.3))
+    a_lo, a_hi = [float(v) for v in _cfg(mc, "AUG_CROP_ASPECT", (0.5, 2.0))]
+    # (centres_inside / window_iou, box by box in Python floats -- the same float64 operations: up to 50 trials per image on a
+    # handful of boxes, where a NumPy call per operation costs more than the whole test)
+    corners = [(float(b[0]), float(b[1]), float(b[0] - b[2] / 2.0), float(b[1] - b[3] / 2.0), float(b[0] + b[2] / 2.0),
+                float(b[1] + b[3] / 2.0)) for b in boxes]
+    for trial in range(1, int(_cfg(mc, "AUG_CROP_TRIALS", 50)) + 1):
+        cw = max(1, int(rs.uniform(lo, 1.0) * Wc))
+        ch = max(1, int(rs.uniform(lo, 1.0) * Hc))
+        aspect = (cw / float(Wc)) / (ch / float(Hc))
+        if aspect < a_lo or aspect > a_hi:
+            continue
+        win = (cx0 + int(rs.randint(0, Wc - cw + 1)), cy0 + int(rs.randint(0, Hc - ch + 1)), cw, ch)
+        if not corners:
+            return win, canvas, mode, trial
+        wx1, wy1, wx2, wy2 = float(win[0]), float(win[1]), win[0] + cw - 1.0, win[1] + ch - 1.0
+        if not any(wx1 <= c[0] <= wx2 and wy1 <= c[1] <= wy2 for c in corners):
+            continue
+        if mode == "any":
+            return win, canvas, mode, trial
+        best = 0.0
+        for _, _, bx1, by1, bx2, by2 in corners:
+            inter = max(min(wx2, bx2) - max(wx1, bx1), 0.0) * max(min(wy2, by2) - max(wy1, by1), 0.0)
+            union = (wx2 - wx1) * (wy2 - wy1) + (bx2 - bx1) * (by2 - by1) - inter
+            if union > 0:
+                best = max(best, inter / union)
+        if best >= mode:
+            return win, canvas, mode, trial
+    return canvas, canvas, mode, 0
+
+
+def window_boxes(win, boxes):
+    """The boxes ([n, 4] cx, cy, w, h) an image keeps under the window: (kept [n] bool, [k, 4] boxes in window coordinates) --
+    those whose centre is inside, shifted by the window's corner, their corners clipped to [0, cw - 1] x [0, ch - 1]."""
+    x0, y0, cw, ch = [float(v) for v in win]
+    keep = centres_inside(win, boxes)
+    b = boxes[keep]
+    x1 = np.clip(b[:, 0] - b[:, 2] / 2.0 - x0, 0.0, cw - 1.0)
+    x2 = np.clip(b[:, 0] + b[:, 2] / 2.0 - x0, 0.0, cw - 1.0)
+    y1 = np.clip(b[:, 1] - b[:, 3] / 2.0 - y0, 0.0, ch - 1.0)
+    y2 = np.clip(b[:, 1] + b[:, 3] / 2.0 - y0, 0.0, ch - 1.0)
+    return keep, np.stack([(x1 + x2) / 2.0, (y1 + y2) / 2.0, x2 - x1, y2 - y1], 1).reshape(-1, 4)
+
+
+def color_matrix(brightness=None, contrast=None, saturation=None, hue_degrees=None):
+    """The float64 3x4 matrix on (b, g, r, 1) of the given factors (None: not applied), composed in this fixed order:
+    brightness (an offset), contrast (a gain on all of it), saturation (about the BT.601 luma), hue (a rotation of the I-Q plane
+    of YIQ).  Nothing applied is the exact identity.  Diverges from SSD's photometric distortion on purpose: SSD clamps (and
+    rounds to bytes) between its steps, converts to HSV for saturation and hue, and draws the order of contrast; here the steps
+    are linear maps multiplied into ONE matrix with no intermediate clamp, and the kernel clamps once to [0, 255] at the end."""
+    A = np.eye(4)
+    if brightness is not None:
+        T = np.eye(4)
+        T[:3, 3] = float(brightness)
+        A = T @ A
+    if contrast is not None:
+        T = np.eye(4)
+        T[:3, :3] *= float(contrast)
+        A = T @ A
+    if saturation is not None:
+        T = np.eye(4)
+        T[:3, :3] = float(saturation) * np.eye(3) + (1.0 - float(saturation)) * np.tile(BT601_BGR, (3, 1))
+        A = T @ A
+    if hue_degrees is not None:
+        t = np.deg2rad(float(hue_degrees))
+        rot = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(t), -np.sin(t)], [0.0, np.sin(t), np.cos(t)]])
+        rgb = YIQ_TO_RGB @ rot @ RGB_TO_YIQ
+        T = np.eye(4)
+        T[:3, :3] = rgb[::-1, ::-1]                                  # the same map on (b, g, r)
+        A = T @ A
+    return A[:3]
+
+
+def draw_color_factors(rs, mc):
+    """(brightness, contrast, saturation, hue_degrees), each None with probability 1/2: per factor randint(2), then, if 1, its
+    value U[range] -- in color_matrix's order."""
+    out = []
+    b = float(_cfg(mc, "AUG_BRIGHTNESS", 32.0))
+    hd = float(_cfg(mc, "AUG_HUE_DEGREES", 18.0))
+    for lo, hi in ((-b, b), _cfg(mc, "AUG_CONTRAST", (0.5, 1.5)), _cfg(mc, "AUG_SATURATION", (0.5, 1.5)), (-hd, hd)):
+        out.append(rs.uniform(float(lo), float(hi)) if rs.randint(2) > 0.5 else None)
+    return tuple(out)
+
+
+def draw_color_matrix(rs, mc):
+    """One image's colour matrix, float32 [12] (row-major 3x4): composed in float64, rounded once."""
+    return color_matrix(*draw_color_factors(rs, mc)).astype(np.float32).reshape(12)
 
 
 class BatchReader:
@@ -44,7 +201,8 @@ class BatchReader:
     [cx, cy, w, h, cls] in original pixels (kitti._rois, dataset/kitti.py:50-90).  resident=True uploads every image
     once and gathers each batch on the device by byte offset; otherwise each batch is packed into a pinned host buffer
     and copied asynchronously on the current stream.  mc supplies BATCH_SIZE, IMAGE_WIDTH / IMAGE_HEIGHT, BGR_MEANS and
-    DATA_AUGMENTATION / DRIFT_X / DRIFT_Y.  The first shuffle is drawn here, as kitti.__init__ does."""
+    DATA_AUGMENTATION / DRIFT_X / DRIFT_Y and, optional, AUG_GEOMETRY / AUG_ZOOM_OUT_MAX / AUG_COLOR with their ranges
+    (config.base_model_config).  The first shuffle is drawn here, as kitti.__init__ does."""
 
     def __init__(self, mc, images, rois, seed=0, device=None, dtype=None, resident=False):
         if len(images) != len(rois) or not images:
@@ -113,8 +271,16 @@ class BatchReader:
         """The host half of read_batch: batch order, random draws and box transform (imdb.py:100-190), in NumPy float64 in
         the reference's order.  Advances the reader; needs no GPU."""
         mc = self.mc
+        geometry = _cfg(mc, "AUG_GEOMETRY", "drift")
+        if geometry not in ("drift", "ssd"):
+            raise ValueError("BatchReader: mc.AUG_GEOMETRY must be 'drift' or 'ssd', got %r" % (geometry,))
+        ssd = bool(mc.DATA_AUGMENTATION) and geometry == "ssd"
+        jitter = bool(mc.DATA_AUGMENTATION) and bool(_cfg(mc, "AUG_COLOR", False))
         batch_idx = self._next_indices(shuffle)
-        aug = np.zeros((len(batch_idx), 3), np.int32)
+        B = len(batch_idx)
+        aug = np.zeros((B, 3), np.int32)
+        window, canvas, trial = np.zeros((B, 4), np.int64), np.zeros((B, 4), np.int64), np.zeros(B, np.int64)
+        modes, color = [], np.zeros((B, 12), np.float32)
         label_per_batch, bbox_per_batch = [], []
         for k, idx in enumerate(batch_idx):
             orig_h, orig_w = [float(v) for v in self.sizes[idx]]
@@ -122,7 +288,16 @@ class BatchReader:
             label_per_batch.append([b[4] for b in roi[:]])
             gt_bbox = np.array([[b[0], b[1], b[2], b[3]] for b in roi[:]]) if roi else np.zeros((0, 4))
             dx = dy = flip = 0
-            if mc.DATA_AUGMENTATION:
+            if ssd:
+                win, canvas[k], mode, trial[k] = ssd_window(self.rs, mc, orig_w, orig_h, gt_bbox)
+                modes.append(mode)
+                keep, gt_bbox = window_boxes(win, gt_bbox)
+                label_per_batch[-1] = [c for c, kept in zip(label_per_batch[-1], keep) if kept]
+                dx, dy, orig_w, orig_h = int(win[0]), int(win[1]), float(win[2]), float(win[3])
+                if self.rs.randint(2) > 0.5:
+                    flip = 1
+                    gt_bbox[:, 0] = orig_w - 1 - gt_bbox[:, 0]
+            elif mc.DATA_AUGMENTATION:
                 assert mc.DRIFT_X >= 0 and mc.DRIFT_Y > 0, 'mc.DRIFT_X and mc.DRIFT_Y must be >= 0'
                 if mc.DRIFT_X > 0 or mc.DRIFT_Y > 0:
                     if len(gt_bbox):
@@ -147,7 +322,15 @@ class BatchReader:
             gt_bbox[:, 1::2] = gt_bbox[:, 1::2] * y_scale
             bbox_per_batch.append(gt_bbox)
             aug[k] = (dx, dy, flip)
-        return Plan(batch_idx, aug, bbox_per_batch, label_per_batch)
+            if not ssd:
+                modes.append("drift")
+                canvas[k] = (0, 0, self.sizes[idx][1], self.sizes[idx][0])
+            window[k] = (dx, dy, int(orig_w), int(orig_h))
+            if jitter:
+                color[k] = draw_color_matrix(self.rs, mc)
+        if not ssd and not jitter:
+            return Plan(batch_idx, aug, bbox_per_batch, label_per_batch)
+        return Plan(batch_idx, aug, bbox_per_batch, label_per_batch, window, modes, color if jitter else None, canvas, trial)
 
     # ---------------------------------------------------------------------------------------------------- device half --
     def _torch(self):
@@ -186,17 +369,21 @@ class BatchReader:
         self._copied.record()
         return self._src[:total], offsets
 
-    def _warp(self, batch_idx, aug):
+    def _warp(self, batch_idx, aug, window=None, color=None):
         from . import ops
         src, offsets = self._source(batch_idx)
-        geom = np.concatenate([self.sizes[batch_idx], aug.astype(np.int64)], axis=1)   # src_h, src_w, dx, dy, flip
-        return ops.augment_bgr(src, offsets, geom, self.mc.IMAGE_HEIGHT, self.mc.IMAGE_WIDTH, self.mc.BGR_MEANS, self.dtype)
+        mc = self.mc
+        if window is None:
+            geom = np.concatenate([self.sizes[batch_idx], aug.astype(np.int64)], axis=1)   # src_h, src_w, dx, dy, flip
+            return ops.augment_bgr(src, offsets, geom, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, self.dtype)
+        geom = np.concatenate([self.sizes[batch_idx], window, aug[:, 2:3].astype(np.int64)], axis=1)   # src_h, src_w, x0, y0, cw, ch, flip
+        return ops.augment_bgr_window(src, offsets, geom, color, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, self.dtype)
 
     def read_batch(self, shuffle=True):
         """imdb.read_batch (imdb.py:100-190): the next batch as a Batch, image_input and ground truth on the device."""
         torch = self._torch()
         p = self.next_plan(shuffle)
-        image_input = self._warp(p.batch_idx, p.aug)
+        image_input = self._warp(p.batch_idx, p.aug, p.window, p.color)
         B, M = len(p.batch_idx), self.max_objects
         gt = np.zeros((B, M, 4), np.float64)
         cls = np.zeros((B, M), np.int32)
@@ -206,7 +393,7 @@ class BatchReader:
             gt[k, :len(lab)] = bb
             cls[k, :len(lab)] = lab
         to = lambda a: torch.from_numpy(a).to(self.device, non_blocking=True)
-        return Batch(image_input, to(gt), to(cls), to(cnt), p.aug, p.bbox_per_batch, p.label_per_batch, p.batch_idx)
+        return Batch(image_input, to(gt), to(cls), to(cnt), p.aug, p.bbox_per_batch, p.label_per_batch, p.batch_idx, p.window, p.mode, p.color)
 
     def read_image_batch(self, shuffle=True):
         """imdb.read_image_batch (imdb.py:63-98): the next batch's images only -- mean-subtracted, then resized, with no drift

@@ -981,6 +981,61 @@ def augment_bgr(src_u8, offsets, geom, dst_h, dst_w, bgr_means, dtype=torch.floa
     return out
 
 
+AUGMENT_MAX_WINDOW = 65535
+
+
+def check_augment_window_geometry(geom, offsets, src_bytes, color=None):
+    """check_augment_geometry for sqdet_augment_bgr_window: geom int [n,7] = (src_h, src_w, x0, y0, cw, ch, flip), color None or
+    float [n,12] (finite).  x0, y0 within +-65535, cw and ch in [1, 65535] -- or larger where the window is a drift's, x0 + cw == src_w
+    (y0 + ch == src_h).  Returns (geom int32, offsets int64, color float32 or None); raises SqdetError on any bad row."""
+    g = np.ascontiguousarray(np.asarray(geom).reshape(-1, 7), dtype=np.int64)
+    o = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
+    if len(g) == 0 or len(o) != len(g):
+        raise _lib.SqdetError("augment_bgr_window: %d geometry rows for %d offsets" % (len(g), len(o)))
+    h, w, x0, y0, cw, ch, flip = g.T
+    # (a window above AUGMENT_MAX_WINDOW only as the drift's own, ending at the image's far edge: what augment_bgr accepts)
+    bad = ((h <= 0) | (w <= 0) | (np.abs(x0) > AUGMENT_MAX_DRIFT) | (np.abs(y0) > AUGMENT_MAX_DRIFT) | (cw < 1) | (ch < 1)
+           | ((cw > AUGMENT_MAX_WINDOW) & (x0 + cw != w)) | ((ch > AUGMENT_MAX_WINDOW) & (y0 + ch != h))
+           | ((flip != 0) & (flip != 1)) | (o < 0) | (o + h * w * 3 > int(src_bytes)))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise _lib.SqdetError("augment_bgr_window: image %d has bad geometry (src_h, src_w, x0, y0, cw, ch, flip) = %s at byte offset "
+                              "%d of %d" % (i, tuple(int(v) for v in g[i]), int(o[i]), int(src_bytes)))
+    if color is not None:
+        color = np.ascontiguousarray(np.asarray(color, dtype=np.float32).reshape(-1, 12))
+        if len(color) != len(g) or not np.isfinite(color).all():
+            raise _lib.SqdetError("augment_bgr_window: color must be %d finite 3x4 matrices, got %s" % (len(g), color.shape))
+    return g.astype(np.int32), o, color
+
+
+def augment_bgr_window(src_u8, offsets, geom7, color, dst_h, dst_w, bgr_means, dtype=torch.float32, out=None):
+    """augment_bgr with a window (x0, y0, cw, ch) of the original image in place of the drift -- a crop, a zoom-out onto a canvas of
+    the mean colour (zero after the mean subtraction) or a window across an edge -- and, when `color` ([n,12]: a row-major 3x4 matrix
+    per image) is given, a colour transform of the source bytes, clamped to [0, 255], before the mean is subtracted (include/sqdet.h).
+    geom7: host int [n,7] = (src_h, src_w, x0, y0, cw, ch, flip).  Checked on the host before anything is uploaded or launched; a
+    rejected call raises and leaves `out` untouched."""
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
+        raise _lib.SqdetError("augment_bgr_window: src must be a uint8 tensor")
+    src_bytes = int(src_u8.numel())
+    g, o, c = check_augment_window_geometry(geom7, offsets, src_bytes, color)
+    n, dst_h, dst_w = len(g), int(dst_h), int(dst_w)
+    if dst_h <= 0 or dst_w <= 0:
+        raise _lib.SqdetError("augment_bgr_window: bad output size %dx%d" % (dst_h, dst_w))
+    dev = src_u8.device
+    if out is None:
+        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
+    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
+        raise _lib.SqdetError("augment_bgr_window: out must be %s [%d,%d,%d,3], got %s %s" % (dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
+    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
+    gd = torch.from_numpy(g).to(dev, non_blocking=True)
+    od = torch.from_numpy(o).to(dev, non_blocking=True)
+    cd = None if c is None else torch.from_numpy(c).to(dev, non_blocking=True)
+    check(lib().sqdet_augment_bgr_window(_dev(src_u8, "src"), src_bytes, _dev(od, "offsets"), _dev(gd, "geom"),
+                                         None if cd is None else _dev(cd, "color"), _dev(out, "out"), n, dst_h, dst_w, m[0], m[1], m[2],
+                                         dtype_code(dtype), stream_ptr()), "sqdet_augment_bgr_window")
+    return out
+
+
 def box_calibration(device, mfma_iters=8192, copy_mib=1024, reps=3):
     """Two fixed microkernels timed with events on the current stream (sqdet_calib_mfma / sqdet_calib_copy): what THIS box
     sustains on a bare MFMA loop (TFLOP/s, float16 16x16x32) and on a plain device copy far larger than the Infinity Cache

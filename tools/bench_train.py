@@ -47,9 +47,11 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "f16"],
                     help="f32 = the reference's training dtype; f16 = mixed precision (float16 activations / activation gradients, "
                          "float32 master weights, weight gradients and optimizer, dynamic loss scale) -- configs[4] is resnet50 + f16")
-    ap.add_argument("--augment", action="store_true",
-                    help="read every batch inside the timed step through a resident BatchReader (the reference's drift / flip "
-                         "augmentation, imdb.read_batch) from synthetic uint8 images of the four KITTI sizes, rois in original pixels")
+    ap.add_argument("--augment", nargs="?", const="reference", default="", choices=["reference", "ssd"],
+                    help="read every batch inside the timed step through a resident BatchReader from synthetic uint8 images of the "
+                         "four KITTI sizes, rois in original pixels.  reference (also the bare flag): the reference's drift / flip "
+                         "augmentation, imdb.read_batch; ssd: crop windows, zoom-out up to 2x and colour jitter (train.py --augment ssd "
+                         "--zoom_out 2 --color_jitter)")
     args = ap.parse_args()
     if args.batch <= 0:
         args.batch = {"squeezeDet": 20, "resnet50": 8, "vgg16": 5}[args.arch]
@@ -81,6 +83,8 @@ def main():
     nobj = float(gcnt.sum().item())      # known to the host: no per-step device -> host sync for sum(input_mask)
     one_step = lambda: tr.step(x, *ops.build_labels(anchors, gt, gcls, gcnt, mc.CLASSES)[:4], num_objects=nobj)
     if args.augment:
+        if args.augment == "ssd":
+            mc.AUG_GEOMETRY, mc.AUG_ZOOM_OUT_MAX, mc.AUG_COLOR = "ssd", 2.0, True
         reader = S.BatchReader(mc, *synthetic_dataset(mc, 2 * args.batch, seed=300 + rank), seed=rank, device=dev,
                                dtype=model.dtype, resident=True)
 
@@ -113,7 +117,7 @@ def main():
                           "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(el / args.steps * 1e3, 3),
                           "host_issue_ms_per_step": round(t_issued / args.steps * 1e3, 3), "dtype": args.dtype,
-                          "data": "synthetic uint8 + BatchReader drift/flip" if args.augment else "synthetic",
+                          "data": ("synthetic uint8 + BatchReader " + {"reference": "drift/flip", "ssd": "ssd windows/zoom-out 2/colour"}[args.augment]) if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
                           "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,

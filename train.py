@@ -22,7 +22,9 @@ or --overwrite (delete, as the reference does).  --dataset PASCAL_VOC trains Squ
 squeezedet_amd.voc.load_voc; the images may differ in size.  (Its ConvDet head is padded to 23 classes: DESIGN.md section 3.9.)
 --anchor_shapes FILE (tools/fit_anchors.py writes it) replaces the config's anchor shapes (config.with_anchor_shapes, before the
 head is padded); the file is copied to <train_dir>/anchor_shapes.json, where eval.py and demo.py find it, and the shapes are
-recorded in every checkpoint: --resume refuses other shapes and, without the flag, uses the recorded ones.  --anchor_report writes
+recorded in every checkpoint: --resume refuses other shapes and, without the flag, uses the recorded ones.  --augment ssd
+[--zoom_out MAX] and --color_jitter switch on BatchReader's crop-window / zoom-out and colour augmentation (squeezedet_amd.imdb);
+the policy is recorded in every checkpoint and --resume under another one is refused.  --anchor_report writes
 <train_dir>/anchor_coverage.json (squeezedet_amd.anchors.dataset_coverage of the training set) once, before the first step.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
@@ -62,11 +64,36 @@ def parse_args(argv=None):
     ap.add_argument("--anchor_shapes", default="", metavar="FILE", help="anchor shapes fitted by tools/fit_anchors.py (default: the config's)")
     ap.add_argument("--anchor_report", action="store_true",
                     help="write <train_dir>/anchor_coverage.json, how the anchors cover the training set, before the first step")
+    # (the three augmentation flags leave no attribute behind when they are not given: augment_policy supplies the defaults, and
+    # the namespace of a command line without them stays what every earlier checkpoint's driver saw)
+    ap.add_argument("--augment", default=argparse.SUPPRESS, choices=["reference", "ssd"],
+                    help="reference (default): the drift and mirror of the reference; ssd: zoom-out and IoU-constrained crop windows "
+                         "(squeezedet_amd.imdb)")
+    ap.add_argument("--zoom_out", type=float, default=argparse.SUPPRESS, metavar="MAX",
+                    help="--augment ssd: with probability 1/2 place the image on a canvas U[1, MAX] times its size (default 1: never)")
+    ap.add_argument("--color_jitter", action="store_true", default=argparse.SUPPRESS,
+                    help="random brightness, contrast, saturation and hue, one 3x4 matrix per image")
     a = ap.parse_args(argv)
     drivers.check_dataset_args(ap, a)
     if a.resume and a.overwrite:
         ap.error("--resume and --overwrite exclude each other")
+    policy = augment_policy(a)
+    if policy["zoom_out"] < 1.0 or (policy["zoom_out"] > 1.0 and policy["geometry"] != "ssd"):
+        ap.error("--zoom_out MAX needs MAX >= 1 and --augment ssd")
     return a
+
+
+AUGMENT_OFF = dict(geometry="reference", zoom_out=1.0, color_jitter=False)      # what a checkpoint without the record was trained with
+
+
+def augment_policy(a, mc=None):
+    """The policy of --augment / --zoom_out / --color_jitter as the checkpoint records it; sets mc's augmentation fields when given."""
+    policy = dict(geometry=getattr(a, "augment", AUGMENT_OFF["geometry"]), zoom_out=float(getattr(a, "zoom_out", AUGMENT_OFF["zoom_out"])),
+                  color_jitter=bool(getattr(a, "color_jitter", AUGMENT_OFF["color_jitter"])))
+    if mc is not None:
+        mc.AUG_GEOMETRY = "ssd" if policy["geometry"] == "ssd" else "drift"
+        mc.AUG_ZOOM_OUT_MAX, mc.AUG_COLOR = policy["zoom_out"], policy["color_jitter"]
+    return policy
 
 
 def make_trainer(a, mc, local_rank=0):
@@ -179,6 +206,7 @@ class Run:
         self.dev = dev = torch.device("cuda", local_rank)
         self.anchor_shapes = resolve_anchor_shapes(a, resume_step)
         self.mc = mc = drivers.make_config(a.net, a.image_size, a.dataset, self.anchor_shapes)
+        policy = augment_policy(a, mc)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)
@@ -186,10 +214,11 @@ class Run:
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
         self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE),
-                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist())
+                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy)
         self.first = 0
         if resume_step is not None:
             saved = checkpoint.read_extra(a.train_dir, resume_step)
+            saved.setdefault("augment", AUGMENT_OFF)
             for key, now in self.extra.items():
                 if saved.get(key) != now:
                     raise SystemExit("--resume: the checkpoint was trained with %s %r, this run asks for %r" % (key, saved.get(key), now))

@@ -176,7 +176,9 @@ int sqdet_conv2d_maxpool2_nhwc_fwd_idx(const void* x, const void* w_packed, cons
 /* ------------------------------------------------------------------ stem --
  * conv1 + pool1 in one launch: relu(conv2d(x, W, stride 2) + b) followed by max_pool 3x3/s2
  * (nets/squeezeDet.py:40-44: k=3, 64 filters, SAME/SAME; nets/squeezeDetPlus.py:40-44: k=7,
- * 96 filters, VALID/VALID).  x: [n,h,w,3]; y: [n,hp,wp,cout].  Only those two stems are fused. */
+ * 96 filters, VALID/VALID).  x: [n,h,w,3]; y: [n,hp,wp,cout].  Only those two stems are fused.
+ * Like sqdet_conv2d_nhwc_fwd, both stem calls refuse a NULL operand and non-positive n / h / w / cout / k (/ next_s) with
+ * SQDET_EINVAL before anything is launched. */
 int sqdet_stem_conv_pool_fwd(const void* x, const void* w_packed, const float* bias, void* y, int n, int h, int w,
                              int cout, int k, int conv_pad_mode, int pool_pad_mode, int dtype, sqdet_stream_t stream);
 /* The same ending with the NEXT layer's squeeze1x1 (fire2/squeeze1x1 of SqueezeDet: 64 -> 16 couts, ReLU,
@@ -193,7 +195,9 @@ int sqdet_stem_conv_pool_squeeze_fwd(const void* x, const void* w_packed, const 
 /* ------------------------------------------------------------------ fire --
  * Replaces SqueezeDet._fire_layer (nets/squeezeDet.py:81-106):
  *   sq = relu(conv1x1(x)); y = concat(relu(conv1x1(sq)), relu(conv3x3(sq))).
- * w_* are packed kernels; sq_scratch: [n,h,w,s1x1] scratch in dtype storage. */
+ * w_* are packed kernels; sq_scratch: [n,h,w,s1x1] scratch in dtype storage.
+ * Every sqdet_fire_*_fwd call below refuses a NULL operand (scratches included) and non-positive n / h / w / channel counts
+ * with SQDET_EINVAL before anything is launched, as sqdet_conv2d_nhwc_fwd does; nothing is written then. */
 int sqdet_fire_fwd(const void* x, const void* w_s, const float* b_s, const void* w_e1, const float* b_e1,
                    const void* w_e3, const float* b_e3, void* sq_scratch, void* y,
                    int n, int h, int w, int cin, int s1x1, int e1x1, int e3x3, int dtype, sqdet_stream_t stream);
@@ -252,7 +256,8 @@ int sqdet_fire_expand_squeeze_next_fwd(const void* sq_in, const void* w_e1, cons
  * ONE packed weight stream (sqdet_fire_chain_pack: float32 HWIO in, any of the three may be NULL = that part of the
  * stream is left as it is); sqdet_fire_chain_stream_bytes returns 0 for shapes the kernel does not cover
  * (float16 only; s1x1 in 8..96 step 8, e1x1 / e3x3 multiples of 64, next_s1x1 in {0,16,32,48} behind a squeeze of up to
- * 32 channels, {0,48,64,96} behind a wider one).  Results are bitwise
+ * 32 channels, {0,48,64,96} behind a wider one -- sqdet_fire_chain_fwd returns SQDET_EUNSUPPORTED exactly where the byte count
+ * is 0).  Results are bitwise
  * those of sqdet_fire_fwd followed by the next module's squeeze conv. */
 size_t sqdet_fire_chain_stream_bytes(int s1x1, int e1x1, int e3x3, int next_s1x1, int dtype);
 int sqdet_fire_chain_pack(const float* w_e1_hwio, const float* w_e3_hwio, const float* w_next_s_hwio, void* stream_buf,

@@ -875,6 +875,7 @@ bool fire_chain_eligible(int s, int e1, int e3, int s2, int dtype) {
   if (!(s2 == 0 || s2 == 16 || s2 == 32 || s2 == 48 || s2 == 64 || s2 == 96)) return false;
   const ChainGeom g = chain_geom(s, e1, e3, s2);
   if (g.nch < 1 || g.nch > 3) return false;
+  if (g.nsq != 0 && (g.nch == 1 ? g.nsq > 3 : g.nsq < 3)) return false;   // (the widths dispatch_chain_nsq instantiates behind each depth class)
   if (e1 + e3 + s2 > 768 + 96) return false;   // (the ring depth is chosen for at most this many biases)
   return chain_lds_bytes(g.nch, g.nsq, chain_ring(g.nch, g.nsq), e1 + e3 + s2) <= 160 * 1024;
 }

@@ -1070,6 +1070,8 @@ static int fire_fwd_impl(const void* x, const void* w_s, const float* b_s, const
                          const void* w_e3, const float* b_e3, void* sq_scratch, void* y, int n, int h, int w,
                          int cin, int s1x1, int e1x1, int e3x3, int dtype, bool keep, sqdet_stream_t stream) {
   SQDET_REQUIRE(sq_scratch, "fire_fwd: null squeeze buffer");
+  SQDET_REQUIRE(x && w_s && b_s && w_e1 && b_e1 && w_e3 && b_e3 && y, "fire_fwd: null pointer");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && s1x1 > 0 && e1x1 > 0 && e3x3 > 0, "fire_fwd: bad dims");
   hipStream_t st = as_stream(stream);
   bool handled = false;
   int rc = SQDET_OK;
@@ -1090,7 +1092,8 @@ extern "C" int sqdet_fire_maxpool_fwd(const void* x, const void* w_s, const floa
                                       const void* w_e3, const float* b_e3, void* sq_scratch, void* fire_scratch, void* y,
                                       int n, int h, int w, int cin, int s1x1, int e1x1, int e3x3, int dtype,
                                       sqdet_stream_t stream) {
-  SQDET_REQUIRE(fire_scratch && y, "fire_maxpool_fwd: null pointer");
+  SQDET_REQUIRE(x && w_s && b_s && w_e1 && b_e1 && w_e3 && b_e3 && sq_scratch && fire_scratch && y, "fire_maxpool_fwd: null pointer");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && s1x1 > 0 && e1x1 > 0 && e3x3 > 0, "fire_maxpool_fwd: bad dims");
   hipStream_t st = as_stream(stream);
   const int ff = tune(TUNE_FIRE_FUSE);
   if (ff != 2 && ff != 3 && ff != 4) {   // one launch when the streaming kernel covers the shape (the scratches stay untouched)
@@ -1109,6 +1112,7 @@ extern "C" int sqdet_fire_expand_fwd(const void* sq_in, const void* w_e1, const 
                                      void* y, int n, int h, int w, int s1x1, int e1x1, int e3x3, int pool, int dtype,
                                      sqdet_stream_t stream) {
   SQDET_REQUIRE(sq_in && w_e1 && b_e1 && w_e3 && b_e3 && y, "fire_expand_fwd: null pointer");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && s1x1 > 0 && e1x1 > 0 && e3x3 > 0, "fire_expand_fwd: bad dims");
   hipStream_t st = as_stream(stream);
   bool handled = false;
   int rc = fire_expand_stream_launch(sq_in, w_e1, b_e1, w_e3, b_e3, y, n, h, w, s1x1, e1x1, e3x3, dtype, pool, st, &handled);
@@ -1130,6 +1134,7 @@ extern "C" int sqdet_fire_squeeze_next_fwd(const void* x, const void* w_s, const
                                            void* sq_out, int n, int h, int w, int cin, int s1x1, int e1x1, int e3x3,
                                            int next_s1x1, int dtype, sqdet_stream_t stream) {
   SQDET_REQUIRE(x && w_s && b_s && w_e1 && b_e1 && w_e3 && b_e3 && w_next_s && b_next_s && sq_out, "fire_squeeze_next_fwd: null pointer");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cin > 0 && s1x1 > 0 && e1x1 > 0 && e3x3 > 0 && next_s1x1 > 0, "fire_squeeze_next_fwd: bad dims");
   bool handled = false;
   const int rc = fire_squeeze_next_launch(x, w_s, b_s, w_e1, b_e1, w_e3, b_e3, w_next_s, b_next_s, sq_out, n, h, w, cin, s1x1, e1x1,
                                           e3x3, next_s1x1, dtype, as_stream(stream), &handled);
@@ -1151,6 +1156,7 @@ extern "C" int sqdet_fire_expand_squeeze_next_fwd(const void* sq_in, const void*
                                                   int n, int h, int w, int s1x1, int e1x1, int e3x3, int next_s1x1, int pool,
                                                   int dtype, sqdet_stream_t stream) {
   SQDET_REQUIRE(sq_in && w_e1 && b_e1 && w_e3 && b_e3 && w_next_s && b_next_s && sq_out, "fire_expand_squeeze_next_fwd: null pointer");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && s1x1 > 0 && e1x1 > 0 && e3x3 > 0 && next_s1x1 > 0, "fire_expand_squeeze_next_fwd: bad dims");
   bool handled = false;
   const int rc = fire_expand_squeeze_next_launch(sq_in, w_e1, b_e1, w_e3, b_e3, w_next_s, b_next_s, sq_out, n, h, w, s1x1, e1x1, e3x3,
                                                  next_s1x1, pool, dtype, as_stream(stream), &handled);

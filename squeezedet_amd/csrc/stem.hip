@@ -97,6 +97,7 @@ extern "C" int sqdet_stem_conv_pool_squeeze_fwd(const void* x, const void* w_pac
                                                 int conv_pad_mode, int pool_pad_mode, int next_s, int dtype, sqdet_stream_t stream) {
   using namespace sqdet;
   SQDET_REQUIRE(x && w_packed && bias && w_next_s_packed && b_next_s && sq_out, "stem_squeeze: null pointer");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cout > 0 && k > 0 && next_s > 0, "stem_squeeze: bad dims");
   bool handled = false;
   const int rc = stem_squeeze_launch(x, w_packed, bias, w_next_s_packed, b_next_s, sq_out, n, h, w, cout, k, conv_pad_mode,
                                      pool_pad_mode, next_s, dtype, as_stream(stream), &handled);
@@ -117,6 +118,7 @@ extern "C" int sqdet_stem_conv_pool_fwd(const void* x, const void* w_packed, con
   using namespace sqdet;
   SQDET_REQUIRE(x && w_packed && bias && y, "stem: null pointer");
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "stem: bad dtype");
+  SQDET_REQUIRE(n > 0 && h > 0 && w > 0 && cout > 0 && k > 0, "stem: bad dims");
   bool handled = false;
   const int saved = conv_algo();
   SQDET_UNSUPPORTED(saved != 0, "stem: fused kernel disabled by conv_algo=generic");

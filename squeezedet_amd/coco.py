@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, stream_ptr
-from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, ptr as _ptr, row_offsets  # noqa: F401
+from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, host_ptr as P, ptr as _ptr, row_offsets  # noqa: F401
 
 MAX_CLASSES = 128                                                # SQDET_COCO_MAX_CLASSES
 MAX_KEPT = 128                                                   # SQDET_COCO_MAX_KEPT: the largest maxDets
@@ -36,8 +36,7 @@ class CocoGroundTruth:
 
     def __init__(self, per_image_rows, class_names=None, image_ids=None, category_ids=None):
         self.num_images = len(per_image_rows)
-        self.offsets = row_offsets(per_image_rows, "COCO evaluation: image %d has %d objects (limit %d)")
-        flat = [row for r in per_image_rows for row in r]
+        self.offsets, flat = row_offsets(per_image_rows, "COCO evaluation: image %d has %d objects (limit %d)")
         self.cls = np.array([row[0] for row in flat], np.int32)
         self.box = np.array([row[1:5] for row in flat], np.float64).reshape(-1, 4)
         self.area = np.array([row[5] for row in flat], np.float64)
@@ -157,6 +156,7 @@ class CocoEvaluator(DetectionTable):
     """Device detection table of (x, y, w, h) rows for one image set + the scoring call.  gt: a CocoGroundTruth.  mc: the
     model config (its TOP_N_DETECTION sizes the table, its CLASS_NAMES name the classes when gt has no names); None for a
     table fed from files.  classes / iou_thrs / rec_thrs / area_rngs / max_dets: the protocol's parameters (defaults: COCO's)."""
+    ROWS_FROM = "CocoEvaluator"
 
     def __init__(self, mc, gt, device="cuda:0", max_detections=None, classes=None, iou_thrs=IOU_THRS, rec_thrs=REC_THRS,
                  area_rngs=AREA_RNGS, max_dets=MAX_DETS):
@@ -174,26 +174,15 @@ class CocoEvaluator(DetectionTable):
         self.area_rngs = np.ascontiguousarray(area_rngs, np.float64).reshape(-1, 2)
         self.max_dets = np.ascontiguousarray(max_dets, np.int32)
         super().__init__(mc, gt, device, max_detections, classes=int(classes))
-        self.gt_offsets = self.up(gt.offsets, torch.int32)
         self.gt_box, self.gt_cls = self.up(gt.box, torch.float64), self.up(gt.cls, torch.int32)
         self.gt_area, self.gt_flags = self.up(gt.area, torch.float64), self.up(gt.flags, torch.int32)
-        self.num_gt = int(gt.offsets[-1])
-        self.workspace = torch.empty((max(1, lib().sqdet_coco_eval_workspace_bytes(gt.num_images, self.cap, self.classes)),),
-                                     dtype=torch.uint8, device=self.device)
         rows = gt.num_images * self.cap
         self.row_rank = torch.zeros((max(1, rows),), dtype=torch.int32, device=self.device)
         self.row_word = torch.zeros((len(self.area_rngs), max(1, rows)), dtype=torch.int32, device=self.device)
         self.precision = self.recall = self.npig = self.num_det = self.stats = self.per_class_ap = None
 
-    @classmethod
-    def from_rows(cls, mc, gt, rows, device="cuda:0", **kw):
-        """An evaluator whose table is just large enough for `rows` (per image (class index, x, y, w, h, score), class-major)."""
-        cap = max([1] + [len(r) for r in rows])
-        if cap > MAX_DETECTIONS:
-            raise _lib.SqdetUnsupported("CocoEvaluator: %d detections in one image (limit %d)" % (cap, MAX_DETECTIONS))
-        ev = cls(mc, gt, device, max_detections=cap, **kw)
-        ev.load_rows(rows)
-        return ev
+    def _workspace_bytes(self):
+        return lib().sqdet_coco_eval_workspace_bytes(self.gt.num_images, self.cap, self.classes)
 
     def _ingest(self, src, dst):
         check(lib().sqdet_coco_ingest(*src, self.classes, *dst), "sqdet_coco_ingest")
@@ -205,8 +194,7 @@ class CocoEvaluator(DetectionTable):
         T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), self.classes, len(self.area_rngs), len(self.max_dets)
         precision, recall = np.zeros((T, R, K, A, M), np.float64), np.zeros((T, K, A, M), np.float64)
         npig, ndet = np.zeros((K, A), np.int32), np.zeros(K, np.int32)
-        P = lambda a: a.ctypes.data_as(_lib.C.c_void_p)
-        check(lib().sqdet_coco_evaluate(*self.table_args(), _ptr(self.status), self.gt.num_images, self.cap, K, _ptr(self.gt_offsets),
+        check(lib().sqdet_coco_evaluate(*self.scoring_args(), K, _ptr(self.gt_offsets),
                                         _ptr(self.gt_box), _ptr(self.gt_cls), _ptr(self.gt_area), _ptr(self.gt_flags), self.num_gt,
                                         P(self.iou_thrs), T, P(self.rec_thrs), R, P(self.area_rngs), A, P(self.max_dets), M,
                                         _ptr(self.workspace), _ptr(self.row_rank), _ptr(self.row_word), P(precision), P(recall),

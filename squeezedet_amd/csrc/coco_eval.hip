@@ -54,8 +54,7 @@ struct CocoParams {  // where the kernels read them
   int T, R, A, M;
 };
 
-// The workspace of sqdet_coco_evaluate.  Class c owns [class_offset(c), class_offset(c) + ndet[c]) of the per-row arrays;
-// inside it (image, class) segments follow each other in image order, each segment's rows by rank.
+// The workspace of sqdet_coco_evaluate; the per-row arrays hold the class lists of det_table.h, each segment's rows by rank.
 struct CocoWorkspace {
   CocoHeader* h;
   double* precision;  // [T, R, K, A, M]
@@ -72,28 +71,20 @@ struct CocoWorkspace {
 
 CocoWorkspace carve(void* p, int num_images, int cap, int classes, int T, int R, int A, int M) {
   const size_t rows = (size_t)num_images * cap, KN = (size_t)classes * num_images;
-  char* b = reinterpret_cast<char*>(p);
-  size_t o = (sizeof(CocoHeader) + 255) & ~(size_t)255;
+  Carver k{reinterpret_cast<char*>(p)};
   CocoWorkspace w;
-  w.h = reinterpret_cast<CocoHeader*>(b);
-  w.precision = reinterpret_cast<double*>(b + o), o += (size_t)T * R * classes * A * M * sizeof(double);
-  w.recall = reinterpret_cast<double*>(b + o), o += (size_t)T * classes * A * M * sizeof(double);
-  w.out_bytes = o;
-  w.cscore = reinterpret_cast<double*>(b + o), o += rows * sizeof(double);
-  w.cnt_det = reinterpret_cast<int*>(b + o), o += KN * sizeof(int);
-  w.base = reinterpret_cast<int*>(b + o), o += KN * sizeof(int);
-  w.crank = reinterpret_cast<int*>(b + o), o += rows * sizeof(int);
-  w.cword = reinterpret_cast<int*>(b + o), o += (size_t)A * rows * sizeof(int);
-  o = (o + 7) & ~(size_t)7;
-  w.lists = reinterpret_cast<CocoLists*>(b + o), o += sizeof(CocoLists);
-  w.bytes = o;
+  w.h = k.take<CocoHeader>(1);
+  w.precision = k.take<double>((size_t)T * R * classes * A * M, 256);
+  w.recall = k.take<double>((size_t)T * classes * A * M);
+  w.out_bytes = k.o;
+  w.cscore = k.take<double>(rows);
+  w.cnt_det = k.take<int>(KN);
+  w.base = k.take<int>(KN);
+  w.crank = k.take<int>(rows);
+  w.cword = k.take<int>((size_t)A * rows);
+  w.lists = k.take<CocoLists>(1);
+  w.bytes = k.o;
   return w;
-}
-
-__device__ __forceinline__ int class_offset(const CocoHeader* h, int c) {
-  int o = 0;
-  for (int k = 0; k < c; ++k) o += h->ndet[k];
-  return o;
 }
 
 // Is the object ignored in the area range [lo, hi]?  (Its ignore or crowd bit, or an area outside; both ends inclusive.)
@@ -115,11 +106,7 @@ __global__ void __launch_bounds__(64) coco_count_kernel(DetTable t, int classes,
   __syncthreads();
   int g0, ngt, nrow;
   if (image_ok(img, t, num_gt, gt_off, &g0, &ngt, &nrow)) {
-    const size_t r0 = (size_t)img * t.cap;
-    for (int j = lane; j < nrow; j += 64) {
-      const int c = t.cls[r0 + j];
-      if (c >= 0 && c < classes) atomicAdd(&nd[c], 1);
-    }
+    count_class_rows(t, img, nrow, classes, nd);
     for (int k = lane; k < ngt; k += 64) {
       const int c = gt_cls[g0 + k];
       if (c < 0 || c >= classes) continue;
@@ -135,23 +122,6 @@ __global__ void __launch_bounds__(64) coco_count_kernel(DetTable t, int classes,
     if (np[q]) atomicAdd(&h->npig[q], np[q]);
 }
 
-// One block per class: where each image's segment starts in the class's list, and the class's total.
-__global__ void __launch_bounds__(SCAN) coco_scan_kernel(int num_images, CocoHeader* h, const int* __restrict__ cnt_det,
-                                                         int* __restrict__ base) {
-  __shared__ int buf[SCAN];
-  const int c = blockIdx.x, t = threadIdx.x;
-  const size_t row = (size_t)c * num_images;
-  int carry = 0;
-  for (int i0 = 0; i0 < num_images; i0 += SCAN) {
-    const int i = i0 + t;
-    const int v = i < num_images ? cnt_det[row + i] : 0;
-    const int incl = block_scan_incl(v, buf);
-    if (i < num_images) base[row + i] = carry + incl - v;
-    carry += buf[SCAN - 1];
-  }
-  if (t == 0) h->ndet[c] = carry;
-}
-
 // The greedy walk for one (image, class), one wave.  The class's rows of the image by descending score (stable in table
 // order), the first max_kept of them walked in that order.  Every lane holds two of the image's objects of the class
 // (k = lane, lane + 64) with their IoU against the row, and, per area range, which thresholds have taken them.  Per (area
@@ -162,10 +132,8 @@ __global__ void __launch_bounds__(SCAN) coco_scan_kernel(int num_images, CocoHea
 __global__ void __launch_bounds__(64) coco_match_kernel(DetTable t, const int32_t* __restrict__ gt_off,
                                                         const double* __restrict__ gt_box, const int32_t* __restrict__ gt_cls,
                                                         const double* __restrict__ gt_area, const int32_t* __restrict__ gt_flags,
-                                                        int num_gt, CocoParams p, int max_kept, const CocoHeader* h,
-                                                        const int* __restrict__ cnt_det, const int* __restrict__ base,
-                                                        double* __restrict__ cscore, int* __restrict__ crank,
-                                                        int* __restrict__ cword, size_t rows) {
+                                                        int num_gt, CocoParams p, ClassLists L, double* __restrict__ cscore,
+                                                        int* __restrict__ crank, int* __restrict__ cword, size_t rows) {
   __shared__ double gbox[CMAXG][4];
   __shared__ double garea[CMAXG];
   __shared__ int gflags[CMAXG];
@@ -173,23 +141,21 @@ __global__ void __launch_bounds__(64) coco_match_kernel(DetTable t, const int32_
   __shared__ double dscore[CMAXD];
   __shared__ int order[CMAXD];
   __shared__ int taken[CMAXA][CMAXG];   // bit t: taken at threshold t in that area range (read and written by the owning lane only)
-  const int img = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-  int g0, ngt, nrow;
-  if (!image_ok(img, t, num_gt, gt_off, &g0, &ngt, &nrow)) return;
-  const int keep = cnt_det[(size_t)c * t.num_images + img];
-  if (keep == 0) return;
+  const int c = blockIdx.y, lane = threadIdx.x;
+  Segment seg;
+  if (!class_segment(t, L, blockIdx.x, c, num_gt, gt_off, dbox, dscore, order, &seg)) return;
+  const int keep = seg.rows, nd = seg.nd, g0 = seg.g0;   // the first `keep` (at most the largest detection limit) are walked
+  const size_t out = seg.out;
   const int ng = wave_compact(
-      ngt, [&](int k) { return gt_cls[g0 + k] == c; },
+      seg.ngt, [&](int k) { return gt_cls[g0 + k] == c; },
       [&](int k, int q) {
         const double* g = gt_box + (size_t)(g0 + k) * 4;
         for (int e = 0; e < 4; ++e) gbox[q][e] = g[e];
         garea[q] = gt_area[g0 + k];
         gflags[q] = gt_flags[g0 + k];
       });
-  const int nd = gather_class_rows(t, img, c, nrow, dbox, dscore);
-  stable_rank_desc(dscore, order, nd);   // (synchronises: the objects' LDS rows are written too)
   for (int a = 0; a < p.A; ++a) taken[a][lane] = taken[a][lane + 64] = 0;
-  const size_t out = (size_t)class_offset(h, c) + base[(size_t)c * t.num_images + img];
+  __syncthreads();
   for (int r = 0; r < keep && r < nd; ++r) {
     const int j = order[r];
     const double dx = dbox[j][0], dy = dbox[j][1], dw = dbox[j][2], dh = dbox[j][3];
@@ -263,23 +229,15 @@ __global__ void __launch_bounds__(64) coco_match_kernel(DetTable t, const int32_
   }
 }
 
-// Each row's position in its class's order -- score descending, then image, then rank in the image, which is the order of
-// the class's list: a stable sort of the per-image lists put one after another -- by counting its predecessors against LDS
-// tiles of the list; its rank and words go to that position of the caller's row arrays.
+// rank_class_rows (det_table.h; equal scores by image, then rank in the image: a stable sort of the per-image lists put
+// one after another): a row's rank and words go to its position in the class's order, in the caller's row arrays.
 __global__ void __launch_bounds__(SCAN) coco_rank_kernel(const CocoHeader* h, const double* __restrict__ cscore,
                                                          const int* __restrict__ crank, const int* __restrict__ cword, int A,
                                                          size_t rows, int32_t* __restrict__ row_rank, int32_t* __restrict__ row_word) {
-  __shared__ double tile[SCAN];
-  const int c = blockIdx.y, n = h->ndet[c];
-  if ((int)(blockIdx.x * SCAN) >= n) return;
-  const size_t off = class_offset(h, c);
-  const int e_idx = blockIdx.x * SCAN + threadIdx.x;
-  const double e = e_idx < n ? cscore[off + e_idx] : 0.0;
-  const Before b = count_before(cscore + off, n, e, e_idx, tile);
-  const int before = b.greater + b.equal_before;
-  if (e_idx >= n || !(e == e)) return;
-  row_rank[off + before] = crank[off + e_idx];
-  for (int a = 0; a < A; ++a) row_word[(size_t)a * rows + off + before] = cword[(size_t)a * rows + off + e_idx];
+  rank_class_rows(h->ndet, cscore, [&](size_t from, size_t to) {
+    row_rank[to] = crank[from];
+    for (int a = 0; a < A; ++a) row_word[(size_t)a * rows + to] = cword[(size_t)a * rows + from];
+  });
 }
 
 // One block per (class, area range x detection limit, threshold): the rows of rank < max_det[m] in class order (the others
@@ -308,7 +266,7 @@ __global__ void __launch_bounds__(SCAN) coco_accumulate_kernel(const CocoHeader*
     return;
   }
   const double npig = (double)npig_i;
-  const size_t off = class_offset(h, c);
+  const size_t off = class_offset(h->ndet, c);
   const int32_t* word = row_word + (size_t)a * rows + off;
   const int32_t* rank = row_rank + off;
   const int mbit = 1 << ti, ibit = 1 << (p.T + ti);
@@ -338,23 +296,14 @@ __global__ void __launch_bounds__(SCAN) coco_accumulate_kernel(const CocoHeader*
       is_tp = kept && !(w & ibit) && (w & mbit);
       is_fp = kept && !(w & ibit) && !(w & mbit);
     }
-    const int stp = block_scan_incl(is_tp, buf);   // tp of rows >= i of the chunk
+    const int stp = block_scan_incl<Sum>((int)is_tp, buf);   // tp of rows >= i of the chunk
     const int chunk_tp = buf[SCAN - 1];
-    const int sfp = block_scan_incl(is_fp, buf);
+    const int sfp = block_scan_incl<Sum>((int)is_fp, buf);
     const int chunk_fp = buf[SCAN - 1];
     const int tp = all_tp - behind_tp - (stp - is_tp), fp = all_fp - behind_fp - (sfp - is_fp);   // running sums up to and with row i
     const double dtp = (double)tp;
     const double pr = kept ? dtp / ((double)fp + dtp + 2.220446049250313e-16) : -1.0;
-    __syncthreads();
-    red[t] = pr;
-    __syncthreads();
-    for (int o = 1; o < SCAN; o <<= 1) {
-      const double x = t >= o ? red[t - o] : -1.0;
-      __syncthreads();
-      if (x > red[t]) red[t] = x;
-      __syncthreads();
-    }
-    const double env = red[t] > carry ? red[t] : carry;   // max of pr over the kept rows >= i
+    const double env = Max()(carry, block_scan_incl<Max>(pr, red));   // max of pr over the kept rows >= i
     if (i < n && (is_tp || i == 0)) {
       const double rc = dtp / npig, rc_prev = (double)(tp - is_tp) / npig;
       for (int r = 0; r < p.R; ++r) {
@@ -362,7 +311,7 @@ __global__ void __launch_bounds__(SCAN) coco_accumulate_kernel(const CocoHeader*
         if (rc >= thr && (i == 0 || !(rc_prev >= thr))) prec[r * pstride] = env;
       }
     }
-    if (red[SCAN - 1] > carry) carry = red[SCAN - 1];
+    carry = Max()(carry, red[SCAN - 1]);
     behind_tp += chunk_tp;
     behind_fp += chunk_fp;
   }
@@ -393,15 +342,13 @@ extern "C" int sqdet_coco_evaluate(const double* det_box, const double* det_scor
                                    void* workspace, int32_t* row_rank, int32_t* row_word, double* host_precision, double* host_recall,
                                    int32_t* host_npig, int32_t* host_num_det, sqdet_stream_t stream) {
   using namespace sqdet;
-  SQDET_REQUIRE(det_box && det_score && det_cls && det_count && gt_offsets && workspace && row_rank && row_word && host_precision &&
-                    host_recall && host_npig && host_num_det && iou_thrs && rec_thrs && area_ranges && max_dets,
-                "coco_evaluate: null pointer");
-  SQDET_REQUIRE(num_images > 0 && cap > 0 && num_gt >= 0 && classes > 0, "coco_evaluate: bad dims");
-  SQDET_REQUIRE(num_gt == 0 || (gt_box && gt_cls && gt_area && gt_ignore), "coco_evaluate: null ground-truth pointer");
+  const DetTable t = read_only_table(det_box, det_score, det_cls, det_count, status, num_images, cap);
+  if (const int rc = check_scoring_args("coco_evaluate", t, gt_offsets, workspace,
+                                        row_rank && row_word && host_precision && host_recall && host_npig && host_num_det && iou_thrs &&
+                                            rec_thrs && area_ranges && max_dets,
+                                        gt_box && gt_cls && gt_area && gt_ignore, num_gt, classes, SQDET_COCO_MAX_CLASSES))
+    return rc;
   SQDET_REQUIRE(num_iou > 0 && num_rec > 0 && num_area > 0 && num_max_dets > 0, "coco_evaluate: an empty threshold list");
-  SQDET_UNSUPPORTED(classes > SQDET_COCO_MAX_CLASSES, "coco_evaluate: %d classes (limit %d)", classes, SQDET_COCO_MAX_CLASSES);
-  SQDET_UNSUPPORTED(cap > DT_MAX_ROWS, "coco_evaluate: %d rows per image (limit %d)", cap, DT_MAX_ROWS);
-  SQDET_UNSUPPORTED((long long)num_images * cap > 0x7fffffffLL, "coco_evaluate: %d images of %d rows: more than 2^31 table rows", num_images, cap);
   SQDET_UNSUPPORTED(num_iou > CMAXT, "coco_evaluate: %d IoU thresholds (limit %d)", num_iou, CMAXT);
   SQDET_UNSUPPORTED(num_rec > SQDET_COCO_MAX_RECALL_THRESHOLDS, "coco_evaluate: %d recall thresholds (limit %d)", num_rec,
                     SQDET_COCO_MAX_RECALL_THRESHOLDS);
@@ -412,9 +359,9 @@ extern "C" int sqdet_coco_evaluate(const double* det_box, const double* det_scor
     SQDET_UNSUPPORTED(max_dets[m] > CMAXK, "coco_evaluate: maxDets %d (limit %d)", max_dets[m], CMAXK);
   }
   hipStream_t st = as_stream(stream);
-  const DetTable t = read_only_table(det_box, det_score, det_cls, det_count, status, num_images, cap);
   const int T = num_iou, R = num_rec, A = num_area, M = num_max_dets, max_kept = max_dets[M - 1];
   const CocoWorkspace w = carve(workspace, num_images, cap, classes, T, R, A, M);
+  const ClassLists L = {w.cnt_det, w.base, w.h->ndet, num_images};
   const size_t rows = (size_t)num_images * cap;
   const unsigned K = (unsigned)classes, N = (unsigned)num_images;
   CocoLists lists = {};   // (the stream is synchronised before this returns)
@@ -430,9 +377,9 @@ extern "C" int sqdet_coco_evaluate(const double* det_box, const double* det_scor
   SQDET_CHECK_HIP(hipMemsetAsync(row_word, 0, (size_t)A * rows * sizeof(int32_t), st));
   hipLaunchKernelGGL(coco_count_kernel, dim3(N), dim3(64), 0, st, t, classes, gt_offsets, gt_cls, gt_area, gt_ignore, num_gt, p, max_kept,
                      w.h, w.cnt_det);
-  hipLaunchKernelGGL(coco_scan_kernel, dim3(K), dim3(SCAN), 0, st, num_images, w.h, w.cnt_det, w.base);
-  hipLaunchKernelGGL(coco_match_kernel, dim3(N, K), dim3(64), 0, st, t, gt_offsets, gt_box, gt_cls, gt_area, gt_ignore, num_gt, p,
-                     max_kept, w.h, w.cnt_det, w.base, w.cscore, w.crank, w.cword, rows);
+  hipLaunchKernelGGL(class_scan_kernel, dim3(K), dim3(SCAN), 0, st, L);
+  hipLaunchKernelGGL(coco_match_kernel, dim3(N, K), dim3(64), 0, st, t, gt_offsets, gt_box, gt_cls, gt_area, gt_ignore, num_gt, p, L,
+                     w.cscore, w.crank, w.cword, rows);
   hipLaunchKernelGGL(coco_rank_kernel, dim3((unsigned)((rows + SCAN - 1) / SCAN), K), dim3(SCAN), 0, st, w.h, w.cscore, w.crank, w.cword,
                      A, rows, row_rank, row_word);
   hipLaunchKernelGGL(coco_accumulate_kernel, dim3(K, (unsigned)(A * M), (unsigned)T), dim3(SCAN), 0, st, w.h, p, classes, rows, row_rank,

@@ -1,7 +1,7 @@
 // The device detection table of the evaluators (include/sqdet.h, "Detection table") and what kitti_eval.hip,
 // voc_eval.hip and coco_eval.hip do with it: the ingest of filter rows, the per-image row gather, the wave and block helpers of their
-// matchers and rank kernels, and the host tails of their entry points.  Build with -ffp-contract=off: the row formats'
-// arithmetic is compared bit for bit with what the host programs print.
+// matchers and rank kernels, the class lists of the VOC and COCO metrics, and the host checks and tails of their entry points.
+// Build with -ffp-contract=off: the row formats' arithmetic is compared bit for bit with what the host programs print.
 #pragma once
 #include "common.h"
 #include "round_decimal.h"
@@ -238,23 +238,32 @@ __device__ __forceinline__ void stable_rank_desc(const double* score, int* order
 }
 
 // ------------------------------------------------------------------------------------------ rank, blocks of DT_RANK
-// Against all n values of v (read through the LDS tile, DT_RANK at a time): how many are greater than e, equal to it, and
-// equal to it at an index below e_idx.  Every thread of the block calls it.
-// Inclusive sum over the block's DT_RANK threads (Hillis-Steele in LDS); buf[DT_RANK - 1] is the total until the next call.
-__device__ __forceinline__ int block_scan_incl(int v, int* buf) {
+struct Sum {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }
+};
+struct Max {
+  template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return b > a ? b : a; }
+};
+
+// Inclusive scan (Op: Sum or Max) over the block's DT_RANK threads (Hillis-Steele in LDS); buf[DT_RANK - 1] is the total
+// until the next call.  Max is exact and integer sums are order-free, so the association order changes no bit.
+template <class Op, class T>
+__device__ __forceinline__ T block_scan_incl(T v, T* buf) {
   const int t = threadIdx.x;
   __syncthreads();
   buf[t] = v;
   __syncthreads();
   for (int off = 1; off < DT_RANK; off <<= 1) {
-    const int x = t >= off ? buf[t - off] : 0;
+    const T x = buf[t >= off ? t - off : t];
     __syncthreads();
-    buf[t] += x;
+    if (t >= off) buf[t] = Op()(x, buf[t]);
     __syncthreads();
   }
   return buf[t];
 }
 
+// Against all n values of v (read through the LDS tile, DT_RANK at a time): how many are greater than e, equal to it, and
+// equal to it at an index below e_idx.  Every thread of the block calls it.
 struct Before {
   int greater, equal, equal_before;
 };
@@ -273,6 +282,114 @@ __device__ __forceinline__ Before count_before(const double* __restrict__ v, int
     }
   }
   return b;
+}
+
+// ------------------------------------------------------------------------------------------------- class lists
+// What voc_eval.hip and coco_eval.hip regroup the table into: class c owns [class_offset(c), class_offset(c) + ndet[c]) of
+// a metric's per-row arrays; inside it (image, class) segments follow each other in image order, so a segment starts at
+// class_offset(c) + base[c][img].  This section is the only code that knows the layout.
+struct ClassLists {
+  int* cnt;   // [C, N] rows of the class in the image
+  int* base;  // [C, N] exclusive prefix of cnt over the images
+  int* ndet;  // [C] rows of the class (in the metric's workspace header)
+  int num_images;
+};
+
+__device__ __forceinline__ int class_offset(const int* ndet, int c) {
+  int o = 0;
+  for (int k = 0; k < c; ++k) o += ndet[k];
+  return o;
+}
+
+// The count kernels' table half, one wave: image img's first nrow rows per class, added to the LDS counters nd[classes].
+__device__ __forceinline__ void count_class_rows(const DetTable& t, int img, int nrow, int classes, int* nd) {
+  const size_t r0 = (size_t)img * t.cap;
+  for (int j = threadIdx.x; j < nrow; j += 64) {
+    const int c = t.cls[r0 + j];
+    if (c >= 0 && c < classes) atomicAdd(&nd[c], 1);
+  }
+}
+
+// One block per class: cnt -> base and ndet[c], DT_RANK images at a time with the running total carried.
+__global__ void __launch_bounds__(DT_RANK) class_scan_kernel(ClassLists L) {
+  __shared__ int buf[DT_RANK];
+  const int c = blockIdx.x, t = threadIdx.x;
+  const size_t row = (size_t)c * L.num_images;
+  int carry = 0;
+  for (int i0 = 0; i0 < L.num_images; i0 += DT_RANK) {
+    const int i = i0 + t;
+    const int v = i < L.num_images ? L.cnt[row + i] : 0;
+    const int incl = block_scan_incl<Sum>(v, buf);
+    if (i < L.num_images) L.base[row + i] = carry + incl - v;
+    carry += buf[DT_RANK - 1];
+  }
+  if (t == 0) L.ndet[c] = carry;
+}
+
+// The matchers' prologue for (image, class), one wave: the class's rows of the image in the LDS arrays box / score and
+// their order by descending score (stable in table order).  False for an image over the limits or an empty segment.
+// Synchronises the block before it returns true.
+struct Segment {
+  int g0, ngt;  // the image's ground-truth rows
+  int rows;     // the segment's rows in the class's list
+  int nd;       // the class's rows of the image in the LDS arrays
+  size_t out;   // where the segment starts in the per-row arrays
+};
+__device__ __forceinline__ bool class_segment(const DetTable& t, const ClassLists& L, int img, int c, int num_gt,
+                                              const int32_t* __restrict__ gt_off, double (*box)[4], double* score, int* order,
+                                              Segment* s) {
+  int nrow;
+  if (!image_ok(img, t, num_gt, gt_off, &s->g0, &s->ngt, &nrow)) return false;
+  s->rows = L.cnt[(size_t)c * L.num_images + img];
+  if (s->rows == 0) return false;
+  s->nd = gather_class_rows(t, img, c, nrow, box, score);
+  stable_rank_desc(score, order, s->nd);
+  s->out = (size_t)class_offset(L.ndet, c) + L.base[(size_t)c * L.num_images + img];
+  return true;
+}
+
+// The rank kernels' body, blocks of DT_RANK over (rows, classes): each row's position in its class's order -- score
+// descending, then the order of the class's list -- by counting its predecessors against LDS tiles of the list;
+// put(from, to) then moves the row's payload there (indices into the per-row arrays).  A NaN score has no position.
+template <class Put>
+__device__ __forceinline__ void rank_class_rows(const int* ndet, const double* __restrict__ cscore, Put put) {
+  __shared__ double tile[DT_RANK];
+  const int c = blockIdx.y, n = ndet[c];
+  if ((int)(blockIdx.x * DT_RANK) >= n) return;
+  const size_t off = class_offset(ndet, c);
+  const int e_idx = blockIdx.x * DT_RANK + threadIdx.x;
+  const double e = e_idx < n ? cscore[off + e_idx] : 0.0;
+  const Before b = count_before(cscore + off, n, e, e_idx, tile);
+  if (e_idx >= n || !(e == e)) return;
+  put(off + e_idx, off + b.greater + b.equal_before);
+}
+
+// ---------------------------------------------------------------------------------------------- host: workspace, checks
+// A running offset into a workspace: take<T>(n) aligns it for T (or to `align` bytes) and steps over n values.
+struct Carver {
+  char* p;
+  size_t o = 0;
+  template <class T>
+  T* take(size_t n, size_t align = alignof(T)) {
+    o = (o + align - 1) & ~(align - 1);
+    T* r = reinterpret_cast<T*>(p + o);
+    o += n * sizeof(T);
+    return r;
+  }
+};
+
+// The checks every sqdet_<who> that scores the table's class lists shares.  pointers / gt_pointers: are the entry
+// point's other pointers (its ground-truth arrays, where num_gt > 0) there?
+inline int check_scoring_args(const char* who, const DetTable& t, const void* gt_offsets, const void* workspace, bool pointers,
+                              bool gt_pointers, int num_gt, int classes, int max_classes) {
+  SQDET_REQUIRE(t.box && t.score && t.cls && t.count && gt_offsets && workspace && pointers, "%s: null pointer", who);
+  SQDET_REQUIRE(t.num_images > 0 && t.cap > 0 && num_gt >= 0 && classes > 0, "%s: bad dims", who);
+  SQDET_REQUIRE(num_gt == 0 || gt_pointers, "%s: null ground-truth pointer", who);
+  SQDET_UNSUPPORTED(classes > max_classes, "%s: %d classes (limit %d)", who, classes, max_classes);
+  SQDET_UNSUPPORTED(t.cap > DT_MAX_ROWS, "%s: %d rows per image (limit %d)", who, t.cap, DT_MAX_ROWS);
+  SQDET_UNSUPPORTED((long long)t.num_images * t.cap > 0x7fffffffLL, "%s: %d images of %d rows: more than 2^31 table rows", who,
+                    t.num_images, t.cap);
+  return SQDET_OK;
 }
 
 }  // namespace

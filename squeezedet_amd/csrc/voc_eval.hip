@@ -34,14 +34,12 @@ struct VocHeader {
   double ap_area[VMAXC];
 };
 
-// The workspace of sqdet_voc_evaluate.  Class c owns [class_offset(c), class_offset(c) + ndet[c]) of the per-row arrays;
-// inside it (image, class) segments follow each other in image order, rows in table order.
+// The workspace of sqdet_voc_evaluate; the per-row arrays ([T]) hold the class lists of det_table.h, rows in table order.
 struct VocWorkspace {
   VocHeader* h;
   double* cscore;  // [T] score, class lists
   double* mpre;    // [T] suffix maximum of precision, class order
   int* cnt_det;    // [C, N] rows of the class in the image
-  int* cnt_pos;    // [C, N] non-difficult objects of the class in the image
   int* base;       // [C, N] exclusive prefix of cnt_det over the images
   int* cflag;      // [T] FLAG_*, class lists
   int* stp;        // [T] tp flags in class order, then their running sum
@@ -51,44 +49,33 @@ struct VocWorkspace {
 
 VocWorkspace carve(void* p, int num_images, int cap, int classes) {
   const size_t T = (size_t)num_images * cap, CN = (size_t)classes * num_images;
-  char* b = reinterpret_cast<char*>(p);
-  size_t o = (sizeof(VocHeader) + 255) & ~(size_t)255;
+  Carver k{reinterpret_cast<char*>(p)};
   VocWorkspace w;
-  w.h = reinterpret_cast<VocHeader*>(b);
-  w.cscore = reinterpret_cast<double*>(b + o), o += T * sizeof(double);
-  w.mpre = reinterpret_cast<double*>(b + o), o += T * sizeof(double);
-  w.cnt_det = reinterpret_cast<int*>(b + o), o += CN * sizeof(int);
-  w.cnt_pos = reinterpret_cast<int*>(b + o), o += CN * sizeof(int);
-  w.base = reinterpret_cast<int*>(b + o), o += CN * sizeof(int);
-  w.cflag = reinterpret_cast<int*>(b + o), o += T * sizeof(int);
-  w.stp = reinterpret_cast<int*>(b + o), o += T * sizeof(int);
-  w.sfp = reinterpret_cast<int*>(b + o), o += T * sizeof(int);
-  w.bytes = o;
+  w.h = k.take<VocHeader>(1);
+  w.cscore = k.take<double>(T, 256);
+  w.mpre = k.take<double>(T);
+  w.cnt_det = k.take<int>(CN);
+  w.base = k.take<int>(CN);
+  w.cflag = k.take<int>(T);
+  w.stp = k.take<int>(T);
+  w.sfp = k.take<int>(T);   // (adjacent to stp: one memset clears both)
+  w.bytes = k.o;
   return w;
 }
 
-__device__ __forceinline__ int class_offset(const VocHeader* h, int c) {
-  int o = 0;
-  for (int k = 0; k < c; ++k) o += h->ndet[k];
-  return o;
-}
-
 // ---------------------------------------------------------------------------------------------------- evaluate
-// One wave per image: rows and non-difficult objects of every class (voc_eval.py:127-132).
+// One wave per image: rows of every class, and its non-difficult objects (voc_eval.py:127-132) added to the header's
+// integer counters.
 __global__ void __launch_bounds__(64) voc_count_kernel(DetTable t, int classes, const int32_t* __restrict__ gt_off,
                                                        const int32_t* __restrict__ gt_cls, const int32_t* __restrict__ gt_difficult,
-                                                       int num_gt, VocHeader* h, int* __restrict__ cnt_det, int* __restrict__ cnt_pos) {
+                                                       int num_gt, VocHeader* h, int* __restrict__ cnt_det) {
   __shared__ int nd[VMAXC], np[VMAXC];
   const int img = blockIdx.x, lane = threadIdx.x;
   for (int c = lane; c < classes; c += 64) nd[c] = np[c] = 0;
   __syncthreads();
   int g0, ngt, nrow;
   if (image_ok(img, t, num_gt, gt_off, &g0, &ngt, &nrow)) {
-    const size_t r0 = (size_t)img * t.cap;
-    for (int j = lane; j < nrow; j += 64) {
-      const int c = t.cls[r0 + j];
-      if (c >= 0 && c < classes) atomicAdd(&nd[c], 1);
-    }
+    count_class_rows(t, img, nrow, classes, nd);
     for (int k = lane; k < ngt; k += 64) {
       const int c = gt_cls[g0 + k];
       if (c >= 0 && c < classes && !gt_difficult[g0 + k]) atomicAdd(&np[c], 1);
@@ -99,33 +86,7 @@ __global__ void __launch_bounds__(64) voc_count_kernel(DetTable t, int classes, 
   __syncthreads();
   for (int c = lane; c < classes; c += 64) {
     cnt_det[(size_t)c * t.num_images + img] = nd[c];
-    cnt_pos[(size_t)c * t.num_images + img] = np[c];
-  }
-}
-
-// One block per class: where each image's segment starts in the class's list, and the class's totals.
-__global__ void __launch_bounds__(SCAN) voc_scan_kernel(int num_images, VocHeader* h, const int* __restrict__ cnt_det,
-                                                        const int* __restrict__ cnt_pos, int* __restrict__ base) {
-  __shared__ int buf[SCAN];
-  __shared__ int pos_total;
-  const int c = blockIdx.x, t = threadIdx.x;
-  const size_t row = (size_t)c * num_images;
-  if (t == 0) pos_total = 0;
-  int carry = 0, pos = 0;
-  for (int i0 = 0; i0 < num_images; i0 += SCAN) {
-    const int i = i0 + t;
-    const int v = i < num_images ? cnt_det[row + i] : 0;
-    pos += i < num_images ? cnt_pos[row + i] : 0;
-    const int incl = block_scan_incl(v, buf);
-    if (i < num_images) base[row + i] = carry + incl - v;
-    carry += buf[SCAN - 1];
-  }
-  __syncthreads();
-  if (pos) atomicAdd(&pos_total, pos);
-  __syncthreads();
-  if (t == 0) {
-    h->ndet[c] = carry;
-    h->npos[c] = pos_total;
+    if (np[c]) atomicAdd(&h->npos[c], np[c]);
   }
 }
 
@@ -135,8 +96,7 @@ __global__ void __launch_bounds__(SCAN) voc_scan_kernel(int num_images, VocHeade
 // class's list.
 __global__ void __launch_bounds__(64) voc_match_kernel(DetTable t, const int32_t* __restrict__ gt_off,
                                                        const double* __restrict__ gt_box, const int32_t* __restrict__ gt_cls,
-                                                       const int32_t* __restrict__ gt_difficult, int num_gt, const VocHeader* h,
-                                                       const int* __restrict__ cnt_det, const int* __restrict__ base,
+                                                       const int32_t* __restrict__ gt_difficult, int num_gt, ClassLists L,
                                                        double* __restrict__ cscore, int* __restrict__ cflag) {
   __shared__ double gbox[VMAXG][4];
   __shared__ int gdiff[VMAXG];
@@ -145,21 +105,20 @@ __global__ void __launch_bounds__(64) voc_match_kernel(DetTable t, const int32_t
   __shared__ double dscore[VMAXD];
   __shared__ int order[VMAXD];
   __shared__ int dflag[VMAXD];
-  const int img = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-  int g0, ngt, nrow;
-  if (!image_ok(img, t, num_gt, gt_off, &g0, &ngt, &nrow)) return;
-  if (cnt_det[(size_t)c * t.num_images + img] == 0) return;
-  // the image's objects and rows of the class, order kept
+  const int c = blockIdx.y, lane = threadIdx.x;
+  Segment s;
+  if (!class_segment(t, L, blockIdx.x, c, num_gt, gt_off, dbox, dscore, order, &s)) return;
+  const int nd = s.nd, g0 = s.g0;
+  // the image's objects of the class, order kept
   const int ng = wave_compact(
-      ngt, [&](int k) { return gt_cls[g0 + k] == c; },
+      s.ngt, [&](int k) { return gt_cls[g0 + k] == c; },
       [&](int k, int p) {
         const double* g = gt_box + (size_t)(g0 + k) * 4;
         for (int q = 0; q < 4; ++q) gbox[p][q] = g[q];
         gdiff[p] = gt_difficult[g0 + k] != 0;
         gtaken[p] = 0;
       });
-  const int nd = gather_class_rows(t, img, c, nrow, dbox, dscore);
-  stable_rank_desc(dscore, order, nd);
+  __syncthreads();
   for (int r = 0; r < nd; ++r) {
     const int j = order[r];
     const double b0 = dbox[j][0], b1 = dbox[j][1], b2 = dbox[j][2], b3 = dbox[j][3];
@@ -190,42 +149,33 @@ __global__ void __launch_bounds__(64) voc_match_kernel(DetTable t, const int32_t
     }
     __syncthreads();
   }
-  const size_t out = (size_t)class_offset(h, c) + base[(size_t)c * t.num_images + img];
   for (int j = lane; j < nd; j += 64) {
-    cscore[out + j] = dscore[j];
-    cflag[out + j] = dflag[j];
+    cscore[s.out + j] = dscore[j];
+    cflag[s.out + j] = dflag[j];
   }
 }
 
-// Each row's position in its class's order -- score descending, then image, then row, which is the order of the class's
-// list -- by counting its predecessors against LDS tiles of the list; its flags go to that position.
+// rank_class_rows (det_table.h; equal scores by image, then row): a row's flags go to its position in the class's order.
 __global__ void __launch_bounds__(SCAN) voc_rank_kernel(const VocHeader* h, const double* __restrict__ cscore,
                                                         const int* __restrict__ cflag, int* __restrict__ stp, int* __restrict__ sfp) {
-  __shared__ double tile[SCAN];
-  const int c = blockIdx.y, n = h->ndet[c];
-  if ((int)(blockIdx.x * SCAN) >= n) return;
-  const size_t off = class_offset(h, c);
-  const int e_idx = blockIdx.x * SCAN + threadIdx.x;
-  const double e = e_idx < n ? cscore[off + e_idx] : 0.0;
-  const Before b = count_before(cscore + off, n, e, e_idx, tile);
-  const int before = b.greater + b.equal_before;
-  if (e_idx >= n || !(e == e)) return;
-  const int f = cflag[off + e_idx];
-  stp[off + before] = f == FLAG_TP;
-  sfp[off + before] = f == FLAG_FP;
+  rank_class_rows(h->ndet, cscore, [&](size_t from, size_t to) {
+    const int f = cflag[from];
+    stp[to] = f == FLAG_TP;
+    sfp[to] = f == FLAG_FP;
+  });
 }
 
 // np.cumsum of tp and fp (voc_eval.py:198-199), one block per class, SCAN rows at a time with the running total carried.
 __global__ void __launch_bounds__(SCAN) voc_prefix_kernel(const VocHeader* h, int* __restrict__ stp, int* __restrict__ sfp) {
   __shared__ int buf[SCAN];
   const int c = blockIdx.x, n = h->ndet[c], t = threadIdx.x;
-  const size_t off = class_offset(h, c);
+  const size_t off = class_offset(h->ndet, c);
   int ctp = 0, cfp = 0;
   for (int i0 = 0; i0 < n; i0 += SCAN) {
     const int i = i0 + t;
-    const int a = block_scan_incl(i < n ? stp[off + i] : 0, buf);
+    const int a = block_scan_incl<Sum>(i < n ? stp[off + i] : 0, buf);
     const int ta = buf[SCAN - 1];
-    const int b = block_scan_incl(i < n ? sfp[off + i] : 0, buf);
+    const int b = block_scan_incl<Sum>(i < n ? sfp[off + i] : 0, buf);
     const int tb = buf[SCAN - 1];
     if (i < n) {
       stp[off + i] = ctp + a;
@@ -253,7 +203,7 @@ __global__ void __launch_bounds__(SCAN) voc_ap_kernel(VocHeader* h, const int* _
     if (t == 0) h->ap07[c] = h->ap_area[c] = 0.0;
     return;
   }
-  const size_t off = class_offset(h, c);
+  const size_t off = class_offset(h->ndet, c);
   const double npos = (double)h->npos[c];
   // ---- the 11-point metric: p_q = max(prec[rec >= q * 0.1]), 0 when there is none (-1 marks "none": prec >= 0)
   double m[NT07];
@@ -294,20 +244,12 @@ __global__ void __launch_bounds__(SCAN) voc_ap_kernel(VocHeader* h, const int* _
   // from the end with the running maximum carried
   double carry = 0.;
   for (int i0 = ((n - 1) / SCAN) * SCAN; i0 >= 0; i0 -= SCAN) {
-    const int i = i0 + t;
+    const int i = i0 + SCAN - 1 - t;   // thread 0 holds the chunk's last row: a prefix over threads is a suffix over rows
     double rec, prec = 0.;
     if (i < n) rec_prec(stp[off + i], sfp[off + i], npos, &rec, &prec);
-    __syncthreads();
-    red[t] = prec;
-    __syncthreads();
-    for (int o = 1; o < SCAN; o <<= 1) {
-      const double x = t + o < SCAN ? red[t + o] : 0.;
-      __syncthreads();
-      if (x > red[t]) red[t] = x;
-      __syncthreads();
-    }
-    if (i < n) mpre[off + i] = red[t] > carry ? red[t] : carry;
-    if (red[0] > carry) carry = red[0];
+    const double env = Max()(carry, block_scan_incl<Max>(prec, red));
+    if (i < n) mpre[off + i] = env;
+    carry = Max()(carry, red[SCAN - 1]);
   }
   __syncthreads();
   // ---- sum (mrec[i + 1] - mrec[i]) * mpre[i + 1] where recall changes (:60-63): a strided partial per thread, then a
@@ -351,26 +293,22 @@ extern "C" int sqdet_voc_evaluate(const double* det_box, const double* det_score
                                   double* host_ap07, double* host_ap_area, int32_t* host_npos, int32_t* host_num_det, int curve_cls,
                                   double* curve_rec, double* curve_prec, sqdet_stream_t stream) {
   using namespace sqdet;
-  SQDET_REQUIRE(det_box && det_score && det_cls && det_count && gt_offsets && workspace && host_ap07 && host_ap_area && host_npos &&
-                    host_num_det, "voc_evaluate: null pointer");
-  SQDET_REQUIRE(num_images > 0 && cap > 0 && num_gt >= 0 && classes > 0, "voc_evaluate: bad dims");
-  SQDET_REQUIRE(num_gt == 0 || (gt_box && gt_cls && gt_difficult), "voc_evaluate: null ground-truth pointer");
-  SQDET_REQUIRE(curve_cls < classes && (curve_cls < 0 || (curve_rec && curve_prec)), "voc_evaluate: bad curve class or null curve buffer");
-  SQDET_UNSUPPORTED(classes > SQDET_VOC_MAX_CLASSES, "voc_evaluate: %d classes (limit %d)", classes, SQDET_VOC_MAX_CLASSES);
-  SQDET_UNSUPPORTED(cap > SQDET_VOC_MAX_DETECTIONS, "voc_evaluate: %d rows per image (limit %d)", cap, SQDET_VOC_MAX_DETECTIONS);
-  SQDET_UNSUPPORTED((long long)num_images * cap > 0x7fffffffLL, "voc_evaluate: %d images of %d rows: more than 2^31 table rows", num_images, cap);
-  hipStream_t st = as_stream(stream);
   const DetTable t = read_only_table(det_box, det_score, det_cls, det_count, status, num_images, cap);
+  if (const int rc = check_scoring_args("voc_evaluate", t, gt_offsets, workspace, host_ap07 && host_ap_area && host_npos && host_num_det,
+                                        gt_box && gt_cls && gt_difficult, num_gt, classes, SQDET_VOC_MAX_CLASSES))
+    return rc;
+  SQDET_REQUIRE(curve_cls < classes && (curve_cls < 0 || (curve_rec && curve_prec)), "voc_evaluate: bad curve class or null curve buffer");
+  hipStream_t st = as_stream(stream);
   const VocWorkspace w = carve(workspace, num_images, cap, classes);
+  const ClassLists L = {w.cnt_det, w.base, w.h->ndet, num_images};
   const size_t T = (size_t)num_images * cap;
   const unsigned C = (unsigned)classes, N = (unsigned)num_images;
   SQDET_CHECK_HIP(hipMemsetAsync(w.h, 0, sizeof(VocHeader), st));
   SQDET_CHECK_HIP(hipMemsetAsync(w.stp, 0, 2 * T * sizeof(int), st));   // stp and sfp are adjacent
-  hipLaunchKernelGGL(voc_count_kernel, dim3(N), dim3(64), 0, st, t, classes, gt_offsets, gt_cls, gt_difficult, num_gt, w.h, w.cnt_det,
-                     w.cnt_pos);
-  hipLaunchKernelGGL(voc_scan_kernel, dim3(C), dim3(SCAN), 0, st, num_images, w.h, w.cnt_det, w.cnt_pos, w.base);
-  hipLaunchKernelGGL(voc_match_kernel, dim3(N, C), dim3(64), 0, st, t, gt_offsets, gt_box, gt_cls, gt_difficult, num_gt, w.h, w.cnt_det,
-                     w.base, w.cscore, w.cflag);
+  hipLaunchKernelGGL(voc_count_kernel, dim3(N), dim3(64), 0, st, t, classes, gt_offsets, gt_cls, gt_difficult, num_gt, w.h, w.cnt_det);
+  hipLaunchKernelGGL(class_scan_kernel, dim3(C), dim3(SCAN), 0, st, L);
+  hipLaunchKernelGGL(voc_match_kernel, dim3(N, C), dim3(64), 0, st, t, gt_offsets, gt_box, gt_cls, gt_difficult, num_gt, L, w.cscore,
+                     w.cflag);
   hipLaunchKernelGGL(voc_rank_kernel, dim3((unsigned)((T + SCAN - 1) / SCAN), C), dim3(SCAN), 0, st, w.h, w.cscore, w.cflag, w.stp, w.sfp);
   hipLaunchKernelGGL(voc_prefix_kernel, dim3(C), dim3(SCAN), 0, st, w.h, w.stp, w.sfp);
   hipLaunchKernelGGL(voc_ap_kernel, dim3(C), dim3(SCAN), 0, st, w.h, w.stp, w.sfp, w.mpre, curve_cls, curve_rec, curve_prec);

@@ -1,6 +1,7 @@
 """The device detection table under the GPU evaluators (include/sqdet.h "Detection table", csrc/det_table.h):
-KittiEvaluator (kitti_ap.py) and VocEvaluator (voc.py) derive from DetectionTable and add their ground truth, workspace,
-scoring and file writers."""
+KittiEvaluator (kitti_ap.py), VocEvaluator (voc.py) and CocoEvaluator (coco.py) derive from DetectionTable, which holds the
+table, the ground truth's offsets, the workspace and the leading arguments of the scoring calls; they add their ground-truth
+fields, scoring and file writers."""
 import numpy as np
 import torch
 
@@ -14,19 +15,26 @@ def ptr(t):
     return _lib.C.c_void_p(t.data_ptr())
 
 
+def host_ptr(a):
+    """A host array's address for a C call."""
+    return a.ctypes.data_as(_lib.C.c_void_p)
+
+
 def row_offsets(per_image, message):
-    """Per-image row lists -> offsets int32 [N+1].  A list over MAX_GROUNDTRUTH: SqdetUnsupported(message % (image, rows,
-    limit))."""
+    """Per-image row lists -> (offsets int32 [N+1], the rows of all images in one list).  A list over MAX_GROUNDTRUTH:
+    SqdetUnsupported(message % (image, rows, limit))."""
     big = [i for i, r in enumerate(per_image) if len(r) > MAX_GROUNDTRUTH]
     if big:
         raise _lib.SqdetUnsupported(message % (big[0], len(per_image[big[0]]), MAX_GROUNDTRUTH))
-    return np.concatenate([[0], np.cumsum([len(r) for r in per_image])]).astype(np.int32)
+    return np.concatenate([[0], np.cumsum([len(r) for r in per_image])]).astype(np.int32), [row for r in per_image for row in r]
 
 
 class DetectionTable:
     """det_box / det_score / det_cls / det_count / status of gt.num_images images on `device`.  max_detections: rows per
     image the table holds (>= the filter's max_out; default mc.TOP_N_DETECTION, else 512).  classes: load_rows rejects a
-    class outside [0, classes) (None: not checked).  A subclass supplies _ingest(src, dst): its sqdet_*_ingest call."""
+    class outside [0, classes) (None: not checked).  Also on the device: gt.offsets (gt_offsets; num_gt rows in all) and the
+    scoring workspace.  A subclass supplies _ingest(src, dst): its sqdet_*_ingest call, and _workspace_bytes()."""
+    ROWS_FROM = "evaluate_detection_files"                      # who from_rows' error names
 
     def __init__(self, mc, gt, device="cuda:0", max_detections=None, classes=None):
         self.mc, self.gt, self.classes = mc, gt, classes
@@ -41,14 +49,17 @@ class DetectionTable:
         self.det_cls = torch.zeros((n, cap), dtype=torch.int32, device=dev)
         self.det_count = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.status = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self.gt_offsets, self.num_gt = self.up(gt.offsets, torch.int32), int(gt.offsets[-1])
+        self.workspace = torch.empty((max(1, self._workspace_bytes()),), dtype=torch.uint8, device=dev)
 
     @classmethod
-    def from_rows(cls, mc, gt, rows, device="cuda:0"):
-        """An evaluator whose table is just large enough for `rows` (load_rows' layout), filled with them."""
+    def from_rows(cls, mc, gt, rows, device="cuda:0", **kw):
+        """An evaluator (kw: its other constructor arguments) whose table is just large enough for `rows` (load_rows' layout),
+        filled with them."""
         cap = max([1] + [len(r) for r in rows])
         if cap > MAX_DETECTIONS:
-            raise _lib.SqdetUnsupported("evaluate_detection_files: %d detections in one image (limit %d)" % (cap, MAX_DETECTIONS))
-        ev = cls(mc, gt, device, max_detections=cap)
+            raise _lib.SqdetUnsupported("%s: %d detections in one image (limit %d)" % (cls.ROWS_FROM, cap, MAX_DETECTIONS))
+        ev = cls(mc, gt, device, max_detections=cap, **kw)
         ev.load_rows(rows)
         return ev
 
@@ -60,6 +71,10 @@ class DetectionTable:
     def table_args(self):
         """The leading arguments of the scoring calls: the four row tensors."""
         return ptr(self.det_box), ptr(self.det_score), ptr(self.det_cls), ptr(self.det_count)
+
+    def scoring_args(self):
+        """The leading arguments of the sqdet_*_evaluate calls: the table, its status and its dimensions."""
+        return self.table_args() + (ptr(self.status), self.gt.num_images, self.cap)
 
     def reset(self):
         """Empties the table (stream-ordered)."""

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, stream_ptr
-from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, ptr as _ptr, row_offsets  # noqa: F401
+from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, host_ptr as P, ptr as _ptr, row_offsets  # noqa: F401
 from .util import bbox_transform_inv
 
 CLASS_NAMES = ("car", "pedestrian", "cyclist")                  # the evaluator's classes (= kitti.py:22)
@@ -110,14 +110,12 @@ class GroundTruth:
         if len(raw) != len(rois):
             raise ValueError("GroundTruth: %d label lists for %d roi lists" % (len(raw), len(rois)))
         self.num_images = len(raw)
-        self.offsets = row_offsets(raw, "KITTI evaluation: image %d has %d ground-truth rows (limit %d)")
-        self.roi_offsets = row_offsets(rois, "KITTI evaluation: image %d has %d roi rows (limit %d)")
-        flat = [row for r in raw for row in r]
+        self.offsets, flat = row_offsets(raw, "KITTI evaluation: image %d has %d ground-truth rows (limit %d)")
+        self.roi_offsets, rflat = row_offsets(rois, "KITTI evaluation: image %d has %d roi rows (limit %d)")
         self.box = np.array([row[1:5] for row in flat], np.float64).reshape(-1, 4)
         self.truncation = np.array([row[5] for row in flat], np.float64)
         self.occlusion = np.array([row[6] for row in flat], np.int32)
         self.type = np.array([row[0] for row in flat], np.int32)
-        rflat = [row for r in rois for row in r]
         self.roi_box = np.array([row[:4] for row in rflat], np.float64).reshape(-1, 4)
         self.roi_cls = np.array([int(row[4]) for row in rflat], np.int32)
 
@@ -179,15 +177,15 @@ class KittiEvaluator(DetectionTable):
             raise _lib.SqdetError("KittiEvaluator: the KITTI classes %s are required, got %s" % (CLASS_NAMES, mc.CLASS_NAMES))
         super().__init__(mc, gt, device, max_detections)
         up = self.up
-        self.gt_offsets = up(gt.offsets, torch.int32)
         self.gt_box, self.gt_trunc = up(gt.box, torch.float64), up(gt.truncation, torch.float64)
         self.gt_occ, self.gt_type = up(gt.occlusion, torch.int32), up(gt.type, torch.int32)
-        self.num_gt = int(gt.offsets[-1])
         self.roi_offsets, self.roi_box, self.roi_cls = up(gt.roi_offsets, torch.int32), up(gt.roi_box, torch.float64), up(gt.roi_cls, torch.int32)
         self.num_rois = int(gt.roi_offsets[-1])
-        self.workspace = torch.empty((lib().sqdet_kitti_eval_workspace_bytes(self.num_gt),), dtype=torch.uint8, device=self.device)
         self.precision = self.aps_raw = self.evaluated = self.analysis = None
         self._records = None
+
+    def _workspace_bytes(self):
+        return lib().sqdet_kitti_eval_workspace_bytes(self.num_gt)
 
     def _ingest(self, src, dst):
         check(lib().sqdet_kitti_ingest(*src, *dst), "sqdet_kitti_ingest")
@@ -199,8 +197,7 @@ class KittiEvaluator(DetectionTable):
         prec = np.zeros((9, 41), np.float64)
         ap = np.zeros(9, np.float64)
         ev = np.zeros(3, np.int32)
-        P = lambda a: a.ctypes.data_as(_lib.C.c_void_p)
-        check(lib().sqdet_kitti_evaluate(*self.table_args(), _ptr(self.status), self.gt.num_images, self.cap, _ptr(self.gt_offsets), _ptr(self.gt_box),
+        check(lib().sqdet_kitti_evaluate(*self.scoring_args(), _ptr(self.gt_offsets), _ptr(self.gt_box),
                                          _ptr(self.gt_trunc), _ptr(self.gt_occ), _ptr(self.gt_type), self.num_gt,
                                          _ptr(self.workspace), P(prec), P(ap), P(ev), stream_ptr()), "sqdet_kitti_evaluate")
         self.precision, self.aps_raw, self.evaluated = prec, ap, ev

@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, stream_ptr
-from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, ptr as _ptr, row_offsets  # noqa: F401
+from .det_table import MAX_DETECTIONS, MAX_GROUNDTRUTH, DetectionTable, host_ptr as P, ptr as _ptr, row_offsets  # noqa: F401
 from .util import bbox_transform_inv
 
 MAX_CLASSES = 64                                                 # SQDET_VOC_MAX_CLASSES
@@ -83,8 +83,7 @@ class GroundTruth:
 
     def __init__(self, raw):
         self.num_images = len(raw)
-        self.offsets = row_offsets(raw, "VOC evaluation: image %d has %d objects (limit %d)")
-        flat = [row for r in raw for row in r]
+        self.offsets, flat = row_offsets(raw, "VOC evaluation: image %d has %d objects (limit %d)")
         self.cls = np.array([row[0] for row in flat], np.int32)
         self.box = np.array([row[1:5] for row in flat], np.float64).reshape(-1, 4)
         self.difficult = np.array([row[5] for row in flat], np.int32)
@@ -115,13 +114,12 @@ class VocEvaluator(DetectionTable):
         if not 0 < len(self.class_names) <= MAX_CLASSES:
             raise _lib.SqdetUnsupported("VocEvaluator: %d classes (limit %d)" % (len(self.class_names), MAX_CLASSES))
         super().__init__(mc, gt, device, max_detections, classes=len(self.class_names))
-        self.gt_offsets = self.up(gt.offsets, torch.int32)
         self.gt_box, self.gt_cls, self.gt_difficult = self.up(gt.box, torch.float64), self.up(gt.cls, torch.int32), self.up(gt.difficult, torch.int32)
-        self.num_gt = int(gt.offsets[-1])
-        self.workspace = torch.empty((max(1, lib().sqdet_voc_eval_workspace_bytes(gt.num_images, self.cap, self.classes)),),
-                                     dtype=torch.uint8, device=self.device)
         self._curve_rec = self._curve_prec = None
         self.ap07 = self.ap_area = self.npos = self.num_det = None
+
+    def _workspace_bytes(self):
+        return lib().sqdet_voc_eval_workspace_bytes(self.gt.num_images, self.cap, self.classes)
 
     def _ingest(self, src, dst):
         check(lib().sqdet_voc_ingest(*src, self.classes, *dst), "sqdet_voc_ingest")
@@ -133,8 +131,7 @@ class VocEvaluator(DetectionTable):
         if curve_cls >= 0 and self._curve_rec is None:
             self._curve_rec = torch.empty((self.gt.num_images * self.cap,), dtype=torch.float64, device=self.device)
             self._curve_prec = torch.empty_like(self._curve_rec)
-        P = lambda a: a.ctypes.data_as(_lib.C.c_void_p)
-        check(lib().sqdet_voc_evaluate(*self.table_args(), _ptr(self.status), self.gt.num_images, self.cap, C, _ptr(self.gt_offsets), _ptr(self.gt_box),
+        check(lib().sqdet_voc_evaluate(*self.scoring_args(), C, _ptr(self.gt_offsets), _ptr(self.gt_box),
                                        _ptr(self.gt_cls), _ptr(self.gt_difficult), self.num_gt, _ptr(self.workspace), P(ap07),
                                        P(ap_area), P(npos), P(ndet), int(curve_cls),
                                        _ptr(self._curve_rec) if curve_cls >= 0 else None,

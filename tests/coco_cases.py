@@ -157,3 +157,35 @@ def random_case(seed=7):
     dets = [sorted(r, key=lambda row: row[0]) for r in dets]          # class-major, order kept within a class
     assert max(len(r) for r in dets) <= 160 and not any(g[0] == 2 for r in gts for g in r)
     return dets, gts, classes
+
+
+def long_case(seed=300):
+    """The second seeded case of tests/test_gpu_coco_ap.py: 300 images (more than the 256 the evaluator's scan over images
+    takes at a time), 2 classes with more than 256 kept rows each (the accumulate kernel walks a class's list 256 rows at a
+    time, from its end) -> (dets, gts, classes).  Image 5: 120 rows of class 0 (more than maxDets[-1] = 100: 100 are kept).
+    Images without rows (i % 11 == 5, i != 5) and without objects (i % 7 == 3), crowd and ignore objects, scores on a grid of
+    1/16: equal scores across images are the rule."""
+    rs = np.random.RandomState(seed)
+    n_img, classes = 300, 2
+    gts, dets = [], []
+    for i in range(n_img):
+        g = []
+        for _ in range(0 if i % 7 == 3 else int(rs.randint(1, 4))):
+            w, h = int(rs.randint(8, 120)), int(rs.randint(8, 120))
+            u = rs.uniform()
+            g.append(_gt(int(rs.randint(0, 2)), int(rs.randint(0, 400)), int(rs.randint(0, 300)), w, h, crowd=int(u < 0.1),
+                         ignore=int(0.1 <= u < 0.2)))
+        rows = []
+        for _ in range(120 if i == 5 else 0 if i % 11 == 5 else int(rs.randint(0, 5))):
+            c = 0 if i == 5 else int(rs.randint(0, 2))
+            if g and rs.uniform() < 0.6:                              # on an object, exact or shifted by a few pixels
+                o = g[int(rs.randint(len(g)))]
+                d = [0, 0, 0, 0] if rs.uniform() < 0.4 else [int(v) for v in rs.randint(-6, 7, 4)]
+                x, y, w, h = o[1] + d[0], o[2] + d[1], max(1, o[3] + d[2]), max(1, o[4] + d[3])
+                c = o[0] if i != 5 else 0
+            else:
+                x, y, w, h = int(rs.randint(0, 400)), int(rs.randint(0, 300)), int(rs.randint(8, 120)), int(rs.randint(8, 120))
+            rows.append((c, x, y, w, h, float(rs.randint(1, 16)) / 16.0))
+        gts.append(g)
+        dets.append(sorted(rows, key=lambda row: row[0]))            # class-major, order kept within a class
+    return dets, gts, classes

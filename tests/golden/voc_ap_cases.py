@@ -173,8 +173,36 @@ def _voc20():
     return _seeded(VOC20, 6, 20)
 
 
+def _wide():
+    """300 images, 2 classes: more images than PREFIX_BLOCK, so where an image's rows start in its class's list needs the total
+    carried from the images before (the evaluator's scan over images works PREFIX_BLOCK at a time).  1-2 objects and 0-3
+    detections in most images; images without detections (k % 11 == 5) and without objects (k % 7 == 3)."""
+    rs = np.random.RandomState(300)
+    names = ("a", "b")
+    b = _Builder(names)
+    pools = [_scores(rs, 990) for _ in names]
+    for k in range(300):
+        objs, dets = [], []
+        for _ in range(0 if k % 7 == 3 else rs.randint(1, 3)):
+            c = rs.randint(2)
+            x1, y1 = rs.randint(1, 400), rs.randint(1, 280)
+            objs.append((names[c], x1, y1, x1 + rs.randint(12, 120), y1 + rs.randint(12, 90), int(rs.uniform() < 0.2)))
+        for _ in range(0 if k % 11 == 5 else rs.randint(0, 4)):
+            if objs and rs.uniform() < 0.6:                         # on an object, mostly of its class
+                name, x1, y1, x2, y2, _ = objs[rs.randint(len(objs))]
+                w, h = x2 - x1, y2 - y1
+                j = rs.normal(0, 0.08, 4) * np.array([w, h, w, h])
+                dc = names.index(name) if rs.uniform() < 0.85 else rs.randint(2)
+                dets.append((dc, (x1 + w / 2.0 + j[0], y1 + h / 2.0 + j[1], w + j[2], h + j[3])))
+            else:
+                dets.append((rs.randint(2), (rs.uniform(10, 480), rs.uniform(10, 350), rs.uniform(8, 150), rs.uniform(8, 120))))
+        b.image(objs, [(dc, box, pools[dc].pop()) for dc, box in dets])
+    assert len(b.image_idx) > PREFIX_BLOCK
+    return b.case()
+
+
 CASES = {"single": _single, "greedy": _greedy, "argmax_first": _argmax_first, "arange_edge": _arange_edge,
-         "long_segments": _long_segments, "many": _many, "ties": _ties, "voc20": _voc20}
+         "long_segments": _long_segments, "many": _many, "ties": _ties, "voc20": _voc20, "wide": _wide}
 
 
 def make_case(name):

@@ -83,6 +83,30 @@ def test_random_case_is_the_restatement_bit_for_bit(random_case):
     assert np.array_equal(_bits(ev.precision), _bits(p1)) and np.array_equal(_bits(ev.recall), _bits(r1)) and torch.equal(ev.row_word, w1)
 
 
+def test_long_case_is_the_restatement_bit_for_bit():
+    """300 images, 2 classes (tests/coco_cases.long_case): more images than the scan over images takes at once and more kept
+    rows per class than the accumulate kernel walks at once, so both carries run; 120 rows of one class in one image (100
+    kept), crowd / ignore objects, images without rows and without objects, equal scores across images."""
+    from squeezedet_amd import coco as CO
+    dets, gts, classes = CC.long_case()
+    precision, recall, flags = CR.evaluate(dets, gts, classes)
+    assert len(dets) > 256 and all(len(f[0]) > 256 for f in flags) and len(flags) == 2       # a later edit cannot shrink the case
+    assert max(sum(1 for r in d if r[0] == 0) for d in dets) == 120 and not all(dets) and not all(gts)
+    assert any(g[6] for gi in gts for g in gi) and any(g[7] for gi in gts for g in gi)
+    ev = _evaluator(dets, gts, classes)
+    stats = ev.evaluate()
+    _same_flags(ev.row_flags(), flags)
+    assert ev.num_det.tolist() == [len(f[0]) for f in flags]
+    assert np.array_equal(_bits(ev.precision), _bits(precision)), np.argwhere(ev.precision != precision)[:8]
+    assert np.array_equal(_bits(ev.recall), _bits(recall)), np.argwhere(ev.recall != recall)[:8]
+    assert np.array_equal(_bits(stats), _bits(CO.summarize_arrays(precision, recall)))
+    assert 0 < stats[0] < 1 and len(set(ev.precision[ev.precision > -1].tolist())) > 10               # not a trivial table
+    # a second call: bitwise the same
+    p1, r1, w1 = ev.precision.copy(), ev.recall.copy(), ev.row_word.clone()
+    ev.evaluate()
+    assert np.array_equal(_bits(ev.precision), _bits(p1)) and np.array_equal(_bits(ev.recall), _bits(r1)) and torch.equal(ev.row_word, w1)
+
+
 @pytest.mark.parametrize("name", sorted(CC.CASES))
 def test_hand_cases_through_the_kernel(name):
     from squeezedet_amd import coco as CO

@@ -105,6 +105,7 @@ struct sqdet_net {
   // live probe: start/stop events around ONE layer's launch inside sqdet_net_forward
   int probe_layer = -1;
   int probe_count = 0;
+  int probe_max = 0;                     // max_records of the latest sqdet_net_set_probe (probe_events only ever grows)
   std::vector<hipEvent_t> probe_events;  // 2 per record
   // sqdet_net_set_scores: when not NULL the ConvDet launch (last layer) also writes interpret_output's det_probs there
   float* scores = nullptr;
@@ -900,7 +901,7 @@ extern "C" int sqdet_net_forward(sqdet_net_t* net, const void* image_input, void
   if (frc != SQDET_OK) return frc;
   const int nl = (int)net->layers.size();
   auto one = [&](int i, int n0, int nb, hipStream_t ls) -> int {
-    const bool probe = n0 == 0 && i == net->probe_layer && 2 * (net->probe_count + 1) <= (int)net->probe_events.size();
+    const bool probe = n0 == 0 && i == net->probe_layer && net->probe_count < net->probe_max;
     if (probe) SQDET_CHECK_HIP(hipEventRecord(net->probe_events[2 * net->probe_count], ls));
     const int rc = run_layer_part(net, net->layers[i], image_input, preds, n0, nb, ls);
     if (rc != SQDET_OK) return rc;
@@ -991,11 +992,13 @@ extern "C" int sqdet_net_set_probe(sqdet_net_t* net, int layer_index, int max_re
                 "net_set_probe: bad arguments");
   net->probe_layer = layer_index;
   net->probe_count = 0;
+  net->probe_max = 0;                    // (raised once the events exist)
   while ((int)net->probe_events.size() < 2 * max_records) {
     hipEvent_t e;
     SQDET_CHECK_HIP(hipEventCreate(&e));
     net->probe_events.push_back(e);
   }
+  net->probe_max = max_records;
   return SQDET_OK;
 }
 
@@ -1042,9 +1045,10 @@ extern "C" int sqdet_net_forward_timed(sqdet_net_t* net, const void* image_input
   SQDET_CHECK_HIP(hipEventRecord(net->events[0], st));
   for (size_t i = 0; i < nl; ++i) {
     const int rc = run_layer(net, net->layers[i], image_input, preds, st);
-    if (rc != SQDET_OK) return rc;
+    if (rc != SQDET_OK) { net->job_set = false; return rc; }
     SQDET_CHECK_HIP(hipEventRecord(net->events[i + 1], st));
   }
+  net->job_set = false;      // (one-shot, as in sqdet_net_forward: the riders went out with this forward's fire_chain launches)
   SQDET_CHECK_HIP(hipEventSynchronize(net->events[nl]));
   for (size_t i = 0; i < nl; ++i) SQDET_CHECK_HIP(hipEventElapsedTime(&host_ms[i], net->events[i], net->events[i + 1]));
   return SQDET_OK;

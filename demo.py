@@ -7,12 +7,17 @@ cv2 is replaced by PIL for file I/O.
 
     python demo.py --input_path 'data/*.png' --out_dir out/ [--weights weights.npz] [--demo_net squeezeDet] [--draw gpu]
     python demo.py --mode video --input_path 'frames/*.png' --out_dir out/ [--crop 500 205 239 439] [--batch 8]
+    python demo.py --mode video --input_path 'frames/*.png' --out_dir out/ --track [--track_out tracks.txt]
 
 --draw pil (default): boxes and labels are drawn with PIL on a host-resized copy of the image.  --draw gpu: they are drawn on
 the device into the preprocessed network input (squeezedet_amd.viz: one launch, the means added back), in the reference's
 cls2clr colours.  --mode video takes a glob of FRAME FILES, sorted by name -- there is no video decoder here -- crops them
 (--crop TOP BOTTOM LEFT RIGHT rows / columns cut off, the reference's frame[500:-205, 239:-439]), runs them in batches of
 --batch with everything from the mean subtraction to the drawing on the device, and writes <out_dir>/%06d.jpg per frame.
+--track (video only) runs the device tracker (squeezedet_amd.track) behind the filter, across batches: the boxes of confirmed
+tracks are drawn as "<name> #<id>", one colour per id, in place of the per-detection boxes.  --track_out FILE writes them as
+MOT-challenge text, `frame,id,left,top,width,height,score,-1,-1,-1` per confirmed row: frame 1-based, network-input pixels.
+--track_opts iou_thresh=0.3,min_hits=3,...: the tracker's parameters (track.PARAMS).
 
 --weights: a {variable name: array} file written by squeezedet_amd.weights.save_params (or converted from a
 reference checkpoint with squeezedet_amd.weights.from_reference_names); without it seeded synthetic weights
@@ -60,7 +65,18 @@ def parse_args(argv=None):
     ap.add_argument("--crop", type=int, nargs=4, default=[500, 205, 239, 439], metavar=("T", "B", "L", "R"),
                     help="video: rows cut off the top / bottom and columns off the left / right of every frame")
     ap.add_argument("--batch", type=int, default=1, help="video: frames per forward pass")
+    # (the tracking flags exist on the namespace only when given: a run without them has the arguments it always had)
+    ap.add_argument("--track", action="store_true", default=argparse.SUPPRESS,
+                    help="video: track the detections across frames and draw the confirmed tracks")
+    ap.add_argument("--track_out", default=argparse.SUPPRESS, metavar="FILE",
+                    help="video, with --track: write the confirmed rows as MOT-challenge text")
+    ap.add_argument("--track_opts", default=argparse.SUPPRESS, metavar="K=V,...",
+                    help="video, with --track: tracker parameters, e.g. min_hits=2,max_age=10")
     a = ap.parse_args(argv)
+    if hasattr(a, "track") and a.mode != "video":
+        ap.error("--track needs --mode video")
+    if (hasattr(a, "track_out") or hasattr(a, "track_opts")) and not hasattr(a, "track"):
+        ap.error("--track_out / --track_opts need --track")
     if a.mode == "video":
         assert a.demo_net in ("squeezeDet", "squeezeDet+"), "Selected nueral net architecture not supported: {}".format(a.demo_net)
         if a.batch < 1 or min(a.crop) < 0:
@@ -131,6 +147,7 @@ def video_demo(a):
     frames = sorted(glob.glob(a.input_path))
     top, bottom, left, right = a.crop
     count = 0
+    tracker = VideoTracker(a, mc, model.device) if getattr(a, "track", False) else None
     for i0 in range(0, len(frames), a.batch):
         t_start = time.time()
         crops = []
@@ -152,14 +169,54 @@ def video_demo(a):
         torch.cuda.synchronize(model.device)
         t_filter = time.time()
         from squeezedet_amd import viz
-        items = viz.make_items(ob, oc, cnt, list(mc.CLASS_NAMES), probs=op, plot_thresh=mc.PLOT_PROB_THRESH,
-                               class_colors=[CLS2CLR.get(c, (0, 255, 0)) for c in mc.CLASS_NAMES], label="name: (p)")
+        if tracker is not None:
+            items = tracker.items(ob, op, oc, cnt, count)      # only the n real frames: the padding never reaches the tracker
+        else:
+            items = viz.make_items(ob, oc, cnt, list(mc.CLASS_NAMES), probs=op, plot_thresh=mc.PLOT_PROB_THRESH,
+                                   class_colors=[CLS2CLR.get(c, (0, 255, 0)) for c in mc.CLASS_NAMES], label="name: (p)")
         pics = viz.draw(input_image[:n].contiguous(), items, bgr_means=mc.BGR_MEANS, order="rgb").cpu().numpy()
         for im in pics:
             count += 1
             Image.fromarray(im).save(os.path.join(a.out_dir, str(count).zfill(6) + ".jpg"))
         print("Total time: {:.4f}, detection time: {:.4f}, filter time: {:.4f}".format(time.time() - t_start, t_detect - t_reshape,
                                                                                         t_filter - t_detect))
+
+
+class VideoTracker:
+    """--track: one stream of tracks across the batches of video_demo (S = 1, F = the batch's real frames)."""
+
+    def __init__(self, a, mc, device):
+        import torch
+        from squeezedet_amd import track, viz
+        opts = {}
+        for kv in filter(None, getattr(a, "track_opts", "").split(",")):
+            k, _, v = kv.partition("=")
+            opts[k.strip()] = int(v) if k.strip() in ("min_hits", "max_age") else float(v)
+        self.track, self.mc = track, mc
+        self.tracker = track.Tracker(1, device, **opts)
+        self.names = viz.pack_names(list(mc.CLASS_NAMES), device)
+        self.palette = torch.tensor(np.asarray(track.PALETTE, np.uint8)).to(device)
+        self.path = getattr(a, "track_out", "")
+        if self.path:
+            open(self.path, "w").close()           # truncated here, appended to batch by batch: no handle is held across the loop
+
+    def items(self, ob, op, oc, cnt, frames_before):
+        """The draw items of this batch's confirmed tracks; appends their MOT lines (frame = frames_before + 1 + index)."""
+        ids, states = self.tracker.update(ob, op, oc, cnt, frames_per_stream=int(ob.shape[0]))
+        items = self.track.make_track_items(ob, op, oc, cnt, ids, states, self.names, plot_thresh=self.mc.PLOT_PROB_THRESH,
+                                            palette=self.palette)
+        if self.path:
+            lines = []
+            b, p, n, i, s = (t.cpu().numpy() for t in (ob, op, cnt, ids, states))
+            for f in range(b.shape[0]):
+                for j in range(min(max(int(n[f]), 0), b.shape[1])):
+                    if s[f, j] == 2 and i[f, j] > 0:
+                        cx, cy, w, h = (float(v) for v in b[f, j])
+                        lines.append("%d,%d,%.2f,%.2f,%.2f,%.2f,%.4f,-1,-1,-1\n" % (frames_before + 1 + f, i[f, j], cx - w / 2, cy - h / 2, w, h,
+                                                                                 float(p[f, j])))
+            with open(self.path, "a") as out:
+                out.writelines(lines)
+        return items
 
 
 def main(argv=None):

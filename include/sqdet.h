@@ -911,6 +911,91 @@ int sqdet_draw_build_items(const void* boxes, int boxes_f64, const float* probs,
                            int32_t* item_counts, int cap, sqdet_stream_t stream);
 int sqdet_draw_font5x7(unsigned char* host_out, size_t capacity);
 
+/* ------------------------------------------------------------ tracking --
+ * Object identities across the frames of a video or of a bank of cameras: tracking-by-detection over the rows that
+ * sqdet_detect_filter* / sqdet_filter_prediction emit (out_boxes float32 [n,rows,4] (cx,cy,w,h), out_probs float32 [n,rows],
+ * out_cls int32 [n,rows], out_count int32 [n]).  The reference has no counterpart: this stage is the project's own, placed
+ * behind the filter so that the rows never go back to the host.  All arithmetic is float64, every operator below ONE IEEE
+ * operation in the order written (csrc/track.hip is built without contraction), so a sequential NumPy restatement
+ * (tests/track_reference.py) agrees with the tables and outputs bit for bit.
+ *
+ * There are S independent STREAMS, each with SQDET_TRACK_CAP (64) track slots.  A call processes n = S*F images: image s*F + f
+ * is frame f of stream s, and a stream's F frames are processed in order (a video: S = 1, F = batch; a camera bank: S = batch,
+ * F = 1).  rows <= 64, else SQDET_EUNSUPPORTED.
+ *
+ * State per slot: for each coordinate c of (cx, cy, w, h) a constant-velocity filter, x[c] = (p, v) and P[c] = (pp, pv, vv);
+ * int32 cls, id, state (0 free, 1 tentative, 2 confirmed), hits, miss, age; float32 score.  Per stream: int32 next_id (1 after
+ * a reset) and dropped.  A reset is: every table zero, next_id one.  A freed slot keeps its other fields as they were.
+ *
+ * One frame of one stream -- slots and rows are always visited in ascending index:
+ *  1. count = clamp(out_count, 0, rows) (the filter reports an overflow as a negative count).
+ *  2. Predict every live slot (state != 0): h = max(x[h].p, 1.0); qp = (w_pos*h)*(w_pos*h); qv = (w_vel*h)*(w_vel*h); per
+ *     coordinate p = p + v, pp' = ((pp + pv) + (pv + vv)) + qp, pv' = pv + vv, vv' = vv + qv; age += 1.  The predicted box is
+ *     (p_cx, p_cy, max(p_w, 1.0), max(p_h, 1.0)).
+ *  3. Valid rows: d < count, the four box values and the prob finite, w > 0 and h > 0.  An invalid row takes part in nothing.
+ *     High rows: double(prob) > high_thresh.  Low rows: low_thresh < double(prob) <= high_thresh.
+ *  4. Affinity M[t,d] of a live slot t and a valid row d of the same class: the IoU of the predicted box (1) and the row's box
+ *     widened to double (2) in the expression of the reference's util.iou (utils/util.py:9-30):
+ *     lr = min(cx1 + 0.5*w1, cx2 + 0.5*w2) - max(cx1 - 0.5*w1, cx2 - 0.5*w2), tb likewise; both > 0: inter = lr*tb,
+ *     M = inter / (w1*h1 + w2*h2 - inter); else 0.  Another class: 0.  (min(a, b) is b < a ? b : a, max(a, b) is b > a ? b : a.)
+ *  5. Greedy association of a set of slots and a set of rows: repeatedly take the free pair with the largest M -- ties go to
+ *     the lower slot, then the lower row -- and stop when no free pair has M >= iou_thresh.  Stage one: all live slots x high
+ *     rows.  Stage two: the still unmatched CONFIRMED slots x low rows.
+ *  6. Update every matched slot, with h = max(x[h].p, 1.0) after the predict and r = (w_pos*h)*(w_pos*h); per coordinate, z the
+ *     row's value: y = z - p; s = pp + r; kp = pp / s; kv = pv / s; p = p + kp*y; v = v + kv*y; pp' = pp - kp*pp;
+ *     pv' = pv - kp*pv; vv' = vv - kv*pv.  hits += 1, miss = 0, score = prob; a tentative slot becomes confirmed when
+ *     hits >= min_hits.  det_track_id[d] = id, det_track_state[d] = state.
+ *  7. Every unmatched live slot: miss += 1; it is freed if it was tentative or if miss > max_age.
+ *  8. Every unmatched high row, in row order, takes the lowest free slot (one freed in step 7 included): x[c] = (z, 0),
+ *     P[c] = (a*a, 0, b*b) with h = max(z_h, 1.0), a = (2*w_pos)*h, b = (10*w_vel)*h; cls and score from the row;
+ *     id = next_id++, hits = 1, miss = 0, age = 1; tentative, or confirmed when min_hits <= 1.  The row gets the new id and
+ *     state.  No free slot: dropped += 1 and the row gets nothing.
+ *  9. Every row j < rows that got nothing -- invalid, unmatched low, dropped, j >= count -- has det_track_id -1 and
+ *     det_track_state 0.
+ *
+ * sqdet_track_update: ONE launch, asynchronous on `stream`, allocates nothing, validates its arguments before it touches the
+ * device.  tables: HOST struct of device pointers, the caller's: x float64 [S,64,4,2], P float64 [S,64,4,3], cls / id /
+ * state / hits / miss / age int32 [S,64], score float32 [S,64], next_id / dropped int32 [S].  params: HOST struct;
+ * iou_thresh > 0, thresholds and weights finite, min_hits and max_age >= 0.  Outputs det_track_id, det_track_state int32
+ * [n,rows].  Stream s is walked by one workgroup; max_workgroups > 0: the S streams are walked by at most that many workgroups
+ * (<= 0: one per stream), as sqdet_detect_filter_scored does.
+ *
+ * sqdet_track_build_items: draw items (sqdet_draw_items) from detection rows and the two outputs.  Image i keeps, in order,
+ * its rows j < clamp(counts[i], 0, rows) with det_track_state == 2, det_track_id > 0 and double(prob) > plot_thresh.
+ * Coordinates as sqdet_draw_build_items with float32 boxes and diagonal = 0; the label is "<name> #<id>" ('?' for a class
+ * out of range), cut at SQDET_DRAW_LABEL_MAX bytes; the colour is palette[id % palette_len], palette a device uint8
+ * [palette_len,3] (BGR).  rows > cap or cap > SQDET_DRAW_MAX_ITEMS: SQDET_EUNSUPPORTED. */
+#define SQDET_TRACK_CAP 64
+typedef struct sqdet_track_tables {
+  double* x;
+  double* P;
+  int32_t* cls;
+  int32_t* id;
+  int32_t* state;
+  int32_t* hits;
+  int32_t* miss;
+  int32_t* age;
+  float* score;
+  int32_t* next_id;
+  int32_t* dropped;
+} sqdet_track_tables_t;
+typedef struct sqdet_track_params {
+  double iou_thresh;      /* 0.3 */
+  double high_thresh;     /* 0.5 */
+  double low_thresh;      /* 0.1 */
+  double w_pos;           /* 1/20 */
+  double w_vel;           /* 1/160 */
+  int32_t min_hits;       /* 3 */
+  int32_t max_age;        /* 30 */
+} sqdet_track_params_t;
+int sqdet_track_update(const sqdet_track_tables_t* tables, const float* boxes, const float* probs, const int32_t* cls,
+                       const int32_t* counts, int streams, int frames, int rows, const sqdet_track_params_t* params,
+                       int32_t* det_track_id, int32_t* det_track_state, int max_workgroups, sqdet_stream_t stream);
+int sqdet_track_build_items(const float* boxes, const float* probs, const int32_t* cls, const int32_t* counts,
+                            const int32_t* det_track_id, const int32_t* det_track_state, int n, int rows, double plot_thresh,
+                            const unsigned char* names, int classes, const unsigned char* palette, int palette_len, int anchor,
+                            void* items, int32_t* item_counts, int cap, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------ utilities --
  * Device -> pinned-host copy issued as a KERNEL: dst is host memory mapped into the device's address space
  * (hipHostMalloc); nbytes a multiple of 16.  Used by the serving loop to hand the <= 64 filtered rows per image

@@ -17,7 +17,10 @@ cls2clr colours.  --mode video takes a glob of FRAME FILES, sorted by name -- th
 --track (video only) runs the device tracker (squeezedet_amd.track) behind the filter, across batches: the boxes of confirmed
 tracks are drawn as "<name> #<id>", one colour per id, in place of the per-detection boxes.  --track_out FILE writes them as
 MOT-challenge text, `frame,id,left,top,width,height,score,-1,-1,-1` per confirmed row: frame 1-based, network-input pixels.
---track_opts iou_thresh=0.3,min_hits=3,...: the tracker's parameters (track.PARAMS).
+--track_opts iou_thresh=0.3,min_hits=3,...: the tracker's parameters (track.PARAMS).  --track_gt FILE scores the tracks against
+labelled objects on the device (squeezedet_amd.mot: MOTA, MOTP, IDF1, switches, fragmentations) and prints the summary at the
+end; FILE is a KITTI tracking label file (--track_gt_format kitti, per class) or a MOTChallenge gt.txt (mot, one class), its
+boxes in network-input pixels, its first frame the first frame file.
 
 --weights: a {variable name: array} file written by squeezedet_amd.weights.save_params (or converted from a
 reference checkpoint with squeezedet_amd.weights.from_reference_names); without it seeded synthetic weights
@@ -72,7 +75,13 @@ def parse_args(argv=None):
                     help="video, with --track: write the confirmed rows as MOT-challenge text")
     ap.add_argument("--track_opts", default=argparse.SUPPRESS, metavar="K=V,...",
                     help="video, with --track: tracker parameters, e.g. min_hits=2,max_age=10")
+    ap.add_argument("--track_gt", default=argparse.SUPPRESS, metavar="FILE",
+                    help="video, with --track: labelled objects to score the tracks against (MOTA, MOTP, IDF1), printed at the end")
+    ap.add_argument("--track_gt_format", default=argparse.SUPPRESS, choices=["kitti", "mot"],
+                    help="video, with --track_gt: a KITTI tracking label file (default) or a MOTChallenge gt.txt")
     a = ap.parse_args(argv)
+    if (hasattr(a, "track_gt") and not hasattr(a, "track")) or (hasattr(a, "track_gt_format") and not hasattr(a, "track_gt")):
+        ap.error("--track_gt needs --track, --track_gt_format needs --track_gt")
     if hasattr(a, "track") and a.mode != "video":
         ap.error("--track needs --mode video")
     if (hasattr(a, "track_out") or hasattr(a, "track_opts")) and not hasattr(a, "track"):
@@ -180,6 +189,8 @@ def video_demo(a):
             Image.fromarray(im).save(os.path.join(a.out_dir, str(count).zfill(6) + ".jpg"))
         print("Total time: {:.4f}, detection time: {:.4f}, filter time: {:.4f}".format(time.time() - t_start, t_detect - t_reshape,
                                                                                         t_filter - t_detect))
+    if tracker is not None and tracker.acc is not None:
+        print(tracker.summary())
 
 
 class VideoTracker:
@@ -199,12 +210,23 @@ class VideoTracker:
         self.path = getattr(a, "track_out", "")
         if self.path:
             open(self.path, "w").close()           # truncated here, appended to batch by batch: no handle is held across the loop
+        self.acc = None
+        if getattr(a, "track_gt", ""):             # --track_gt: the tracks are scored where they are, batch by batch
+            from squeezedet_amd import mot
+            self.mot, self.per_class = mot, getattr(a, "track_gt_format", "kitti") == "kitti"
+            self.gt = (mot.MotGroundTruth.from_kitti_tracking(a.track_gt, list(mc.CLASS_NAMES)) if self.per_class
+                       else mot.MotGroundTruth.from_mot_text(a.track_gt))
+            self.acc = mot.MotAccumulator(1, device, len(mc.CLASS_NAMES) if self.per_class else 1)
 
     def items(self, ob, op, oc, cnt, frames_before):
         """The draw items of this batch's confirmed tracks; appends their MOT lines (frame = frames_before + 1 + index)."""
         ids, states = self.tracker.update(ob, op, oc, cnt, frames_per_stream=int(ob.shape[0]))
         items = self.track.make_track_items(ob, op, oc, cnt, ids, states, self.names, plot_thresh=self.mc.PLOT_PROB_THRESH,
                                             palette=self.palette)
+        if self.acc is not None:
+            n = int(ob.shape[0])
+            self.acc.update(ob, oc if self.per_class else oc * 0, cnt, ids, states,
+                            self.gt.device(ob.device, frames_before + 1, n, self.gt.max_objects), frames_per_stream=n)
         if self.path:
             lines = []
             b, p, n, i, s = (t.cpu().numpy() for t in (ob, op, cnt, ids, states))
@@ -217,6 +239,11 @@ class VideoTracker:
             with open(self.path, "a") as out:
                 out.writelines(lines)
         return items
+
+
+    def summary(self):
+        """--track_gt: the evaluation of everything seen so far, as text."""
+        return self.mot.format_summary(self.acc.evaluate(), list(self.mc.CLASS_NAMES) if self.per_class else ["all"])
 
 
 def main(argv=None):

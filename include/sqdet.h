@@ -996,6 +996,109 @@ int sqdet_track_build_items(const float* boxes, const float* probs, const int32_
                             const unsigned char* names, int classes, const unsigned char* palette, int palette_len, int anchor,
                             void* items, int32_t* item_counts, int cap, sqdet_stream_t stream);
 
+/* ------------------------------------------------- tracking evaluation --
+ * The published CLEAR-MOT counts (MOTA, MOTP, identity switches, fragmentations, mostly tracked / mostly lost) and IDF1 of the
+ * tracker's outputs against labelled objects, on the device and straight from sqdet_track_update's arrays, so that identities
+ * never return to the host.  The reference has no tracker and no tracking metric: this stage is the project's own, and THIS TEXT
+ * is its definition (tests/mot_reference.py restates it sequentially in NumPy; csrc/mot_eval.hip is built without contraction
+ * and agrees with it bit for bit in every counter, in iou_sum and in every table).
+ *
+ * Layout as the tracker's: S independent streams, a call takes n = S*F images, image s*F + f is frame f of stream s; state
+ * persists across calls until a reset (every table zero).
+ *
+ * Hypotheses are the tracker's arrays: boxes float32 [n,rows,4] (cx,cy,w,h), cls int32 [n,rows], counts int32 [n],
+ * det_track_id and det_track_state int32 [n,rows]; rows <= SQDET_MOT_CAP (64).  Row j is a hypothesis when
+ * j < clamp(count, 0, rows), state == 2, id > 0, the four box values are finite, w > 0 and h > 0, 0 <= cls < classes, and no
+ * lower row of the frame that passes these tests carries the same id.  Ground truth: gt_box float64 [n,G,4] (cx,cy,w,h), gt_id
+ * int32 [n,G] (> 0), gt_cls, gt_flags int32 [n,G] (bit 0: IGNORE -- KITTI DontCare, a MOT distractor or conf 0), gt_count int32
+ * [n]; G <= 64; row j is an object by the same rule without the state.  classes <= SQDET_MOT_MAX_CLASSES (128).
+ *
+ * One frame of one stream.  "In order" is ascending row index.  All floating arithmetic is float64 (a hypothesis box is widened,
+ * exactly), one IEEE operation per operator.  A stream whose status word is not zero skips the frame altogether.
+ *  5. (first, because it can stop the stream) Identities get DENSE INDICES in order of first appearance: the frame's non-ignored
+ *     objects in order, then its hypotheses in order.  A stream holds at most SQDET_MOT_MAX_OBJECTS (256) object identities and
+ *     SQDET_MOT_MAX_HYPOTHESES (1024) hypothesis identities; obj_id / obj_cls and hyp_id / hyp_cls record an identity's id and
+ *     the class of its first appearance.  If the frame's new identities do not all fit, the stream's status word gets
+ *     SQDET_MOT_STATUS_OBJECTS and / or SQDET_MOT_STATUS_HYPOTHESES and NOTHING else changes, in this frame or a later one.
+ *     An ignored object has no identity.
+ *  1. IoU of every (object, hypothesis) pair of the same class in the expression of the tracker's step 4 (box 1 the object, box 2
+ *     the hypothesis); another class: 0.  A pair is ALLOWED when IoU >= iou_thresh (inclusive; 0 < iou_thresh <= 1).  Its integer
+ *     cost is q = (int64) floor((1.0 - IoU) * 1048576.0).
+ *  2. Continuity (CLEAR-MOT; the rule of py-motmetrics).  For each non-ignored object in order whose `last` -- the hypothesis id
+ *     it was most recently matched to, however long ago -- is the id of a hypothesis of this frame that is still free and allowed
+ *     with it: the pair is matched and both ends leave the pool.
+ *  3. Optimal assignment of the remaining objects (ignored ones included) and the remaining hypotheses, each compacted in order
+ *     to rows i and columns j: a square matrix of side N = max(rows, columns) with cost q for an allowed pair and BIG = 2^32 for a
+ *     pair that is not allowed and for a padding cell, solved by assign() below; a pair assigned at BIG is unmatched.  (64 * 2^20
+ *     < BIG: the optimum first maximises the number of matches, then minimises the summed q, exactly, in integers.)  With no
+ *     remaining object or no remaining hypothesis nothing is assigned.
+ *  4. Counts, per class (counts int64 [S,classes,5]: tp, fn, fp, idsw, ignored_hyp; iou_sum float64 [S,classes]).  A hypothesis
+ *     matched to an ignored object is DROPPED from everything: ignored_hyp += 1.  A matched non-ignored object: tp += 1;
+ *     iou_sum = iou_sum + IoU (objects in order); idsw += 1 when it has a `last` that differs from the hypothesis id; then
+ *     last = that id.  An unmatched non-ignored object: fn += 1 (it keeps its `last`).  An unmatched hypothesis: fp += 1.  Per
+ *     object identity: obj_present += 1; matched: obj_tracked += 1, obj_frag += 1 when obj_run == 2, obj_run = 1; unmatched:
+ *     obj_run 1 becomes 2 (obj_run: 0 never matched, 1 matched at its previous present frame, 2 matched before but not at its
+ *     previous present frame).  Per hypothesis identity that was not dropped: hyp_frames += 1.  For every allowed pair of a
+ *     non-ignored object and a hypothesis that was not dropped, matched or not: overlap[g][t] += 1 at their dense indices.
+ *
+ * assign(cost[R][C]), R <= C, int64 -> the row of every column, -1 for a free one.  The shortest-augmenting-path Hungarian method
+ * with integer potentials u[R], v[C] (zero at first).  Rows are inserted in ascending order.  Inserting row i: minv[j] = 2^62,
+ * way[j] = -1, no column scanned; i0 = i, j0 = -1; then rounds: column j0 (if any) becomes scanned; for every unscanned column j,
+ * cur = cost[i0][j] - u[i0] - v[j], and cur < minv[j] sets minv[j] = cur, way[j] = j0; j1 is the unscanned column of smallest
+ * minv, the LOWEST index among equals, and delta its minv; every scanned column j: u[row of j] += delta, v[j] -= delta; every
+ * unscanned one: minv[j] -= delta; u[i] += delta; j0 = j1; a free j0 ends the rounds, otherwise i0 = the row of j0.  Then the
+ * path is flipped: while j0 >= 0: w = way[j0]; the row of j0 becomes the row of w (row i when w < 0); j0 = w.  Optimal
+ * assignments are not unique and MOTP depends on the pairs: the kernels return THESE pairs, not merely this cost.
+ *
+ * sqdet_mot_evaluate, per stream with G_ids object and T_ids hypothesis identities: IDF1's global matching is assign() on the
+ * G_ids x max(T_ids, G_ids) matrix of cost -overlap[g][t] (columns past T_ids are zero); idtp[c] is the sum of overlap over the
+ * assigned pairs whose object identity has class c, idfn[c] the sum of obj_present of that class minus idtp[c], idfp[c] the sum of
+ * hyp_frames of the hypothesis identities of class c minus idtp[c].  An object identity is mostly tracked when 5*tracked >=
+ * 4*present, mostly lost when 5*tracked < present, partly tracked otherwise.  Output per stream and class, SQDET_MOT_COUNTERS
+ * (14) int64 words: tp, fn, fp, idsw, ignored_hyp, frag, mt, pt, ml, idtp, idfn, idfp, gt_ids, hyp_ids; and iou_sum.  The caller
+ * derives MOTA = 1 - (fn + fp + idsw) / (tp + fn), MOTP = iou_sum / tp, IDF1 = 2 idtp / (2 idtp + idfp + idfn), precision and
+ * recall, and sums counters over streams and classes for an overall line.
+ *
+ * sqdet_mot_update: ONE launch, asynchronous on `stream`, allocates nothing, validates its arguments before it touches the
+ * device; one wave walks a stream; max_workgroups as sqdet_track_update.  tables: HOST struct of device pointers, the caller's:
+ * obj_id / obj_cls / obj_last / obj_present / obj_tracked / obj_frag / obj_run int32 [S,256], hyp_id / hyp_cls / hyp_frames int32
+ * [S,1024], n_obj / n_hyp / status int32 [S], counts int64 [S,classes,5], iou_sum float64 [S,classes], overlap int32
+ * [S,256,1024].  sqdet_mot_evaluate: one workgroup per stream; result_device: int64 [S,classes,14] device words it may
+ * overwrite; it synchronises `stream` ONCE and then fills host_counters int64 [S,classes,14] and host_iou_sum float64
+ * [S,classes].  A stream with a status word set: SQDET_EUNSUPPORTED, and -- as on every failure -- the host outputs are untouched.
+ * It changes no table: updates may go on after it.  Both use plain vector loads and stores only, and no atomics. */
+#define SQDET_MOT_CAP 64
+#define SQDET_MOT_MAX_OBJECTS 256
+#define SQDET_MOT_MAX_HYPOTHESES 1024
+#define SQDET_MOT_MAX_CLASSES 128
+#define SQDET_MOT_COUNTERS 14
+#define SQDET_MOT_STATUS_OBJECTS 1
+#define SQDET_MOT_STATUS_HYPOTHESES 2
+typedef struct sqdet_mot_tables {
+  int32_t* obj_id;
+  int32_t* obj_cls;
+  int32_t* obj_last;
+  int32_t* obj_present;
+  int32_t* obj_tracked;
+  int32_t* obj_frag;
+  int32_t* obj_run;
+  int32_t* hyp_id;
+  int32_t* hyp_cls;
+  int32_t* hyp_frames;
+  int32_t* n_obj;
+  int32_t* n_hyp;
+  int32_t* status;
+  int64_t* counts;
+  double* iou_sum;
+  int32_t* overlap;
+} sqdet_mot_tables_t;
+int sqdet_mot_update(const sqdet_mot_tables_t* tables, const float* boxes, const int32_t* cls, const int32_t* counts,
+                     const int32_t* det_track_id, const int32_t* det_track_state, const double* gt_box, const int32_t* gt_id,
+                     const int32_t* gt_cls, const int32_t* gt_flags, const int32_t* gt_count, int streams, int frames, int rows,
+                     int gt_rows, int classes, double iou_thresh, int max_workgroups, sqdet_stream_t stream);
+int sqdet_mot_evaluate(const sqdet_mot_tables_t* tables, int streams, int classes, int64_t* result_device, int64_t* host_counters,
+                       double* host_iou_sum, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------ utilities --
  * Device -> pinned-host copy issued as a KERNEL: dst is host memory mapped into the device's address space
  * (hipHostMalloc); nbytes a multiple of 16.  Used by the serving loop to hand the <= 64 filtered rows per image

@@ -140,6 +140,8 @@ SIGNATURES = {
     "sqdet_draw_font5x7": (ci, [vp, sz]),
     "sqdet_track_update": (ci, [vp] * 5 + [ci, ci, ci, vp, vp, vp, ci, vp]),
     "sqdet_track_build_items": (ci, [vp] * 6 + [ci, ci, cd, vp, ci, vp, ci, ci, vp, vp, ci, vp]),
+    "sqdet_mot_update": (ci, [vp] * 11 + [ci] * 5 + [cd, ci, vp]),
+    "sqdet_mot_evaluate": (ci, [vp, ci, ci, vp, vp, vp, vp]),
     "sqdet_copy_to_mapped_host": (ci, [vp, vp, sz, vp]),
     "sqdet_probe_mfma_layout": (ci, [C.POINTER(C.c_int32), ci]),
     "sqdet_calib_mfma": (ci, [vp, sz, ci, C.POINTER(cd), vp]),

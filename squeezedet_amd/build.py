@@ -68,6 +68,9 @@ SOURCES = [
     # (-ffp-contract=off: the tracker's filter and IoU are float64 expressions of one IEEE operation each, compared bit for bit with the
     # sequential NumPy restatement -- a fused multiply-add in kp*y or pp - kp*pp would round once where NumPy rounds twice)
     ("track.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the IoU and the integer cost floor((1 - IoU) * 2^20) are the float64 expressions of the sequential NumPy
+    # restatement, one IEEE operation each; the matched pairs, iou_sum and every table are compared bit for bit)
+    ("mot_eval.hip", ["-ffp-contract=off"]),
     ("wgrad.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     # (the calibration loops: hipcc's default AGPR form ROTATES the 16x16x32 loop's accumulators -- a[24:27] = mfma(.., a[22:25]) plus
     # v_accvgpr copies inside the loop -- so consecutive MFMAs depend on each other and the "bare MFMA loop" of rounds 3-4 read half

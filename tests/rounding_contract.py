@@ -22,6 +22,13 @@ CHECKS of a device tensor `got` against a reference Val (exact float64 value `v`
       4 x the largest emulation value, for the count never below 8 elements.  The three orders differ by up to 7 x among
       themselves; every defect planted in tests/test_rounding_contract_host.py sits 10 x or more above the cap.
       The compared elements (want != 0) must be at least 2000 and at least 25 % of the tensor; the others are covered by (a).
+
+REGIMES.  The same contract away from unit magnitude (tests/test_gpu_rounding_range.py): move() scales the operands of a program
+by powers of two -- "sub" (float16 subnormal inputs, intermediates and outputs), "subw" (subnormal weights), "top" (the last
+stored tensor overflows to +-inf; everything a conv reads stays finite), "big" (the backward-filter conv on dY x 2^13), or an
+integer k (input and biases x 2^k: the exact-scaling property, Fragile).  storage() rounds into the subnormal range and to
++-inf from 65520 on, so the reference and both checks stay as they are; conditions() states what the reference of a moved
+case must show before a device value is looked at.
 """
 import numpy as np
 import torch
@@ -46,7 +53,8 @@ def gamma(K):
 def storage(v64, dtype):
     """ONE round-to-nearest-even of float64 values to the storage type (NumPy converts float64 straight to float16, without
     a float32 step in between), returned as float64."""
-    return torch.from_numpy(v64.contiguous().numpy().astype(_NPT[dtype]).astype(np.float64))
+    with np.errstate(over="ignore"):          # from 65520 on a float16 is +-inf: that is the contract, not an accident
+        return torch.from_numpy(v64.contiguous().numpy().astype(_NPT[dtype]).astype(np.float64))
 
 
 def _pads(n, k, s, padding):
@@ -108,11 +116,14 @@ class Reference:
 
     def __init__(self, dtype):
         self.dtype = dtype
+        self.reads_finite = True        # every tensor a conv has read so far is finite over its whole interval
 
     def input(self, t):
         return t if isinstance(t, Val) else Val(t.double())
 
     def conv(self, x, w, b, stride=1, padding="SAME", relu=True, res=None):
+        for t in (x,) if res is None else (x, res):
+            self.reads_finite = self.reads_finite and all(bool(torch.isfinite(getattr(t, f)).all()) for f in ("want", "lo", "hi"))
         w64, b64 = w.double(), b.double()
         K = w.shape[0] * w.shape[1] * w.shape[2] + 1 + (res is not None)
         ex = _conv64(x.want, w64, b64, stride, padding)
@@ -166,6 +177,19 @@ def matmul_ordered(A, B, order, carry=None):
 
 
 DEFECTS = ("rz", "bias_after", "half_carry", "bf16_w", "half_x")
+# defects of range, invisible at unit magnitude: float16 subnormals flushed to zero at the conv's input, in its weights, at
+# its store; a store that saturates at +-65504 instead of overflowing to +-inf
+RANGE_DEFECTS = ("ftz_in", "ftz_w", "ftz_out", "sat")
+H_MIN_NORMAL, H_MAX = 2.0 ** -14, 65504.0
+
+
+def subnormal16(t):
+    """Non-zero and below the smallest normal float16."""
+    return (t != 0) & (t.abs() < H_MIN_NORMAL)
+
+
+def flush16(t):
+    return torch.where(subnormal16(t), torch.zeros_like(t), t)
 
 
 class Emulation:
@@ -197,6 +221,10 @@ class Emulation:
             w = w.bfloat16().float()
         if defect == "half_x":
             x = x.half().float()
+        if defect == "ftz_w":
+            w = flush16(w)
+        if defect == "ftz_in":
+            x = flush16(x)
         acc = self._accumulate(x, w, stride, padding, defect)
         if defect == "bias_after":
             v = (acc.half().float() + b.half().float()).half().float()
@@ -208,7 +236,14 @@ class Emulation:
             v = torch.relu(v)
         if self.dtype == "fp32":
             return v
-        return round_half_toward_zero(v) if defect == "rz" else v.half().float()
+        if defect == "rz":
+            return round_half_toward_zero(v)
+        v = v.half().float()
+        if defect == "ftz_out":
+            v = flush16(v)
+        if defect == "sat":
+            v = v.clamp(-H_MAX, H_MAX)
+        return v
 
     def cat(self, vals):
         return torch.cat(vals, dim=3)
@@ -259,8 +294,170 @@ class Case:
 
     def __init__(self, program, dtype, orders=ORDERS):
         self.dtype = dtype
-        self.ref = program(Reference(dtype))
+        reference = Reference(dtype)
+        self.ref = program(reference)
+        self.reads_finite = reference.reads_finite
         self.emus = [program(Emulation(dtype, o)) for o in orders]
+
+
+# ------------------------------------------------------------------------------------------------------------------- regimes
+# A regime is a name of REGIMES, or an integer k: input and every bias x 2^k ("sub" is k = -16).  All factors are powers of two.
+REGIMES = ("sub", "subw", "top")
+SUB, SUBW, TOP_IN, TOP_W, TOP_OUT, TOP_RES, BIG = -16, 12, 8, 7, 15, 13, 13
+MIN_SUBNORMAL, TOP_MIN_INF, TOP_MIN_FINITE = 0.5, 0.01, 0.25
+# "top" with the last stage one power of two lower (weights x 2^6, bias x 2^14), under the same conditions: for a launch more
+# than half of whose last tensor is zero, where the factors of "top" push more elements to inf than they leave finite
+TOP14 = "top14"
+
+
+def scaled(t, k, dtype):
+    """t x 2^k, storage-rounded again (the operands are what the kernel sees), as float32."""
+    return storage(t.double() * 2.0 ** k, dtype).float()
+
+
+def on_grid(t, q, dtype):
+    """t with the bits dropped that t x 2^-q would lose: every t x 2^k, k >= -q, is then exact in the storage type."""
+    return scaled(scaled(t, -q, dtype), q, dtype)
+
+
+def input_exponent(regime):
+    return regime if isinstance(regime, int) else {"sub": SUB, "subw": SUBW, "top": TOP_IN, TOP14: TOP_IN}[regime]
+
+
+def conv_exponents(regime, stage, last):
+    """(weights, bias, output) exponents of a conv in stage `stage` (1, 2, ...) of a launch whose last stage is `last`.
+    sub / k: only the biases follow the input.  subw: every conv's weights x 2^-12 under an input x 2^12, so stage i stores
+    x 2^(-12 (i - 1)) and its bias carries that factor.  top: x 2^8 up to the last stage, whose weights x 2^7 and bias x 2^15
+    make it the only one that stores x 2^15."""
+    if isinstance(regime, int) or regime == "sub":
+        k = input_exponent(regime)
+        return 0, k, k
+    if regime == "subw":
+        return -SUBW, -SUBW * (stage - 1), -SUBW * (stage - 1)
+    assert regime in ("top", TOP14), regime
+    lower = regime == TOP14
+    return (TOP_W - lower, TOP_OUT - lower, TOP_OUT - lower) if stage == last else (0, TOP_IN, TOP_IN)
+
+
+def move(regime, x, convs, dtype):
+    """x and convs = [(w, b, stage)] in program order, moved into `regime`: (x', [(w', b')]).  None is the unit regime."""
+    if regime is None:
+        return x, [(w, b) for w, b, _ in convs]
+    last = max(st for _, _, st in convs)
+    out = []
+    for w, b, st in convs:
+        kw, kb, _ = conv_exponents(regime, st, last)
+        out.append((scaled(w, kw, dtype) if kw else w, b * np.float32(2.0 ** kb)))
+    return scaled(x, input_exponent(regime), dtype), out
+
+
+def conv_keys(wt):
+    """[(weight key, bias key, stage)] of the convs of a weight dict, in program order: a stem ("w", then the squeeze "wn") or a
+    fire module ("ws" when it starts from the module input, both expands in one stage, then the next squeeze "wn")."""
+    if "w" in wt:
+        return [("w", "b", 1)] + ([("wn", "bn", 2)] if "wn" in wt else [])
+    s = 1 if "ws" in wt else 0
+    return ([("ws", "bs", 1)] if s else []) + [("w1", "b1", s + 1), ("w3", "b3", s + 1)] + ([("wn", "bn", s + 2)] if "wn" in wt else [])
+
+
+def move_weights(regime, x, wt, dtype):
+    """move() on a weight dict of tests/fused_launch_cases.py make_weights (or a stem's): (x', wt')."""
+    keys = conv_keys(wt)
+    x2, moved = move(regime, x, [(wt[kw], wt[kb], st) for kw, kb, st in keys], dtype)
+    out = {}
+    for (kw, kb, _), (w, b) in zip(keys, moved):
+        out[kw], out[kb] = w, b
+    return x2, out
+
+
+def residual_exponent(regime):
+    """The exponent of the residual (the prior dx) of a single conv: that of the conv's output -- but 2^13 in "top", the largest
+    power of two at which a randn residual (|r| < 7.9) stays finite: at the output's 2^15 one element in 22 of the residual
+    would itself be +-inf, and no conv may read a non-finite value."""
+    return 0 if regime is None else TOP_RES if regime == "top" else conv_exponents(regime, 1, 1)[2]
+
+
+def conditions(regime, case, written, x=None, weights=()):
+    """What the REFERENCE of a moved case must show, asserted before any device value is looked at.  written: the names of the
+    tensors the launch writes, the last one last; x, weights: the moved input and stored weights (subw).  Returns the figures."""
+    out = {}
+    for nm in written:
+        ref = case.ref[nm]
+        n, share, ok = honest(ref)
+        assert ok, "%s: only %d compared elements (%.1f %% of the tensor)" % (nm, n, 100 * share)
+        if regime == "sub":
+            out[nm] = float(subnormal16(ref.want[ref.compared]).double().mean())
+            assert out[nm] >= MIN_SUBNORMAL, "%s: only %.1f %% of the compared elements are subnormal" % (nm, 100 * out[nm])
+    if regime == "subw":
+        assert x is not None and bool(torch.isfinite(x).all()), "the scaled input overflows"
+        out["w"] = min(float(subnormal16(w).double().mean()) for w in weights)
+        assert out["w"] >= MIN_SUBNORMAL, "only %.1f %% of a conv's weights are subnormal and non-zero" % (100 * out["w"])
+    if regime in ("top", TOP14):
+        assert case.reads_finite, "a conv reads a non-finite value"
+        for nm in written[:-1]:
+            ref = case.ref[nm]
+            assert all(bool(torch.isfinite(getattr(ref, f)).all()) for f in ("want", "lo", "hi")), nm + " is written before the last stage"
+        want = case.ref[written[-1]].want
+        out["inf"] = float(torch.isinf(want).double().mean())
+        out["finite"] = float((torch.isfinite(want) & (want != 0)).double().mean())
+        assert out["inf"] >= TOP_MIN_INF and out["finite"] >= TOP_MIN_FINITE, \
+            "%s: %.2f %% infinite, %.1f %% finite and non-zero" % (written[-1], 100 * out["inf"], 100 * out["finite"])
+    return out
+
+
+class Fragile:
+    """An arithmetic that tells where scaling a float16 launch's input and biases by 2^k need not scale its result by exactly 2^k.
+    A power of two commutes with every rounding that neither underflows nor overflows, so a stored element is safe unless it can
+    be float16 subnormal or overflow in one of the two runs -- read off the reference's interval for it -- or a conv computed it
+    from an element that is not safe.  A tensor is (Val, upstream, own): `upstream` marks elements computed from an unsafe one;
+    `own` the elements that may themselves round differently.  A test takes `upstream` for the tensor it compares (what the
+    device stored tells the rest) and `own` for the share of a hidden tensor that is unsafe."""
+
+    def __init__(self, k):
+        self.ref, self.k = Reference("fp16"), k
+
+    def _own(self, v):
+        small, big = H_MIN_NORMAL * 2.0 ** max(-self.k, 0), 65520.0 * 2.0 ** min(-self.k, 0)
+        return (((v.lo != 0) | (v.hi != 0)) & (v.lo < small) & (v.hi > -small)) | (torch.maximum(v.lo.abs(), v.hi.abs()) >= big)
+
+    def input(self, t):
+        """An operand is safe: the test hands over values whose scaling is exact (on_grid)."""
+        v = self.ref.input(t)
+        none = torch.zeros_like(v.want, dtype=torch.bool)
+        return v, none, none
+
+    def conv(self, x, w, b, stride=1, padding="SAME", relu=True, res=None):
+        v = self.ref.conv(x[0], w, b, stride, padding, relu, None if res is None else res[0])
+        unsafe = (x[1] | x[2]).any(dim=3, keepdim=True).double()
+        k = w.shape[0]
+        up = _conv64(unsafe, torch.ones(k, k, 1, 1, dtype=torch.float64), torch.zeros(1, dtype=torch.float64), stride, padding) > 0
+        up = up.expand_as(v.want)
+        if res is not None:
+            up = up | res[1] | res[2]
+        return v, up, self._own(v)
+
+    def cat(self, vals):
+        return (self.ref.cat([v[0] for v in vals]),) + tuple(torch.cat([v[i] for v in vals], dim=3) for i in (1, 2))
+
+    def pool(self, x, size, stride, padding):
+        return (self.ref.pool(x[0], size, stride, padding),) + tuple(maxpool(x[i].double(), size, stride, padding) > 0 for i in (1, 2))
+
+    def mask(self, x, keep):
+        return (self.ref.mask(x[0], keep),) + tuple(x[i] & keep for i in (1, 2))
+
+
+def scales_exactly(unit, moved, k, upstream=None):
+    """moved against 2^k * unit, bit for bit: (elements that differ among the compared, share of the tensor left out by the
+    device's own values, share of the tensor compared).  float16 tensors: an element is left out when it is not finite or is
+    subnormal in one of the runs, and not compared either when it is in `upstream`; other types: every element is compared."""
+    u, m = unit.double(), moved.double()
+    ok = torch.ones_like(u, dtype=torch.bool)
+    if unit.dtype == torch.float16:
+        ok = torch.isfinite(u) & torch.isfinite(m) & ~subnormal16(u) & ~subnormal16(m)
+    left = 1.0 - float(ok.double().mean())
+    if upstream is not None:
+        ok = ok & ~upstream
+    return int(((m != u * 2.0 ** k) & ok).sum()), left, float(ok.double().mean())
 
 
 # ----------------------------------------------------------------------------------------------------- backward-filter conv

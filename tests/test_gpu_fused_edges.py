@@ -113,24 +113,31 @@ def _pad(p):
     return 0 if p == "SAME" else 1
 
 
+def _weights(sp):
+    """The seeded float32 CPU kernels (storage-rounded) and biases of a Spec."""
+    if sp.entry.startswith("stem"):
+        rs = np.random.RandomState(_seed("stem", sp.id))
+        rnd = (lambda t: t.half().float()) if sp.dtype == "fp16" else (lambda t: t)
+        wt = {"w": rnd(torch.from_numpy((rs.randn(sp.k, sp.k, 3, sp.cout) * (2.0 / (sp.k * sp.k * 3)) ** 0.5).astype(np.float32))),
+              "b": torch.from_numpy(rs.uniform(-0.5, 0.5, sp.cout).astype(np.float32))}
+        if sp.s2:
+            wt["wn"] = rnd(torch.from_numpy((rs.randn(1, 1, sp.cout, sp.s2) * (2.0 / sp.cout) ** 0.5).astype(np.float32)))
+            wt["bn"] = torch.from_numpy(rs.uniform(-0.3, 0.3, sp.s2).astype(np.float32))
+        return wt
+    return FC.make_weights(sp, _seed("fire", sp.id))
+
+
 class Op:
     """A Spec with seeded weights on the device: calls the entry point on caller-owned buffers, and computes what the
     unfused path gives."""
 
-    def __init__(self, spec):
+    def __init__(self, spec, wt=None):
+        """wt: the float32 CPU kernels (storage-rounded) and biases to use in place of the seeded ones of _weights()."""
         ops = _ops()
         self.spec, self.tdt = spec, FC.TDT[spec.dtype]
         sp = spec
-        if sp.entry.startswith("stem"):
-            rs = np.random.RandomState(_seed("stem", sp.id))
-            rnd = (lambda t: t.half().float()) if sp.dtype == "fp16" else (lambda t: t)
-            wt = {"w": rnd(torch.from_numpy((rs.randn(sp.k, sp.k, 3, sp.cout) * (2.0 / (sp.k * sp.k * 3)) ** 0.5).astype(np.float32))),
-                  "b": torch.from_numpy(rs.uniform(-0.5, 0.5, sp.cout).astype(np.float32))}
-            if sp.s2:
-                wt["wn"] = rnd(torch.from_numpy((rs.randn(1, 1, sp.cout, sp.s2) * (2.0 / sp.cout) ** 0.5).astype(np.float32)))
-                wt["bn"] = torch.from_numpy(rs.uniform(-0.3, 0.3, sp.s2).astype(np.float32))
-        else:
-            wt = FC.make_weights(sp, _seed("fire", sp.id))
+        if wt is None:
+            wt = _weights(sp)
         self.wt = wt
         self.packed = {k: ops.pack_conv_weights(v.to(DEV), self.tdt) for k, v in wt.items() if k.startswith("w")}
         self.operands = OrderedDict((k, (self.packed[k].data if k.startswith("w") else v.to(DEV))) for k, v in wt.items())

@@ -656,6 +656,26 @@ int sqdet_augment_bgr_window(const uint8_t* src, size_t src_bytes, const int64_t
                              const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g,
                              double mean_r, int dtype, sqdet_stream_t stream);
 
+/* The mosaic: FOUR source images per output image, each in its own pane.  Output image i is cut at column xc = split[i][0] and
+ * row yc = split[i][1] (device int32 [n,2], 0 <= xc <= dst_w, 0 <= yc <= dst_h) into
+ *   pane 0 = rows [0, yc) x columns [0, xc)        pane 1 = rows [0, yc) x columns [xc, dst_w)
+ *   pane 2 = rows [yc, dst_h) x columns [0, xc)    pane 3 = rows [yc, dst_h) x columns [xc, dst_w)
+ * and pane p, ph x pw pixels, holds cv2.resize(D_p, (pw, ph)), where D_p is exactly the window D that sqdet_augment_bgr_window
+ * builds -- colour, mean in double rounded once, window with 0.0f outside the image, mirror, in this order -- for the source image
+ * at byte part_offsets[i][p] (device int64 [n,4]) with geom[i][p] = (src_h, src_w, x0, y0, cw, ch, flip) (device int32 [n,4,7]) and
+ * the matrix color[i][p] (device float32 [n,4,12], or NULL: no matrix).  The resize coordinates are those of (cw, ch) -> (pw, ph)
+ * and the taps clamp at the window's border: nothing is blended across a seam, a pane never uses a pixel of another pane's source.
+ * A pane without pixels (xc = 0 or dst_w, yc = 0 or dst_h) is never examined: its offset, geometry and matrix may hold anything, and
+ * split = (dst_w, dst_h) gives sqdet_augment_bgr_window's output for part 0 bit for bit.  dst [n,dst_h,dst_w,3] in dtype storage;
+ * float16 is the float32 value converted once.
+ * As above, THIS CALL CANNOT VALIDATE split, geom or part_offsets: the caller must reject a split outside [0, dst_w] x [0, dst_h] and,
+ * for every pane that has pixels, whatever sqdet_augment_bgr_window's caller must reject for an image (ops.augment_bgr_mosaic
+ * does).  A pane with pixels that breaks the rules anyway is left unwritten while the image's other panes are written; an image
+ * whose split is out of range is left unwritten; no load ever leaves [src, src + src_bytes). */
+int sqdet_augment_bgr_mosaic(const uint8_t* src, size_t src_bytes, const int64_t* part_offsets, const int32_t* geom,
+                             const int32_t* split, const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b,
+                             double mean_g, double mean_r, int dtype, sqdet_stream_t stream);
+
 /* -------------------------------------------------------- detection table --
  * What the KITTI, the Pascal VOC and the COCO-style evaluation below score: ONE layout, filled by sqdet_kitti_ingest /
  * sqdet_voc_ingest with the values of the respective dataset's detection files, by sqdet_coco_ingest with unrounded x,y,w,h

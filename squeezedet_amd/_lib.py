@@ -122,6 +122,7 @@ SIGNATURES = {
     "sqdet_preprocess_bgr": (ci, [vp, vp] + [ci] * 5 + [cf, cf, cf, ci, vp]),
     "sqdet_augment_bgr": (ci, [vp, sz, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, vp]),
     "sqdet_augment_bgr_window": (ci, [vp, sz, vp, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, vp]),
+    "sqdet_augment_bgr_mosaic": (ci, [vp, sz, vp, vp, vp, vp, vp, ci, ci, ci, cd, cd, cd, ci, vp]),
     "sqdet_kitti_ingest": (ci, [vp] * 5 + [ci, ci] + [vp] * 5 + [ci, ci, ci, vp]),
     "sqdet_kitti_eval_workspace_bytes": (sz, [ci]),
     "sqdet_kitti_evaluate": (ci, [vp] * 5 + [ci, ci] + [vp] * 5 + [ci] + [vp] * 4 + [vp]),

@@ -78,6 +78,10 @@ def base_model_config(dataset="PASCAL_VOC"):
     cfg.AUG_CONTRAST = (0.5, 1.5)               # gain
     cfg.AUG_SATURATION = (0.5, 1.5)             # about the BT.601 luma
     cfg.AUG_HUE_DEGREES = 18.0                  # rotation U[-h, h] in YIQ
+    cfg.AUG_MOSAIC_PROB = 0.0                   # probability that a batch image is a mosaic of four dataset images (0.0: never)
+    cfg.AUG_MOSAIC_CENTER = (0.3, 0.7)          # the split (xc, yc), U[range] of the input's width and height
+    cfg.AUG_MOSAIC_ZOOM_MAX = 1.5               # per part an extra zoom U[1, max] beyond the one that fills its pane
+    cfg.AUG_MOSAIC_MIN_BOX = 2.0                # a box narrower or lower than this, in network-input pixels, is dropped
     cfg.EXCLUDE_HARD_EXAMPLES = True
     cfg.BATCH_NORM_EPSILON = 1e-5
     cfg.NUM_THREAD = 4

@@ -13,6 +13,9 @@
 // Unlike sqdet_preprocess_bgr (demo.py's order: resize, then subtract the mean) the mean is subtracted BEFORE the
 // interpolation, so the kernel interpolates the float32 mean-subtracted values and the zero padding stays exactly 0.0f.
 // Built with -ffp-contract=off: the same float32 operations in the same order as the CPU restatement.
+//
+// sqdet_augment_bgr_mosaic cuts every output image at (xc, yc) into four panes and fills each pane with the window form of its own
+// source image, resized to the pane: the same body once more, with the pane in place of the destination image.
 #include "common.h"
 
 namespace sqdet {
@@ -41,15 +44,30 @@ __device__ __forceinline__ float color_sub_mean(unsigned long long q, int k, int
   return (float)((double)v - mean);
 }
 
-// WINDOW: geom is [n,7] (src_h, src_w, x0, y0, cw, ch, flip), else [n,5] (src_h, src_w, dx, dy, flip); COLOR: color is [n,12]
-template <typename T, bool WINDOW, bool COLOR>
+// WINDOW: geom is [n,7] (src_h, src_w, x0, y0, cw, ch, flip), else [n,5] (src_h, src_w, dx, dy, flip); COLOR: color is [n,12].
+// MOSAIC (with WINDOW): offsets, geom and color hold FOUR rows per image, one per pane, and split [n,2] = (xc, yc) cuts the image;
+// the grid has one more workgroup per row, each side of xc is covered by its own 256-pixel chunks (the left side's first), so the
+// pane -- and with it the geometry -- stays workgroup-uniform; Hp x Wp at (py0, px0) is the pane, the whole image without MOSAIC.
+template <typename T, bool WINDOW, bool COLOR, bool MOSAIC = false>
 __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __restrict__ src, size_t src_bytes,
                                                      const int64_t* __restrict__ offsets, const int32_t* __restrict__ geom,
                                                      const float* __restrict__ color, T* __restrict__ dst, int Hd, int Wd,
-                                                     double m0, double m1, double m2) {
+                                                     double m0, double m1, double m2, const int32_t* __restrict__ split) {
+  static_assert(WINDOW || !MOSAIC, "a mosaic pane is a window");
   const int row = blockIdx.y;                     // n * Hd + y
-  const int n = row / Hd, y = row - n * Hd;
+  int n = row / Hd, y = row - n * Hd;
   constexpr int GS = WINDOW ? 7 : 5;
+  int Hp = Hd, Wp = Wd, px0 = 0, chunk = blockIdx.x;
+  if constexpr (MOSAIC) {
+    const int xc = split[2 * n], yc = split[2 * n + 1];
+    if (xc < 0 || xc > Wd || yc < 0 || yc > Hd) return;          // (rejected by the host wrapper) the image is left unwritten
+    const int nl = (xc + 64 * APX - 1) / (64 * APX);             // chunks of the left side; an empty pane gets no workgroup
+    const bool right = chunk >= nl, bottom = y >= yc;
+    if (right) { chunk -= nl; px0 = xc; Wp = Wd - xc; } else Wp = xc;
+    if (bottom) { y -= yc; Hp = Hd - yc; } else Hp = yc;
+    if (chunk * 64 * APX >= Wp) return;
+    n = 4 * n + 2 * (int)bottom + (int)right;                    // the pane's row of offsets, geom and color
+  }
   const AugGeom g{geom[GS * n], geom[GS * n + 1], geom[GS * n + 2], geom[GS * n + 3], geom[GS * n + GS - 1]};
   const int64_t off = offsets[n];
   int Hs, Ws;                                      // the window D: the drifted image, or (ch, cw)
@@ -72,7 +90,7 @@ __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __rest
 #pragma unroll
     for (int k = 0; k < 12; ++k) M[k] = color[12 * n + k];
   }
-  const double scale_x = (double)Ws / (double)Wd, scale_y = (double)Hs / (double)Hd;
+  const double scale_x = (double)Ws / (double)Wp, scale_y = (double)Hs / (double)Hp;
   float fy = (float)((y + 0.5) * scale_y - 0.5);
   int sy = (int)floorf(fy);
   fy -= sy;
@@ -84,12 +102,12 @@ __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __rest
   const size_t o0 = (size_t)off + (size_t)(r0 ? oy0 : 0) * g.w * 3, o1 = (size_t)off + (size_t)(r1 ? oy1 : 0) * g.w * 3;
   const float ay0 = 1.f - fy;
   const double mean[3] = {m0, m1, m2};
-  const int x0 = (blockIdx.x * 64 + threadIdx.x) * APX;
-  if (x0 >= Wd) return;
+  const int x0 = (chunk * 64 + threadIdx.x) * APX;     // in the pane
+  if (x0 >= Wp) return;
   float out[APX * 3];
 #pragma unroll
   for (int p = 0; p < APX; ++p) {
-    const int x = x0 + p < Wd ? x0 + p : Wd - 1;
+    const int x = x0 + p < Wp ? x0 + p : Wp - 1;
     float fx = (float)((x + 0.5) * scale_x - 0.5);
     int sx = (int)floorf(fx);
     fx -= sx;
@@ -141,8 +159,8 @@ __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __rest
       out[p * 3 + c] = h0 * ay0 + h1 * fy;
     }
   }
-  T* d = dst + ((size_t)row * Wd + x0) * 3;
-  if (x0 + APX <= Wd && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
+  T* d = dst + ((size_t)row * Wd + px0 + x0) * 3;
+  if (x0 + APX <= Wp && (reinterpret_cast<uintptr_t>(d) & 7) == 0) {
     if constexpr (sizeof(T) == 2) {
       typedef f16 h4 __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -153,32 +171,32 @@ __global__ __launch_bounds__(64) void augment_kernel(const unsigned char* __rest
 #pragma unroll
       for (int k = 0; k < 6; ++k) reinterpret_cast<f2*>(d)[k] = f2{out[2 * k], out[2 * k + 1]};
     }
-  } else if (sizeof(T) == 2 && x0 + APX <= Wd && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+  } else if (sizeof(T) == 2 && x0 + APX <= Wp && (reinterpret_cast<uintptr_t>(d) & 3) == 0) {
     typedef f16 h2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int k = 0; k < 6; ++k) reinterpret_cast<h2*>(d)[k] = h2{(f16)out[2 * k], (f16)out[2 * k + 1]};
   } else {
-    for (int p = 0; p < APX && x0 + p < Wd; ++p)
+    for (int p = 0; p < APX && x0 + p < Wp; ++p)
       for (int c = 0; c < 3; ++c) d[p * 3 + c] = (T)out[p * 3 + c];
   }
 }
 
-template <bool WINDOW, bool COLOR>
+template <bool WINDOW, bool COLOR, bool MOSAIC = false>
 static int launch_augment(const char* name, const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
-                          const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g, double mean_r,
+                          const int32_t* split, const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g, double mean_r,
                           int dtype, sqdet_stream_t stream) {
-  SQDET_REQUIRE(src && src_offsets && geom && dst, "%s: null pointer", name);
+  SQDET_REQUIRE(src && src_offsets && geom && dst && (split || !MOSAIC), "%s: null pointer", name);
   SQDET_REQUIRE(n > 0 && dst_h > 0 && dst_w > 0 && src_bytes > 0, "%s: bad dims", name);
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "%s: bad dtype %d", name, dtype);
   SQDET_REQUIRE((long)n * dst_h <= 0x7fffffffL / 4, "%s: too many rows", name);
-  const dim3 grid((unsigned)((dst_w + 64 * APX - 1) / (64 * APX)), (unsigned)(n * dst_h));
+  const dim3 grid((unsigned)((dst_w + 64 * APX - 1) / (64 * APX)) + (MOSAIC ? 1u : 0u), (unsigned)(n * dst_h));
   SQDET_REQUIRE(grid.y <= 65535u * 1024u, "%s: too many rows", name);
   if (dtype == SQDET_F16)
-    hipLaunchKernelGGL((augment_kernel<f16, WINDOW, COLOR>), grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets,
-                       geom, color, (f16*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
+    hipLaunchKernelGGL((augment_kernel<f16, WINDOW, COLOR, MOSAIC>), grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets,
+                       geom, color, (f16*)dst, dst_h, dst_w, mean_b, mean_g, mean_r, split);
   else
-    hipLaunchKernelGGL((augment_kernel<float, WINDOW, COLOR>), grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets,
-                       geom, color, (float*)dst, dst_h, dst_w, mean_b, mean_g, mean_r);
+    hipLaunchKernelGGL((augment_kernel<float, WINDOW, COLOR, MOSAIC>), grid, dim3(64), 0, as_stream(stream), src, src_bytes, src_offsets,
+                       geom, color, (float*)dst, dst_h, dst_w, mean_b, mean_g, mean_r, split);
   SQDET_CHECK_HIP(hipGetLastError());
   return SQDET_OK;
 }
@@ -188,7 +206,7 @@ static int launch_augment(const char* name, const uint8_t* src, size_t src_bytes
 extern "C" int sqdet_augment_bgr(const uint8_t* src, size_t src_bytes, const int64_t* src_offsets, const int32_t* geom,
                                  void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g, double mean_r,
                                  int dtype, sqdet_stream_t stream) {
-  return sqdet::launch_augment<false, false>("augment_bgr", src, src_bytes, src_offsets, geom, nullptr, dst, n, dst_h, dst_w, mean_b,
+  return sqdet::launch_augment<false, false>("augment_bgr", src, src_bytes, src_offsets, geom, nullptr, nullptr, dst, n, dst_h, dst_w, mean_b,
                                              mean_g, mean_r, dtype, stream);
 }
 
@@ -196,6 +214,14 @@ extern "C" int sqdet_augment_bgr_window(const uint8_t* src, size_t src_bytes, co
                                         const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b, double mean_g,
                                         double mean_r, int dtype, sqdet_stream_t stream) {
   const auto launch = color ? sqdet::launch_augment<true, true> : sqdet::launch_augment<true, false>;
-  return launch("augment_bgr_window", src, src_bytes, src_offsets, geom, color, dst, n, dst_h, dst_w, mean_b, mean_g, mean_r, dtype,
+  return launch("augment_bgr_window", src, src_bytes, src_offsets, geom, nullptr, color, dst, n, dst_h, dst_w, mean_b, mean_g, mean_r, dtype,
                 stream);
+}
+
+extern "C" int sqdet_augment_bgr_mosaic(const uint8_t* src, size_t src_bytes, const int64_t* part_offsets, const int32_t* geom,
+                                        const int32_t* split, const float* color, void* dst, int n, int dst_h, int dst_w, double mean_b,
+                                        double mean_g, double mean_r, int dtype, sqdet_stream_t stream) {
+  const auto launch = color ? sqdet::launch_augment<true, true, true> : sqdet::launch_augment<true, false, true>;
+  return launch("augment_bgr_mosaic", src, src_bytes, part_offsets, geom, split, color, dst, n, dst_h, dst_w, mean_b, mean_g, mean_r,
+                dtype, stream);
 }

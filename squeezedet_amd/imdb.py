@@ -24,6 +24,9 @@ these fields -- the reader draws the reference's numbers and launches ``sqdet_au
     cut to the window (``window_boxes``);
   * ``mc.AUG_COLOR``: per image a 3x4 colour matrix (``draw_color_matrix`` / ``color_matrix``).
 Both are a few float64 scalars per image on the host and still ONE launch per batch: ``sqdet_augment_bgr_window``.
+  * ``mc.AUG_MOSAIC_PROB > 0``: with that probability a batch image is a MOSAIC of four dataset images, each a crop shown at
+    roughly half scale in its own pane of the network input (``mosaic_part`` / ``mosaic_part_boxes``); the other images keep the
+    policy above as part 0 of a mosaic with one pane.  The whole batch is ONE launch of ``sqdet_augment_bgr_mosaic``.
 
 Kept on purpose, as in the reference: the shuffled branch reshuffles as soon as ``cur + BATCH_SIZE >= len`` (imdb.py:
 121-123), so the last full batch of every epoch is never served and each epoch serves ``ceil(len / B) - 1`` batches.
@@ -33,20 +36,34 @@ from collections import namedtuple
 import numpy as np
 
 Batch = namedtuple("Batch", ["image_input", "gt_boxes", "gt_classes", "gt_counts", "aug", "bbox_per_batch",
-                             "label_per_batch", "batch_idx", "window", "mode", "color"], defaults=(None, None, None))
+                             "label_per_batch", "batch_idx", "window", "mode", "color", "split", "parts", "part_window", "part_flip",
+                             "part_color"], defaults=(None,) * 8)
 Batch.__doc__ = """One training batch.  image_input: device [B, IMAGE_HEIGHT, IMAGE_WIDTH, 3] in the reader's dtype;
 gt_boxes float64 [B, M, 4] (cx, cy, w, h in network-input pixels), gt_classes int32 [B, M], gt_counts int32 [B]: device
-tensors padded to M = the dataset's largest object count, ready for ops.build_labels / trainer.step / GraphedStep.step;
+tensors padded to M = the dataset's largest object count (four times that with the mosaic on), ready for ops.build_labels / trainer.step / GraphedStep.step;
 aug: host int32 [B, 3] = (dx, dy, flip) per image; bbox_per_batch / label_per_batch: host lists as the reference returns
-them; batch_idx: the dataset indices of the batch; window / mode / color: as in Plan (None with the new options off)."""
+them; batch_idx: the dataset indices of the batch; window / mode / color and split / parts / part_window / part_flip / part_color: as in Plan (None with the options off)."""
 
 # the plan of one batch, all host side: dataset indices, per-image (dx, dy, flip), the reference's box / label lists.  With
 # AUG_GEOMETRY "ssd" or AUG_COLOR also: window int64 [B, 4] = (x0, y0, cw, ch) in original-image pixels (aug[:, :2] is its corner),
 # canvas int64 [B, 4] = the zoom-out canvas the window was drawn in, mode = per image "whole" | 0.1 .. 0.9 | "any" | "drift",
 # trial int64 [B] = the 1-based trial that was accepted (0: none was made, or all failed and the window is the whole canvas),
-# color float32 [B, 12] = the row-major 3x4 colour matrices, or None without AUG_COLOR
-Plan = namedtuple("Plan", ["batch_idx", "aug", "bbox_per_batch", "label_per_batch", "window", "mode", "color", "canvas", "trial"],
-                  defaults=(None, None, None, None, None))
+# color float32 [B, 12] = the row-major 3x4 colour matrices, or None without AUG_COLOR.  With AUG_MOSAIC_PROB > 0 also (else None):
+# split int64 [B, 2] = (xc, yc), parts int64 [B, 4] = the dataset index of every pane's image (-1: a pane that is not used),
+# part_window int64 [B, 4, 4] = (x0, y0, cw, ch) per pane, part_flip int64 [B, 4], part_color float32 [B, 4, 12] or None; the fields
+# above then describe part 0 (mode "mosaic" for a mosaic image), bbox_per_batch / label_per_batch hold the boxes of panes 0, 1, 2, 3
+_PLAN_FIELDS = ["batch_idx", "aug", "bbox_per_batch", "label_per_batch", "window", "mode", "color", "canvas", "trial"]
+MOSAIC_FIELDS = ["split", "parts", "part_window", "part_flip", "part_color"]
+
+
+class Plan(namedtuple("Plan", _PLAN_FIELDS, defaults=(None, None, None, None, None))):
+    """The plan with the mosaic off: the nine-field tuple it has always been; the mosaic's fields read None."""
+    __slots__ = ()
+    split = parts = part_window = part_flip = part_color = None
+
+
+# the plan with the mosaic on: Plan's fields, then the mosaic's
+MosaicPlan = namedtuple("MosaicPlan", _PLAN_FIELDS + MOSAIC_FIELDS)
 
 CROP_MODES = ("whole", 0.1, 0.3, 0.5, 0.7, 0.9, "any")
 BT601_BGR = np.array([0.114, 0.587, 0.299])                      # luma weights of (b, g, r)
@@ -194,6 +211,84 @@ def draw_color_matrix(rs, mc):
     return color_matrix(*draw_color_factors(rs, mc)).astype(np.float32).reshape(12)
 
 
+def mosaic_panes(xc, yc, W, H):
+    """The four panes of a W x H input cut at (xc, yc), as (px0, py0, pw, ph): top left, top right, bottom left, bottom right."""
+    return [(0, 0, xc, yc), (xc, 0, W - xc, yc), (0, yc, xc, H - yc), (xc, yc, W - xc, H - yc)]
+
+
+def mosaic_part(rs, mc, w, h, pw, ph):
+    """One part of a mosaic: the window of a w x h image that fills a pw x ph pane, as ((x0, y0, cw, ch), flip, colour matrix or
+    None).  Draws from rs in this order:
+      the zoom z = max(pw / w, ph / h) * U[1, AUG_MOSAIC_ZOOM_MAX] -- at U = 1 the largest window of the pane's shape that the
+        image holds --, the window cw = min(w, max(1, int(pw / z))), ch = min(h, max(1, int(ph / z)));
+      its corner, randint(0, w - cw + 1) then randint(0, h - ch + 1);
+      the mirror, randint(2);
+      with AUG_COLOR, draw_color_matrix.
+    The window is always a crop inside its image, shown at the isotropic zoom z up to the truncation to pixels: no padding and no
+    trial loop."""
+    w, h, pw, ph = int(w), int(h), int(pw), int(ph)
+    z = max(pw / float(w), ph / float(h)) * rs.uniform(1.0, float(_cfg(mc, "AUG_MOSAIC_ZOOM_MAX", 1.5)))
+    cw, ch = min(w, max(1, int(pw / z))), min(h, max(1, int(ph / z)))
+    x0 = int(rs.randint(0, w - cw + 1))
+    y0 = int(rs.randint(0, h - ch + 1))
+    flip = 1 if rs.randint(2) > 0.5 else 0
+    color = draw_color_matrix(rs, mc) if _cfg(mc, "AUG_COLOR", False) else None
+    return (x0, y0, cw, ch), flip, color
+
+
+def mosaic_part_boxes(win, flip, pane, boxes, min_box):
+    """The boxes ([n, 4] cx, cy, w, h in the part's original pixels) in network-input pixels, for the window `win` shown in
+    pane = (px0, py0, pw, ph): (kept [n] bool, [k, 4]).  In this order: window_boxes (centre inside, shifted, clipped), the mirror
+    cw - 1 - cx, the scaling by pw / cw and ph / ch, the filter -- a box narrower or lower than min_box is dropped --, the pane's
+    origin added to the centre."""
+    px0, py0, pw, ph = [float(v) for v in pane]
+    cw, ch = float(win[2]), float(win[3])
+    keep, b = window_boxes(win, boxes)
+    if flip:
+        b[:, 0] = cw - 1 - b[:, 0]
+    b[:, 0::2] = b[:, 0::2] * (pw / cw)
+    b[:, 1::2] = b[:, 1::2] * (ph / ch)
+    big = (b[:, 2] >= float(min_box)) & (b[:, 3] >= float(min_box))
+    keep[np.flatnonzero(keep)[~big]] = False
+    b = b[big]
+    b[:, 0] = b[:, 0] + px0
+    b[:, 1] = b[:, 1] + py0
+    return keep, b
+
+
+def _mosaic_part_rows(win, flip, pane, roi, min_box):
+    """mosaic_part_boxes on a roi list ([cx, cy, w, h, cls] rows), box by box in Python floats: ([[cx, cy, w, h]], [cls]) of the
+    boxes kept.  The same float64 operations in the same order -- np.clip is min(max(v, lo), hi) -- so the rows are
+    mosaic_part_boxes' bit for bit (tests/test_mosaic_host.py compares them); a part has a handful of boxes, where a NumPy call per
+    operation costs ten times the arithmetic, as in ssd_window."""
+    x0, y0, cw, ch = [float(v) for v in win]
+    px0, py0, pw, ph = [float(v) for v in pane]
+    sx, sy, min_box = pw / cw, ph / ch, float(min_box)
+    rows, labels = [], []
+    for b in roi:
+        cx, cy, w, h = float(b[0]), float(b[1]), float(b[2]), float(b[3])
+        if not (x0 <= cx <= x0 + cw - 1.0 and y0 <= cy <= y0 + ch - 1.0):
+            continue
+        x1, x2 = min(max(cx - w / 2.0 - x0, 0.0), cw - 1.0), min(max(cx + w / 2.0 - x0, 0.0), cw - 1.0)
+        y1, y2 = min(max(cy - h / 2.0 - y0, 0.0), ch - 1.0), min(max(cy + h / 2.0 - y0, 0.0), ch - 1.0)
+        cx, cy, w, h = (x1 + x2) / 2.0, (y1 + y2) / 2.0, x2 - x1, y2 - y1
+        if flip:
+            cx = cw - 1 - cx
+        cx, w, cy, h = cx * sx, w * sx, cy * sy, h * sy
+        if w >= min_box and h >= min_box:
+            rows.append([cx + px0, cy + py0, w, h])
+            labels.append(b[4])
+    return rows, labels
+
+
+def mosaic_prob(mc):
+    """mc.AUG_MOSAIC_PROB where it applies: 0.0 without DATA_AUGMENTATION or for a config without the field."""
+    p = float(_cfg(mc, "AUG_MOSAIC_PROB", 0.0)) if mc.DATA_AUGMENTATION else 0.0
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("BatchReader: mc.AUG_MOSAIC_PROB must be in [0, 1], got %r" % (p,))
+    return p
+
+
 class BatchReader:
     """``BatchReader(mc, images, rois, seed=0, device=None, dtype=torch.float32, resident=False)``
 
@@ -201,8 +296,10 @@ class BatchReader:
     [cx, cy, w, h, cls] in original pixels (kitti._rois, dataset/kitti.py:50-90).  resident=True uploads every image
     once and gathers each batch on the device by byte offset; otherwise each batch is packed into a pinned host buffer
     and copied asynchronously on the current stream.  mc supplies BATCH_SIZE, IMAGE_WIDTH / IMAGE_HEIGHT, BGR_MEANS and
-    DATA_AUGMENTATION / DRIFT_X / DRIFT_Y and, optional, AUG_GEOMETRY / AUG_ZOOM_OUT_MAX / AUG_COLOR with their ranges
-    (config.base_model_config).  The first shuffle is drawn here, as kitti.__init__ does."""
+    DATA_AUGMENTATION / DRIFT_X / DRIFT_Y and, optional, AUG_GEOMETRY / AUG_ZOOM_OUT_MAX / AUG_COLOR with their ranges and
+    AUG_MOSAIC_PROB / _CENTER / _ZOOM_MAX / _MIN_BOX (config.base_model_config).  With the mosaic on, max_objects -- the M of every
+    Batch -- is FOUR times the dataset's largest object count: the three further images of a mosaic are drawn independently, so one
+    image can fill all four panes, and the sum of the four largest counts would not bound that.  The first shuffle is drawn here, as kitti.__init__ does."""
 
     def __init__(self, mc, images, rois, seed=0, device=None, dtype=None, resident=False):
         if len(images) != len(rois) or not images:
@@ -218,6 +315,15 @@ class BatchReader:
         self.sizes = np.array([im.shape[:2] for im in self.images], np.int64)
         self.nbytes = self.sizes[:, 0] * self.sizes[:, 1] * 3
         self.max_objects = max(1, max(len(r) for r in self.rois))
+        self.parts_per_image = 1
+        if mosaic_prob(mc) > 0.0:
+            self.parts_per_image = 4
+            self.max_objects *= 4
+            anchor_box = _cfg(mc, "ANCHOR_BOX", None)
+            limit = 1024 if anchor_box is None else min(1024, len(anchor_box))      # what sqdet_build_labels accepts
+            if self.max_objects > limit:
+                raise ValueError("BatchReader: a mosaic can hold %d objects, ops.build_labels takes at most %d per image"
+                                 % (self.max_objects, limit))
         self.rs = np.random.RandomState(seed)
         self.device, self.dtype, self.resident = device, dtype, bool(resident)
         self._image_idx = list(range(len(self.images)))
@@ -269,8 +375,18 @@ class BatchReader:
 
     def next_plan(self, shuffle=True):
         """The host half of read_batch: batch order, random draws and box transform (imdb.py:100-190), in NumPy float64 in
-        the reference's order.  Advances the reader; needs no GPU."""
+        the reference's order.  Advances the reader; needs no GPU.
+
+        With AUG_MOSAIC_PROB > 0 every batch image first draws a coin, random_sample() < AUG_MOSAIC_PROB.  If it fails, the image's
+        own policy below runs unchanged and becomes part 0 of a mosaic with split = (IMAGE_WIDTH, IMAGE_HEIGHT), a drift as its
+        window.  If it succeeds, the draws are, in this order: xc = int(U[AUG_MOSAIC_CENTER] * IMAGE_WIDTH), then yc alike with
+        IMAGE_HEIGHT; three further dataset indices, randint(len(images)) each, independent of the epoch's permutation (part 0 is the
+        batch image itself); then per pane 0..3 that has pixels the draws of mosaic_part.  The image's boxes and labels are those of
+        pane 0, then 1, 2 and 3 (mosaic_part_boxes): ops.build_labels lets earlier boxes claim their anchors first."""
         mc = self.mc
+        prob = mosaic_prob(mc)
+        if (prob > 0.0) != (self.parts_per_image == 4):
+            raise ValueError("BatchReader: mc.AUG_MOSAIC_PROB was switched %s after the reader was built" % ("on" if prob > 0.0 else "off"))
         geometry = _cfg(mc, "AUG_GEOMETRY", "drift")
         if geometry not in ("drift", "ssd"):
             raise ValueError("BatchReader: mc.AUG_GEOMETRY must be 'drift' or 'ssd', got %r" % (geometry,))
@@ -282,7 +398,38 @@ class BatchReader:
         window, canvas, trial = np.zeros((B, 4), np.int64), np.zeros((B, 4), np.int64), np.zeros(B, np.int64)
         modes, color = [], np.zeros((B, 12), np.float32)
         label_per_batch, bbox_per_batch = [], []
+        W, H = int(mc.IMAGE_WIDTH), int(mc.IMAGE_HEIGHT)
+        split, parts = np.tile(np.array([W, H], np.int64), (B, 1)), np.full((B, 4), -1, np.int64)
+        part_window, part_flip = np.zeros((B, 4, 4), np.int64), np.zeros((B, 4), np.int64)
+        part_color = np.zeros((B, 4, 12), np.float32)
         for k, idx in enumerate(batch_idx):
+            if prob > 0.0 and self.rs.random_sample() < prob:
+                lo, hi = [float(v) for v in _cfg(mc, "AUG_MOSAIC_CENTER", (0.3, 0.7))]
+                xc = min(max(int(self.rs.uniform(lo, hi) * W), 0), W)
+                yc = min(max(int(self.rs.uniform(lo, hi) * H), 0), H)
+                split[k] = (xc, yc)
+                sources = [idx] + [int(self.rs.randint(len(self.images))) for _ in range(3)]
+                boxes, labels = [], []
+                min_box = _cfg(mc, "AUG_MOSAIC_MIN_BOX", 2.0)
+                for p, pane in enumerate(mosaic_panes(xc, yc, W, H)):
+                    if pane[2] <= 0 or pane[3] <= 0:
+                        continue
+                    sh, sw = [int(v) for v in self.sizes[sources[p]]]
+                    win, fl, M = mosaic_part(self.rs, mc, sw, sh, pane[2], pane[3])
+                    parts[k, p], part_window[k, p], part_flip[k, p] = sources[p], win, fl
+                    if M is not None:
+                        part_color[k, p] = M
+                    rows, kept = _mosaic_part_rows(win, fl, pane, self.rois[sources[p]], min_box)     # = mosaic_part_boxes
+                    boxes += rows
+                    labels += kept
+                bbox_per_batch.append(np.array(boxes, np.float64).reshape(-1, 4))
+                label_per_batch.append(labels)
+                modes.append("mosaic")
+                first = next(p for p in range(4) if parts[k, p] >= 0)       # part 0, unless AUG_MOSAIC_CENTER left it no pixels
+                window[k], color[k] = part_window[k, first], part_color[k, first]
+                aug[k] = (window[k, 0], window[k, 1], part_flip[k, first])
+                canvas[k] = (0, 0, self.sizes[parts[k, first]][1], self.sizes[parts[k, first]][0])
+                continue
             orig_h, orig_w = [float(v) for v in self.sizes[idx]]
             roi = self.rois[idx]
             label_per_batch.append([b[4] for b in roi[:]])
@@ -328,6 +475,10 @@ class BatchReader:
             window[k] = (dx, dy, int(orig_w), int(orig_h))
             if jitter:
                 color[k] = draw_color_matrix(self.rs, mc)
+            parts[k, 0], part_window[k, 0], part_flip[k, 0], part_color[k, 0] = idx, window[k], flip, color[k]
+        if prob > 0.0:
+            return MosaicPlan(batch_idx, aug, bbox_per_batch, label_per_batch, window, modes, color if jitter else None, canvas, trial,
+                              split, parts, part_window, part_flip, part_color if jitter else None)
         if not ssd and not jitter:
             return Plan(batch_idx, aug, bbox_per_batch, label_per_batch)
         return Plan(batch_idx, aug, bbox_per_batch, label_per_batch, window, modes, color if jitter else None, canvas, trial)
@@ -343,7 +494,9 @@ class BatchReader:
         return torch
 
     def _source(self, batch_idx):
-        """(flat device uint8 buffer, byte offset of each batch image in it)."""
+        """(flat device uint8 buffer, byte offset of each batch image in it).  With the mosaic on batch_idx lists up to four images
+        per batch image, and the packed mode's buffers hold 4 * BATCH_SIZE of the largest images; an image that is listed twice is
+        packed twice."""
         torch = self._torch()
         if self.resident:
             if self._src is None:
@@ -354,7 +507,7 @@ class BatchReader:
         offsets = np.concatenate([[0], np.cumsum(nb)[:-1]]).astype(np.int64)
         total = int(nb.sum())
         if self._pinned is None or self._pinned.numel() < total:
-            cap = int(np.sort(self.nbytes)[::-1][:max(1, self.mc.BATCH_SIZE)].sum())   # the largest possible batch
+            cap = int(np.sort(self.nbytes)[::-1][:max(1, self.mc.BATCH_SIZE)].sum()) * self.parts_per_image   # the largest possible batch
             cap = max(cap, total)
             self._pinned = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
             self._src = torch.empty(cap, dtype=torch.uint8, device=self.device)
@@ -379,11 +532,23 @@ class BatchReader:
         geom = np.concatenate([self.sizes[batch_idx], window, aug[:, 2:3].astype(np.int64)], axis=1)   # src_h, src_w, x0, y0, cw, ch, flip
         return ops.augment_bgr_window(src, offsets, geom, color, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, self.dtype)
 
+    def _warp_mosaic(self, p):
+        from . import ops
+        mc = self.mc
+        used = p.parts >= 0
+        src, offsets = self._source(p.parts[used])
+        part_offsets = np.zeros(p.parts.shape, np.int64)
+        part_offsets[used] = offsets
+        geom = np.zeros(p.parts.shape + (7,), np.int64)              # src_h, src_w, x0, y0, cw, ch, flip
+        geom[used] = np.concatenate([self.sizes[p.parts[used]], p.part_window[used], p.part_flip[used][:, None]], axis=1)
+        return ops.augment_bgr_mosaic(src, part_offsets, geom, p.split, p.part_color, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS,
+                                      self.dtype)
+
     def read_batch(self, shuffle=True):
         """imdb.read_batch (imdb.py:100-190): the next batch as a Batch, image_input and ground truth on the device."""
         torch = self._torch()
         p = self.next_plan(shuffle)
-        image_input = self._warp(p.batch_idx, p.aug, p.window, p.color)
+        image_input = self._warp(p.batch_idx, p.aug, p.window, p.color) if p.split is None else self._warp_mosaic(p)
         B, M = len(p.batch_idx), self.max_objects
         gt = np.zeros((B, M, 4), np.float64)
         cls = np.zeros((B, M), np.int32)
@@ -393,7 +558,8 @@ class BatchReader:
             gt[k, :len(lab)] = bb
             cls[k, :len(lab)] = lab
         to = lambda a: torch.from_numpy(a).to(self.device, non_blocking=True)
-        return Batch(image_input, to(gt), to(cls), to(cnt), p.aug, p.bbox_per_batch, p.label_per_batch, p.batch_idx, p.window, p.mode, p.color)
+        return Batch(image_input, to(gt), to(cls), to(cnt), p.aug, p.bbox_per_batch, p.label_per_batch, p.batch_idx, p.window, p.mode, p.color,
+                     p.split, p.parts, p.part_window, p.part_flip, p.part_color)
 
     def read_image_batch(self, shuffle=True):
         """imdb.read_image_batch (imdb.py:63-98): the next batch's images only -- mean-subtracted, then resized, with no drift

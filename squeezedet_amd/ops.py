@@ -1036,6 +1036,67 @@ def augment_bgr_window(src_u8, offsets, geom7, color, dst_h, dst_w, bgr_means, d
     return out
 
 
+def check_augment_mosaic_geometry(part_offsets, geom, split, src_bytes, dst_h, dst_w, color=None):
+    """check_augment_window_geometry for sqdet_augment_bgr_mosaic: part_offsets int [n,4], geom int [n,4,7], split int [n,2] =
+    (xc, yc) with 0 <= xc <= dst_w and 0 <= yc <= dst_h, color None or float [n,4,12].  Every pane that has pixels must pass
+    check_augment_window_geometry; a pane without pixels is not looked at (its rows are uploaded as zeros).  Returns (offsets int64
+    [n,4], geom int32 [n,4,7], split int32 [n,2], color float32 [n,4,12] or None); raises SqdetError on any bad row."""
+    s = np.ascontiguousarray(np.asarray(split).reshape(-1, 2), dtype=np.int64)
+    n = len(s)
+    try:
+        g = np.array(np.asarray(geom).reshape(n, 4, 7), dtype=np.int64)
+        o = np.array(np.asarray(part_offsets).reshape(n, 4), dtype=np.int64)
+        c = None if color is None else np.array(np.asarray(color, dtype=np.float32).reshape(n, 4, 12))
+    except ValueError:
+        raise _lib.SqdetError("augment_bgr_mosaic: %d splits need part_offsets [n,4], geom [n,4,7] and color [n,4,12]" % n)
+    if n == 0:
+        raise _lib.SqdetError("augment_bgr_mosaic: no images")
+    bad = (s[:, 0] < 0) | (s[:, 0] > int(dst_w)) | (s[:, 1] < 0) | (s[:, 1] > int(dst_h))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise _lib.SqdetError("augment_bgr_mosaic: image %d has its split (xc, yc) = %s outside [0, %d] x [0, %d]"
+                              % (i, tuple(int(v) for v in s[i]), int(dst_w), int(dst_h)))
+    pw = np.stack([s[:, 0], int(dst_w) - s[:, 0]], 1)[:, [0, 1, 0, 1]]
+    ph = np.stack([s[:, 1], int(dst_h) - s[:, 1]], 1)[:, [0, 0, 1, 1]]
+    live = (pw > 0) & (ph > 0)
+    g[~live], o[~live] = 0, 0
+    if c is not None:
+        c[~live] = 0
+    try:
+        check_augment_window_geometry(g[live], o[live], src_bytes, None if c is None else c[live])
+    except _lib.SqdetError as e:
+        raise _lib.SqdetError("augment_bgr_mosaic: a pane with pixels is invalid (its index below counts those panes only): %s" % e)
+    return o, g.astype(np.int32), s.astype(np.int32), c
+
+
+def augment_bgr_mosaic(src_u8, part_offsets, geom, split, color, dst_h, dst_w, bgr_means, dtype=torch.float32, out=None):
+    """Four images per network input (include/sqdet.h, sqdet_augment_bgr_mosaic): output image i is cut at split[i] = (xc, yc) into
+    four panes, and pane p holds augment_bgr_window's window of the image at byte part_offsets[i][p] under geom[i][p] = (src_h, src_w,
+    x0, y0, cw, ch, flip) and color[i][p] (or no matrix: color None), resized to the pane.  A pane without pixels may hold anything.
+    Checked on the host before anything is uploaded or launched; a rejected call raises and leaves `out` untouched."""
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
+        raise _lib.SqdetError("augment_bgr_mosaic: src must be a uint8 tensor")
+    src_bytes, dst_h, dst_w = int(src_u8.numel()), int(dst_h), int(dst_w)
+    if dst_h <= 0 or dst_w <= 0:
+        raise _lib.SqdetError("augment_bgr_mosaic: bad output size %dx%d" % (dst_h, dst_w))
+    o, g, s, c = check_augment_mosaic_geometry(part_offsets, geom, split, src_bytes, dst_h, dst_w, color)
+    n = len(s)
+    dev = src_u8.device
+    if out is None:
+        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
+    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
+        raise _lib.SqdetError("augment_bgr_mosaic: out must be %s [%d,%d,%d,3], got %s %s" % (dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
+    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
+    gd = torch.from_numpy(g).to(dev, non_blocking=True)
+    od = torch.from_numpy(o).to(dev, non_blocking=True)
+    sd = torch.from_numpy(s).to(dev, non_blocking=True)
+    cd = None if c is None else torch.from_numpy(c).to(dev, non_blocking=True)
+    check(lib().sqdet_augment_bgr_mosaic(_dev(src_u8, "src"), src_bytes, _dev(od, "part_offsets"), _dev(gd, "geom"), _dev(sd, "split"),
+                                         None if cd is None else _dev(cd, "color"), _dev(out, "out"), n, dst_h, dst_w, m[0], m[1], m[2],
+                                         dtype_code(dtype), stream_ptr()), "sqdet_augment_bgr_mosaic")
+    return out
+
+
 def box_calibration(device, mfma_iters=8192, copy_mib=1024, reps=3):
     """Two fixed microkernels timed with events on the current stream (sqdet_calib_mfma / sqdet_calib_copy): what THIS box
     sustains on a bare MFMA loop (TFLOP/s, float16 16x16x32) and on a plain device copy far larger than the Infinity Cache

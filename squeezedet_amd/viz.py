@@ -205,7 +205,12 @@ class ImageSummary:
         """uint8 RGB [n, H, W, 3] on the device, n = min(max_images, batch size)."""
         mc = self.mc
         n = min(self.max_images, int(batch.image_input.shape[0]))
-        gt = make_items(batch.gt_boxes[:n].contiguous(), batch.gt_classes[:n].contiguous(), batch.gt_counts[:n].contiguous(), self.names,
+        m = int(batch.gt_boxes.shape[1])
+        if m + int(mc.TOP_N_DETECTION) > MAX_ITEMS and getattr(batch, "label_per_batch", None) is not None:
+            # a mosaic reader pads to four times the dataset's largest object count: keep the columns these images use (known to the
+            # host), so that the two tables fit one draw launch wherever the boxes themselves do
+            m = max(1, max(len(lab) for lab in batch.label_per_batch[:n]))
+        gt = make_items(batch.gt_boxes[:n, :m].contiguous(), batch.gt_classes[:n, :m].contiguous(), batch.gt_counts[:n].contiguous(), self.names,
                         color=self.GT_COLOR, label="name")
         ob, op, oc, _, cnt = self.filtered(preds[:n].contiguous())
         det = make_items(ob, oc, cnt, self.names, probs=op, plot_thresh=mc.PLOT_PROB_THRESH, color=self.DET_COLOR, label="name: (p)")

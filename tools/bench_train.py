@@ -52,7 +52,11 @@ def main():
                          "four KITTI sizes, rois in original pixels.  reference (also the bare flag): the reference's drift / flip "
                          "augmentation, imdb.read_batch; ssd: crop windows, zoom-out up to 2x and colour jitter (train.py --augment ssd "
                          "--zoom_out 2 --color_jitter)")
+    ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
+                    help="with --augment: a batch image is a mosaic of four images with probability P (train.py --mosaic P)")
     args = ap.parse_args()
+    if not 0.0 <= args.mosaic <= 1.0 or (args.mosaic > 0.0 and not args.augment):
+        ap.error("--mosaic P needs 0 <= P <= 1 and --augment")
     if args.batch <= 0:
         args.batch = {"squeezeDet": 20, "resnet50": 8, "vgg16": 5}[args.arch]
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -85,6 +89,7 @@ def main():
     if args.augment:
         if args.augment == "ssd":
             mc.AUG_GEOMETRY, mc.AUG_ZOOM_OUT_MAX, mc.AUG_COLOR = "ssd", 2.0, True
+        mc.AUG_MOSAIC_PROB = args.mosaic
         reader = S.BatchReader(mc, *synthetic_dataset(mc, 2 * args.batch, seed=300 + rank), seed=rank, device=dev,
                                dtype=model.dtype, resident=True)
 
@@ -117,7 +122,8 @@ def main():
                           "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(el / args.steps * 1e3, 3),
                           "host_issue_ms_per_step": round(t_issued / args.steps * 1e3, 3), "dtype": args.dtype,
-                          "data": ("synthetic uint8 + BatchReader " + {"reference": "drift/flip", "ssd": "ssd windows/zoom-out 2/colour"}[args.augment]) if args.augment else "synthetic",
+                          "data": ("synthetic uint8 + BatchReader " + {"reference": "drift/flip", "ssd": "ssd windows/zoom-out 2/colour"}[args.augment]
+                                   + (" + mosaic %g" % args.mosaic if args.mosaic > 0.0 else "")) if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
                           "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,

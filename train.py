@@ -24,7 +24,9 @@ squeezedet_amd.voc.load_voc; the images may differ in size.  (Its ConvDet head i
 head is padded); the file is copied to <train_dir>/anchor_shapes.json, where eval.py and demo.py find it, and the shapes are
 recorded in every checkpoint: --resume refuses other shapes and, without the flag, uses the recorded ones.  --augment ssd
 [--zoom_out MAX] and --color_jitter switch on BatchReader's crop-window / zoom-out and colour augmentation (squeezedet_amd.imdb);
-the policy is recorded in every checkpoint and --resume under another one is refused.  --anchor_report writes
+the policy is recorded in every checkpoint and --resume under another one is refused.  --mosaic P makes a batch image, with
+probability P, a mosaic of four training images (one sqdet_augment_bgr_mosaic launch per batch); P is recorded under its own key,
+`mosaic`, and --resume under another P is refused (a checkpoint without the key was trained with 0).  --anchor_report writes
 <train_dir>/anchor_coverage.json (squeezedet_amd.anchors.dataset_coverage of the training set) once, before the first step.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
@@ -73,8 +75,13 @@ def parse_args(argv=None):
                     help="--augment ssd: with probability 1/2 place the image on a canvas U[1, MAX] times its size (default 1: never)")
     ap.add_argument("--color_jitter", action="store_true", default=argparse.SUPPRESS,
                     help="random brightness, contrast, saturation and hue, one 3x4 matrix per image")
+    ap.add_argument("--mosaic", type=float, default=argparse.SUPPRESS, metavar="P",
+                    help="with probability P a batch image is a mosaic: four training images, each cropped into its own pane of the "
+                         "network input (default 0: never)")
     a = ap.parse_args(argv)
     drivers.check_dataset_args(ap, a)
+    if not 0.0 <= getattr(a, "mosaic", 0.0) <= 1.0:
+        ap.error("--mosaic P needs 0 <= P <= 1")
     if a.resume and a.overwrite:
         ap.error("--resume and --overwrite exclude each other")
     policy = augment_policy(a)
@@ -207,6 +214,9 @@ class Run:
         self.anchor_shapes = resolve_anchor_shapes(a, resume_step)
         self.mc = mc = drivers.make_config(a.net, a.image_size, a.dataset, self.anchor_shapes)
         policy = augment_policy(a, mc)
+        mc.AUG_MOSAIC_PROB = mosaic = float(getattr(a, "mosaic", 0.0))
+        if mosaic > 0.0 and not mc.DATA_AUGMENTATION:
+            raise SystemExit("--mosaic needs a config with DATA_AUGMENTATION on")
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)
@@ -214,11 +224,12 @@ class Run:
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
         self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE),
-                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy)
+                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy, mosaic=mosaic)
         self.first = 0
         if resume_step is not None:
             saved = checkpoint.read_extra(a.train_dir, resume_step)
             saved.setdefault("augment", AUGMENT_OFF)
+            saved.setdefault("mosaic", 0.0)
             for key, now in self.extra.items():
                 if saved.get(key) != now:
                     raise SystemExit("--resume: the checkpoint was trained with %s %r, this run asks for %r" % (key, saved.get(key), now))

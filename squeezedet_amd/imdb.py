@@ -289,6 +289,35 @@ def mosaic_prob(mc):
     return p
 
 
+def reference_drift(rs, mc, boxes):
+    """The reference's drift (imdb.py:150-166) of an image with [n, 4] boxes (cx, cy, w, h in its pixels): (dx, dy), each in
+    [-DRIFT, DRIFT] and so small that no box is cut at the left or the top -- the bound is min(cx - w / 2 + 1) as a float, which
+    randint truncates.  Draws from rs dy BEFORE dx, one randint each; nothing with DRIFT_X = DRIFT_Y = 0.  Diverges from the
+    reference on purpose: an image with no boxes draws from the full range, where the reference crashes."""
+    assert mc.DRIFT_X >= 0 and mc.DRIFT_Y > 0, 'mc.DRIFT_X and mc.DRIFT_Y must be >= 0'
+    if not (mc.DRIFT_X > 0 or mc.DRIFT_Y > 0):
+        return 0, 0
+    max_drift_x, max_drift_y = mc.DRIFT_X + 1, mc.DRIFT_Y + 1
+    if len(boxes):
+        max_drift_x = min(boxes[:, 0] - boxes[:, 2] / 2.0 + 1)
+        max_drift_y = min(boxes[:, 1] - boxes[:, 3] / 2.0 + 1)
+        assert max_drift_x >= 0 and max_drift_y >= 0, 'bbox out of image'
+    dy = rs.randint(-mc.DRIFT_Y, min(mc.DRIFT_Y + 1, max_drift_y))
+    dx = rs.randint(-mc.DRIFT_X, min(mc.DRIFT_X + 1, max_drift_x))
+    return dx, dy
+
+
+# one batch image of a plan, as a mosaic -- a single image is part 0 of a mosaic with one pane, split (IMAGE_WIDTH, IMAGE_HEIGHT):
+# aug = (dx, dy, flip), the boxes in network-input pixels, the labels, window, mode, color, canvas, trial, and split, parts,
+# part_window, part_flip, part_color with four entries each.  The fields are MosaicPlan's after batch_idx, one row of each; a
+# plan's columns are lists or arrays of these types (float32: None without AUG_COLOR).
+_ImagePlan = namedtuple("_ImagePlan", MosaicPlan._fields[1:])
+_PLAN_COLUMNS = (np.int32, list, list, np.int64, list, np.float32, np.int64, np.int64) + (np.int64,) * 4 + (np.float32,)
+_NO_COLOR = np.zeros(12, np.float32)
+_NO_COLOR.setflags(write=False)
+_NO_PART = (-1, (0, 0, 0, 0), 0, _NO_COLOR)         # a pane without pixels: (source, window, flip, colour matrix)
+
+
 class BatchReader:
     """``BatchReader(mc, images, rois, seed=0, device=None, dtype=torch.float32, resident=False)``
 
@@ -377,9 +406,12 @@ class BatchReader:
         """The host half of read_batch: batch order, random draws and box transform (imdb.py:100-190), in NumPy float64 in
         the reference's order.  Advances the reader; needs no GPU.
 
+        Four steps: the flags are validated, the indices taken, every image becomes one _ImagePlan -- _single_image under the "drift"
+        or "ssd" policy, _mosaic_image as a mosaic --, and the records' columns become the plan's arrays.
+
         With AUG_MOSAIC_PROB > 0 every batch image first draws a coin, random_sample() < AUG_MOSAIC_PROB.  If it fails, the image's
-        own policy below runs unchanged and becomes part 0 of a mosaic with split = (IMAGE_WIDTH, IMAGE_HEIGHT), a drift as its
-        window.  If it succeeds, the draws are, in this order: xc = int(U[AUG_MOSAIC_CENTER] * IMAGE_WIDTH), then yc alike with
+        own policy runs unchanged (_single_image) and is part 0 of a mosaic with split = (IMAGE_WIDTH, IMAGE_HEIGHT), a drift as its
+        window.  If it succeeds, the draws are (_mosaic_image), in this order: xc = int(U[AUG_MOSAIC_CENTER] * IMAGE_WIDTH), then yc alike with
         IMAGE_HEIGHT; three further dataset indices, randint(len(images)) each, independent of the epoch's permutation (part 0 is the
         batch image itself); then per pane 0..3 that has pixels the draws of mosaic_part.  The image's boxes and labels are those of
         pane 0, then 1, 2 and 3 (mosaic_part_boxes): ops.build_labels lets earlier boxes claim their anchors first."""
@@ -390,98 +422,76 @@ class BatchReader:
         geometry = _cfg(mc, "AUG_GEOMETRY", "drift")
         if geometry not in ("drift", "ssd"):
             raise ValueError("BatchReader: mc.AUG_GEOMETRY must be 'drift' or 'ssd', got %r" % (geometry,))
-        ssd = bool(mc.DATA_AUGMENTATION) and geometry == "ssd"
-        jitter = bool(mc.DATA_AUGMENTATION) and bool(_cfg(mc, "AUG_COLOR", False))
+        augment = bool(mc.DATA_AUGMENTATION)
+        ssd, jitter = augment and geometry == "ssd", augment and bool(_cfg(mc, "AUG_COLOR", False))
         batch_idx = self._next_indices(shuffle)
-        B = len(batch_idx)
-        aug = np.zeros((B, 3), np.int32)
-        window, canvas, trial = np.zeros((B, 4), np.int64), np.zeros((B, 4), np.int64), np.zeros(B, np.int64)
-        modes, color = [], np.zeros((B, 12), np.float32)
-        label_per_batch, bbox_per_batch = [], []
+        rows = [self._mosaic_image(idx) if prob > 0.0 and self.rs.random_sample() < prob else self._single_image(idx, augment, ssd, jitter)
+                for idx in batch_idx]
+        # the reference's four fields, nine with "ssd" or colour, all fourteen with the mosaic: only those columns are made
+        n = 14 if prob > 0.0 else 9 if ssd or jitter else 4
+        columns = [list(c) if kind is list else np.array(c, kind) if jitter or kind is not np.float32 else None
+                   for c, kind in zip(zip(*rows), _PLAN_COLUMNS[:n - 1])]
+        return (MosaicPlan if n == 14 else Plan)(batch_idx, *columns)
+
+    def _image_plan(self, bbox, label, mode, trial, canvas, split, panes):
+        """The record of one batch image from its four panes, each (source index, window, flip, colour matrix) or _NO_PART: the
+        single-image fields describe the first pane that has pixels -- part 0, unless AUG_MOSAIC_CENTER left it none --, and the canvas,
+        where no zoom-out drew one (None), is that part's whole image."""
+        source, win, flip, color = next(p for p in panes if p[0] >= 0)
+        if canvas is None:
+            canvas = (0, 0, self.images[source].shape[1], self.images[source].shape[0])
+        return _ImagePlan((win[0], win[1], flip), bbox, label, win, mode, color, canvas, trial, split, *zip(*panes))
+
+    def _single_image(self, idx, augment, ssd, jitter):
+        """One image under the "drift" or the "ssd" policy (imdb.py:141-190): its geometry's draws (reference_drift / ssd_window), the
+        mirror, randint(2), and with AUG_COLOR draw_color_matrix; nothing is drawn without DATA_AUGMENTATION.  The drift (dx, dy) is the
+        window (dx, dy, w - dx, h - dy); the image is the only pane of a mosaic split at (IMAGE_WIDTH, IMAGE_HEIGHT)."""
+        mc, rs = self.mc, self.rs
+        h, w = self.images[idx].shape[:2]
+        roi = self.rois[idx]
+        label = [b[4] for b in roi]
+        gt_bbox = np.array([[b[0], b[1], b[2], b[3]] for b in roi]) if roi else np.zeros((0, 4))
+        win, canvas, mode, trial, flip = (0, 0, w, h), None, "drift", 0, 0
+        if ssd:
+            win, canvas, mode, trial = ssd_window(rs, mc, w, h, gt_bbox)
+            keep, gt_bbox = window_boxes(win, gt_bbox)
+            label = [c for c, kept in zip(label, keep) if kept]
+        elif augment:
+            dx, dy = reference_drift(rs, mc, gt_bbox)
+            gt_bbox[:, 0] = gt_bbox[:, 0] - dx
+            gt_bbox[:, 1] = gt_bbox[:, 1] - dy
+            win = (dx, dy, w - dx, h - dy)
+        if augment and rs.randint(2) > 0.5:
+            flip = 1
+            gt_bbox[:, 0] = float(win[2]) - 1 - gt_bbox[:, 0]
+        gt_bbox[:, 0::2] = gt_bbox[:, 0::2] * (mc.IMAGE_WIDTH / float(win[2]))
+        gt_bbox[:, 1::2] = gt_bbox[:, 1::2] * (mc.IMAGE_HEIGHT / float(win[3]))
+        color = draw_color_matrix(rs, mc) if jitter else _NO_COLOR
+        return self._image_plan(gt_bbox, label, mode, trial, canvas, (int(mc.IMAGE_WIDTH), int(mc.IMAGE_HEIGHT)),
+                                ((idx, win, flip, color), _NO_PART, _NO_PART, _NO_PART))
+
+    def _mosaic_image(self, idx):
+        """One mosaic of image idx and three more (next_plan states the draws): every pane that has pixels shows a mosaic_part of its
+        image, and the boxes are those of pane 0, then 1, 2 and 3."""
+        mc, rs = self.mc, self.rs
         W, H = int(mc.IMAGE_WIDTH), int(mc.IMAGE_HEIGHT)
-        split, parts = np.tile(np.array([W, H], np.int64), (B, 1)), np.full((B, 4), -1, np.int64)
-        part_window, part_flip = np.zeros((B, 4, 4), np.int64), np.zeros((B, 4), np.int64)
-        part_color = np.zeros((B, 4, 12), np.float32)
-        for k, idx in enumerate(batch_idx):
-            if prob > 0.0 and self.rs.random_sample() < prob:
-                lo, hi = [float(v) for v in _cfg(mc, "AUG_MOSAIC_CENTER", (0.3, 0.7))]
-                xc = min(max(int(self.rs.uniform(lo, hi) * W), 0), W)
-                yc = min(max(int(self.rs.uniform(lo, hi) * H), 0), H)
-                split[k] = (xc, yc)
-                sources = [idx] + [int(self.rs.randint(len(self.images))) for _ in range(3)]
-                boxes, labels = [], []
-                min_box = _cfg(mc, "AUG_MOSAIC_MIN_BOX", 2.0)
-                for p, pane in enumerate(mosaic_panes(xc, yc, W, H)):
-                    if pane[2] <= 0 or pane[3] <= 0:
-                        continue
-                    sh, sw = [int(v) for v in self.sizes[sources[p]]]
-                    win, fl, M = mosaic_part(self.rs, mc, sw, sh, pane[2], pane[3])
-                    parts[k, p], part_window[k, p], part_flip[k, p] = sources[p], win, fl
-                    if M is not None:
-                        part_color[k, p] = M
-                    rows, kept = _mosaic_part_rows(win, fl, pane, self.rois[sources[p]], min_box)     # = mosaic_part_boxes
-                    boxes += rows
-                    labels += kept
-                bbox_per_batch.append(np.array(boxes, np.float64).reshape(-1, 4))
-                label_per_batch.append(labels)
-                modes.append("mosaic")
-                first = next(p for p in range(4) if parts[k, p] >= 0)       # part 0, unless AUG_MOSAIC_CENTER left it no pixels
-                window[k], color[k] = part_window[k, first], part_color[k, first]
-                aug[k] = (window[k, 0], window[k, 1], part_flip[k, first])
-                canvas[k] = (0, 0, self.sizes[parts[k, first]][1], self.sizes[parts[k, first]][0])
+        lo, hi = [float(v) for v in _cfg(mc, "AUG_MOSAIC_CENTER", (0.3, 0.7))]
+        xc = min(max(int(rs.uniform(lo, hi) * W), 0), W)
+        yc = min(max(int(rs.uniform(lo, hi) * H), 0), H)
+        sources = [idx] + [int(rs.randint(len(self.images))) for _ in range(3)]
+        min_box = _cfg(mc, "AUG_MOSAIC_MIN_BOX", 2.0)
+        boxes, labels, panes = [], [], []
+        for source, pane in zip(sources, mosaic_panes(xc, yc, W, H)):
+            if pane[2] <= 0 or pane[3] <= 0:
+                panes.append(_NO_PART)
                 continue
-            orig_h, orig_w = [float(v) for v in self.sizes[idx]]
-            roi = self.rois[idx]
-            label_per_batch.append([b[4] for b in roi[:]])
-            gt_bbox = np.array([[b[0], b[1], b[2], b[3]] for b in roi[:]]) if roi else np.zeros((0, 4))
-            dx = dy = flip = 0
-            if ssd:
-                win, canvas[k], mode, trial[k] = ssd_window(self.rs, mc, orig_w, orig_h, gt_bbox)
-                modes.append(mode)
-                keep, gt_bbox = window_boxes(win, gt_bbox)
-                label_per_batch[-1] = [c for c, kept in zip(label_per_batch[-1], keep) if kept]
-                dx, dy, orig_w, orig_h = int(win[0]), int(win[1]), float(win[2]), float(win[3])
-                if self.rs.randint(2) > 0.5:
-                    flip = 1
-                    gt_bbox[:, 0] = orig_w - 1 - gt_bbox[:, 0]
-            elif mc.DATA_AUGMENTATION:
-                assert mc.DRIFT_X >= 0 and mc.DRIFT_Y > 0, 'mc.DRIFT_X and mc.DRIFT_Y must be >= 0'
-                if mc.DRIFT_X > 0 or mc.DRIFT_Y > 0:
-                    if len(gt_bbox):
-                        # the drift never cuts a box (imdb.py:154-160); a float bound, which randint truncates
-                        max_drift_x = min(gt_bbox[:, 0] - gt_bbox[:, 2] / 2.0 + 1)
-                        max_drift_y = min(gt_bbox[:, 1] - gt_bbox[:, 3] / 2.0 + 1)
-                        assert max_drift_x >= 0 and max_drift_y >= 0, 'bbox out of image'
-                    else:                      # no boxes: the full range (the reference crashes here)
-                        max_drift_x, max_drift_y = mc.DRIFT_X + 1, mc.DRIFT_Y + 1
-                    dy = self.rs.randint(-mc.DRIFT_Y, min(mc.DRIFT_Y + 1, max_drift_y))
-                    dx = self.rs.randint(-mc.DRIFT_X, min(mc.DRIFT_X + 1, max_drift_x))
-                    gt_bbox[:, 0] = gt_bbox[:, 0] - dx
-                    gt_bbox[:, 1] = gt_bbox[:, 1] - dy
-                    orig_h -= dy
-                    orig_w -= dx
-                if self.rs.randint(2) > 0.5:
-                    flip = 1
-                    gt_bbox[:, 0] = orig_w - 1 - gt_bbox[:, 0]
-            x_scale = mc.IMAGE_WIDTH / orig_w
-            y_scale = mc.IMAGE_HEIGHT / orig_h
-            gt_bbox[:, 0::2] = gt_bbox[:, 0::2] * x_scale
-            gt_bbox[:, 1::2] = gt_bbox[:, 1::2] * y_scale
-            bbox_per_batch.append(gt_bbox)
-            aug[k] = (dx, dy, flip)
-            if not ssd:
-                modes.append("drift")
-                canvas[k] = (0, 0, self.sizes[idx][1], self.sizes[idx][0])
-            window[k] = (dx, dy, int(orig_w), int(orig_h))
-            if jitter:
-                color[k] = draw_color_matrix(self.rs, mc)
-            parts[k, 0], part_window[k, 0], part_flip[k, 0], part_color[k, 0] = idx, window[k], flip, color[k]
-        if prob > 0.0:
-            return MosaicPlan(batch_idx, aug, bbox_per_batch, label_per_batch, window, modes, color if jitter else None, canvas, trial,
-                              split, parts, part_window, part_flip, part_color if jitter else None)
-        if not ssd and not jitter:
-            return Plan(batch_idx, aug, bbox_per_batch, label_per_batch)
-        return Plan(batch_idx, aug, bbox_per_batch, label_per_batch, window, modes, color if jitter else None, canvas, trial)
+            sh, sw = self.images[source].shape[:2]
+            win, flip, M = mosaic_part(rs, mc, sw, sh, pane[2], pane[3])
+            panes.append((source, win, flip, _NO_COLOR if M is None else M))
+            rows, kept = _mosaic_part_rows(win, flip, pane, self.rois[source], min_box)     # = mosaic_part_boxes
+            boxes += rows
+            labels += kept
+        return self._image_plan(np.array(boxes, np.float64).reshape(-1, 4), labels, "mosaic", 0, None, (xc, yc), panes)
 
     # ---------------------------------------------------------------------------------------------------- device half --
     def _torch(self):
@@ -522,33 +532,31 @@ class BatchReader:
         self._copied.record()
         return self._src[:total], offsets
 
-    def _warp(self, batch_idx, aug, window=None, color=None):
-        from . import ops
-        src, offsets = self._source(batch_idx)
-        mc = self.mc
-        if window is None:
-            geom = np.concatenate([self.sizes[batch_idx], aug.astype(np.int64)], axis=1)   # src_h, src_w, dx, dy, flip
-            return ops.augment_bgr(src, offsets, geom, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, self.dtype)
-        geom = np.concatenate([self.sizes[batch_idx], window, aug[:, 2:3].astype(np.int64)], axis=1)   # src_h, src_w, x0, y0, cw, ch, flip
-        return ops.augment_bgr_window(src, offsets, geom, color, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, self.dtype)
-
-    def _warp_mosaic(self, p):
+    def _warp(self, p):
+        """The plan's images in ONE launch; its shape chooses the entry point: split -> the mosaic, window -> the window form, else the
+        drift with the reference's five-column geometry."""
         from . import ops
         mc = self.mc
-        used = p.parts >= 0
-        src, offsets = self._source(p.parts[used])
-        part_offsets = np.zeros(p.parts.shape, np.int64)
-        part_offsets[used] = offsets
-        geom = np.zeros(p.parts.shape + (7,), np.int64)              # src_h, src_w, x0, y0, cw, ch, flip
-        geom[used] = np.concatenate([self.sizes[p.parts[used]], p.part_window[used], p.part_flip[used][:, None]], axis=1)
-        return ops.augment_bgr_mosaic(src, part_offsets, geom, p.split, p.part_color, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS,
-                                      self.dtype)
+        dst = (mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, mc.BGR_MEANS, self.dtype)
+        if p.split is not None:
+            used = p.parts >= 0
+            src, offsets = self._source(p.parts[used])
+            part_offsets = np.zeros(p.parts.shape, np.int64)
+            part_offsets[used] = offsets
+            geom = np.zeros(p.parts.shape + (7,), np.int64)              # src_h, src_w, x0, y0, cw, ch, flip
+            geom[used] = np.concatenate([self.sizes[p.parts[used]], p.part_window[used], p.part_flip[used][:, None]], axis=1)
+            return ops.augment_bgr_mosaic(src, part_offsets, geom, p.split, p.part_color, *dst)
+        src, offsets = self._source(p.batch_idx)
+        sizes, aug = self.sizes[p.batch_idx], p.aug.astype(np.int64)
+        if p.window is not None:
+            return ops.augment_bgr_window(src, offsets, np.concatenate([sizes, p.window, aug[:, 2:3]], axis=1), p.color, *dst)
+        return ops.augment_bgr(src, offsets, np.concatenate([sizes, aug], axis=1), *dst)     # src_h, src_w, dx, dy, flip
 
     def read_batch(self, shuffle=True):
         """imdb.read_batch (imdb.py:100-190): the next batch as a Batch, image_input and ground truth on the device."""
         torch = self._torch()
         p = self.next_plan(shuffle)
-        image_input = self._warp(p.batch_idx, p.aug, p.window, p.color) if p.split is None else self._warp_mosaic(p)
+        image_input = self._warp(p)
         B, M = len(p.batch_idx), self.max_objects
         gt = np.zeros((B, M, 4), np.float64)
         cls = np.zeros((B, M), np.int32)
@@ -558,8 +566,7 @@ class BatchReader:
             gt[k, :len(lab)] = bb
             cls[k, :len(lab)] = lab
         to = lambda a: torch.from_numpy(a).to(self.device, non_blocking=True)
-        return Batch(image_input, to(gt), to(cls), to(cnt), p.aug, p.bbox_per_batch, p.label_per_batch, p.batch_idx, p.window, p.mode, p.color,
-                     p.split, p.parts, p.part_window, p.part_flip, p.part_color)
+        return Batch(image_input, to(gt), to(cls), to(cnt), *[getattr(p, f) for f in Batch._fields[4:]])
 
     def read_image_batch(self, shuffle=True):
         """imdb.read_image_batch (imdb.py:63-98): the next batch's images only -- mean-subtracted, then resized, with no drift
@@ -570,4 +577,4 @@ class BatchReader:
         for idx in batch_idx:
             orig_h, orig_w = [float(v) for v in self.sizes[idx]]
             scales.append((self.mc.IMAGE_WIDTH / orig_w, self.mc.IMAGE_HEIGHT / orig_h))
-        return self._warp(batch_idx, np.zeros((len(batch_idx), 3), np.int32)), scales
+        return self._warp(Plan(batch_idx, np.zeros((len(batch_idx), 3), np.int32), None, None)), scales

@@ -935,24 +935,57 @@ def preprocess_bgr(images_u8, dst_h, dst_w, bgr_means, dtype=torch.float32):
 
 
 AUGMENT_MAX_DRIFT = 65535
+AUGMENT_MAX_WINDOW = 65535
+
+
+def _check_augment_rows(name, fields, geom, offsets, src_bytes, bad_geometry):
+    """What the drift and the window validators share: geom int [n, len(fields)] with src_h, src_w first, an offset (dx, dy or x0, y0)
+    within +-AUGMENT_MAX_DRIFT next and flip last, offsets int [n] of images that lie inside src_bytes.  bad_geometry(*columns) ->
+    [n] bool adds the caller's own conditions; the first bad row is reported under the caller's name and field list.  Returns (geom
+    int32, offsets int64) as contiguous NumPy arrays."""
+    g = np.ascontiguousarray(np.asarray(geom).reshape(-1, len(fields)), dtype=np.int64)
+    o = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
+    if len(g) == 0 or len(o) != len(g):
+        raise _lib.SqdetError("%s: %d geometry rows for %d offsets" % (name, len(g), len(o)))
+    h, w, x, y, flip = g[:, 0], g[:, 1], g[:, 2], g[:, 3], g[:, -1]
+    bad = ((h <= 0) | (w <= 0) | (np.abs(x) > AUGMENT_MAX_DRIFT) | (np.abs(y) > AUGMENT_MAX_DRIFT) | ((flip != 0) & (flip != 1))
+           | (o < 0) | (o + h * w * 3 > int(src_bytes)) | bad_geometry(*g.T))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise _lib.SqdetError("%s: image %d has bad geometry (%s) = %s at byte offset %d of %d"
+                              % (name, i, ", ".join(fields), tuple(int(v) for v in g[i]), int(o[i]), int(src_bytes)))
+    return g.astype(np.int32), o
+
+
+def _augment_launch(entry, src_u8, dst_h, dst_w, bgr_means, dtype, out, validate):
+    """The body of the three augment wrappers: the source and output-size checks, validate(src_bytes, dst_h, dst_w) -> the entry
+    point's host arrays as [(argument name, array or None)] in its order, the first with a row per output image, then `out`, the
+    float64 means, the uploads and the launch.  Nothing is uploaded or launched, and `out` is not touched, before every check passed."""
+    name = entry[len("sqdet_"):]
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
+        raise _lib.SqdetError("%s: src must be a uint8 tensor" % name)
+    src_bytes, dst_h, dst_w = int(src_u8.numel()), int(dst_h), int(dst_w)
+    if dst_h <= 0 or dst_w <= 0:
+        raise _lib.SqdetError("%s: bad output size %dx%d" % (name, dst_h, dst_w))
+    arrays = validate(src_bytes, dst_h, dst_w)
+    n, dev = len(arrays[0][1]), src_u8.device
+    if out is None:
+        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
+    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
+        raise _lib.SqdetError("%s: out must be %s [%d,%d,%d,3], got %s %s" % (name, dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
+    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
+    uploaded = [(k, None if a is None else torch.from_numpy(a).to(dev, non_blocking=True)) for k, a in arrays]
+    check(getattr(lib(), entry)(_dev(src_u8, "src"), src_bytes, *[None if t is None else _dev(t, k) for k, t in uploaded], _dev(out, "out"),
+                                n, dst_h, dst_w, m[0], m[1], m[2], dtype_code(dtype), stream_ptr()), entry)
+    return out
 
 
 def check_augment_geometry(geom, offsets, src_bytes):
     """Host-side validation of sqdet_augment_bgr's per-image geometry (the kernel reads it from the device and cannot
     reject it): geom int [n,5] = (src_h, src_w, dx, dy, flip), offsets int [n] byte offsets into a buffer of src_bytes.
     Returns (geom int32, offsets int64) as contiguous NumPy arrays; raises SqdetError on any bad row."""
-    g = np.ascontiguousarray(np.asarray(geom).reshape(-1, 5), dtype=np.int64)
-    o = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
-    if len(g) == 0 or len(o) != len(g):
-        raise _lib.SqdetError("augment_bgr: %d geometry rows for %d offsets" % (len(g), len(o)))
-    h, w, dx, dy, flip = g.T
-    bad = ((h <= 0) | (w <= 0) | (dx >= w) | (dy >= h) | (np.abs(dx) > AUGMENT_MAX_DRIFT) | (np.abs(dy) > AUGMENT_MAX_DRIFT)
-           | ((flip != 0) & (flip != 1)) | (o < 0) | (o + h * w * 3 > int(src_bytes)))
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise _lib.SqdetError("augment_bgr: image %d has bad geometry (src_h, src_w, dx, dy, flip) = %s at byte offset %d of %d"
-                              % (i, tuple(int(v) for v in g[i]), int(o[i]), int(src_bytes)))
-    return g.astype(np.int32), o
+    return _check_augment_rows("augment_bgr", ("src_h", "src_w", "dx", "dy", "flip"), geom, offsets, src_bytes,
+                               lambda h, w, dx, dy, flip: (dx >= w) | (dy >= h))
 
 
 def augment_bgr(src_u8, offsets, geom, dst_h, dst_w, bgr_means, dtype=torch.float32, out=None):
@@ -961,51 +994,25 @@ def augment_bgr(src_u8, offsets, geom, dst_h, dst_w, bgr_means, dtype=torch.floa
     (float64 means, rounded once), drifted (zero padding), mirrored, resized (cv2 INTER_LINEAR) NHWC network input
     [n, dst_h, dst_w, 3] in `dtype` (written into `out` when given).  The geometry is checked on the host before anything is
     uploaded or launched; a rejected call raises and leaves `out` untouched."""
-    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
-        raise _lib.SqdetError("augment_bgr: src must be a uint8 tensor")
-    src_bytes = int(src_u8.numel())
-    g, o = check_augment_geometry(geom, offsets, src_bytes)
-    n, dst_h, dst_w = len(g), int(dst_h), int(dst_w)
-    if dst_h <= 0 or dst_w <= 0:
-        raise _lib.SqdetError("augment_bgr: bad output size %dx%d" % (dst_h, dst_w))
-    dev = src_u8.device
-    if out is None:
-        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
-    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
-        raise _lib.SqdetError("augment_bgr: out must be %s [%d,%d,%d,3], got %s %s" % (dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
-    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
-    gd = torch.from_numpy(g).to(dev, non_blocking=True)
-    od = torch.from_numpy(o).to(dev, non_blocking=True)
-    check(lib().sqdet_augment_bgr(_dev(src_u8, "src"), src_bytes, _dev(od, "offsets"), _dev(gd, "geom"), _dev(out, "out"), n,
-                                  dst_h, dst_w, m[0], m[1], m[2], dtype_code(dtype), stream_ptr()), "sqdet_augment_bgr")
-    return out
-
-
-AUGMENT_MAX_WINDOW = 65535
+    def validate(src_bytes, dst_h, dst_w):
+        g, o = check_augment_geometry(geom, offsets, src_bytes)
+        return ("offsets", o), ("geom", g)
+    return _augment_launch("sqdet_augment_bgr", src_u8, dst_h, dst_w, bgr_means, dtype, out, validate)
 
 
 def check_augment_window_geometry(geom, offsets, src_bytes, color=None):
     """check_augment_geometry for sqdet_augment_bgr_window: geom int [n,7] = (src_h, src_w, x0, y0, cw, ch, flip), color None or
     float [n,12] (finite).  x0, y0 within +-65535, cw and ch in [1, 65535] -- or larger where the window is a drift's, x0 + cw == src_w
     (y0 + ch == src_h).  Returns (geom int32, offsets int64, color float32 or None); raises SqdetError on any bad row."""
-    g = np.ascontiguousarray(np.asarray(geom).reshape(-1, 7), dtype=np.int64)
-    o = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.int64)
-    if len(g) == 0 or len(o) != len(g):
-        raise _lib.SqdetError("augment_bgr_window: %d geometry rows for %d offsets" % (len(g), len(o)))
-    h, w, x0, y0, cw, ch, flip = g.T
     # (a window above AUGMENT_MAX_WINDOW only as the drift's own, ending at the image's far edge: what augment_bgr accepts)
-    bad = ((h <= 0) | (w <= 0) | (np.abs(x0) > AUGMENT_MAX_DRIFT) | (np.abs(y0) > AUGMENT_MAX_DRIFT) | (cw < 1) | (ch < 1)
-           | ((cw > AUGMENT_MAX_WINDOW) & (x0 + cw != w)) | ((ch > AUGMENT_MAX_WINDOW) & (y0 + ch != h))
-           | ((flip != 0) & (flip != 1)) | (o < 0) | (o + h * w * 3 > int(src_bytes)))
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise _lib.SqdetError("augment_bgr_window: image %d has bad geometry (src_h, src_w, x0, y0, cw, ch, flip) = %s at byte offset "
-                              "%d of %d" % (i, tuple(int(v) for v in g[i]), int(o[i]), int(src_bytes)))
+    g, o = _check_augment_rows("augment_bgr_window", ("src_h", "src_w", "x0", "y0", "cw", "ch", "flip"), geom, offsets, src_bytes,
+                               lambda h, w, x0, y0, cw, ch, flip: ((cw < 1) | (ch < 1) | ((cw > AUGMENT_MAX_WINDOW) & (x0 + cw != w))
+                                                                   | ((ch > AUGMENT_MAX_WINDOW) & (y0 + ch != h))))
     if color is not None:
         color = np.ascontiguousarray(np.asarray(color, dtype=np.float32).reshape(-1, 12))
         if len(color) != len(g) or not np.isfinite(color).all():
             raise _lib.SqdetError("augment_bgr_window: color must be %d finite 3x4 matrices, got %s" % (len(g), color.shape))
-    return g.astype(np.int32), o, color
+    return g, o, color
 
 
 def augment_bgr_window(src_u8, offsets, geom7, color, dst_h, dst_w, bgr_means, dtype=torch.float32, out=None):
@@ -1014,26 +1021,10 @@ def augment_bgr_window(src_u8, offsets, geom7, color, dst_h, dst_w, bgr_means, d
     per image) is given, a colour transform of the source bytes, clamped to [0, 255], before the mean is subtracted (include/sqdet.h).
     geom7: host int [n,7] = (src_h, src_w, x0, y0, cw, ch, flip).  Checked on the host before anything is uploaded or launched; a
     rejected call raises and leaves `out` untouched."""
-    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
-        raise _lib.SqdetError("augment_bgr_window: src must be a uint8 tensor")
-    src_bytes = int(src_u8.numel())
-    g, o, c = check_augment_window_geometry(geom7, offsets, src_bytes, color)
-    n, dst_h, dst_w = len(g), int(dst_h), int(dst_w)
-    if dst_h <= 0 or dst_w <= 0:
-        raise _lib.SqdetError("augment_bgr_window: bad output size %dx%d" % (dst_h, dst_w))
-    dev = src_u8.device
-    if out is None:
-        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
-    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
-        raise _lib.SqdetError("augment_bgr_window: out must be %s [%d,%d,%d,3], got %s %s" % (dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
-    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
-    gd = torch.from_numpy(g).to(dev, non_blocking=True)
-    od = torch.from_numpy(o).to(dev, non_blocking=True)
-    cd = None if c is None else torch.from_numpy(c).to(dev, non_blocking=True)
-    check(lib().sqdet_augment_bgr_window(_dev(src_u8, "src"), src_bytes, _dev(od, "offsets"), _dev(gd, "geom"),
-                                         None if cd is None else _dev(cd, "color"), _dev(out, "out"), n, dst_h, dst_w, m[0], m[1], m[2],
-                                         dtype_code(dtype), stream_ptr()), "sqdet_augment_bgr_window")
-    return out
+    def validate(src_bytes, dst_h, dst_w):
+        g, o, c = check_augment_window_geometry(geom7, offsets, src_bytes, color)
+        return ("offsets", o), ("geom", g), ("color", c)
+    return _augment_launch("sqdet_augment_bgr_window", src_u8, dst_h, dst_w, bgr_means, dtype, out, validate)
 
 
 def check_augment_mosaic_geometry(part_offsets, geom, split, src_bytes, dst_h, dst_w, color=None):
@@ -1074,27 +1065,10 @@ def augment_bgr_mosaic(src_u8, part_offsets, geom, split, color, dst_h, dst_w, b
     four panes, and pane p holds augment_bgr_window's window of the image at byte part_offsets[i][p] under geom[i][p] = (src_h, src_w,
     x0, y0, cw, ch, flip) and color[i][p] (or no matrix: color None), resized to the pane.  A pane without pixels may hold anything.
     Checked on the host before anything is uploaded or launched; a rejected call raises and leaves `out` untouched."""
-    if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
-        raise _lib.SqdetError("augment_bgr_mosaic: src must be a uint8 tensor")
-    src_bytes, dst_h, dst_w = int(src_u8.numel()), int(dst_h), int(dst_w)
-    if dst_h <= 0 or dst_w <= 0:
-        raise _lib.SqdetError("augment_bgr_mosaic: bad output size %dx%d" % (dst_h, dst_w))
-    o, g, s, c = check_augment_mosaic_geometry(part_offsets, geom, split, src_bytes, dst_h, dst_w, color)
-    n = len(s)
-    dev = src_u8.device
-    if out is None:
-        out = torch.empty((n, dst_h, dst_w, 3), dtype=dtype, device=dev)
-    elif tuple(out.shape) != (n, dst_h, dst_w, 3) or out.dtype != dtype:
-        raise _lib.SqdetError("augment_bgr_mosaic: out must be %s [%d,%d,%d,3], got %s %s" % (dtype, n, dst_h, dst_w, out.dtype, tuple(out.shape)))
-    m = [float(v) for v in np.asarray(bgr_means, dtype=np.float64).reshape(-1)[:3]]
-    gd = torch.from_numpy(g).to(dev, non_blocking=True)
-    od = torch.from_numpy(o).to(dev, non_blocking=True)
-    sd = torch.from_numpy(s).to(dev, non_blocking=True)
-    cd = None if c is None else torch.from_numpy(c).to(dev, non_blocking=True)
-    check(lib().sqdet_augment_bgr_mosaic(_dev(src_u8, "src"), src_bytes, _dev(od, "part_offsets"), _dev(gd, "geom"), _dev(sd, "split"),
-                                         None if cd is None else _dev(cd, "color"), _dev(out, "out"), n, dst_h, dst_w, m[0], m[1], m[2],
-                                         dtype_code(dtype), stream_ptr()), "sqdet_augment_bgr_mosaic")
-    return out
+    def validate(src_bytes, dst_h, dst_w):
+        o, g, s, c = check_augment_mosaic_geometry(part_offsets, geom, split, src_bytes, dst_h, dst_w, color)
+        return ("part_offsets", o), ("geom", g), ("split", s), ("color", c)
+    return _augment_launch("sqdet_augment_bgr_mosaic", src_u8, dst_h, dst_w, bgr_means, dtype, out, validate)
 
 
 def box_calibration(device, mfma_iters=8192, copy_mib=1024, reps=3):

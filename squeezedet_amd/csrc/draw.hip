@@ -15,8 +15,7 @@
 // or label meets the band's rows.  A group that straddles two images, or the tail of the batch, goes element by element.
 //
 // -ffp-contract=off (build.py): the restore rule rint(float32(x) + mean) and bbox_transform's cx - w/2 are single roundings.
-#include "common.h"
-#include "round_decimal.h"
+#include "draw_items.h"
 
 namespace sqdet {
 namespace {
@@ -28,23 +27,11 @@ namespace {
 #include "font5x7.h"
 #undef SQDET_FONT5X7_DECL
 
-constexpr int THREADS = 256;
+constexpr int THREADS = ITEM_THREADS;              // one item per thread at staging
 constexpr int PX = 4;                              // pixels per lane and step
 constexpr int STEPS = 4;
 constexpr int CHUNK = THREADS * PX * STEPS;        // 4096 pixels per workgroup
-constexpr int COORD_LIM = 1 << 30;
 constexpr int GLYPHS = 95;
-static_assert(SQDET_DRAW_MAX_ITEMS == THREADS, "one item per thread at staging");
-static_assert(SQDET_DRAW_ITEM_BYTES == 64, "item layout");
-
-struct Item {                 // include/sqdet.h
-  int32_t x0, y0, x1, y1;
-  uint8_t b, g, r, anchor;
-  int32_t label_len;
-  unsigned char label[32];
-  int32_t pad[2];
-};
-static_assert(sizeof(Item) == SQDET_DRAW_ITEM_BYTES, "item layout");
 
 struct Staged {               // an item as the pixels test it
   int xa, ya, xb, yb;         // the rectangle, corners ordered
@@ -158,7 +145,7 @@ __global__ void __launch_bounds__(THREADS) draw_kernel(const DrawArgs a) {
   __shared__ Staged s_item[SQDET_DRAW_MAX_ITEMS];
   __shared__ unsigned char s_font[GLYPHS * 8];
   __shared__ int s_wave[THREADS / 64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
   for (int i = tid; i < GLYPHS * 7; i += THREADS) s_font[(i / 7) * 8 + i % 7] = kFontDev[i / 7][i % 7];
 
   const int64_t hw = (int64_t)a.h * a.w, total = hw * a.n;
@@ -200,16 +187,9 @@ __global__ void __launch_bounds__(THREADS) draw_kernel(const DrawArgs a) {
       const bool text = e.len > 0 && e.ly <= yhi && e.ly + 6 >= ylo && e.lx <= a.w - 1 && e.lx + 6 * e.len - 1 >= 0;
       hit = rect || text;
     }
-    const uint64_t mask = __ballot(hit);
-    if (lane == 0) s_wave[wave] = __popcll(mask);
-    __syncthreads();
-    int base = 0, kept = 0;
-#pragma unroll
-    for (int v = 0; v < THREADS / 64; ++v) {
-      if (v < wave) base += s_wave[v];
-      kept += s_wave[v];
-    }
-    if (hit) s_item[base + __popcll(mask & ((1ull << lane) - 1ull))] = e;
+    int kept;
+    const int pos = block_compact(hit, s_wave, &kept);
+    if (hit) s_item[pos] = e;
     __syncthreads();
     // ---- paint
     for (int step = 0; step < STEPS; ++step) {
@@ -255,122 +235,30 @@ __global__ void __launch_bounds__(THREADS) draw_kernel(const DrawArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ item builder
-struct BuildArgs {
+// build_items_kernel's rule (draw_items.h) for detection or ground-truth rows: float32 or float64 boxes, centre or diagonal,
+// one colour or one per class, "<name>", "<name>: (p)" or "<name> (p)".
+struct DetectionRule {
   const void* boxes;
-  const float* probs;
-  const int32_t* cls;
-  const int32_t* counts;
-  const unsigned char* names;
   const unsigned char* class_bgr;
-  unsigned char* items;
-  int32_t* item_counts;
-  int boxes_f64, rows, diagonal, classes, label_format, anchor, cap;
-  double plot_thresh;
-  uint32_t colour;            // b | g << 8 | r << 16
-};
-
-// int(): truncation toward zero, clamped to the range the rasteriser uses; NaN -> 0
-__device__ __forceinline__ int32_t to_int(double v) {
-  if (v != v) return 0;
-  if (v >= (double)COORD_LIM) return COORD_LIM;
-  if (v <= -(double)COORD_LIM) return -COORD_LIM;
-  return (int32_t)v;
-}
-
-struct LabelWriter {
-  unsigned char* s;
-  int n;
-  __device__ void put(unsigned char c) {
-    if (n < SQDET_DRAW_LABEL_MAX) s[n++] = c;
+  int boxes_f64, diagonal, label_format;
+  uint32_t fixed;             // b | g << 8 | r << 16
+  __device__ bool keep(size_t) const { return true; }
+  __device__ void corners(size_t row, double v[4]) const {
+    if (boxes_f64) corners_of(reinterpret_cast<const double*>(boxes) + row * 4, diagonal, v);
+    else corners_of(reinterpret_cast<const float*>(boxes) + row * 4, diagonal, v);
   }
-  __device__ void puts(const char* t) {
-    for (; *t; ++t) put((unsigned char)*t);
+  __device__ uint32_t colour(size_t, int c, bool known) const {
+    if (!known || class_bgr == nullptr) return fixed;
+    const unsigned char* q = class_bgr + (size_t)c * 3;
+    return pack_bgr(q[0], q[1], q[2]);
   }
-  // '%.2f' % v with Python's digits
-  __device__ void fixed2(double v) {
-    if (v != v) { puts("nan"); return; }
-    if (__builtin_signbit(v)) put('-');
-    const double m = __builtin_fabs(v);
-    if (m == __builtin_inf()) { puts("inf"); return; }
-    if (m >= 1e7) { puts("?.??"); return; }
-    const long long units = (long long)round_decimal_units(m, 100.0);
-    long long ip = units / 100;
-    const int fp = (int)(units % 100);
-    char d[12];
-    int nd = 0;
-    do { d[nd++] = (char)('0' + ip % 10); ip /= 10; } while (ip > 0 && nd < 12);
-    while (nd > 0) put((unsigned char)d[--nd]);
-    put('.');
-    put((unsigned char)('0' + fp / 10));
-    put((unsigned char)('0' + fp % 10));
-  }
-};
-
-// One workgroup per image, one thread per row.
-__global__ void __launch_bounds__(THREADS) build_items_kernel(const BuildArgs a) {
-  __shared__ int s_wave[THREADS / 64];
-  const int img = blockIdx.x, j = threadIdx.x, wave = j >> 6, lane = j & 63;
-  const int cnt = clampi(a.counts[img], 0, a.rows);
-  const size_t row = (size_t)img * a.rows + j;
-  bool keep = j < cnt;
-  float prob = 0.0f;
-  if (keep && a.probs != nullptr) {
-    prob = a.probs[row];
-    keep = (double)prob > a.plot_thresh;      // float32 against a Python float: the reference compares in double
-  }
-  const uint64_t mask = __ballot(keep);
-  if (lane == 0) s_wave[wave] = __popcll(mask);
-  __syncthreads();
-  int base = 0, kept = 0;
-#pragma unroll
-  for (int v = 0; v < THREADS / 64; ++v) {
-    if (v < wave) base += s_wave[v];
-    kept += s_wave[v];
-  }
-  if (j == 0) a.item_counts[img] = kept;
-  if (!keep) return;
-  const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));        // < cnt <= rows <= cap
-  Item it;
-  double v[4];
-  if (a.boxes_f64) {
-    const double* s = reinterpret_cast<const double*>(a.boxes) + row * 4;
-    if (a.diagonal) { v[0] = s[0]; v[1] = s[1]; v[2] = s[2]; v[3] = s[3]; }
-    else { v[0] = s[0] - s[2] / 2; v[1] = s[1] - s[3] / 2; v[2] = s[0] + s[2] / 2; v[3] = s[1] + s[3] / 2; }
-  } else {
-    const float* s = reinterpret_cast<const float*>(a.boxes) + row * 4;
-    if (a.diagonal) { v[0] = s[0]; v[1] = s[1]; v[2] = s[2]; v[3] = s[3]; }
-    else {      // float32 arithmetic, then widened exactly
-      const float xmin = s[0] - s[2] / 2, ymin = s[1] - s[3] / 2, xmax = s[0] + s[2] / 2, ymax = s[1] + s[3] / 2;
-      v[0] = xmin; v[1] = ymin; v[2] = xmax; v[3] = ymax;
-    }
-  }
-  it.x0 = to_int(v[0]); it.y0 = to_int(v[1]); it.x1 = to_int(v[2]); it.y1 = to_int(v[3]);
-  const int c = a.cls[row];
-  const bool known = c >= 0 && c < a.classes;
-  uint32_t colour = a.colour;
-  if (known && a.class_bgr != nullptr) {
-    const unsigned char* q = a.class_bgr + (size_t)c * 3;
-    colour = pack_bgr(q[0], q[1], q[2]);
-  }
-  it.b = (uint8_t)(colour & 0xffu); it.g = (uint8_t)((colour >> 8) & 0xffu); it.r = (uint8_t)((colour >> 16) & 0xffu);
-  it.anchor = (uint8_t)a.anchor;
-  for (int i = 0; i < 32; ++i) it.label[i] = 0;
-  it.pad[0] = it.pad[1] = 0;
-  LabelWriter w{it.label, 0};
-  if (known) {
-    const unsigned char* nm = a.names + (size_t)c * SQDET_DRAW_NAME_BYTES;
-    for (int i = 0; i < SQDET_DRAW_NAME_BYTES && nm[i]; ++i) w.put(nm[i]);
-  } else {
-    w.put('?');
-  }
-  if (a.label_format != SQDET_DRAW_LABEL_NAME) {
-    w.puts(a.label_format == SQDET_DRAW_LABEL_NAME_COLON_PROB ? ": (" : " (");
-    w.fixed2((double)prob);
+  __device__ void label(LabelWriter& w, const ItemArgs& a, size_t row) const {
+    if (label_format == SQDET_DRAW_LABEL_NAME) return;
+    w.puts(label_format == SQDET_DRAW_LABEL_NAME_COLON_PROB ? ": (" : " (");
+    w.fixed2((double)a.probs[row]);       // (the entry point requires probs for these formats)
     w.put(')');
   }
-  it.label_len = w.n;
-  *reinterpret_cast<Item*>(a.items + ((size_t)img * a.cap + pos) * SQDET_DRAW_ITEM_BYTES) = it;
-}
+};
 
 }  // namespace
 }  // namespace sqdet
@@ -430,17 +318,11 @@ extern "C" int sqdet_draw_build_items(const void* boxes, int boxes_f64, const fl
   SQDET_REQUIRE(n > 0 && rows > 0 && classes > 0 && cap > 0, "sqdet_draw_build_items: bad sizes n %d rows %d classes %d cap %d", n, rows, classes, cap);
   SQDET_REQUIRE(label_format >= SQDET_DRAW_LABEL_NAME && label_format <= SQDET_DRAW_LABEL_NAME_PROB, "sqdet_draw_build_items: bad label_format %d", label_format);
   SQDET_REQUIRE(label_format == SQDET_DRAW_LABEL_NAME || probs != nullptr, "sqdet_draw_build_items: a label with a probability needs probs");
-  SQDET_REQUIRE(anchor == SQDET_DRAW_BOTTOM_LEFT || anchor == SQDET_DRAW_TOP_LEFT, "sqdet_draw_build_items: bad anchor %d", anchor);
   SQDET_REQUIRE(((b | g | r) & ~0xff) == 0, "sqdet_draw_build_items: colour (%d, %d, %d)", b, g, r);
-  SQDET_UNSUPPORTED(cap > SQDET_DRAW_MAX_ITEMS || rows > cap, "sqdet_draw_build_items: %d rows into %d items per image (at most %d)", rows, cap, SQDET_DRAW_MAX_ITEMS);
-  SQDET_REQUIRE((reinterpret_cast<uintptr_t>(items) & 15) == 0, "sqdet_draw_build_items: items must be 16-byte aligned");
-  BuildArgs a{};
-  a.boxes = boxes; a.probs = probs; a.cls = cls; a.counts = counts; a.names = names; a.class_bgr = class_bgr;
-  a.items = reinterpret_cast<unsigned char*>(items); a.item_counts = item_counts;
-  a.boxes_f64 = boxes_f64 ? 1 : 0; a.rows = rows; a.diagonal = diagonal ? 1 : 0; a.classes = classes; a.label_format = label_format;
-  a.anchor = anchor; a.cap = cap; a.plot_thresh = plot_thresh;
-  a.colour = (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
-  hipLaunchKernelGGL(build_items_kernel, dim3((unsigned)n), dim3(THREADS), 0, as_stream(stream), a);
-  SQDET_CHECK_HIP(hipGetLastError());
-  return SQDET_OK;
+  ItemArgs a{};
+  a.probs = probs; a.cls = cls; a.counts = counts; a.names = names; a.items = reinterpret_cast<unsigned char*>(items);
+  a.item_counts = item_counts; a.rows = rows; a.classes = classes; a.anchor = anchor; a.cap = cap; a.plot_thresh = plot_thresh;
+  const DetectionRule rule{boxes, class_bgr, boxes_f64 ? 1 : 0, diagonal ? 1 : 0, label_format,
+                           (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16)};
+  return build_items("sqdet_draw_build_items", a, rule, n, stream);
 }

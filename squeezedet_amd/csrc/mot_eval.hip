@@ -18,7 +18,7 @@
 // floor((1 - IoU) * 2^20) are one IEEE operation per operator, compared bit for bit.
 #include <vector>
 #include <string.h>
-#include "common.h"
+#include "stream_wave.h"
 
 namespace sqdet {
 namespace {
@@ -49,24 +49,9 @@ struct MotArgs {
   double iou_thresh;
 };
 
-__device__ __forceinline__ double dmin(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double dmax(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for NaN
-__device__ __forceinline__ bool finite_d(double v) { return __builtin_fabs(v) < __builtin_inf(); }
-__device__ __forceinline__ uint64_t below(int lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ long long shfl_xor64(long long v, int m) {
   const int lo = __shfl_xor((int)(unsigned long long)v, m), hi = __shfl_xor((int)((unsigned long long)v >> 32), m);
   return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// util.iou (utils/util.py:9-30), the expression of track.hip; box 1 the object, box 2 the hypothesis
-__device__ __forceinline__ double iou(const double a[4], const double b[4]) {
-  const double lr = dmin(a[0] + 0.5 * a[2], b[0] + 0.5 * b[2]) - dmax(a[0] - 0.5 * a[2], b[0] - 0.5 * b[2]);
-  if (!(lr > 0.0)) return 0.0;
-  const double tb = dmin(a[1] + 0.5 * a[3], b[1] + 0.5 * b[3]) - dmax(a[1] - 0.5 * a[3], b[1] - 0.5 * b[3]);
-  if (!(tb > 0.0)) return 0.0;
-  const double inter = lr * tb;
-  return inter / (a[2] * a[3] + b[2] * b[3] - inter);
 }
 
 // assign() of the header on an R x C matrix, R <= C <= THREADS * COLS: column j belongs to thread j % THREADS.  On return
@@ -194,8 +179,8 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
 
   for (int s = blockIdx.x; s < a.S; s += gridDim.x) {
     int n_obj = a.t.n_obj[s], n_hyp = a.t.n_hyp[s], status = a.t.status[s];
-    n_obj = n_obj < 0 ? 0 : (n_obj > MAXO ? MAXO : n_obj);            // (a loaded table is the caller's: stay inside it)
-    n_hyp = n_hyp < 0 ? 0 : (n_hyp > MAXH ? MAXH : n_hyp);
+    n_obj = clamp_count(n_obj, MAXO);                                 // (a loaded table is the caller's: stay inside it)
+    n_hyp = clamp_count(n_hyp, MAXH);
     __syncthreads();                    // the previous stream's tables are no longer read
     for (int e = lane; e < n_obj; e += CAP) s_objid[e] = a.t.obj_id[(size_t)s * MAXO + e];
     for (int e = lane; e < n_hyp; e += CAP) s_hypid[e] = a.t.hyp_id[(size_t)s * MAXH + e];
@@ -212,9 +197,9 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
 
     for (int f = 0; f < a.F && status == 0; ++f) {
       const size_t img = (size_t)s * a.F + f;
-      int hc = a.counts[img], gc = a.gt_count[img];
-      hc = hc < 0 ? 0 : (hc > rows ? rows : hc);
-      gc = gc < 0 ? 0 : (gc > G ? G : gc);
+      int hc = a.counts[img], gc = a.gt_count[img];               // (both loads issued before either is waited for)
+      hc = clamp_count(hc, rows);
+      gc = clamp_count(gc, G);
       __syncthreads();                  // the previous frame's LDS is no longer read
       // ---- validity: lane = hypothesis row, lane = object row
       bool hv = false, ov = false, ign = false;
@@ -224,8 +209,8 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
         const f32x4 b = {a.boxes[r * 4], a.boxes[r * 4 + 1], a.boxes[r * 4 + 2], a.boxes[r * 4 + 3]};
         hid = a.ids[r];
         hcl = a.cls[r];
-        hv = a.states[r] == 2 && hid > 0 && finite_f(b[0]) && finite_f(b[1]) && finite_f(b[2]) && finite_f(b[3]) && b[2] > 0.0f && b[3] > 0.0f &&
-             hcl >= 0 && hcl < classes;
+        const bool box = valid_box(b);  // (ahead of the chain below: inside it the kernel measured 2 % slower, profiles/tracking_refactor_bench.txt)
+        hv = a.states[r] == 2 && hid > 0 && box && hcl >= 0 && hcl < classes;
         if (hv) { s_hbox[lane][0] = (double)b[0]; s_hbox[lane][1] = (double)b[1]; s_hbox[lane][2] = (double)b[2]; s_hbox[lane][3] = (double)b[3]; }
       }
       if (lane < gc) {
@@ -233,7 +218,8 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
         const double b[4] = {a.gt_box[r * 4], a.gt_box[r * 4 + 1], a.gt_box[r * 4 + 2], a.gt_box[r * 4 + 3]};
         oid = a.gt_id[r];
         ocl = a.gt_cls[r];
-        ov = oid > 0 && finite_d(b[0]) && finite_d(b[1]) && finite_d(b[2]) && finite_d(b[3]) && b[2] > 0.0 && b[3] > 0.0 && ocl >= 0 && ocl < classes;
+        const bool box = valid_box(b);
+        ov = oid > 0 && box && ocl >= 0 && ocl < classes;
         ign = (a.gt_flags[r] & 1) != 0;
         if (ov) { s_obox[lane][0] = b[0]; s_obox[lane][1] = b[1]; s_obox[lane][2] = b[2]; s_obox[lane][3] = b[3]; }
       }
@@ -264,13 +250,13 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
       if (n_hyp + __popcll(newh) > MAXH) status |= SQDET_MOT_STATUS_HYPOTHESES;
       if (status != 0) break;           // (uniform) the stream stops here: this frame and every later one changes nothing
       if ((newo >> lane) & 1ull) {
-        gi = n_obj + __popcll(newo & below(lane));
+        gi = n_obj + rank_in(newo, lane);
         s_objid[gi] = oid;
         a.t.obj_id[(size_t)s * MAXO + gi] = oid;
         a.t.obj_cls[(size_t)s * MAXO + gi] = ocl;
       }
       if ((newh >> lane) & 1ull) {
-        ti = n_hyp + __popcll(newh & below(lane));
+        ti = n_hyp + rank_in(newh, lane);
         s_hypid[ti] = hid;
         a.t.hyp_id[(size_t)s * MAXH + ti] = hid;
         a.t.hyp_cls[(size_t)s * MAXH + ti] = hcl;
@@ -286,17 +272,17 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
       }
       // ---- 1: IoU and cost of every (valid object, valid hypothesis) pair, dealt to the lanes
       const int n_o = __popcll(om), n_h = __popcll(hm);
-      if (ov) s_olist[__popcll(om & below(lane))] = lane;
-      if (hv) { s_hlist[__popcll(hm & below(lane))] = lane; s_hti[lane] = ti; }
+      list_lane(ov, om, s_olist, lane);
+      list_lane(hv, hm, s_hlist, lane);
+      if (hv) s_hti[lane] = ti;
       __syncthreads();
-      for (int q = lane; q < n_o * n_h; q += CAP) {
-        const int oi = q / n_h, o = s_olist[oi], h = s_hlist[q - oi * n_h];
+      deal_pairs(n_o, n_h, s_olist, s_hlist, lane, [&](int o, int h) {                  // box 1 the object, box 2 the hypothesis
         const double ob[4] = {s_obox[o][0], s_obox[o][1], s_obox[o][2], s_obox[o][3]};
         const double hb[4] = {s_hbox[h][0], s_hbox[h][1], s_hbox[h][2], s_hbox[h][3]};
         const double v = s_ocls[o] == s_hcls[h] ? iou(ob, hb) : 0.0;
         s_iou[o * MSTRIDE + h] = v;
         s_q[o * MSTRIDE + h] = v >= a.iou_thresh ? (int)(long long)__builtin_floor((1.0 - v) * 1048576.0) : -1;
-      }
+      });
       __syncthreads();
       // ---- 2: continuity (lane = object): the hypothesis that carries the object's last id, if the pair is allowed; of several
       // objects after one hypothesis the lowest row has it
@@ -328,8 +314,8 @@ __global__ void __launch_bounds__(CAP) mot_update_kernel(const MotArgs a) {
         const uint64_t ro = om & ~__ballot(match >= 0), rh = hm & ~__ballot(hv && s_taken[lane] >= 0);
         const int R = __popcll(ro), C = __popcll(rh), N = R > C ? R : C;
         if (R > 0 && C > 0) {
-          if ((ro >> lane) & 1ull) s_rowobj[__popcll(ro & below(lane))] = lane;
-          if ((rh >> lane) & 1ull) s_colhyp[__popcll(rh & below(lane))] = lane;
+          list_lane((ro >> lane) & 1ull, ro, s_rowobj, lane);
+          list_lane((rh >> lane) & 1ull, rh, s_colhyp, lane);
           __syncthreads();
           const int mycol = lane < C ? s_colhyp[lane] : -1;            // (column j is lane j)
           const int* rowobj = s_rowobj;
@@ -424,9 +410,7 @@ __global__ void __launch_bounds__(EV_THREADS) mot_evaluate_kernel(const sqdet_mo
   __shared__ int s_p[MAXH], s_way[MAXH], s_hcls[MAXH], s_hfr[MAXH];
   __shared__ int s_ocls[MAXO], s_opres[MAXO], s_otrk[MAXO], s_ofrag[MAXO], s_oidtp[MAXO];
   const int s = blockIdx.x, tid = threadIdx.x;
-  int R = t.n_obj[s], T = t.n_hyp[s];
-  R = R < 0 ? 0 : (R > MAXO ? MAXO : R);                                // (a loaded table is the caller's: stay inside it)
-  T = T < 0 ? 0 : (T > MAXH ? MAXH : T);
+  const int R = clamp_count(t.n_obj[s], MAXO), T = clamp_count(t.n_hyp[s], MAXH);      // (a loaded table is the caller's: stay inside it)
   const int C = T > R ? T : R;
   const int32_t* overlap = t.overlap + (size_t)s * MAXO * MAXH;
   for (int i = tid; i < R; i += EV_THREADS) {
@@ -507,8 +491,7 @@ extern "C" int sqdet_mot_update(const sqdet_mot_tables_t* tables, const float* b
   a.t = *tables; a.boxes = boxes; a.cls = cls; a.counts = counts; a.ids = det_track_id; a.states = det_track_state;
   a.gt_box = gt_box; a.gt_id = gt_id; a.gt_cls = gt_cls; a.gt_flags = gt_flags; a.gt_count = gt_count;
   a.S = streams; a.F = frames; a.rows = rows; a.G = gt_rows; a.classes = classes; a.iou_thresh = iou_thresh;
-  const int grid = max_workgroups > 0 && max_workgroups < streams ? max_workgroups : streams;
-  hipLaunchKernelGGL(mot_update_kernel, dim3((unsigned)grid), dim3(CAP), 0, as_stream(stream), a);
+  hipLaunchKernelGGL(mot_update_kernel, dim3((unsigned)stream_grid(max_workgroups, streams)), dim3(CAP), 0, as_stream(stream), a);
   SQDET_CHECK_HIP(hipGetLastError());
   return SQDET_OK;
 }

@@ -16,8 +16,8 @@
 // the lanes whose cached best was just taken rescan.  Sets of rows and slots are 64-bit ballot masks, uniform over the wave.
 //
 // -ffp-contract=off (build.py): every operator of the header's definition is one IEEE operation, compared bit for bit.
-#include <stddef.h>
-#include "common.h"
+#include "draw_items.h"
+#include "stream_wave.h"
 
 namespace sqdet {
 namespace {
@@ -37,21 +37,6 @@ struct TrackArgs {
   int S, F, rows;
   sqdet_track_params_t p;
 };
-
-__device__ __forceinline__ double dmin(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double dmax(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) < __builtin_inff(); }      // false for NaN
-__device__ __forceinline__ uint64_t below(int lane) { return (1ull << lane) - 1ull; }
-
-// util.iou (utils/util.py:9-30); box 1 the prediction, box 2 the row
-__device__ __forceinline__ double iou(const double a[4], const double b[4]) {
-  const double lr = dmin(a[0] + 0.5 * a[2], b[0] + 0.5 * b[2]) - dmax(a[0] - 0.5 * a[2], b[0] - 0.5 * b[2]);
-  if (!(lr > 0.0)) return 0.0;
-  const double tb = dmin(a[1] + 0.5 * a[3], b[1] + 0.5 * b[3]) - dmax(a[1] - 0.5 * a[3], b[1] - 0.5 * b[3]);
-  if (!(tb > 0.0)) return 0.0;
-  const double inter = lr * tb;
-  return inter / (a[2] * a[3] + b[2] * b[3] - inter);
-}
 
 // The best candidate of `mask` (uniform) among base[i * STRIDE]: the largest value >= thresh, the lowest index among equals; -1 / -1 if
 // none.  Four set bits at a time, so that four LDS reads are in flight (a short tail repeats its last index: harmless under the
@@ -137,8 +122,7 @@ __global__ void __launch_bounds__(CAP) track_kernel(const TrackArgs a) {
 
     for (int f = 0; f < a.F; ++f) {
       const size_t img = (size_t)s * a.F + f;
-      int count = a.counts[img];
-      count = count < 0 ? 0 : (count > rows ? rows : count);                                       // 1
+      const int count = clamp_count(a.counts[img], rows);                                          // 1
       __syncthreads();                  // the previous frame's LDS is no longer read
       // ---- 3: rows (lane = row)
       bool high = false, low = false;
@@ -146,7 +130,7 @@ __global__ void __launch_bounds__(CAP) track_kernel(const TrackArgs a) {
         const size_t r = img * rows + lane;
         const f32x4 b = {a.boxes[r * 4], a.boxes[r * 4 + 1], a.boxes[r * 4 + 2], a.boxes[r * 4 + 3]};
         const float pr = a.probs[r];
-        if (finite_f(b[0]) && finite_f(b[1]) && finite_f(b[2]) && finite_f(b[3]) && finite_f(pr) && b[2] > 0.0f && b[3] > 0.0f) {
+        if (valid_box(b) && finite_f(pr)) {
           high = (double)pr > p.high_thresh;
           low = !high && (double)pr > p.low_thresh;
           s_box[lane][0] = (double)b[0]; s_box[lane][1] = (double)b[1]; s_box[lane][2] = (double)b[2]; s_box[lane][3] = (double)b[3];
@@ -180,16 +164,15 @@ __global__ void __launch_bounds__(CAP) track_kernel(const TrackArgs a) {
       if (live) {
         s_pbox[lane][0] = box[0]; s_pbox[lane][1] = box[1]; s_pbox[lane][2] = box[2]; s_pbox[lane][3] = box[3];
         s_pcls[lane] = cls;
-        s_live[__popcll(livem & below(lane))] = lane;
       }
-      if ((validm >> lane) & 1ull) s_valid[__popcll(validm & below(lane))] = lane;
+      list_lane(live, livem, s_live, lane);
+      list_lane((validm >> lane) & 1ull, validm, s_valid, lane);
       __syncthreads();                  // the rows, the predictions and the two lists are staged
-      for (int q = lane; q < n_live * n_valid; q += CAP) {
-        const int ti = q / n_valid, t = s_live[ti], d = s_valid[q - ti * n_valid];
+      deal_pairs(n_live, n_valid, s_live, s_valid, lane, [&](int t, int d) {           // box 1 the prediction, box 2 the row
         const double pb[4] = {s_pbox[t][0], s_pbox[t][1], s_pbox[t][2], s_pbox[t][3]};
         const double z[4] = {s_box[d][0], s_box[d][1], s_box[d][2], s_box[d][3]};
         s_M[t * MSTRIDE + d] = s_cls[d] == s_pcls[t] ? iou(pb, z) : 0.0;
-      }
+      });
       __syncthreads();                  // M is read across lanes: a row lane scans its column
       uint64_t free_high = highm, free_low = lowm;
       int match = greedy(s_M, s_bestrow, s_bestslot, live, free_high, p.iou_thresh, lane);
@@ -224,9 +207,9 @@ __global__ void __launch_bounds__(CAP) track_kernel(const TrackArgs a) {
       // ---- 8: the k-th unmatched high row takes the k-th free slot
       const uint64_t freem = __ballot(state == 0);
       const int n_free = __popcll(freem), n_new = __popcll(free_high);
-      if ((free_high >> lane) & 1ull) s_birth[__popcll(free_high & below(lane))] = lane;
+      list_lane((free_high >> lane) & 1ull, free_high, s_birth, lane);
       __syncthreads();
-      const int rank = __popcll(freem & below(lane));
+      const int rank = rank_in(freem, lane);
       if (state == 0 && rank < n_new) {
         const int d = s_birth[rank];
         const double h = dmax(s_box[d][3], 1.0);
@@ -267,97 +250,24 @@ __global__ void __launch_bounds__(CAP) track_kernel(const TrackArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ item builder
-constexpr int THREADS = 256;
-constexpr int COORD_LIM = 1 << 30;
-static_assert(SQDET_DRAW_MAX_ITEMS == THREADS, "one row per thread");
-
-struct Item {                 // include/sqdet.h, "drawing"
-  int32_t x0, y0, x1, y1;
-  uint8_t b, g, r, anchor;
-  int32_t label_len;
-  unsigned char label[32];
-  int32_t pad[2];
-};
-static_assert(sizeof(Item) == SQDET_DRAW_ITEM_BYTES, "item layout");
-// (the layout include/sqdet.h documents, field by field: draw.hip reads the items this file writes, and is not to change)
-static_assert(offsetof(Item, x0) == 0 && offsetof(Item, y1) == 12 && offsetof(Item, b) == 16 && offsetof(Item, anchor) == 19 &&
-                  offsetof(Item, label_len) == 20 && offsetof(Item, label) == 24 && offsetof(Item, pad) == 56,
-              "item layout");
-
-struct ItemArgs {
+// build_items_kernel's rule (draw_items.h) for the rows of confirmed tracks: "<name> #<id>", one colour per id.
+struct TrackRule {
   const float* boxes;
-  const float* probs;
-  const int32_t* cls;
-  const int32_t* counts;
   const int32_t* ids;
   const int32_t* states;
-  const unsigned char* names;
   const unsigned char* palette;
-  unsigned char* items;
-  int32_t* item_counts;
-  int rows, classes, palette_len, anchor, cap;
-  double plot_thresh;
+  int palette_len;
+  __device__ bool keep(size_t row) const { return states[row] == 2 && ids[row] > 0; }
+  __device__ void corners(size_t row, double v[4]) const { corners_of(boxes + row * 4, false, v); }
+  __device__ uint32_t colour(size_t row, int, bool) const {
+    const unsigned char* q = palette + (size_t)(ids[row] % palette_len) * 3;
+    return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+  }
+  __device__ void label(LabelWriter& w, const ItemArgs&, size_t row) const {
+    w.puts(" #");
+    w.decimal(ids[row]);
+  }
 };
-
-// int(): truncation toward zero, clamped to the range the rasteriser uses; NaN -> 0 (draw.hip's rule)
-__device__ __forceinline__ int32_t to_int(double v) {
-  if (v != v) return 0;
-  if (v >= (double)COORD_LIM) return COORD_LIM;
-  if (v <= -(double)COORD_LIM) return -COORD_LIM;
-  return (int32_t)v;
-}
-
-// One workgroup per image, one thread per row.
-__global__ void __launch_bounds__(THREADS) track_items_kernel(const ItemArgs a) {
-  __shared__ int s_wave[THREADS / 64];
-  const int img = blockIdx.x, j = threadIdx.x, wave = j >> 6, lane = j & 63;
-  int cnt = a.counts[img];
-  cnt = cnt < 0 ? 0 : (cnt > a.rows ? a.rows : cnt);
-  const size_t row = (size_t)img * a.rows + j;
-  bool keep = j < cnt;
-  int id = 0;
-  if (keep) {
-    id = a.ids[row];
-    keep = a.states[row] == 2 && id > 0 && (double)a.probs[row] > a.plot_thresh;
-  }
-  const uint64_t mask = __ballot(keep);
-  if (lane == 0) s_wave[wave] = __popcll(mask);
-  __syncthreads();
-  int base = 0, kept = 0;
-#pragma unroll
-  for (int v = 0; v < THREADS / 64; ++v) {
-    if (v < wave) base += s_wave[v];
-    kept += s_wave[v];
-  }
-  if (j == 0) a.item_counts[img] = kept;
-  if (!keep) return;
-  const int pos = base + __popcll(mask & below(lane));        // < cnt <= rows <= cap
-  Item it;
-  const float* s = a.boxes + row * 4;
-  const float xmin = s[0] - s[2] / 2, ymin = s[1] - s[3] / 2, xmax = s[0] + s[2] / 2, ymax = s[1] + s[3] / 2;      // float32, then widened
-  it.x0 = to_int((double)xmin); it.y0 = to_int((double)ymin); it.x1 = to_int((double)xmax); it.y1 = to_int((double)ymax);
-  const unsigned char* q = a.palette + (size_t)(id % a.palette_len) * 3;
-  it.b = q[0]; it.g = q[1]; it.r = q[2];
-  it.anchor = (uint8_t)a.anchor;
-  for (int i = 0; i < 32; ++i) it.label[i] = 0;
-  it.pad[0] = it.pad[1] = 0;
-  int n = 0;
-  const int c = a.cls[row];
-  if (c >= 0 && c < a.classes) {
-    const unsigned char* nm = a.names + (size_t)c * SQDET_DRAW_NAME_BYTES;
-    for (int i = 0; i < SQDET_DRAW_NAME_BYTES && nm[i] && n < SQDET_DRAW_LABEL_MAX; ++i) it.label[n++] = nm[i];
-  } else {
-    it.label[n++] = '?';
-  }
-  char digits[12];
-  int nd = 0;
-  for (int v = id; v > 0 && nd < 12; v /= 10) digits[nd++] = (char)('0' + v % 10);
-  if (n < SQDET_DRAW_LABEL_MAX) it.label[n++] = ' ';
-  if (n < SQDET_DRAW_LABEL_MAX) it.label[n++] = '#';
-  while (nd > 0 && n < SQDET_DRAW_LABEL_MAX) it.label[n++] = (unsigned char)digits[--nd];
-  it.label_len = n;
-  *reinterpret_cast<Item*>(a.items + ((size_t)img * a.cap + pos) * SQDET_DRAW_ITEM_BYTES) = it;
-}
 
 }  // namespace
 }  // namespace sqdet
@@ -386,8 +296,7 @@ extern "C" int sqdet_track_update(const sqdet_track_tables_t* tables, const floa
   TrackArgs a{};
   a.t = t; a.boxes = boxes; a.probs = probs; a.cls = cls; a.counts = counts; a.out_id = det_track_id; a.out_state = det_track_state;
   a.S = streams; a.F = frames; a.rows = rows; a.p = p;
-  const int grid = max_workgroups > 0 && max_workgroups < streams ? max_workgroups : streams;
-  hipLaunchKernelGGL(track_kernel, dim3((unsigned)grid), dim3(CAP), 0, as_stream(stream), a);
+  hipLaunchKernelGGL(track_kernel, dim3((unsigned)stream_grid(max_workgroups, streams)), dim3(CAP), 0, as_stream(stream), a);
   SQDET_CHECK_HIP(hipGetLastError());
   return SQDET_OK;
 }
@@ -401,15 +310,8 @@ extern "C" int sqdet_track_build_items(const float* boxes, const float* probs, c
                 "sqdet_track_build_items: null pointer");
   SQDET_REQUIRE(n > 0 && rows > 0 && classes > 0 && palette_len > 0 && cap > 0,
                 "sqdet_track_build_items: bad sizes n %d rows %d classes %d palette %d cap %d", n, rows, classes, palette_len, cap);
-  SQDET_REQUIRE(anchor == SQDET_DRAW_BOTTOM_LEFT || anchor == SQDET_DRAW_TOP_LEFT, "sqdet_track_build_items: bad anchor %d", anchor);
-  SQDET_UNSUPPORTED(cap > SQDET_DRAW_MAX_ITEMS || rows > cap, "sqdet_track_build_items: %d rows into %d items per image (at most %d)", rows, cap,
-                    SQDET_DRAW_MAX_ITEMS);
-  SQDET_REQUIRE((reinterpret_cast<uintptr_t>(items) & 15) == 0, "sqdet_track_build_items: items must be 16-byte aligned");
   ItemArgs a{};
-  a.boxes = boxes; a.probs = probs; a.cls = cls; a.counts = counts; a.ids = det_track_id; a.states = det_track_state; a.names = names;
-  a.palette = palette; a.items = reinterpret_cast<unsigned char*>(items); a.item_counts = item_counts;
-  a.rows = rows; a.classes = classes; a.palette_len = palette_len; a.anchor = anchor; a.cap = cap; a.plot_thresh = plot_thresh;
-  hipLaunchKernelGGL(track_items_kernel, dim3((unsigned)n), dim3(THREADS), 0, as_stream(stream), a);
-  SQDET_CHECK_HIP(hipGetLastError());
-  return SQDET_OK;
+  a.probs = probs; a.cls = cls; a.counts = counts; a.names = names; a.items = reinterpret_cast<unsigned char*>(items);
+  a.item_counts = item_counts; a.rows = rows; a.classes = classes; a.anchor = anchor; a.cap = cap; a.plot_thresh = plot_thresh;
+  return build_items("sqdet_track_build_items", a, TrackRule{boxes, det_track_id, det_track_state, palette, palette_len}, n, stream);
 }

@@ -13,6 +13,8 @@ import ctypes as C
 
 import numpy as np
 
+from .stream_tables import StreamTables, tables_struct
+
 CAP, MAX_OBJECTS, MAX_HYPOTHESES, MAX_CLASSES = 64, 256, 1024, 128
 COUNTERS = ("tp", "fn", "fp", "idsw", "ignored_hyp", "frag", "mt", "pt", "ml", "idtp", "idfn", "idfp", "gt_ids", "hyp_ids")
 K = len(COUNTERS)
@@ -24,8 +26,7 @@ FIELDS = OBJ_FIELDS + HYP_FIELDS + ("n_obj", "n_hyp", "status", "counts", "iou_s
 MOT_DISTRACTORS = (2, 7, 8, 12)
 
 
-class _Tables(C.Structure):                      # sqdet_mot_tables_t
-    _fields_ = [(f, C.c_void_p) for f in FIELDS]
+_Tables = tables_struct(FIELDS)                  # sqdet_mot_tables_t
 
 
 def table_shapes(streams, classes):
@@ -53,7 +54,9 @@ def metrics(counters, iou_sum):
     return c
 
 
-class MotAccumulator:
+class MotAccumulator(StreamTables):
+    FIELDS, STRUCT = FIELDS, _Tables
+
     def __init__(self, streams, device, classes, iou_thresh=0.5, tables=None):
         """tables: {name: device tensor} of the caller's own in the shapes and dtypes of ``table_shapes(streams, classes)``,
         already reset (zero); None: the accumulator allocates them (1 MiB of `overlap` per stream)."""
@@ -65,27 +68,9 @@ class MotAccumulator:
             raise SqdetUnsupported("MotAccumulator: %d classes (at most %d)" % (classes, MAX_CLASSES))
         if not 0.0 < float(iou_thresh) <= 1.0:
             raise SqdetError("MotAccumulator: iou_thresh %r must be in (0, 1]" % (iou_thresh,))
-        self.streams, self.classes, self.device, self.iou_thresh = int(streams), int(classes), torch.device(device), float(iou_thresh)
-        for f, (shape, dtype) in table_shapes(self.streams, self.classes).items():
-            if tables is None:
-                t = torch.zeros(shape, dtype=getattr(torch, dtype), device=self.device)
-            else:
-                t = tables[f]
-                if tuple(t.shape) != shape or t.dtype != getattr(torch, dtype) or not t.is_cuda or not t.is_contiguous():
-                    raise SqdetError("MotAccumulator: table %s must be a contiguous device %s %s" % (f, dtype, shape))
-            setattr(self, f, t)
-        self._tables = _Tables(*[getattr(self, f).data_ptr() for f in FIELDS])
+        self.classes, self.iou_thresh = int(classes), float(iou_thresh)
+        super().__init__(streams, device, table_shapes(streams, classes), tables)
         self._result = torch.zeros((self.streams, self.classes, K), dtype=torch.int64, device=self.device)
-
-    def tables(self):
-        return {f: getattr(self, f) for f in FIELDS}
-
-    def reset(self, streams=None):
-        """Forgets everything of `streams` (a list of stream indices; None: all): every table zero."""
-        import torch
-        idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.device)
-        for f in FIELDS:
-            getattr(self, f)[idx] = 0
 
     def update(self, boxes, cls, counts, ids, states, gt, frames_per_stream=1, stream=None, max_workgroups=0):
         """boxes float32 [n, rows, 4], cls int32 [n, rows], counts int32 [n] -- the filter's outputs -- and ids, states int32
@@ -94,13 +79,8 @@ class MotAccumulator:
         (None: the current one)."""
         import torch
         from . import ops
-        from ._lib import SqdetError, check, lib, stream_ptr
-        F = int(frames_per_stream)
-        if boxes.dim() != 3 or int(boxes.shape[2]) != 4:
-            raise SqdetError("MotAccumulator.update: boxes must be [n, rows, 4]")
-        n, rows = int(boxes.shape[0]), int(boxes.shape[1])
-        if F < 1 or n != self.streams * F:
-            raise SqdetError("MotAccumulator.update: %d images are not %d streams x %d frames" % (n, self.streams, F))
+        from ._lib import SqdetError, check, lib
+        F, n, rows = self._frames(boxes, frames_per_stream)
         for t, what in ((cls, "cls"), (ids, "ids"), (states, "states")):
             if tuple(t.shape) != (n, rows):
                 raise SqdetError("MotAccumulator.update: %s must be [%d, %d]" % (what, n, rows))
@@ -119,22 +99,21 @@ class MotAccumulator:
             raise SqdetError("MotAccumulator.update: gt_count must be [%d]" % n)
         if boxes.device != self.device or gt_box.device != self.device:
             raise SqdetError("MotAccumulator.update: rows on %s, ground truth on %s, tables on %s" % (boxes.device, gt_box.device, self.device))
-        sp = stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
         check(lib().sqdet_mot_update(
             C.byref(self._tables), ops._dev(boxes, "boxes", torch.float32), ops._dev(cls, "cls", torch.int32),
             ops._dev(counts, "counts", torch.int32), ops._dev(ids, "ids", torch.int32), ops._dev(states, "states", torch.int32),
             ops._dev(gt_box, "gt_box", torch.float64), ops._dev(gt_id, "gt_id", torch.int32), ops._dev(gt_cls, "gt_cls", torch.int32),
             ops._dev(gt_flags, "gt_flags", torch.int32), ops._dev(gt_count, "gt_count", torch.int32), self.streams, F, rows, G,
-            self.classes, self.iou_thresh, int(max_workgroups), sp), "sqdet_mot_update")
+            self.classes, self.iou_thresh, int(max_workgroups), self._stream(stream)), "sqdet_mot_update")
 
     def evaluate_raw(self, stream=None):
         """-> (counters int64 [S, classes, K], iou_sum float64 [S, classes]) on the host (synchronises once)."""
-        from ._lib import check, lib, stream_ptr
+        from ._lib import check, lib
         counters = np.zeros((self.streams, self.classes, K), np.int64)
         iou_sum = np.zeros((self.streams, self.classes), np.float64)
-        sp = stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
         check(lib().sqdet_mot_evaluate(C.byref(self._tables), self.streams, self.classes, C.c_void_p(self._result.data_ptr()),
-                                       counters.ctypes.data_as(C.c_void_p), iou_sum.ctypes.data_as(C.c_void_p), sp), "sqdet_mot_evaluate")
+                                       counters.ctypes.data_as(C.c_void_p), iou_sum.ctypes.data_as(C.c_void_p), self._stream(stream)),
+              "sqdet_mot_evaluate")
         return counters, iou_sum
 
     def evaluate(self, stream=None):
@@ -142,21 +121,11 @@ class MotAccumulator:
         (summed over classes) and overall -- each a dict of the counters and mota, motp, idf1, precision, recall."""
         return summarize(*self.evaluate_raw(stream))
 
-    def state_dict(self):
-        """Host copies of every table; continuing after load_state_dict is bitwise the uninterrupted run."""
-        d = {f: getattr(self, f).cpu().clone() for f in FIELDS}
-        d["iou_thresh"], d["classes"] = self.iou_thresh, self.classes
-        return d
+    def _settings(self):
+        return {"iou_thresh": self.iou_thresh, "classes": self.classes}
 
-    def load_state_dict(self, d):
-        from ._lib import SqdetError
-        if d.get("iou_thresh", self.iou_thresh) != self.iou_thresh or d.get("classes", self.classes) != self.classes:
-            raise SqdetError("MotAccumulator.load_state_dict: saved with iou_thresh %s and %s classes" % (d.get("iou_thresh"), d.get("classes")))
-        for f in FIELDS:
-            if tuple(d[f].shape) != tuple(getattr(self, f).shape):
-                raise SqdetError("MotAccumulator.load_state_dict: %s is %s, expected %s" % (f, tuple(d[f].shape), tuple(getattr(self, f).shape)))
-        for f in FIELDS:
-            getattr(self, f).copy_(d[f])          # in place: the tables keep their addresses
+    def _settings_error(self, d):
+        return "saved with iou_thresh %s and %s classes" % (d.get("iou_thresh"), d.get("classes"))
 
 
 def summarize(counters, iou_sum):

@@ -12,7 +12,7 @@ Parameters (PARAMS): iou_thresh, high_thresh, low_thresh, min_hits, max_age, w_p
 """
 import ctypes as C
 
-import numpy as np
+from .stream_tables import StreamTables, tables_struct
 
 CAP = 64
 PARAMS = dict(iou_thresh=0.3, high_thresh=0.5, low_thresh=0.1, min_hits=3, max_age=30, w_pos=1.0 / 20, w_vel=1.0 / 160)
@@ -23,8 +23,7 @@ PALETTE = ((255, 191, 0), (0, 191, 255), (255, 0, 191), (0, 255, 0), (0, 0, 255)
            (128, 0, 255), (0, 255, 191), (191, 255, 0), (255, 128, 128))
 
 
-class _Tables(C.Structure):                      # sqdet_track_tables_t
-    _fields_ = [(f, C.c_void_p) for f in FIELDS]
+_Tables = tables_struct(FIELDS)                  # sqdet_track_tables_t
 
 
 class _Params(C.Structure):                      # sqdet_track_params_t
@@ -41,45 +40,23 @@ def table_shapes(streams):
     return d
 
 
-class Tracker:
+class Tracker(StreamTables):
+    FIELDS, STRUCT, RESET = FIELDS, _Tables, {"next_id": 1}
+
     def __init__(self, streams, device, tables=None, **params):
         """tables: {name: device tensor} of the caller's own (a serving arena; tests' guarded buffers) in the shapes and dtypes of
         ``table_shapes(streams)``, already reset; None: the tracker allocates them."""
-        import torch
         from ._lib import SqdetError
         if int(streams) < 1:
             raise SqdetError("Tracker: streams must be positive")
         unknown = set(params) - set(PARAMS)
         if unknown:
             raise SqdetError("Tracker: unknown parameter(s) %s (known: %s)" % (sorted(unknown), sorted(PARAMS)))
-        self.streams, self.device = int(streams), torch.device(device)
-        self.params = dict(PARAMS, **params)
-        for f, (shape, dtype) in table_shapes(self.streams).items():
-            if tables is None:
-                t = torch.zeros(shape, dtype=getattr(torch, dtype), device=self.device)
-            else:
-                t = tables[f]
-                if tuple(t.shape) != shape or t.dtype != getattr(torch, dtype) or not t.is_cuda or not t.is_contiguous():
-                    raise SqdetError("Tracker: table %s must be a contiguous device %s %s" % (f, dtype, shape))
-            setattr(self, f, t)
-        if tables is None:
-            self.next_id.fill_(1)
-        self._tables = _Tables(*[getattr(self, f).data_ptr() for f in FIELDS])
-        p = self.params
+        super().__init__(streams, device, table_shapes(streams), tables)
+        p = self.params = dict(PARAMS, **params)
         self._params = _Params(float(p["iou_thresh"]), float(p["high_thresh"]), float(p["low_thresh"]), float(p["w_pos"]),
                                float(p["w_vel"]), int(p["min_hits"]), int(p["max_age"]))
         self._out = None
-
-    def tables(self):
-        """{name: device tensor}: the state tables themselves (x, P, cls, id, state, hits, miss, age, score, next_id, dropped)."""
-        return {f: getattr(self, f) for f in FIELDS}
-
-    def reset(self, streams=None):
-        """Forgets every track of `streams` (a list of stream indices; None: all): tables zero, next_id one."""
-        import torch
-        idx = slice(None) if streams is None else torch.as_tensor(list(streams), dtype=torch.long, device=self.device)
-        for f in FIELDS:
-            getattr(self, f)[idx] = 1 if f == "next_id" else 0
 
     def update(self, boxes, probs, cls, counts, frames_per_stream=1, stream=None, max_workgroups=0, out=None):
         """boxes float32 [n, rows, 4] (cx, cy, w, h), probs float32 [n, rows], cls int32 [n, rows], counts int32 [n] -- the
@@ -88,13 +65,8 @@ class Tracker:
         -> (det_track_id, det_track_state), reused by the next call of the same shape (or `out`, a pair of int32 [n, rows])."""
         import torch
         from . import ops
-        from ._lib import SqdetError, check, lib, stream_ptr
-        F = int(frames_per_stream)
-        if boxes.dim() != 3 or int(boxes.shape[2]) != 4:
-            raise SqdetError("Tracker.update: boxes must be [n, rows, 4]")
-        n, rows = int(boxes.shape[0]), int(boxes.shape[1])
-        if F < 1 or n != self.streams * F:
-            raise SqdetError("Tracker.update: %d images are not %d streams x %d frames" % (n, self.streams, F))
+        from ._lib import SqdetError, check, lib
+        F, n, rows = self._frames(boxes, frames_per_stream)
         if tuple(probs.shape) != (n, rows) or tuple(cls.shape) != (n, rows) or tuple(counts.shape) != (n,):
             raise SqdetError("Tracker.update: probs / cls must be [n, rows], counts [n]")
         if boxes.device != self.device:
@@ -106,12 +78,11 @@ class Tracker:
             out = self._out
         if tuple(out[0].shape) != (n, rows) or tuple(out[1].shape) != (n, rows):
             raise SqdetError("Tracker.update: out must be two int32 [%d, %d]" % (n, rows))
-        sp = stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
         check(lib().sqdet_track_update(
             C.byref(self._tables), ops._dev(boxes, "boxes", torch.float32), ops._dev(probs, "probs", torch.float32),
             ops._dev(cls, "cls", torch.int32), ops._dev(counts, "counts", torch.int32), self.streams, F, rows, C.byref(self._params),
-            ops._dev(out[0], "det_track_id", torch.int32), ops._dev(out[1], "det_track_state", torch.int32), int(max_workgroups), sp),
-            "sqdet_track_update")
+            ops._dev(out[0], "det_track_id", torch.int32), ops._dev(out[1], "det_track_state", torch.int32), int(max_workgroups),
+            self._stream(stream)), "sqdet_track_update")
         return out
 
     def tracks(self, s):
@@ -123,21 +94,11 @@ class Tracker:
                      box=tuple(float(v) for v in t["x"][k, :, 0]), velocity=tuple(float(v) for v in t["x"][k, :, 1]))
                 for k in range(CAP) if t["state"][k] != 0]
 
-    def state_dict(self):
-        """Host copies of every table and the parameters; continuing after load_state_dict is bitwise the uninterrupted run."""
-        d = {f: getattr(self, f).cpu().clone() for f in FIELDS}
-        d["params"] = dict(self.params)
-        return d
+    def _settings(self):
+        return {"params": dict(self.params)}
 
-    def load_state_dict(self, d):
-        from ._lib import SqdetError
-        if d.get("params", self.params) != self.params:
-            raise SqdetError("Tracker.load_state_dict: saved with parameters %s, this tracker has %s" % (d["params"], self.params))
-        for f in FIELDS:
-            if tuple(d[f].shape) != tuple(getattr(self, f).shape):
-                raise SqdetError("Tracker.load_state_dict: %s is %s, expected %s" % (f, tuple(d[f].shape), tuple(getattr(self, f).shape)))
-        for f in FIELDS:
-            getattr(self, f).copy_(d[f])          # in place: the tables keep their addresses
+    def _settings_error(self, d):
+        return "saved with parameters %s, this tracker has %s" % (d["params"], self.params)
 
 
 def make_track_items(boxes, probs, cls, counts, det_track_id, det_track_state, names, plot_thresh=0.0, palette=PALETTE,
@@ -148,25 +109,14 @@ def make_track_items(boxes, probs, cls, counts, det_track_id, det_track_state, n
     tensor."""
     import torch
     from . import ops, viz
-    from ._lib import SqdetError, check, lib, stream_ptr
-    if boxes.dtype != torch.float32 or boxes.dim() != 3 or int(boxes.shape[2]) != 4:
-        raise SqdetError("make_track_items: boxes must be [B, M, 4] float32")
-    B, M, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
-    for t, what in ((probs, "probs"), (cls, "cls"), (det_track_id, "det_track_id"), (det_track_state, "det_track_state")):
-        if tuple(t.shape) != (B, M):
-            raise SqdetError("make_track_items: %s must be [%d, %d]" % (what, B, M))
-    if tuple(counts.shape) != (B,):
-        raise SqdetError("make_track_items: counts must be [%d]" % B)
-    if not isinstance(names, torch.Tensor):
-        names = viz.pack_names(names, dev)
-    if not isinstance(palette, torch.Tensor):
-        palette = torch.tensor(np.asarray(palette, np.uint8).reshape(-1, 3)).to(dev)
+    from ._lib import check, lib, stream_ptr
+    B, M, names, palette, out = viz._item_tables(
+        "make_track_items", boxes, ("float32",),
+        [(t, what + " must be [%(B)d, %(M)d]") for t, what in ((probs, "probs"), (cls, "cls"), (det_track_id, "det_track_id"),
+                                                               (det_track_state, "det_track_state"))],
+        (counts, "counts must be [%(B)d]"), names, palette, out)
     if M == 0:
-        return viz.DrawItems(torch.zeros((B, 1, viz.ITEM_BYTES), dtype=torch.uint8, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
-    if out is None:
-        out = viz.DrawItems(torch.empty((B, M, viz.ITEM_BYTES), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-    if out.n != B:
-        raise SqdetError("make_track_items: out holds %d images, boxes %d" % (out.n, B))
+        return out
     check(lib().sqdet_track_build_items(
         ops._dev(boxes, "boxes", torch.float32), ops._dev(probs, "probs", torch.float32), ops._dev(cls, "cls", torch.int32),
         ops._dev(counts, "counts", torch.int32), ops._dev(det_track_id, "det_track_id", torch.int32),

@@ -86,6 +86,33 @@ def pack_names(names, device):
     return torch.from_numpy(t).to(device)
 
 
+def _item_tables(who, boxes, dtypes, rows, counts, names, colours, out):
+    """What the item builders' wrappers (make_items, track.make_track_items) do before their launch: boxes [B, M, 4] of one of
+    `dtypes` (torch dtype names); rows: (tensor or None, message) pairs, each tensor [B, M]; counts: (tensor [B], message) --
+    a message may hold %(B)d and %(M)d; names and colours (a list of (b, g, r), or None) packed for the device unless they are
+    tensors already; the table to fill: `out`, a new one, or for M == 0 an empty one with nothing to launch.
+    -> (B, M, names, colours, out)."""
+    import torch
+    from ._lib import SqdetError
+    if boxes.dtype not in [getattr(torch, d) for d in dtypes] or boxes.dim() != 3 or int(boxes.shape[2]) != 4:
+        raise SqdetError("%s: boxes must be [B, M, 4] %s" % (who, " or ".join(dtypes)))
+    B, M, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
+    for t, shape, message in [(t, (B, M), m) for t, m in rows] + [(counts[0], (B,), counts[1])]:
+        if t is not None and tuple(t.shape) != shape:
+            raise SqdetError("%s: %s" % (who, message % {"B": B, "M": M}))
+    if not isinstance(names, torch.Tensor):
+        names = pack_names(names, dev)
+    if colours is not None and not isinstance(colours, torch.Tensor):
+        colours = torch.tensor(np.asarray(colours, np.uint8).reshape(-1, 3)).to(dev)
+    if M == 0:
+        out = DrawItems(torch.zeros((B, 1, ITEM_BYTES), dtype=torch.uint8, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+    elif out is None:
+        out = DrawItems(torch.empty((B, M, ITEM_BYTES), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    if out.n != B:
+        raise SqdetError("%s: out holds %d images, boxes %d" % (who, out.n, B))
+    return B, M, names, colours, out
+
+
 def make_items(boxes, classes, counts, names, probs=None, plot_thresh=0.0, form="center", color=(0, 255, 0), class_colors=None,
                label="name", anchor="bottom_left", out=None):
     """Box rows -> DrawItems, on the device (sqdet_draw_build_items).  boxes [B, M, 4] float32 or float64, classes int32 [B, M],
@@ -96,25 +123,15 @@ def make_items(boxes, classes, counts, names, probs=None, plot_thresh=0.0, form=
     import torch
     from . import ops
     from ._lib import SqdetError, check, lib, stream_ptr
-    if boxes.dtype not in (torch.float32, torch.float64) or boxes.dim() != 3 or int(boxes.shape[2]) != 4:
-        raise SqdetError("make_items: boxes must be [B, M, 4] float32 or float64")
     if form not in ("center", "diagonal"):
         raise SqdetError("bounding box format not accepted: {}.".format(form))
-    B, M, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
-    if tuple(classes.shape) != (B, M) or tuple(counts.shape) != (B,) or (probs is not None and tuple(probs.shape) != (B, M)):
-        raise SqdetError("make_items: classes / probs must be [B, M], counts [B]")
-    if not isinstance(names, torch.Tensor):
-        names = pack_names(names, dev)
-    if class_colors is not None and not isinstance(class_colors, torch.Tensor):
-        class_colors = torch.tensor(np.asarray(class_colors, np.uint8).reshape(-1, 3)).to(dev)
+    shape = "classes / probs must be [B, M], counts [B]"
+    B, M, names, class_colors, out = _item_tables("make_items", boxes, ("float32", "float64"), [(classes, shape), (probs, shape)],
+                                                  (counts, shape), names, class_colors, out)
     if class_colors is not None and int(class_colors.shape[0]) != int(names.shape[0]):
         raise SqdetError("make_items: %d class colours for %d names" % (int(class_colors.shape[0]), int(names.shape[0])))
-    if M == 0:                                         # no rows: an empty table, nothing to launch
-        return DrawItems(torch.zeros((B, 1, ITEM_BYTES), dtype=torch.uint8, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
-    if out is None:
-        out = DrawItems(torch.empty((B, max(M, 1), ITEM_BYTES), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
-    if out.n != B:
-        raise SqdetError("make_items: out holds %d images, boxes %d" % (out.n, B))
+    if M == 0:
+        return out
     check(lib().sqdet_draw_build_items(
         ops._dev(boxes, "boxes"), int(boxes.dtype == torch.float64), ops._dev(probs, "probs", torch.float32) if probs is not None else None,
         ops._dev(classes, "classes", torch.int32), ops._dev(counts, "counts", torch.int32), B, M, int(form == "diagonal"),

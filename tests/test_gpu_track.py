@@ -376,6 +376,37 @@ def test_track_items_and_draw():
     assert np.array_equal(got, DR.draw(img, [want], viz.font(), "bgr")) and not np.array_equal(got, img)
 
 
+def test_track_items_across_waves():
+    """B = 2, M = 130: three waves of rows, the last one of two rows.  Every wave of image 0 keeps some rows and drops some, so
+    a kept row's place depends on the waves before it; image 1 counts 65 rows, so its second wave keeps exactly its first row
+    though every later row is a confirmed track too."""
+    B, M = 2, 130
+    j = np.arange(M)
+    boxes = np.zeros((B, M, 4), np.float32)
+    for i in range(B):
+        boxes[i] = np.stack([20.5 + 3.0 * j + i, 30.25 + 2.0 * (j % 50), 11.0 + (j % 7), 9.0 + (j % 5)], 1)
+    probs = np.full((B, M), 0.9, np.float32)
+    cls = np.stack([j % 3, (j + 1) % 3]).astype(np.int32)
+    ids = np.stack([1 + j, 1000 + 7 * j]).astype(np.int32)
+    sts = np.full((B, M), 2, np.int32)
+    sts[0, j % 3 == 0] = 1                                   # tentative: rows 0, 3, .. 129
+    probs[0, j % 5 == 1] = 0.3                               # below plot_thresh
+    ids[0, 64] = 0                                           # no track
+    ids[0, 127] = -1
+    sts[0, 128], sts[0, 129] = 0, 2                          # the last wave drops its first row and keeps its second
+    sts[1, 1:40:2] = 0
+    counts = np.asarray([130, 65], np.int32)
+    want = R.track_items(boxes, probs, cls, counts, ids, sts, NAMES, track.PALETTE, 0.4)
+    kept = [[(sts[i, r] == 2 and ids[i, r] > 0 and probs[i, r] > 0.4 and r < counts[i]) for r in range(M)] for i in range(B)]
+    for lo, hi in ((0, 64), (64, 128), (128, 130)):
+        assert 0 < sum(kept[0][lo:hi]) < hi - lo
+    assert not kept[0][128] and kept[0][129] and 0 < sum(kept[1][:64]) < 64 and kept[1][64] and sum(kept[1][64:]) == 1
+    assert [len(w) for w in want] == [sum(k) for k in kept]
+    items = track.make_track_items(*dev(boxes, probs, cls, counts, ids, sts), NAMES, plot_thresh=0.4)
+    assert items.counts.cpu().tolist() == [len(w) for w in want]
+    assert items.decode() == want
+
+
 # ------------------------------------------------------------------------------------------------ demo.py --
 def _frames(tmp_path):
     """Six frames: the golden sample, shifted by 3 px after every second frame (a pair of equal frames confirms its tracks)."""

@@ -125,7 +125,8 @@ int sqdet_fold_batchnorm_bwd(const float* w_hwio, const float* dw_folded, const 
                              const float* conv_bias, const float* gamma, const float* mean, const float* var, float eps,
                              float* dw, float* dgamma, float* dbeta, float* workspace, int k, int cin, int cout,
                              sqdet_stream_t stream);
-/* The same for MANY convs in two launches (per conv the results are bitwise sqdet_fold_batchnorm_bwd's): prepare() fills
+/* The same for MANY convs in two launches (per conv the results are bitwise sqdet_fold_batchnorm_bwd's: its kernels' own
+ * device code, run on a workgroup range per conv -- the table mechanism of sqdet_conv_pack_many and sqdet_slab_reduce_many): prepare() fills
  * a host table of sqdet_fold_batchnorm_bwd_many_table_bytes(n_items) bytes from per-item pointer arrays (conv_bias[i] may
  * be NULL; workspace[i]: that conv's sqdet_fold_batchnorm_bwd_workspace_bytes) and reports the two grids; the caller copies
  * the table to the device once. */
@@ -334,13 +335,13 @@ int sqdet_detect_filter_scored(const void* preds, const float* anchors, const fl
  * SqueezeDet's step).  sqdet_conv_pack_many_prepare fills a HOST table of sqdet_conv_pack_many_table_bytes(n) bytes from
  * per-item arrays (device pointers of the float32 HWIO kernels and of the packed outputs, k / cin / cout, bwd_data flags)
  * and reports the grid; the caller copies the table to the device once; sqdet_conv_pack_many runs it (same bytes as the
- * per-kernel entry points produce). */
+ * per-kernel entry points produce: one index decomposition and one element fetch per order under all three kernels). */
 size_t sqdet_conv_pack_many_table_bytes(int nitems);
 int sqdet_conv_pack_many_prepare(const float* const* w_hwio_f32, void* const* packed, const int* k, const int* cin, const int* cout,
                                  const int* bwd_data, int nitems, int dtype, void* table_host, int* total_blocks);
 /* With the batch norm of _conv_bn_layer convs folded on the way (items whose gamma[i] != NULL): what is packed is
- * W[..., c] * gamma[c] / sqrt(var[c] + eps) -- sqdet_fold_batchnorm followed by the packer, bit for bit, without the folded
- * float32 kernel ever being written -- and b_folded[i] (when not NULL) receives the folded bias.  The pointer arrays may be
+ * W[..., c] * gamma[c] / sqrt(var[c] + eps) -- sqdet_fold_batchnorm (its scale and bias expressions themselves) followed by
+ * the packer, bit for bit, without the folded float32 kernel ever being written -- and b_folded[i] (when not NULL) receives the folded bias.  The pointer arrays may be
  * NULL altogether (= sqdet_conv_pack_many_prepare). */
 int sqdet_conv_pack_many_prepare_bn(const float* const* w_hwio_f32, void* const* packed, const int* k, const int* cin,
                                     const int* cout, const int* bwd_data, const float* const* gamma, const float* const* beta,
@@ -381,7 +382,8 @@ int sqdet_conv2d_nhwc_bwd_filter(const void* x, const void* dy, float* dw_hwio, 
  * the backward pass sums the slabs of all of them (a SqueezeDet step: 31 reductions, each a 10 us launch behind its
  * gradient kernel).  prepare() fills a host table (sqdet_slab_reduce_many_table_bytes(n_items) bytes; the caller copies it
  * to the device once) from the per-item workspace / dW / dbias (NULL: none) / decay-weight (NULL: none) pointers and the
- * conv shapes the partial launches used; per item the arithmetic is sqdet_conv2d_nhwc_bwd_filter's, bit for bit. */
+ * conv shapes the partial launches used; per item the reduction is sqdet_conv2d_nhwc_bwd_filter's own device code on that
+ * item's block count, so its bits. */
 int sqdet_conv2d_nhwc_bwd_filter_partial(const void* x, const void* dy, float* workspace, int want_bias, int n, int h, int w,
                                          int cin, int cout, int k, int x_cstride, int x_coffset, int dy_cstride,
                                          int dy_coffset, int dtype, sqdet_stream_t stream);

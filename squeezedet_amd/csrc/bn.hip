@@ -4,6 +4,8 @@
 // with x = conv2d(in, W) [+ biases]; mean / var are non-trainable variables (:437-438), so the whole
 // thing is the conv with W[..., c] * inv[c] and bias (biases[c] - mean[c]) * inv[c] + beta[c].
 // A load-time transform: one pass over the kernel, HBM-streaming, one thread per 4 output channels.
+#include "bn_fold.h"
+#include "item_table.h"
 #include "launch.h"
 
 namespace sqdet {
@@ -20,12 +22,12 @@ __global__ __launch_bounds__(256) void fold_bn_kernel(const float* w, const floa
     const int c = (int)(idx % cv) * 4;
     f32x4 inv;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) inv[e] = gamma[c + e] / sqrtf(var[c + e] + eps);
+    for (int e = 0; e < 4; ++e) inv[e] = bn_fold_scale(gamma[c + e], var[c + e], eps);
     const f32x4 v = *reinterpret_cast<const f32x4*>(w + idx * 4);
     *reinterpret_cast<f32x4*>(wf + idx * 4) = v * inv;
     if (idx < (size_t)cv) {  // first kernel row's threads also produce the folded bias
 #pragma unroll
-      for (int e = 0; e < 4; ++e) bf[c + e] = ((cbias ? cbias[c + e] : 0.f) - mean[c + e]) * inv[e] + beta[c + e];
+      for (int e = 0; e < 4; ++e) bf[c + e] = bn_fold_bias(cbias, mean, beta, c + e, inv[e]);
     }
   }
 }
@@ -56,13 +58,15 @@ int fold_bn_launch(const float* w, const float* cbias, const float* gamma, const
 // workgroups -- 4 for a 256-channel conv -- and was 29 % of the ResNet50 mixed-precision step.)
 constexpr int FB_ROWS = 32;
 
-__global__ __launch_bounds__(256) void fold_bn_bwd_kernel(const float* __restrict__ w, const float* dwf,
-                                                          const float* __restrict__ gamma, const float* __restrict__ var,
-                                                          float eps, float* dw, float* __restrict__ partial, int rows, int cout) {
+// The bodies of kernels (1) and (2), for workgroup (bx, by) of the conv and for the thread of channel c: the per-conv kernels
+// pass their blockIdx, the many-conv kernels below what their table gave them.
+__device__ __forceinline__ void fold_bn_bwd_body(const float* __restrict__ w, const float* dwf, const float* __restrict__ gamma,
+                                                 const float* __restrict__ var, float eps, float* dw, float* __restrict__ partial,
+                                                 int rows, int cout, unsigned bx, unsigned by) {
   __shared__ float part[4][64];
   const int cl = threadIdx.x & 63, rp = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  const int r0 = blockIdx.y * FB_ROWS;
+  const int c = bx * 64 + cl;
+  const int r0 = by * FB_ROWS;
   float s = 0.f;
   if (c < cout) {
     const float inv = gamma[c] * (1.f / sqrtf(var[c] + eps));
@@ -76,14 +80,13 @@ __global__ __launch_bounds__(256) void fold_bn_bwd_kernel(const float* __restric
   }
   part[rp][cl] = s;
   __syncthreads();
-  if (rp == 0 && c < cout) partial[(size_t)blockIdx.y * cout + c] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+  if (rp == 0 && c < cout) partial[(size_t)by * cout + c] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
 }
 
-__global__ void fold_bn_bwd_finish_kernel(const float* __restrict__ partial, const float* __restrict__ dbf,
-                                          const float* __restrict__ cbias, const float* __restrict__ mean,
-                                          const float* __restrict__ var, float eps, float* __restrict__ dgamma,
-                                          float* __restrict__ dbeta, int nblocks, int cout) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void fold_bn_bwd_finish_body(const float* __restrict__ partial, const float* __restrict__ dbf,
+                                                        const float* __restrict__ cbias, const float* __restrict__ mean,
+                                                        const float* __restrict__ var, float eps, float* __restrict__ dgamma,
+                                                        float* __restrict__ dbeta, int nblocks, int cout, int c) {
   if (c >= cout) return;
   float tot = 0.f;
   for (int b = 0; b < nblocks; ++b) tot += partial[(size_t)b * cout + c];
@@ -91,6 +94,19 @@ __global__ void fold_bn_bwd_finish_kernel(const float* __restrict__ partial, con
   const float db = dbf[c];
   dgamma[c] = r * (tot + ((cbias ? cbias[c] : 0.f) - mean[c]) * db);
   dbeta[c] = db;
+}
+
+__global__ __launch_bounds__(256) void fold_bn_bwd_kernel(const float* __restrict__ w, const float* dwf,
+                                                          const float* __restrict__ gamma, const float* __restrict__ var,
+                                                          float eps, float* dw, float* __restrict__ partial, int rows, int cout) {
+  fold_bn_bwd_body(w, dwf, gamma, var, eps, dw, partial, rows, cout, blockIdx.x, blockIdx.y);
+}
+
+__global__ void fold_bn_bwd_finish_kernel(const float* __restrict__ partial, const float* __restrict__ dbf,
+                                          const float* __restrict__ cbias, const float* __restrict__ mean,
+                                          const float* __restrict__ var, float eps, float* __restrict__ dgamma,
+                                          float* __restrict__ dbeta, int nblocks, int cout) {
+  fold_bn_bwd_finish_body(partial, dbf, cbias, mean, var, eps, dgamma, dbeta, nblocks, cout, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 size_t fold_bn_bwd_workspace_bytes(int k, int cin, int cout) {
@@ -114,9 +130,7 @@ int fold_bn_bwd_launch(const float* w, const float* dwf, const float* dbf, const
 }
 
 // The same for MANY _conv_bn_layer convs in two launches (a ResNet50 step has 19 trainable ones: 38 launches of 5-10 us
-// behind as many slab reductions): a table entry per conv, workgroup b of launch (1) serves the entry whose range holds b
-// with fold_bn_bwd_kernel's block shape and arithmetic, launch (2) likewise with fold_bn_bwd_finish_kernel's -- per conv the
-// results are bitwise sqdet_fold_batchnorm_bwd's.
+// behind as many slab reductions): a table entry per conv (item_table.h), one workgroup range per conv in either launch.
 struct FoldBwdItem {
   const float *w, *dwf, *dbf, *cbias, *gamma, *mean, *var;
   float *dw, *dgamma, *dbeta, *partial;
@@ -125,49 +139,16 @@ struct FoldBwdItem {
 };
 
 __global__ __launch_bounds__(256) void fold_bn_bwd_many_kernel(const FoldBwdItem* __restrict__ items, int n, float eps) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (items[mid].first_block <= blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const FoldBwdItem it = items[lo];
+  const FoldBwdItem it = item_of_block<FoldBwdItem, &FoldBwdItem::first_block>(items, n, blockIdx.x);
   const unsigned local = blockIdx.x - it.first_block;
-  const int bx = (int)(local % (unsigned)it.blocks_x), by = (int)(local / (unsigned)it.blocks_x);
-  __shared__ float part[4][64];
-  const int cl = threadIdx.x & 63, rp = threadIdx.x >> 6;
-  const int c = bx * 64 + cl;
-  const int r0 = by * FB_ROWS;
-  float s = 0.f;
-  if (c < it.cout) {
-    const float inv = it.gamma[c] * (1.f / sqrtf(it.var[c] + eps));
-    const int r1 = min(it.rows, r0 + FB_ROWS);
-    for (int row = r0 + rp; row < r1; row += 4) {
-      const size_t i = (size_t)row * it.cout + c;
-      const float g = it.dwf[i];
-      s += g * it.w[i];
-      it.dw[i] = g * inv;
-    }
-  }
-  part[rp][cl] = s;
-  __syncthreads();
-  if (rp == 0 && c < it.cout) it.partial[(size_t)by * it.cout + c] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+  fold_bn_bwd_body(it.w, it.dwf, it.gamma, it.var, eps, it.dw, it.partial, it.rows, it.cout, local % (unsigned)it.blocks_x,
+                   local / (unsigned)it.blocks_x);
 }
 
 __global__ void fold_bn_bwd_finish_many_kernel(const FoldBwdItem* __restrict__ items, int n, float eps) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (items[mid].first_finish <= blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const FoldBwdItem it = items[lo];
-  const int c = (int)(blockIdx.x - it.first_finish) * blockDim.x + threadIdx.x;
-  if (c >= it.cout) return;
-  float tot = 0.f;
-  for (int b = 0; b < it.nblocks_y; ++b) tot += it.partial[(size_t)b * it.cout + c];
-  const float r = 1.f / sqrtf(it.var[c] + eps);
-  const float db = it.dbf[c];
-  it.dgamma[c] = r * (tot + ((it.cbias ? it.cbias[c] : 0.f) - it.mean[c]) * db);
-  it.dbeta[c] = db;
+  const FoldBwdItem it = item_of_block<FoldBwdItem, &FoldBwdItem::first_finish>(items, n, blockIdx.x);
+  fold_bn_bwd_finish_body(it.partial, it.dbf, it.cbias, it.mean, it.var, eps, it.dgamma, it.dbeta, it.nblocks_y, it.cout,
+                          (int)(blockIdx.x - it.first_finish) * blockDim.x + threadIdx.x);
 }
 
 // y[n, oy, ox, :] = x[n, oy*stride, ox*stride, :]: the pixels a 1x1 / stride-s SAME conv reads (the
@@ -241,7 +222,7 @@ extern "C" int sqdet_fold_batchnorm_bwd_many_prepare(const float* const* w_hwio,
   SQDET_REQUIRE(w_hwio && dw_folded && db_folded && conv_bias && gamma && mean && var && dw && dgamma && dbeta && workspace && k &&
                     cin && cout && table_host && blocks && finish_blocks && n_items > 0, "fold_batchnorm_bwd_many_prepare: bad arguments");
   sqdet::FoldBwdItem* t = static_cast<sqdet::FoldBwdItem*>(table_host);
-  unsigned nb = 0, nf = 0;
+  sqdet::BlockCursor nb, nf;
   for (int i = 0; i < n_items; ++i) {
     SQDET_REQUIRE(w_hwio[i] && dw_folded[i] && db_folded[i] && gamma[i] && mean[i] && var[i] && dw[i] && dgamma[i] && dbeta[i] &&
                       workspace[i] && k[i] > 0 && cin[i] > 0 && cout[i] > 0, "fold_batchnorm_bwd_many_prepare: bad item %d", i);
@@ -251,11 +232,10 @@ extern "C" int sqdet_fold_batchnorm_bwd_many_prepare(const float* const* w_hwio,
     it.rows = k[i] * k[i] * cin[i]; it.cout = cout[i];
     it.nblocks_y = (it.rows + sqdet::FB_ROWS - 1) / sqdet::FB_ROWS;
     it.blocks_x = (cout[i] + 63) / 64;
-    it.first_block = nb; it.first_finish = nf;
-    nb += (unsigned)(it.blocks_x * it.nblocks_y);
-    nf += (unsigned)((cout[i] + 255) / 256);
+    it.first_block = nb.take((unsigned)(it.blocks_x * it.nblocks_y));
+    it.first_finish = nf.take((unsigned)((cout[i] + 255) / 256));
   }
-  *blocks = (int)nb; *finish_blocks = (int)nf;
+  *blocks = (int)nb.total; *finish_blocks = (int)nf.total;
   return SQDET_OK;
 }
 

@@ -215,28 +215,13 @@ __global__ __launch_bounds__(256) void conv_gather(ConvArgs a) {
   conv_epilogue<T, MT, NT>(a, acc, pix, valid, group, g);
 }
 
-// ---- weight packing: float32 HWIO -> [group][step][nt][lane][KG] fragments ----
-// element (group, step=(tap,chunk), n, lane=(i=lane&15, g=lane>>4), e):
-//   cout = group*16*NT + (i>>2)*4*NT + n*4 + (i&3)      (row i of tile n <-> consecutive couts per lane)
-//   cin  = chunk*KC + g*KG + e
+// ---- weight packing (the fragment order: conv_common.h) ----
 template <typename T>
 __global__ void pack_weights_kernel(const float* __restrict__ w, T* __restrict__ out, int taps, int kdim, int cout,
                                     int nchunk, int nt, size_t total) {
-  constexpr int KG = Tr<T>::KG;
-  constexpr int KC = 4 * KG;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    size_t t = idx;
-    const int e = t % KG; t /= KG;
-    const int lane = t % 64; t /= 64;
-    const int n = t % nt; t /= nt;
-    const int step = t % (taps * nchunk); t /= (taps * nchunk);
-    const int group = (int)t;
-    const int tap = step / nchunk, chunk = step - tap * nchunk;
-    const int i = lane & 15, g = lane >> 4;
-    const int co = group * 16 * nt + (i >> 2) * 4 * nt + n * 4 + (i & 3);
-    const int ci = chunk * KC + g * KG + e;
-    float v = 0.f;
-    if (co < cout && ci < kdim) v = w[((size_t)tap * kdim + ci) * cout + co];
+    float v;
+    pack_fetch_fwd(w, pack_index<T>(idx, nt, nchunk, taps), kdim, cout, v);
     out[idx] = (T)v;
   }
 }

@@ -1,4 +1,5 @@
-// Shared device helpers of the conv kernels (conv.hip, conv3x3.hip); their host-side launchers are declared in launch.h.
+// Shared device helpers of the conv kernels (conv.hip, conv3x3.hip) and of the weight packers (conv.hip, train.hip); their
+// host-side launchers are declared in launch.h.
 #pragma once
 #include "common.h"
 #include "launch.h"
@@ -87,6 +88,44 @@ __device__ __forceinline__ void store_couts(T* dst, const f32x4 (&v)[NT], int nt
     for (int t = 0; t < NT; ++t)
       if (t < nt_valid) store4<T>(dst + t * 4, v[t]);
   }
+}
+
+// ---- weight packing: float32 HWIO -> [group][step][nt][lane][KG] fragments of the conv that will read them ----
+// element idx = (group, step=(tap,chunk), n, lane=(i=lane&15, g=lane>>4), e):
+//   co = group*16*NT + (i>>2)*4*NT + n*4 + (i&3)      (row i of tile n <-> consecutive output channels per lane)
+//   ci = chunk*KC + g*KG + e
+struct PackIdx { int tap, ci, co; };
+
+template <typename T>
+__device__ __forceinline__ PackIdx pack_index(size_t idx, int nt, int nchunk, int taps) {
+  constexpr int KG = Tr<T>::KG;
+  constexpr int KC = 4 * KG;
+  size_t t = idx;
+  const int e = t % KG; t /= KG;
+  const int lane = t % 64; t /= 64;
+  const int n = t % nt; t /= nt;
+  const int step = t % (taps * nchunk); t /= (taps * nchunk);
+  const int group = (int)t;
+  const int tap = step / nchunk, chunk = step - tap * nchunk;
+  const int i = lane & 15, g = lane >> 4;
+  return {tap, chunk * KC + g * KG + e, group * 16 * nt + (i >> 2) * 4 * nt + n * 4 + (i & 3)};
+}
+
+// The element's value in v (0 in the padding beyond the kernel's channels); returns whether the element exists.
+// Forward order: the conv reads taps x kdim input values per output channel.
+__device__ __forceinline__ bool pack_fetch_fwd(const float* __restrict__ w, const PackIdx& p, int kdim, int cout, float& v) {
+  const bool in = p.co < cout && p.ci < kdim;
+  v = in ? w[((size_t)p.tap * kdim + p.ci) * cout + p.co] : 0.f;
+  return in;
+}
+
+// Backward-data order: dgrad(dy)[ci] = sum_{tap,co} W[k-1-ty][k-1-tx][ci][co] * dy@tap[co] is a forward conv with kernel
+// W'[ty][tx][co][ci], so its output channel p.co is an original cin and its input channel p.ci an original cout.
+__device__ __forceinline__ bool pack_fetch_bwd(const float* __restrict__ w, const PackIdx& p, int k, int cin, int cout, float& v) {
+  const int ty = p.tap / k, tx = p.tap - ty * k;
+  const bool in = p.co < cin && p.ci < cout;
+  v = in ? w[(((size_t)(k - 1 - ty) * k + (k - 1 - tx)) * cin + p.co) * cout + p.ci] : 0.f;
+  return in;
 }
 
 }  // namespace sqdet

@@ -12,50 +12,38 @@
 
 #include <vector>
 
+#include "bn_fold.h"
 #include "conv_common.h"
+#include "item_table.h"
 
 namespace sqdet {
 
 // ------------------------------------------------------------------ backward-data weight packing
-// dgrad(dy)[ci] = sum_{tap,co} W[k-1-ty][k-1-tx][ci][co] * dy@tap[co]: a forward conv with
-// kernel W'[ty][tx][co][ci].  Packed in the forward fragment order for a [k,k,cout,cin] kernel.
+// The kernel of the backward-data conv, packed in the forward fragment order for a [k,k,cout,cin] kernel (conv_common.h).
 template <typename T>
 __global__ void pack_bwd_data_kernel(const float* __restrict__ w, T* __restrict__ out, int k, int cin, int cout,
                                      int nchunk, int nt, size_t total) {
-  constexpr int KG = Tr<T>::KG;
-  constexpr int KC = 4 * KG;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    size_t t = idx;
-    const int e = t % KG; t /= KG;
-    const int lane = t % 64; t /= 64;
-    const int n = t % nt; t /= nt;
-    const int step = t % (k * k * nchunk); t /= (k * k * nchunk);
-    const int group = (int)t;
-    const int tap = step / nchunk, chunk = step - tap * nchunk;
-    const int i = lane & 15, g = lane >> 4;
-    const int o = group * 16 * nt + (i >> 2) * 4 * nt + n * 4 + (i & 3);   // output channel of the dgrad = original cin
-    const int c = chunk * KC + g * KG + e;                                  // input channel of the dgrad = original cout
-    const int ty = tap / k, tx = tap - ty * k;
-    float v = 0.f;
-    if (o < cin && c < cout) v = w[(((size_t)(k - 1 - ty) * k + (k - 1 - tx)) * cin + o) * cout + c];
+    float v;
+    pack_fetch_bwd(w, pack_index<T>(idx, nt, nchunk, k * k), k, cin, cout, v);
     out[idx] = (T)v;
   }
 }
 
-
 // ------------------------------------------------------------------ packing MANY kernels in one launch
 // A training step re-packs every trainable conv kernel twice (forward fragment order + the backward-data conv's order) after
-// the optimizer has changed it: 62 launches of ~4.7 us in SqueezeDet's step -- 0.29 ms of 3.5.  One launch walks a table.
+// the optimizer has changed it: 62 launches of ~4.7 us in SqueezeDet's step -- 0.29 ms of 3.5.  One launch walks a table
+// (item_table.h).
 struct PackItem {
   const float* w;        // HWIO float32 [k,k,cin,cout]
   void* out;             // packed buffer
   int k, cin, cout;
   int taps, kdim, nchunk, nt;   // of the conv that will READ the packed kernel (forward: cin -> cout; backward-data: cout -> cin)
-  int bwd;               // 0 forward order (pack_weights_kernel), 1 backward-data order (pack_bwd_data_kernel)
+  int bwd;               // 0 forward order, 1 backward-data order
   unsigned long long total;
-  int first_block, nblocks;
-  // gamma != NULL: the kernel of a _conv_bn_layer -- what is packed is the FOLDED kernel W[..., c] * gamma[c] / sqrt(var[c] + eps)
-  // (fold_bn_kernel's expression, bn.hip), and the item's first workgroup also writes the folded bias b_folded (when not NULL)
+  unsigned first_block, nblocks;
+  // gamma != NULL: the kernel of a _conv_bn_layer -- what is packed is the FOLDED kernel W[..., c] * bn_fold_scale(c), and the
+  // item's first workgroup also writes the folded bias b_folded (when not NULL)
   const float *gamma, *var, *beta, *mean, *cbias;
   float* b_folded;
   float eps;
@@ -63,41 +51,22 @@ struct PackItem {
 
 template <typename T>
 __global__ __launch_bounds__(256) void pack_many_kernel(const PackItem* __restrict__ items, int nitems) {
-  constexpr int KG = Tr<T>::KG;
-  constexpr int KC = 4 * KG;
-  int it = 0;
-  while (it + 1 < nitems && (int)blockIdx.x >= items[it + 1].first_block) ++it;     // (<= a few dozen entries)
-  const PackItem p = items[it];
+  const PackItem p = item_of_block<PackItem, &PackItem::first_block>(items, nitems, blockIdx.x);
   const float* __restrict__ w = p.w;
   T* __restrict__ out = reinterpret_cast<T*>(p.out);
   for (size_t idx = (size_t)(blockIdx.x - p.first_block) * 256 + threadIdx.x; idx < p.total; idx += (size_t)p.nblocks * 256) {
-    size_t t = idx;
-    const int e = t % KG; t /= KG;
-    const int lane = t % 64; t /= 64;
-    const int n = t % p.nt; t /= p.nt;
-    const int steps = p.taps * p.nchunk;
-    const int step = t % steps; t /= steps;
-    const int group = (int)t;
-    const int tap = step / p.nchunk, chunk = step - tap * p.nchunk;
-    const int i = lane & 15, g = lane >> 4;
-    const int co = group * 16 * p.nt + (i >> 2) * 4 * p.nt + n * 4 + (i & 3);
-    const int ci = chunk * KC + g * KG + e;
-    float v = 0.f;
-    int oc = -1;             // the ORIGINAL output channel of the element (the batch-norm channel)
-    if (!p.bwd) {            // exactly pack_weights_kernel (conv.hip)
-      if (co < p.cout && ci < p.kdim) { v = w[((size_t)tap * p.kdim + ci) * p.cout + co]; oc = co; }
-    } else {                 // exactly pack_bwd_data_kernel: output channel of the dgrad = original cin, input = original cout
-      const int ty = tap / p.k, tx = tap - ty * p.k;
-      if (co < p.cin && ci < p.cout) { v = w[(((size_t)(p.k - 1 - ty) * p.k + (p.k - 1 - tx)) * p.cin + co) * p.cout + ci]; oc = ci; }
+    const PackIdx x = pack_index<T>(idx, p.nt, p.nchunk, p.taps);
+    float v;
+    const bool in = p.bwd ? pack_fetch_bwd(w, x, p.k, p.cin, p.cout, v) : pack_fetch_fwd(w, x, p.kdim, p.cout, v);
+    if (p.gamma && in) {
+      const int oc = p.bwd ? x.ci : x.co;       // the ORIGINAL output channel of the element (the batch-norm channel)
+      v = v * bn_fold_scale(p.gamma[oc], p.var[oc], p.eps);
     }
-    if (p.gamma && oc >= 0) v = v * (p.gamma[oc] / sqrtf(p.var[oc] + p.eps));
     out[idx] = (T)v;
   }
-  if (p.gamma && p.b_folded && (int)blockIdx.x == p.first_block) {
-    for (int c = threadIdx.x; c < p.cout; c += 256) {
-      const float inv = p.gamma[c] / sqrtf(p.var[c] + p.eps);
-      p.b_folded[c] = ((p.cbias ? p.cbias[c] : 0.f) - p.mean[c]) * inv + p.beta[c];
-    }
+  if (p.gamma && p.b_folded && blockIdx.x == p.first_block) {
+    for (int c = threadIdx.x; c < p.cout; c += 256)
+      p.b_folded[c] = bn_fold_bias(p.cbias, p.mean, p.beta, c, bn_fold_scale(p.gamma[c], p.var[c], p.eps));
   }
 }
 
@@ -770,7 +739,7 @@ extern "C" int sqdet_conv_pack_many_prepare_bn(const float* const* w_hwio_f32, v
   SQDET_REQUIRE(dtype == SQDET_F16 || dtype == SQDET_F32, "pack_many_prepare: bad dtype");
   SQDET_REQUIRE(!gamma || (beta && mean && var && conv_bias && b_folded && eps >= 0.f), "pack_many_prepare: incomplete batch-norm arrays");
   sqdet::PackItem* t = reinterpret_cast<sqdet::PackItem*>(table_host);
-  int blocks = 0;
+  sqdet::BlockCursor blocks;
   for (int i = 0; i < nitems; ++i) {
     SQDET_REQUIRE(w_hwio_f32[i] && packed[i] && k[i] > 0 && cin[i] > 0 && cout[i] > 0, "pack_many_prepare: bad item %d", i);
     const ConvGeom g = bwd_data[i] ? conv_geom(k[i], cout[i], cin[i], dtype) : conv_geom(k[i], cin[i], cout[i], dtype);
@@ -779,17 +748,16 @@ extern "C" int sqdet_conv_pack_many_prepare_bn(const float* const* w_hwio_f32, v
     p.w = w_hwio_f32[i]; p.out = packed[i]; p.k = k[i]; p.cin = cin[i]; p.cout = cout[i];
     p.taps = g.taps; p.kdim = g.kdim; p.nchunk = g.nchunk; p.nt = g.nt; p.bwd = bwd_data[i] ? 1 : 0;
     p.total = (unsigned long long)g.ngroups * g.steps * g.nt * 64 * g.kg;
-    int nb = (int)((p.total + 255) / 256);
-    if (nb > 256) nb = 256;
-    p.first_block = blocks; p.nblocks = nb;
-    blocks += nb;
+    const unsigned long long nb = (p.total + 255) / 256;
+    p.nblocks = nb > 256 ? 256u : (unsigned)nb;
+    p.first_block = blocks.take(p.nblocks);
     p.gamma = p.var = p.beta = p.mean = p.cbias = nullptr; p.b_folded = nullptr; p.eps = eps;
     if (gamma && gamma[i]) {
       SQDET_REQUIRE(beta[i] && mean[i] && var[i], "pack_many_prepare: item %d: gamma without beta / mean / var", i);
       p.gamma = gamma[i]; p.beta = beta[i]; p.mean = mean[i]; p.var = var[i]; p.cbias = conv_bias[i]; p.b_folded = b_folded[i];
     }
   }
-  *total_blocks = blocks;
+  *total_blocks = (int)blocks.total;
   return SQDET_OK;
 }
 

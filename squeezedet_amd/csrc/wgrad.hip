@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "item_table.h"
 
 namespace sqdet {
 
@@ -319,8 +320,8 @@ __global__ void slab_reduce2_kernel(const float* __restrict__ partial, float* __
 }
 
 // The slab reductions of MANY backward-filter launches in one launch (a training step's 31: each was a launch of its own
-// behind its wgrad_tile, 10 us apiece): workgroup b serves the item whose block range holds b, with exactly the arithmetic
-// of slab_reduce2_kernel for that item's own block count -- bitwise the per-layer results.
+// behind its wgrad_tile, 10 us apiece): workgroup b serves the item whose block range holds b (item_table.h), on that item's
+// own block count.
 struct ReduceItem {
   const float* partial;
   float* dw;
@@ -334,12 +335,7 @@ struct ReduceItem {
 };
 
 __global__ void slab_reduce_many_kernel(const ReduceItem* __restrict__ items, int n, float scale) {
-  int lo = 0, hi = n - 1;           // the last item whose first_block <= blockIdx.x
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (items[mid].first_block <= blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const ReduceItem it = items[lo];
+  const ReduceItem it = item_of_block<ReduceItem, &ReduceItem::first_block>(items, n, blockIdx.x);
   slab_reduce_body(it.partial, it.dw, it.dbias, it.w, it.decay, scale, it.count, it.cout, it.stride, it.nslabs,
                    blockIdx.x - it.first_block, it.nblocks, it.wide_ok);
 }
@@ -488,7 +484,7 @@ extern "C" int sqdet_slab_reduce_many_prepare(const float* const* workspaces, fl
   SQDET_REQUIRE(workspaces && dws && dbiases && w_for_decay && decays && n && h && w && cin && cout && k && table_host &&
                     total_blocks && n_items > 0, "slab_reduce_many_prepare: bad arguments");
   ReduceItem* t = static_cast<ReduceItem*>(table_host);
-  unsigned next = 0;
+  BlockCursor blocks;
   for (int i = 0; i < n_items; ++i) {
     SQDET_REQUIRE(workspaces[i] && dws[i] && (k[i] == 1 || k[i] == 3) && n[i] > 0 && h[i] > 0 && w[i] > 0 && cin[i] > 0 && cout[i] > 0,
                   "slab_reduce_many_prepare: bad item %d", i);
@@ -496,12 +492,11 @@ extern "C" int sqdet_slab_reduce_many_prepare(const float* const* workspaces, fl
     ReduceItem& it = t[i];
     it.partial = workspaces[i]; it.dw = dws[i]; it.dbias = dbiases[i]; it.w = w_for_decay[i];
     it.count = p.count; it.stride = p.slab_stride; it.decay = decays[i]; it.cout = cout[i]; it.nslabs = p.ksplit;
-    it.first_block = next;
     it.wide_ok = tune(TUNE_DBG) == 52 ? 0 : 1;
     it.nblocks = (unsigned)reduce_blocks(p.count + (dbiases[i] ? (size_t)cout[i] : 0));
-    next += it.nblocks;
+    it.first_block = blocks.take(it.nblocks);
   }
-  *total_blocks = (int)next;
+  *total_blocks = (int)blocks.total;
   return SQDET_OK;
 }
 

@@ -34,14 +34,22 @@ class PackedConv:
 
     def __init__(self, w_hwio, dtype):
         w = w_hwio.detach().to(torch.float32).contiguous()
-        self.k, k2, self.cin, self.cout = [int(v) for v in w.shape]
-        assert self.k == k2, "square kernels only"
-        self.dtype = dtype
-        code = dtype_code(dtype)
-        nbytes = lib().sqdet_conv_packed_bytes(self.k, self.cin, self.cout, code)
-        self.data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        k, k2, cin, cout = [int(v) for v in w.shape]
+        assert k == k2, "square kernels only"
+        self._alloc(k, cin, cout, dtype, w.device)
         check(lib().sqdet_conv_pack_weights(_dev(w, "w_hwio"), _dev(self.data, "packed"), self.k, self.cin, self.cout,
-                                            code, stream_ptr()), "sqdet_conv_pack_weights")
+                                            dtype_code(dtype), stream_ptr()), "sqdet_conv_pack_weights")
+
+    def _alloc(self, k, cin, cout, dtype, device):
+        self.k, self.cin, self.cout, self.dtype = k, cin, cout, dtype
+        self.data = torch.empty(int(lib().sqdet_conv_packed_bytes(k, cin, cout, dtype_code(dtype))), dtype=torch.uint8, device=device)
+
+    @classmethod
+    def empty(cls, k, cin, cout, dtype, device):
+        """The buffer of a [k,k,cin,cout] kernel, allocated and not packed (PackPlan packs it)."""
+        self = cls.__new__(cls)
+        self._alloc(k, cin, cout, dtype, device)
+        return self
 
 
 def pack_conv_weights(w_hwio, dtype):
@@ -439,16 +447,47 @@ class PackedConvBwd:
 
     def __init__(self, w_hwio, dtype=torch.float32):
         w = w_hwio.detach().to(torch.float32).contiguous()
-        self.k, _, self.cin, self.cout = [int(v) for v in w.shape]
-        self.dtype = dtype
-        code = dtype_code(dtype)
-        nbytes = lib().sqdet_conv_packed_bytes(self.k, self.cout, self.cin, code)
-        self.data = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        k, _, cin, cout = [int(v) for v in w.shape]
+        self._alloc(k, cin, cout, dtype, w.device)
         check(lib().sqdet_conv_pack_weights_bwd_data(_dev(w, "w_hwio"), _dev(self.data, "packed"), self.k, self.cin,
-                                                     self.cout, code, stream_ptr()), "sqdet_conv_pack_weights_bwd_data")
+                                                     self.cout, dtype_code(dtype), stream_ptr()), "sqdet_conv_pack_weights_bwd_data")
+
+    def _alloc(self, k, cin, cout, dtype, device):      # (the backward-data conv reads cout channels and writes cin)
+        self.k, self.cin, self.cout, self.dtype = k, cin, cout, dtype
+        self.data = torch.empty(int(lib().sqdet_conv_packed_bytes(k, cout, cin, dtype_code(dtype))), dtype=torch.uint8, device=device)
+
+    empty = classmethod(PackedConv.empty.__func__)
 
 
-class PackPlan:
+class _ItemTable:
+    """The host half of a "many" launch (csrc/item_table.h), under PackPlan, FoldBwdPlan and WgradPlan: one-entry-per-item
+    columns for a `*_prepare` entry, the device table that entry fills, and the references that keep the items' tensors alive
+    for as long as the table points at them."""
+
+    def __init__(self, n, keep):
+        self.n, self._keep = n, keep
+
+    def _ptrs(self, tensors):
+        """A pointer column; a None tensor is a NULL entry."""
+        return (C.c_void_p * self.n)(*[t.data_ptr() if t is not None else None for t in tensors])
+
+    def _ints(self, vals):
+        return (C.c_int * self.n)(*[int(v) for v in vals])
+
+    def _floats(self, vals):
+        return (C.c_float * self.n)(*[float(v) for v in vals])
+
+    def _fill(self, table_bytes, prepare, args, counters, device):
+        """lib().<prepare>(*args, host table of lib().<table_bytes>(n) bytes, &count, ...): uploads the table to self.table and
+        returns the counts (the launches' grids)."""
+        host = (C.c_ubyte * int(getattr(lib(), table_bytes)(self.n)))()
+        counts = [C.c_int() for _ in range(counters)]
+        check(getattr(lib(), prepare)(*args, host, *[C.byref(c) for c in counts]), prepare)
+        self.table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
+        return [int(c.value) for c in counts]
+
+
+class PackPlan(_ItemTable):
     """Every trainable conv kernel of a trainer packed in ONE launch (sqdet_conv_pack_many): the forward fragment order
     (PackedConv) and, for the convs whose input needs a gradient, the backward-data conv's order (PackedConvBwd), into
     persistent buffers.  weights: {name: float32 HWIO tensor (a VIEW whose storage does not move: the trainer's flat
@@ -459,10 +498,9 @@ class PackPlan:
 
     def __init__(self, weights, dtype, bwd_names=(), bn=None, eps=0.0):
         self.dtype = dtype
-        code = dtype_code(dtype)
         bn = bn or {}
         self.fwd, self.bwd, self.bias = {}, {}, {}
-        items = []
+        items = []          # (w, packed buffer, k, cin, cout, backward-data order, (gamma, beta, mean, var, conv_bias), folded bias)
         for name, w in weights.items():
             if w.dtype != torch.float32 or not w.is_contiguous():
                 raise _lib.SqdetError("PackPlan: %s must be a contiguous float32 HWIO tensor" % name)
@@ -473,62 +511,37 @@ class PackPlan:
                     if t.dtype != torch.float32 or not t.is_contiguous() or int(t.numel()) != cout:
                         raise _lib.SqdetError("PackPlan: %s: batch-norm vectors must be contiguous float32 [cout]" % name)
                 self.bias[name] = torch.empty(cout, dtype=torch.float32, device=w.device)
-            pc = PackedConv.__new__(PackedConv)
-            pc.k, pc.cin, pc.cout, pc.dtype = k, cin, cout, dtype
-            pc.data = torch.empty(int(lib().sqdet_conv_packed_bytes(k, cin, cout, code)), dtype=torch.uint8, device=w.device)
-            self.fwd[name] = pc
-            items.append((w, pc.data, k, cin, cout, 0, fold, self.bias.get(name)))
+            self.fwd[name] = PackedConv.empty(k, cin, cout, dtype, w.device)
+            items.append((w, self.fwd[name].data, k, cin, cout, 0, fold or (None,) * 5, self.bias.get(name)))
             if name in bwd_names:
-                pb = PackedConvBwd.__new__(PackedConvBwd)
-                pb.k, pb.cin, pb.cout, pb.dtype = k, cin, cout, dtype
-                pb.data = torch.empty(int(lib().sqdet_conv_packed_bytes(k, cout, cin, code)), dtype=torch.uint8, device=w.device)
-                self.bwd[name] = pb
-                items.append((w, pb.data, k, cin, cout, 1, fold, None))
-        n = len(items)
-        self.n = n
-        self._keep = items
-        dev = items[0][0].device
-        arr = lambda vals, ct: (ct * n)(*vals)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        wp = arr([it[0].data_ptr() for it in items], C.c_void_p)
-        op = arr([it[1].data_ptr() for it in items], C.c_void_p)
-        ks, cis, cos, bw = [arr([it[j] for it in items], C.c_int) for j in (2, 3, 4, 5)]
-        bnp = [arr([ptr(it[6][j]) if it[6] is not None else None for it in items], C.c_void_p) for j in range(5)]   # gamma beta mean var conv_bias
-        bfp = arr([ptr(it[7]) for it in items], C.c_void_p)
-        nbytes = int(lib().sqdet_conv_pack_many_table_bytes(n))
-        host = (C.c_ubyte * nbytes)()
-        blocks = C.c_int()
-        check(lib().sqdet_conv_pack_many_prepare_bn(wp, op, ks, cis, cos, bw, bnp[0], bnp[1], bnp[2], bnp[3], bnp[4], bfp, float(eps), n,
-                                                    code, host, C.byref(blocks)), "sqdet_conv_pack_many_prepare_bn")
-        self.blocks = int(blocks.value)
-        self.table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(dev)
+                self.bwd[name] = PackedConvBwd.empty(k, cin, cout, dtype, w.device)
+                items.append((w, self.bwd[name].data, k, cin, cout, 1, fold or (None,) * 5, None))
+        super().__init__(len(items), items)
+        cols = [self._ptrs(it[j] for it in items) for j in (0, 1)] + [self._ints(it[j] for it in items) for j in (2, 3, 4, 5)]
+        cols += [self._ptrs(it[6][j] for it in items) for j in range(5)] + [self._ptrs(it[7] for it in items)]
+        self.blocks, = self._fill("sqdet_conv_pack_many_table_bytes", "sqdet_conv_pack_many_prepare_bn",
+                                  cols + [float(eps), self.n, dtype_code(dtype)], 1, items[0][0].device)
 
     def run(self):
         check(lib().sqdet_conv_pack_many(_dev(self.table, "table"), self.n, self.blocks, dtype_code(self.dtype), stream_ptr()),
               "sqdet_conv_pack_many")
 
 
-class FoldBwdPlan:
+class FoldBwdPlan(_ItemTable):
     """sqdet_fold_batchnorm_bwd for MANY _conv_bn_layer convs in two launches.  items: [(w, dw_folded, db_folded, conv_bias or
     None, gamma, mean, var, dw, dgamma, dbeta)] -- persistent float32 tensors; run() after the folded gradients are in place."""
 
     def __init__(self, items, eps):
-        self.n, self.eps, self._keep = len(items), float(eps), items
+        super().__init__(len(items), items)
+        self.eps = float(eps)
         dev = items[0][0].device
         dims = [[int(v) for v in it[0].shape] for it in items]
         self.ws = [torch.empty(int(lib().sqdet_fold_batchnorm_bwd_workspace_bytes(d[0], d[2], d[3])) // 4 + 16, dtype=torch.float32, device=dev)
                    for d in dims]
-        arr = lambda vals, ct: (ct * self.n)(*vals)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        cols = [arr([ptr(it[j]) for it in items], C.c_void_p) for j in range(10)]
-        wsp = arr([t.data_ptr() for t in self.ws], C.c_void_p)
-        ks, cis, cos = [arr([d[j] for d in dims], C.c_int) for j in (0, 2, 3)]
-        host = (C.c_ubyte * int(lib().sqdet_fold_batchnorm_bwd_many_table_bytes(self.n)))()
-        b1, b2 = C.c_int(), C.c_int()
-        check(lib().sqdet_fold_batchnorm_bwd_many_prepare(*cols, wsp, ks, cis, cos, self.n, host, C.byref(b1), C.byref(b2)),
-              "sqdet_fold_batchnorm_bwd_many_prepare")
-        self.blocks, self.finish_blocks = int(b1.value), int(b2.value)
-        self.table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(dev)
+        cols = [self._ptrs(it[j] for it in items) for j in range(10)] + [self._ptrs(self.ws)]
+        cols += [self._ints(d[j] for d in dims) for j in (0, 2, 3)]
+        self.blocks, self.finish_blocks = self._fill("sqdet_fold_batchnorm_bwd_many_table_bytes", "sqdet_fold_batchnorm_bwd_many_prepare",
+                                                     cols + [self.n], 2, dev)
 
     def run(self):
         check(lib().sqdet_fold_batchnorm_bwd_many(_dev(self.table, "table"), self.n, self.blocks, self.finish_blocks, self.eps, stream_ptr()),
@@ -580,15 +593,15 @@ def conv2d_bwd_filter(x, dy, k, cin, cout, w_for_decay=None, weight_decay=0.0, x
     return dw, db
 
 
-class WgradPlan:
+class WgradPlan(_ItemTable):
     """The weight gradients of a whole backward pass with ONE slab reduction (sqdet_conv2d_nhwc_bwd_filter_partial per conv
     into a workspace of its own, sqdet_slab_reduce_many at the end) instead of a reduction launch behind every gradient
     kernel.  items: [(key, (n, h, w, cin, cout, k), dw, db or None, w_for_decay or None, weight_decay)] -- dw / db are
     persistent float32 tensors (a trainer's flat gradient views).  Per conv the results are conv2d_bwd_filter's, bitwise."""
 
     def __init__(self, items):
-        self.n = len(items)
-        self.shape, self.ws, self.has_bias, self._keep = {}, {}, {}, items
+        super().__init__(len(items), items)
+        self.shape, self.ws, self.has_bias = {}, {}, {}
         dev = items[0][2].device
         for key, shp, dw, db, wd, decay in items:
             n, h, w, cin, cout, k = [int(v) for v in shp]
@@ -598,19 +611,9 @@ class WgradPlan:
             self.has_bias[key] = db is not None
             self.ws[key] = torch.empty(int(lib().sqdet_conv2d_bwd_filter_workspace_bytes(n, h, w, cin, cout, k)) // 4 + 64,
                                        dtype=torch.float32, device=dev)
-        arr = lambda vals, ct: (ct * self.n)(*vals)
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        wsp = arr([self.ws[it[0]].data_ptr() for it in items], C.c_void_p)
-        dwp = arr([it[2].data_ptr() for it in items], C.c_void_p)
-        dbp = arr([ptr(it[3]) for it in items], C.c_void_p)
-        wdp = arr([ptr(it[4]) for it in items], C.c_void_p)
-        dec = arr([float(it[5]) for it in items], C.c_float)
-        dims = [arr([int(it[1][j]) for it in items], C.c_int) for j in range(6)]
-        host = (C.c_ubyte * int(lib().sqdet_slab_reduce_many_table_bytes(self.n)))()
-        blocks = C.c_int()
-        check(lib().sqdet_slab_reduce_many_prepare(wsp, dwp, dbp, wdp, dec, *dims, self.n, host, C.byref(blocks)), "sqdet_slab_reduce_many_prepare")
-        self.blocks = int(blocks.value)
-        self.table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(dev)
+        cols = [self._ptrs(self.ws[it[0]] for it in items)] + [self._ptrs(it[j] for it in items) for j in (2, 3, 4)]
+        cols += [self._floats(it[5] for it in items)] + [self._ints(it[1][j] for it in items) for j in range(6)]
+        self.blocks, = self._fill("sqdet_slab_reduce_many_table_bytes", "sqdet_slab_reduce_many_prepare", cols + [self.n], 1, dev)
 
     def partial(self, key, x, dy, x_coffset=0, dy_coffset=0):
         """The gradient kernel of conv `key` on (x, dy): its partial slabs only."""

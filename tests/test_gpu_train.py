@@ -853,3 +853,51 @@ def test_pack_many_equals_the_per_kernel_packers():
                 assert torch.equal(plan.bwd[n].data, ops.PackedConvBwd(w, tdt).data), (n, tdt)
             for w in ws.values():
                 w.mul_(-0.5)                       # in place: the plan reads the same storage
+
+
+@pytest.mark.parametrize("with_bn", [False, True], ids=["plain", "bn"])
+@pytest.mark.parametrize("tdt", [torch.float32, torch.float16], ids=["fp32", "fp16"])
+def test_pack_plan_lookup_at_one_workgroup_items(tdt, with_bn):
+    """The block -> item lookup of sqdet_conv_pack_many at its edges: a table of ONE item, and a table whose first five items are
+    the smallest there are (1x1, 16 -> 16: one workgroup each in float32, so five adjacent ranges of length 1; two workgroups
+    in float16, where a fragment group is 512 halves whatever it holds) followed by a many-workgroup 3x3 24 -> 40.  Forward
+    order alone and both orders interleaved, plain and with batch-norm vectors on every second kernel: every packed buffer and
+    folded bias is bitwise pack_conv_weights / PackedConvBwd / fold_batchnorm on that kernel alone, twice.  The forward-only
+    grids are the fixture's (tests/golden/train_tables.json), which pins them to the block ranges checked on the host."""
+    import collections
+    import json
+    ops = _ops()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "train_tables.json")) as f:
+        golden = json.load(f)
+    dname = "f32" if tdt == torch.float32 else "f16"
+    eps = 1e-5
+    rs = np.random.RandomState(31)
+    t = lambda *shape: torch.from_numpy(rs.randn(*shape).astype(np.float32)).to(DEV)
+    for shapes, fixture in (([(1, 16, 16)], "pack one %s %s" % (dname, "bn" if with_bn else "plain")),
+                            ([(1, 16, 16)] * 5 + [(3, 24, 40)], "pack run order 0 %s %s" % (dname, "bn on every second item" if with_bn else "plain"))):
+        ws = collections.OrderedDict(("k%d" % i, t(k, k, ci, co)) for i, (k, ci, co) in enumerate(shapes))
+        bn = {}
+        if with_bn:
+            for i, (name, w) in enumerate(ws.items()):
+                if i % 2 == 0:
+                    co = int(w.shape[3])
+                    bn[name] = (t(co).abs() + 0.5, t(co), t(co), t(co).abs() + 0.5, t(co) if i % 4 == 0 else None)
+        for bwd_names in ((), tuple(ws)):
+            plan = ops.PackPlan(ws, tdt, bwd_names=bwd_names, bn=bn, eps=eps)
+            assert plan.n == len(ws) + len(bwd_names)
+            if not bwd_names:
+                assert [plan.blocks] == golden[fixture]["counts"], fixture
+            for rep in range(2):
+                plan.run()
+                torch.cuda.synchronize()
+                for name, w in ws.items():
+                    wf = w
+                    if name in bn:
+                        gamma, beta, mean, var, cb = bn[name]
+                        wf, bf = ops.fold_batchnorm(w, cb, gamma, beta, mean, var, eps)
+                        assert torch.equal(plan.bias[name], bf), (name, rep)
+                    assert torch.equal(plan.fwd[name].data, ops.pack_conv_weights(wf, tdt).data), (name, rep)
+                    if bwd_names:
+                        assert torch.equal(plan.bwd[name].data, ops.PackedConvBwd(wf, tdt).data), (name, rep)
+                for w in ws.values():
+                    w.mul_(-0.5)                       # in place: the plan reads the same storage

@@ -455,6 +455,29 @@ int sqdet_loss_fwd_bwd_mixed(const void* preds_f16, const float* anchors, const 
                              int classes, float img_w, float img_h, float exp_thresh, float epsilon, float coef_class,
                              float coef_conf_pos, float coef_conf_neg, float coef_bbox, float num_objects,
                              const float* num_objects_dev, int global_batch, sqdet_stream_t stream);
+
+/* The loss with options (OURS): one function for float32 preds (preds_dtype SQDET_F32; dpreds_scaled_f16 and
+ * loss_scale ignored) and float16 preds (SQDET_F16: the mixed form above, both gradients written in one pass), for the host
+ * num_objects and -- num_objects_dev != NULL -- the device one, and for global_batch.
+ *   box_loss     what replaces the squared error on the four deltas: coef_bbox * sum_a m * (1 - X) / num_objects with X the
+ *                IoU / GIoU / DIoU / CIoU of the decoded, clipped box (the corners `ious` is formed on) and the ground truth.
+ *   focal_gamma  g > 0: the class term lab * (1-pc)^g * (-log(pc+eps)) + (1-lab) * pc^g * (-log(1-pc+eps)).
+ * Gradients are the exact chain rule through the corner form, the clip to the image, safe_exp's two branches and the
+ * softmax; CIoU's alpha is a constant in the backward pass.  Tie rule: a coordinate of the prediction receives gradient
+ * through a min / max / clip only where it is strictly the selected argument -- at equality the ground truth's coordinate,
+ * the 0 of the intersection's max(0, .) or the image border takes it; an edge exactly on the border counts as clipped.
+ * `ious` stays the plain IoU, losses3 keeps its three slots, the reductions their fixed order.
+ * {SQDET_BOX_LOSS_DELTA_L2, 0} returns the bits of the three functions above (it calls them).  A box_loss outside 0..4 or a
+ * negative / non-finite focal_gamma: SQDET_EINVAL, nothing launched. */
+enum { SQDET_BOX_LOSS_DELTA_L2 = 0, SQDET_BOX_LOSS_IOU = 1, SQDET_BOX_LOSS_GIOU = 2, SQDET_BOX_LOSS_DIOU = 3, SQDET_BOX_LOSS_CIOU = 4 };
+typedef struct { int box_loss; float focal_gamma; } sqdet_loss_options_t;
+int sqdet_loss_fwd_bwd_opt(const void* preds, int preds_dtype, const float* anchors, const float* input_mask,
+                           const float* box_delta_input, const float* box_input, const float* labels, float* dpreds,
+                           void* dpreds_scaled_f16, float loss_scale, float* ious, float* losses3, float* workspace, int batch,
+                           int gh, int gw, int apg, int classes, float img_w, float img_h, float exp_thresh, float epsilon,
+                           float coef_class, float coef_conf_pos, float coef_conf_neg, float coef_bbox, float num_objects,
+                           const float* num_objects_dev, int global_batch, const sqdet_loss_options_t* opt,
+                           sqdet_stream_t stream);
 /* out[0] = sum(x[0..count)) in a fixed order (deterministic): tf.reduce_sum(self.input_mask), nn_skeleton.py:180. */
 int sqdet_sum_f32(const float* x, size_t count, float* out, sqdet_stream_t stream);
 /* y = max(a + b, 0): tf.nn.relu(shortcut + branch) (nets/resnet50_convDet.py:55) where the producing conv could not take

@@ -53,6 +53,9 @@ def base_model_config(dataset="PASCAL_VOC"):
     cfg.LOSS_COEF_CONF = 1.0
     cfg.LOSS_COEF_CLASS = 1.0
     cfg.LOSS_COEF_BBOX = 10.0
+    # OURS (the reference has neither): what the box term is, and the class term's focal exponent
+    cfg.BBOX_LOSS = "delta_l2"                  # "delta_l2": the reference's squared delta error; "iou", "giou", "diou", "ciou"
+    cfg.FOCAL_GAMMA = 0.0                       # 0.0: the reference's unweighted log loss
     cfg.DECAY_STEPS = 10000
     cfg.LR_DECAY_FACTOR = 0.1
     cfg.LEARNING_RATE = 0.005

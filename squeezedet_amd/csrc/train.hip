@@ -562,6 +562,212 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
   if (lane == 0 && j < 3) losses3[j] = s;
 }
 
+// ------------------------------------------------------------------ loss with options (OURS: not in the reference)
+// loss_kernel with two of its three terms replaceable (sqdet_loss_fwd_bwd_opt); the confidence term, the
+// decode, `ious`, the partial sums and loss_finish_kernel are loss_kernel's, expression for expression.
+//
+// Box term, box_loss 1..4: coef_bbox * sum_a m * (1 - X) / num_objects on the corners loss_kernel already has -- the
+// prediction (ax0, ay0, ax1, ay1) = the clipped decoded box with its '+1' sides, the ground truth (bx0 .. by1) -- so that the
+// term's IoU is the float32 value stored in `ious`.  With pw, ph / gw, gh the sides, Cw, Ch the sides of the enclosing box,
+// rho2 the squared distance of the centres:
+//   iou   X = IoU = inter / (uni + eps)
+//   giou  X = IoU - (Cw*Ch - uni) / (Cw*Ch + eps)
+//   diou  X = IoU - rho2 / (Cw^2 + Ch^2 + eps)
+//   ciou  X = IoU - rho2 / (Cw^2 + Ch^2 + eps) - alpha * v,  v = 4/pi^2 * (atan(gw/gh) - atan(pw/ph))^2,
+//         alpha = v / (1 - IoU + v + eps), a constant in the backward pass; dv/dpw = -8/pi^2 * (..) * ph / (pw^2 + ph^2) (the true one).
+// An anchor with m == 0 takes no part in it (its ground truth is all zeros) and gets zero delta gradients.
+//
+// Backward: dX / d(corner) by the quotient rule on the expressions above, then the chain through  ax0 = xmin, ax1 = xmax + 1,
+// xmin / xmax = clip(cx -+ bw/2, 0, w1), bw = anc_w * safe_exp(d2) (derivative exp(d2), or `slope` on the linear branch d2 > thr),
+// cx = anc_x + d0 * anc_w:   dL/dd0 = anc_w * (g_x0 + g_x1),  dL/dd2 = anc_w * safe_exp'(d2) / 2 * (g_x1 - g_x0); y alike.
+//
+// TIE RULE (one rule for every min, max and clip): a coordinate of the prediction receives gradient through a min / max / clip
+// only where it is STRICTLY the selected argument; at equality the other argument -- the ground truth's coordinate, the 0 of
+// the intersection's max(0, .), the image border -- takes it, and nothing flows.  So
+//   min(ax1, bx1) passes to ax1 iff ax1 < bx1, max(ax0, bx0) to ax0 iff ax0 > bx0 (intersection; and only if its side is > 0),
+//   max(ax1, bx1) passes to ax1 iff ax1 > bx1, min(ax0, bx0) to ax0 iff ax0 < bx0 (enclosing box),
+//   an edge passes the clip iff 0 < cx -+ bw/2 < w1: an edge exactly on the border counts as clipped.
+// tests/loss_options_reference.py restates the same rule in NumPy.
+//
+// Class term, focal_gamma g > 0:  lab * (1-pc)^g * (-log(pc+eps)) + (1-lab) * pc^g * (-log(1-pc+eps)), its derivative in pc
+// exact, the modulating factor's included: d(b^g)/db = g * b^g / b, taken as 0 where b == 0 (there the other factor, the
+// log, is 0 as well).  g == 0 is the reference expression itself, no powf.
+struct LossOpt { int box_loss; float gamma; };
+
+// one class's term f(pc) and df/dpc
+__device__ __forceinline__ void focal_term(float pc, float lab, float eps, float g, float& f, float& df) {
+  const float lp = -logf(pc + eps), lq = -logf(1.0f - pc + eps);
+  if (g == 0.f) {
+    f = lab * lp + (1.0f - lab) * lq;
+    df = -lab / (pc + eps) + (1.0f - lab) / (1.0f - pc + eps);
+    return;
+  }
+  const float q = fmaxf(1.0f - pc, 0.0f);
+  const float qg = powf(q, g), pg = powf(pc, g);
+  const float dqg = q > 0.f ? g * qg / q : 0.f, dpg = pc > 0.f ? g * pg / pc : 0.f;
+  f = lab * (qg * lp) + (1.0f - lab) * (pg * lq);
+  df = lab * (-dqg * lp - qg / (pc + eps)) + (1.0f - lab) * (dpg * lq + pg / (1.0f - pc + eps));
+}
+
+template <typename PT>
+__global__ __launch_bounds__(256) void loss_opt_kernel(LossArgs a, LossOpt o) {
+  const float nobj = a.num_obj_dev ? a.num_obj_dev[0] : a.num_obj;
+  __shared__ float red[3][256];
+  const int A = a.cells * a.K;
+  const int ch = a.K * (a.C + 5);
+  const long total = (long)a.B * A;
+  float l_class = 0.f, l_conf = 0.f, l_bbox = 0.f;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(idx / A);
+    const int an = (int)(idx - (long)b * A);
+    const int cell = an / a.K, k = an - cell * a.K;
+    const PT* p = reinterpret_cast<const PT*>(a.preds) + ((size_t)b * a.cells + cell) * ch;
+    float* dp = a.dpreds + ((size_t)b * a.cells + cell) * ch;
+    f16* gp = a.g16 ? a.g16 + ((size_t)b * a.cells + cell) * ch : nullptr;
+    auto put = [&](int off, float v) {
+      dp[off] = v;
+      if (sizeof(PT) == 2) gp[off] = scaled_to<f16>(v, a.gscale);
+    };
+    const float m = a.mask[idx];
+    // class probabilities (softmax) and the class term
+    const PT* lg = p + k * a.C;
+    float mx = (float)lg[0];
+    for (int c = 1; c < a.C; ++c) mx = fmaxf(mx, (float)lg[c]);
+    float sum = expf((float)lg[0] - mx);
+    for (int c = 1; c < a.C; ++c) sum = sum + expf((float)lg[c] - mx);
+    const float inv = 1.0f / sum;
+    float gdotp = 0.f;
+    if (o.gamma != 0.f && m == 0.f) {
+      // an unlabelled anchor's term and gradient are m * (finite) = 0: no powf for it (nearly every anchor: the focal launch
+      // took 46 us against 25 us before this branch, batch 20)
+      for (int c = 0; c < a.C; ++c) put(k * a.C + c, 0.f);
+    } else {
+      for (int c = 0; c < a.C; ++c) {
+        const float pc = expf((float)lg[c] - mx) * inv;
+        float f, df;
+        focal_term(pc, a.labels[idx * a.C + c], a.eps, o.gamma, f, df);
+        l_class += f * m * a.coef_class;
+        const float gc = m * a.coef_class / nobj * df;
+        gdotp += gc * pc;
+      }
+      for (int c = 0; c < a.C; ++c) {
+        const float pc = expf((float)lg[c] - mx) * inv;
+        float f, df;
+        focal_term(pc, a.labels[idx * a.C + c], a.eps, o.gamma, f, df);
+        const float gc = m * a.coef_class / nobj * df;
+        put(k * a.C + c, pc * (gc - gdotp));
+      }
+    }
+    // decode -> IoU with the ground-truth box: loss_kernel's expressions
+    const float zc = (float)p[a.K * a.C + k];
+    const float conf = 1.0f / (1.0f + expf(-zc));
+    const PT* dlp = p + a.K * (a.C + 1) + 4 * k;
+    const float dl[4] = {(float)dlp[0], (float)dlp[1], (float)dlp[2], (float)dlp[3]};
+    const f32x4 anc = *reinterpret_cast<const f32x4*>(a.anchors + (size_t)an * 4);
+    const float cx = anc[0] + dl[0] * anc[2];
+    const float cy = anc[1] + dl[1] * anc[3];
+    const float ew = dl[2] > a.thr ? a.slope * ((dl[2] - a.thr) + 1.0f) : expf(dl[2]);
+    const float eh = dl[3] > a.thr ? a.slope * ((dl[3] - a.thr) + 1.0f) : expf(dl[3]);
+    const float bw = anc[2] * ew, bh = anc[3] * eh;
+    const float rx0 = cx - bw / 2.0f, ry0 = cy - bh / 2.0f, rx1 = cx + bw / 2.0f, ry1 = cy + bh / 2.0f;
+    float xmin = fminf(fmaxf(0.0f, rx0), a.w1), ymin = fminf(fmaxf(0.0f, ry0), a.h1);
+    float xmax = fmaxf(fminf(a.w1, rx1), 0.0f), ymax = fmaxf(fminf(a.h1, ry1), 0.0f);
+    const float w2 = xmax - xmin + 1.0f, h2 = ymax - ymin + 1.0f;
+    const float dcx = xmin + 0.5f * w2, dcy = ymin + 0.5f * h2;
+    const float ax0 = dcx - w2 / 2.0f, ay0 = dcy - h2 / 2.0f, ax1 = dcx + w2 / 2.0f, ay1 = dcy + h2 / 2.0f;
+    const f32x4 gb = *reinterpret_cast<const f32x4*>(a.box_in + idx * 4);
+    const float bx0 = gb[0] - gb[2] / 2.0f, by0 = gb[1] - gb[3] / 2.0f, bx1 = gb[0] + gb[2] / 2.0f, by1 = gb[1] + gb[3] / 2.0f;
+    const float iwr = fminf(ax1, bx1) - fmaxf(ax0, bx0), ihr = fminf(ay1, by1) - fmaxf(ay0, by0);
+    const float iw = fmaxf(0.0f, iwr);
+    const float ih = fmaxf(0.0f, ihr);
+    const float inter = iw * ih;
+    const float uni = (ax1 - ax0) * (ay1 - ay0) + (bx1 - bx0) * (by1 - by0) - inter;
+    const float iou1 = inter / (uni + a.eps);
+    const float iou = iou1 * m;
+    a.ious[idx] = iou;
+    // confidence loss: loss_kernel's
+    const float wgt = m * a.coef_pos / nobj + (1.0f - m) * a.coef_neg / ((float)A - nobj);
+    const float dc = iou - conf;
+    l_conf += dc * dc * wgt / (float)a.Bmean;
+    put(a.K * a.C + k, 2.0f * (conf - iou) * wgt / (float)a.Bmean * conf * (1.0f - conf));
+    // box term
+    const int doff = a.K * (a.C + 1) + 4 * k;
+    if (o.box_loss == 0) {
+      for (int d = 0; d < 4; ++d) {
+        const float df = m * (dl[d] - a.delta_in[idx * 4 + d]);
+        l_bbox += a.coef_bbox * (df * df);          // (divided by num_objects once, below, as the class term is)
+        put(doff + d, 2.0f * a.coef_bbox * m * df / nobj);
+      }
+    } else if (m == 0.f) {
+      for (int d = 0; d < 4; ++d) put(doff + d, 0.f);
+    } else {
+      // corner order x0, y0, x1, y1; every flag is the tie rule of the header comment
+      const float pw = ax1 - ax0, ph = ay1 - ay0, gw = bx1 - bx0, gh = by1 - by0;
+      const float fx = iwr > 0.f ? 1.f : 0.f, fy = ihr > 0.f ? 1.f : 0.f;
+      const float di[4] = {ax0 > bx0 ? -fx * ih : 0.f, ay0 > by0 ? -fy * iw : 0.f, ax1 < bx1 ? fx * ih : 0.f, ay1 < by1 ? fy * iw : 0.f};
+      const float da[4] = {-ph, -pw, ph, pw};
+      const float ue = uni + a.eps;
+      float X = iou1, du[4], dX[4];
+      for (int j = 0; j < 4; ++j) {
+        du[j] = da[j] - di[j];
+        dX[j] = (di[j] - iou1 * du[j]) / ue;
+      }
+      if (o.box_loss >= 2) {
+        const float Cw = fmaxf(ax1, bx1) - fminf(ax0, bx0), Ch = fmaxf(ay1, by1) - fminf(ay0, by0);
+        const float sx0 = ax0 < bx0 ? -1.f : 0.f, sy0 = ay0 < by0 ? -1.f : 0.f, sx1 = ax1 > bx1 ? 1.f : 0.f, sy1 = ay1 > by1 ? 1.f : 0.f;
+        if (o.box_loss == 2) {
+          const float Ca = Cw * Ch, ce = Ca + a.eps;
+          const float T = (Ca - uni) / ce;
+          const float dC[4] = {sx0 * Ch, sy0 * Cw, sx1 * Ch, sy1 * Cw};
+          X = X - T;
+          for (int j = 0; j < 4; ++j) dX[j] = dX[j] - ((dC[j] - du[j]) - T * dC[j]) / ce;
+        } else {
+          const float c2e = (Cw * Cw + Ch * Ch) + a.eps;
+          const float ex = (ax0 + ax1) * 0.5f - (bx0 + bx1) * 0.5f, ey = (ay0 + ay1) * 0.5f - (by0 + by1) * 0.5f;
+          const float D = (ex * ex + ey * ey) / c2e;
+          const float dr[4] = {ex, ey, ex, ey};
+          const float dc2[4] = {2.0f * Cw * sx0, 2.0f * Ch * sy0, 2.0f * Cw * sx1, 2.0f * Ch * sy1};
+          X = X - D;
+          for (int j = 0; j < 4; ++j) dX[j] = dX[j] - (dr[j] - D * dc2[j]) / c2e;
+          if (o.box_loss == 4) {
+            const float k4 = 0.40528473456935109f;       // 4 / pi^2
+            const float dat = atanf(gw / gh) - atanf(pw / ph);
+            const float v = k4 * dat * dat;
+            const float alpha = v / (((1.0f - iou1) + v) + a.eps);
+            const float s2 = pw * pw + ph * ph;
+            const float vw = -2.0f * k4 * dat * ph / s2, vh = 2.0f * k4 * dat * pw / s2;      // dv/dpw, dv/dph
+            const float dv[4] = {-vw, -vh, vw, vh};
+            X = X - alpha * v;
+            for (int j = 0; j < 4; ++j) dX[j] = dX[j] - alpha * dv[j];
+          }
+        }
+      }
+      const float sc = a.coef_bbox * m / nobj;
+      l_bbox += a.coef_bbox * m * (1.0f - X);
+      const float gx0 = rx0 > 0.f && rx0 < a.w1 ? -sc * dX[0] : 0.f, gy0 = ry0 > 0.f && ry0 < a.h1 ? -sc * dX[1] : 0.f;
+      const float gx1 = rx1 > 0.f && rx1 < a.w1 ? -sc * dX[2] : 0.f, gy1 = ry1 > 0.f && ry1 < a.h1 ? -sc * dX[3] : 0.f;
+      const float dew = dl[2] > a.thr ? a.slope : ew, deh = dl[3] > a.thr ? a.slope : eh;
+      put(doff + 0, anc[2] * (gx0 + gx1));
+      put(doff + 1, anc[3] * (gy0 + gy1));
+      put(doff + 2, 0.5f * anc[2] * dew * (gx1 - gx0));
+      put(doff + 3, 0.5f * anc[3] * deh * (gy1 - gy0));
+    }
+  }
+  l_class = l_class / nobj;
+  l_bbox = l_bbox / nobj;
+  red[0][threadIdx.x] = l_class; red[1][threadIdx.x] = l_conf; red[2][threadIdx.x] = l_bbox;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + off];
+      red[1][threadIdx.x] += red[1][threadIdx.x + off];
+      red[2][threadIdx.x] += red[2][threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) a.partial[blockIdx.x * 4 + threadIdx.x] = threadIdx.x < 3 ? red[threadIdx.x][0] : 0.f;
+}
+
 // ------------------------------------------------------------------ optimizer
 // Segment table: variable v occupies [seg[v].off, +count) of the flat parameter / gradient / momentum
 // buffers.  Pass 1 adds the weight-decay gradient and writes per-block partial sums of squares; pass 2
@@ -990,7 +1196,7 @@ static int loss_fwd_bwd_impl(const void* preds, const float* anchors, const floa
                              int apg, int classes, float img_w, float img_h, float exp_thresh, float epsilon,
                              float coef_class, float coef_conf_pos, float coef_conf_neg, float coef_bbox,
                              float num_objects, const float* num_objects_dev, int global_batch, sqdet_stream_t stream,
-                             void* g16 = nullptr, float gscale = 1.f);
+                             void* g16 = nullptr, float gscale = 1.f, const LossOpt* opt = nullptr);
 
 extern "C" int sqdet_loss_fwd_bwd_mixed(const void* preds_f16, const float* anchors, const float* input_mask,
                                         const float* box_delta_input, const float* box_input, const float* labels,
@@ -1035,7 +1241,7 @@ static int loss_fwd_bwd_impl(const void* preds, const float* anchors, const floa
                                   int apg, int classes, float img_w, float img_h, float exp_thresh, float epsilon,
                                   float coef_class, float coef_conf_pos, float coef_conf_neg, float coef_bbox,
                                   float num_objects, const float* num_objects_dev, int global_batch, sqdet_stream_t stream,
-                                  void* g16, float gscale) {
+                                  void* g16, float gscale, const LossOpt* opt) {
   SQDET_REQUIRE(preds && anchors && input_mask && box_delta_input && box_input && labels && dpreds && ious && losses3 &&
                     workspace, "loss_fwd_bwd: null pointer");
   SQDET_REQUIRE(batch > 0 && gh > 0 && gw > 0 && apg > 0 && classes > 0 && num_objects > 0.f, "loss_fwd_bwd: bad arguments");
@@ -1053,12 +1259,49 @@ static int loss_fwd_bwd_impl(const void* preds, const float* anchors, const floa
   int blocks = (int)((total + 255) / 256);
   if (blocks > 512) blocks = 512;
   hipStream_t st = as_stream(stream);
-  if (g16) hipLaunchKernelGGL(loss_kernel<f16>, dim3(blocks), dim3(256), 0, st, a);
+  if (opt && g16) hipLaunchKernelGGL(loss_opt_kernel<f16>, dim3(blocks), dim3(256), 0, st, a, *opt);
+  else if (opt) hipLaunchKernelGGL(loss_opt_kernel<float>, dim3(blocks), dim3(256), 0, st, a, *opt);
+  else if (g16) hipLaunchKernelGGL(loss_kernel<f16>, dim3(blocks), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(loss_kernel<float>, dim3(blocks), dim3(256), 0, st, a);
   SQDET_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, workspace, losses3, blocks);
   SQDET_CHECK_HIP(hipGetLastError());
   return SQDET_OK;
+}
+
+// The loss with options: the defaults ARE the three entry points above; anything else is loss_opt_kernel.
+extern "C" int sqdet_loss_fwd_bwd_opt(const void* preds, int preds_dtype, const float* anchors, const float* input_mask,
+                                      const float* box_delta_input, const float* box_input, const float* labels,
+                                      float* dpreds, void* dpreds_scaled_f16, float loss_scale, float* ious, float* losses3,
+                                      float* workspace, int batch, int gh, int gw, int apg, int classes, float img_w,
+                                      float img_h, float exp_thresh, float epsilon, float coef_class, float coef_conf_pos,
+                                      float coef_conf_neg, float coef_bbox, float num_objects, const float* num_objects_dev,
+                                      int global_batch, const sqdet_loss_options_t* opt, sqdet_stream_t stream) {
+  SQDET_REQUIRE(opt, "loss_fwd_bwd_opt: null options");
+  SQDET_REQUIRE(opt->box_loss >= SQDET_BOX_LOSS_DELTA_L2 && opt->box_loss <= SQDET_BOX_LOSS_CIOU, "loss_fwd_bwd_opt: box_loss %d is not one of 0..4", opt->box_loss);
+  SQDET_REQUIRE(opt->focal_gamma >= 0.f && opt->focal_gamma < INFINITY, "loss_fwd_bwd_opt: focal_gamma must be finite and >= 0");
+  SQDET_REQUIRE(preds_dtype == SQDET_F32 || preds_dtype == SQDET_F16, "loss_fwd_bwd_opt: bad dtype");
+  const bool mixed = preds_dtype == SQDET_F16;
+  SQDET_REQUIRE(!mixed || (dpreds_scaled_f16 && loss_scale > 0.f), "loss_fwd_bwd_opt: float16 preds need dpreds_scaled_f16 and a loss scale");
+  if (opt->box_loss == SQDET_BOX_LOSS_DELTA_L2 && opt->focal_gamma == 0.f) {
+    if (mixed)
+      return sqdet_loss_fwd_bwd_mixed(preds, anchors, input_mask, box_delta_input, box_input, labels, dpreds, dpreds_scaled_f16,
+                                      loss_scale, ious, losses3, workspace, batch, gh, gw, apg, classes, img_w, img_h, exp_thresh,
+                                      epsilon, coef_class, coef_conf_pos, coef_conf_neg, coef_bbox, num_objects, num_objects_dev,
+                                      global_batch, stream);
+    if (num_objects_dev)
+      return sqdet_loss_fwd_bwd_dev((const float*)preds, anchors, input_mask, box_delta_input, box_input, labels, dpreds, ious,
+                                    losses3, workspace, batch, gh, gw, apg, classes, img_w, img_h, exp_thresh, epsilon, coef_class,
+                                    coef_conf_pos, coef_conf_neg, coef_bbox, num_objects_dev, global_batch, stream);
+    return sqdet_loss_fwd_bwd((const float*)preds, anchors, input_mask, box_delta_input, box_input, labels, dpreds, ious, losses3,
+                              workspace, batch, gh, gw, apg, classes, img_w, img_h, exp_thresh, epsilon, coef_class, coef_conf_pos,
+                              coef_conf_neg, coef_bbox, num_objects, global_batch, stream);
+  }
+  const LossOpt o = {opt->box_loss, opt->focal_gamma};
+  return loss_fwd_bwd_impl(preds, anchors, input_mask, box_delta_input, box_input, labels, dpreds, ious, losses3, workspace,
+                           batch, gh, gw, apg, classes, img_w, img_h, exp_thresh, epsilon, coef_class, coef_conf_pos,
+                           coef_conf_neg, coef_bbox, num_objects_dev ? 1.0f : num_objects, num_objects_dev, global_batch, stream,
+                           mixed ? dpreds_scaled_f16 : nullptr, mixed ? loss_scale : 1.f, &o);
 }
 
 extern "C" size_t sqdet_loss_workspace_bytes(void) { return (4 * 512 + 4) * sizeof(float); }

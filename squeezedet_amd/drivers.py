@@ -117,3 +117,37 @@ def check_dataset_args(ap, a):
     assert a.dataset in DATASETS, "Currently only supports KITTI dataset (and PASCAL_VOC)"
     if a.dataset == "PASCAL_VOC" and a.net != "squeezeDet":
         ap.error("--dataset PASCAL_VOC: only --net squeezeDet has a VOC config")
+
+
+BOX_LOSSES = ("delta_l2", "iou", "giou", "diou", "ciou")       # sqdet_loss_options_t.box_loss by index; the one list (ops imports it)
+
+
+def add_loss_args(ap):
+    """--bbox_loss, --focal_gamma, --bbox_loss_coef (train.py, tools/bench_train.py).  A flag that is not given leaves no
+    attribute behind: loss_policy supplies the defaults."""
+    import argparse
+    ap.add_argument("--bbox_loss", default=argparse.SUPPRESS, choices=BOX_LOSSES,
+                    help="the box term: delta_l2 (default), the reference's squared error on the four deltas; iou, giou, diou, ciou: "
+                         "1 - that measure of the decoded box and the ground truth (DESIGN.md section 3.16)")
+    ap.add_argument("--focal_gamma", type=float, default=argparse.SUPPRESS, metavar="G",
+                    help="G > 0: the class term is weighted by (1 - p)^G on the labelled class and p^G on the others (default 0: the reference's)")
+    ap.add_argument("--bbox_loss_coef", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="overrides the config's LOSS_COEF_BBOX (default: the config's)")
+
+
+def check_loss_args(ap, a):
+    g, x = float(getattr(a, "focal_gamma", 0.0)), float(getattr(a, "bbox_loss_coef", 0.0))
+    if not (0.0 <= g < float("inf")):
+        ap.error("--focal_gamma G needs a finite G >= 0")
+    if not (0.0 <= x < float("inf")):
+        ap.error("--bbox_loss_coef X needs a finite X >= 0")
+
+
+def loss_policy(a, mc):
+    """(the loss policy of --bbox_loss / --focal_gamma / --bbox_loss_coef as a checkpoint records it, the policy of a run without
+    the flags -- what a checkpoint without the record was trained with); sets mc.BBOX_LOSS, mc.FOCAL_GAMMA and mc.LOSS_COEF_BBOX."""
+    off = dict(bbox_loss="delta_l2", focal_gamma=0.0, bbox_loss_coef=float(mc.LOSS_COEF_BBOX))
+    policy = dict(bbox_loss=str(getattr(a, "bbox_loss", off["bbox_loss"])), focal_gamma=float(getattr(a, "focal_gamma", off["focal_gamma"])),
+                  bbox_loss_coef=float(getattr(a, "bbox_loss_coef", off["bbox_loss_coef"])))
+    mc.BBOX_LOSS, mc.FOCAL_GAMMA, mc.LOSS_COEF_BBOX = policy["bbox_loss"], policy["focal_gamma"], policy["bbox_loss_coef"]
+    return policy, off

@@ -757,6 +757,45 @@ def dropout_mask_into(mask, keep_prob, seed):
     return mask
 
 
+from .drivers import BOX_LOSSES      # sqdet_loss_options_t.box_loss, by index (drivers imports no torch: the flags use the same list)
+
+
+class _LossOptions(C.Structure):
+    _fields_ = [("box_loss", C.c_int), ("focal_gamma", C.c_float)]
+
+
+def loss_options(mc):
+    """(box-loss name, focal gamma) of a config; a config without the two fields (the reference's) means the reference's loss.
+    An unknown name is refused here; a negative gamma by the library."""
+    def field(key, default):          # (mc may be any attribute dict: one whose __getattr__ raises KeyError included)
+        try:
+            return mc[key] if isinstance(mc, dict) else getattr(mc, key)
+        except (KeyError, AttributeError):
+            return default
+    name, gamma = str(field("BBOX_LOSS", "delta_l2")), float(field("FOCAL_GAMMA", 0.0))
+    if name not in BOX_LOSSES:
+        raise _lib.SqdetError("mc.BBOX_LOSS %r is not one of %s" % (name, ", ".join(BOX_LOSSES)))
+    return name, gamma
+
+
+def _loss_fwd_bwd_opt(opt, preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, g16, loss_scale,
+                      ious, losses, ws, global_batch):
+    """sqdet_loss_fwd_bwd_opt: the one entry for float32 / float16 preds and host / device num_objects."""
+    n, gh, gw, ch = [int(v) for v in preds.shape]
+    on_dev = isinstance(num_objects, torch.Tensor)
+    o = _LossOptions(BOX_LOSSES.index(opt[0]), opt[1])
+    check(lib().sqdet_loss_fwd_bwd_opt(_dev(preds, "preds", torch.float32 if g16 is None else torch.float16), dtype_code(preds.dtype), _dev(anchors_f32, "anchors", torch.float32),
+                                       _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
+                                       _dev(box_input, "box", torch.float32), _dev(labels, "labels", torch.float32),
+                                       _dev(dpreds, "dpreds", torch.float32), None if g16 is None else _dev(g16, "g16", torch.float16),
+                                       float(loss_scale), _dev(ious, "ious"), _dev(losses, "losses"), _dev(ws, "ws"), n, gh, gw,
+                                       int(mc.ANCHOR_PER_GRID), int(mc.CLASSES), float(mc.IMAGE_WIDTH), float(mc.IMAGE_HEIGHT),
+                                       float(mc.EXP_THRESH), float(mc.EPSILON), float(mc.LOSS_COEF_CLASS), float(mc.LOSS_COEF_CONF_POS),
+                                       float(mc.LOSS_COEF_CONF_NEG), float(mc.LOSS_COEF_BBOX), 1.0 if on_dev else float(num_objects),
+                                       _dev(num_objects, "num_objects", torch.float32) if on_dev else None, int(global_batch),
+                                       C.cast(C.pointer(o), C.c_void_p), stream_ptr()), "sqdet_loss_fwd_bwd_opt")
+
+
 def loss_fwd_bwd_mixed(preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, loss_scale, global_batch=0):
     """loss_fwd_bwd on FLOAT16 preds (sqdet_loss_fwd_bwd_mixed): also returns the loss-scaled float16 gradient the float16
     backward starts from -- bitwise convert_scale(dpreds, float16, loss_scale) -- written in the same pass.
@@ -769,6 +808,11 @@ def loss_fwd_bwd_mixed(preds, anchors_f32, input_mask, box_delta_input, box_inpu
     ious = torch.empty((n, A), dtype=torch.float32, device=dev)
     losses = torch.empty((3,), dtype=torch.float32, device=dev)
     ws = torch.empty(int(lib().sqdet_loss_workspace_bytes()) // 4 + 16, dtype=torch.float32, device=dev)
+    opt = loss_options(mc)
+    if opt != ("delta_l2", 0.0):      # (mc.BBOX_LOSS / mc.FOCAL_GAMMA: DESIGN.md 3.16; the defaults take the call below, as ever)
+        _loss_fwd_bwd_opt(opt, preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, g16, loss_scale,
+                          ious, losses, ws, global_batch)
+        return g16, dpreds, ious, losses
     on_dev = isinstance(num_objects, torch.Tensor)
     check(lib().sqdet_loss_fwd_bwd_mixed(_dev(preds, "preds", torch.float16), _dev(anchors_f32, "anchors", torch.float32),
                                          _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
@@ -795,6 +839,11 @@ def loss_fwd_bwd(preds, anchors_f32, input_mask, box_delta_input, box_input, lab
     ious = torch.empty((n, A), dtype=torch.float32, device=dev)
     losses = torch.empty((3,), dtype=torch.float32, device=dev)
     ws = torch.empty(int(lib().sqdet_loss_workspace_bytes()) // 4 + 16, dtype=torch.float32, device=dev)
+    opt = loss_options(mc)
+    if opt != ("delta_l2", 0.0):
+        _loss_fwd_bwd_opt(opt, preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, None, 1.0,
+                          ious, losses, ws, global_batch)
+        return dpreds, ious, losses
     if isinstance(num_objects, torch.Tensor):
         check(lib().sqdet_loss_fwd_bwd_dev(_dev(preds, "preds", torch.float32), _dev(anchors_f32, "anchors", torch.float32),
                                            _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),

@@ -35,7 +35,7 @@ def synthetic_ground_truth(mc, batch, seed, max_objects=8):
 from squeezedet_amd.synthetic import KITTI_SIZES, synthetic_dataset  # noqa: E402,F401  (lives in the package: train.py --synthetic reads it too)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -54,11 +54,31 @@ def main():
                          "--zoom_out 2 --color_jitter)")
     ap.add_argument("--mosaic", type=float, default=0.0, metavar="P",
                     help="with --augment: a batch image is a mosaic of four images with probability P (train.py --mosaic P)")
-    args = ap.parse_args()
+    from squeezedet_amd import drivers
+    drivers.add_loss_args(ap)             # --bbox_loss, --focal_gamma, --bbox_loss_coef as train.py takes them
+    args = ap.parse_args(argv)
+    drivers.check_loss_args(ap, args)
     if not 0.0 <= args.mosaic <= 1.0 or (args.mosaic > 0.0 and not args.augment):
         ap.error("--mosaic P needs 0 <= P <= 1 and --augment")
     if args.batch <= 0:
         args.batch = {"squeezeDet": 20, "resnet50": 8, "vgg16": 5}[args.arch]
+    return args
+
+
+def make_config(args):
+    """(mc of --arch with the batch size and the loss flags applied, the loss policy as train.py records it)."""
+    import squeezedet_amd as S
+    from squeezedet_amd import drivers
+    mc = {"squeezeDet": S.kitti_squeezeDet_config, "resnet50": S.kitti_res50_config, "vgg16": S.kitti_vgg16_config}[args.arch]()
+    mc.LOAD_PRETRAINED_MODEL = False
+    mc.IS_TRAINING = True
+    mc.BATCH_SIZE = args.batch
+    loss_policy, _ = drivers.loss_policy(args, mc)
+    return mc, loss_policy
+
+
+def main():
+    args = parse_args()
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -69,10 +89,7 @@ def main():
     import squeezedet_amd as S
     from squeezedet_amd import nets, synthetic
     from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer, VGG16ConvDetTrainer
-    mc = {"squeezeDet": S.kitti_squeezeDet_config, "resnet50": S.kitti_res50_config, "vgg16": S.kitti_vgg16_config}[args.arch]()
-    mc.LOAD_PRETRAINED_MODEL = False
-    mc.IS_TRAINING = True
-    mc.BATCH_SIZE = args.batch
+    mc, loss_policy = make_config(args)
     cls, trainer = {"squeezeDet": (nets.SqueezeDet, SqueezeDetTrainer), "resnet50": (nets.ResNet50ConvDet, ResNet50ConvDetTrainer),
                     "vgg16": (nets.VGG16ConvDet, VGG16ConvDetTrainer)}[args.arch]
     model = cls(mc, gpu_id=str(local_rank), dtype=torch.float32 if args.dtype == "f32" else torch.float16)
@@ -126,7 +143,7 @@ def main():
                                    + (" + mosaic %g" % args.mosaic if args.mosaic > 0.0 else "")) if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
-                          "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
+                          "loss": loss_policy, "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
                           "losses": {k: float(out[k]) for k in ("class_loss", "conf_loss", "bbox_loss")}}))
     if world > 1:
         dist.destroy_process_group()

@@ -7,6 +7,7 @@ with on-device summaries.
     python train.py --synthetic 40 --train_dir /tmp/run --max_steps 100          # seeded synthetic data, no dataset needed
     python train.py ... --resume                                                  # continue from the newest checkpoint
     python train.py ... --anchor_shapes anchors.json --anchor_report             # shapes from tools/fit_anchors.py; coverage report
+    python train.py ... --bbox_loss giou --focal_gamma 2                          # a GIoU box term and a focal class term
 
 Per step as the reference (train.py:266-330): a summary step (step % summary_step == 0) runs the eager trainer step with the
 activations kept and hands it to squeezedet_amd.summary.TrainSummary (-> <train_dir>/summaries.jsonl, in place of TF event
@@ -26,7 +27,10 @@ recorded in every checkpoint: --resume refuses other shapes and, without the fla
 [--zoom_out MAX] and --color_jitter switch on BatchReader's crop-window / zoom-out and colour augmentation (squeezedet_amd.imdb);
 the policy is recorded in every checkpoint and --resume under another one is refused.  --mosaic P makes a batch image, with
 probability P, a mosaic of four training images (one sqdet_augment_bgr_mosaic launch per batch); P is recorded under its own key,
-`mosaic`, and --resume under another P is refused (a checkpoint without the key was trained with 0).  --anchor_report writes
+`mosaic`, and --resume under another P is refused (a checkpoint without the key was trained with 0).  --bbox_loss
+{delta_l2,iou,giou,diou,ciou}, --focal_gamma G and --bbox_loss_coef X choose the box term, the class term's focal exponent and
+mc.LOSS_COEF_BBOX (the defaults are the reference's loss); the three are recorded under the key `loss`, and
+--resume under another loss policy is refused (a checkpoint without the key was trained with the defaults).  --anchor_report writes
 <train_dir>/anchor_coverage.json (squeezedet_amd.anchors.dataset_coverage of the training set) once, before the first step.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
@@ -78,8 +82,10 @@ def parse_args(argv=None):
     ap.add_argument("--mosaic", type=float, default=argparse.SUPPRESS, metavar="P",
                     help="with probability P a batch image is a mosaic: four training images, each cropped into its own pane of the "
                          "network input (default 0: never)")
+    drivers.add_loss_args(ap)
     a = ap.parse_args(argv)
     drivers.check_dataset_args(ap, a)
+    drivers.check_loss_args(ap, a)
     if not 0.0 <= getattr(a, "mosaic", 0.0) <= 1.0:
         ap.error("--mosaic P needs 0 <= P <= 1")
     if a.resume and a.overwrite:
@@ -101,6 +107,18 @@ def augment_policy(a, mc=None):
         mc.AUG_GEOMETRY = "ssd" if policy["geometry"] == "ssd" else "drift"
         mc.AUG_ZOOM_OUT_MAX, mc.AUG_COLOR = policy["zoom_out"], policy["color_jitter"]
     return policy
+
+
+def check_resume_record(saved, extra, loss_off):
+    """--resume: what the checkpoint records (`saved`) against what this run asks for (`extra`); SystemExit on the first key that
+    differs.  A checkpoint from before a key existed was trained with that key's defaults (`loss_off`: drivers.loss_policy's)."""
+    saved = dict(saved)
+    saved.setdefault("augment", AUGMENT_OFF)
+    saved.setdefault("mosaic", 0.0)
+    saved.setdefault("loss", loss_off)
+    for key, now in extra.items():
+        if saved.get(key) != now:
+            raise SystemExit("--resume: the checkpoint was trained with %s %r, this run asks for %r" % (key, saved.get(key), now))
 
 
 def make_trainer(a, mc, local_rank=0):
@@ -217,6 +235,7 @@ class Run:
         mc.AUG_MOSAIC_PROB = mosaic = float(getattr(a, "mosaic", 0.0))
         if mosaic > 0.0 and not mc.DATA_AUGMENTATION:
             raise SystemExit("--mosaic needs a config with DATA_AUGMENTATION on")
+        loss, loss_off = drivers.loss_policy(a, mc)         # (before the model is built: a padded head's config is a copy of mc)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)
@@ -224,15 +243,10 @@ class Run:
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
         self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE),
-                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy, mosaic=mosaic)
+                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy, mosaic=mosaic, loss=loss)
         self.first = 0
         if resume_step is not None:
-            saved = checkpoint.read_extra(a.train_dir, resume_step)
-            saved.setdefault("augment", AUGMENT_OFF)
-            saved.setdefault("mosaic", 0.0)
-            for key, now in self.extra.items():
-                if saved.get(key) != now:
-                    raise SystemExit("--resume: the checkpoint was trained with %s %r, this run asks for %r" % (key, saved.get(key), now))
+            check_resume_record(checkpoint.read_extra(a.train_dir, resume_step), self.extra, loss_off)
             checkpoint.load(a.train_dir, resume_step, self.model, self.tr, self.reader)
             self.first = resume_step + 1
         self.anchors = torch.from_numpy(np.asarray(mc.ANCHOR_BOX, np.float64)).to(dev)

@@ -572,6 +572,10 @@ int sqdet_net_rider_capacity(const sqdet_net_t* net);
 int sqdet_net_num_layers(const sqdet_net_t* net);
 int sqdet_net_layer_info(const sqdet_net_t* net, int index, char* name, size_t name_cap, double* flops,
                          double* bytes);
+/* 1 when the launcher of layer `index` takes it at the plan's batch and map size under the current options, else 0 (host
+ * only).  Every layer of a created plan is launchable: the fused launches address tensors with 32-bit offsets and decline
+ * one of 2^31 bytes or more, and plan creation asks the launchers' own predicates, so such a layer is planned unfused. */
+int sqdet_net_layer_launchable(const sqdet_net_t* net, int index);
 /* Same as sqdet_net_forward but brackets every launch with HIP events on
  * `stream` and, after synchronising, writes per-launch milliseconds to
  * host_ms[num_layers]. */

@@ -113,6 +113,7 @@ SIGNATURES = {
     "sqdet_net_forward": (ci, [vp, vp, vp, vp]),
     "sqdet_net_num_layers": (ci, [vp]),
     "sqdet_net_layer_info": (ci, [vp, ci, C.c_char_p, sz, C.POINTER(cd), C.POINTER(cd)]),
+    "sqdet_net_layer_launchable": (ci, [vp, ci]),
     "sqdet_net_forward_timed": (ci, [vp, vp, vp, C.POINTER(cf), vp]),
     "sqdet_net_set_probe": (ci, [vp, ci, ci]),
     "sqdet_net_read_probe": (ci, [vp, C.POINTER(cf), ci, C.POINTER(ci)]),

@@ -880,6 +880,14 @@ bool fire_chain_eligible(int s, int e1, int e3, int s2, int dtype) {
   return chain_lds_bytes(g.nch, g.nsq, chain_ring(g.nch, g.nsq), e1 + e3 + s2) <= 160 * 1024;
 }
 
+// 32-bit buffer offsets into the squeeze tensors and the concat tensor: the concat extent, the largest of the three, bounds them
+// all -- also where only sq_out is written (the kernels share their index arithmetic)
+static bool chain_sizes_ok(int n, int h, int w, int e1, int e3) { return (long)n * h * w * (e1 + e3) * 2 < (1L << 31); }
+
+bool fire_chain_eligible_at(int n, int h, int w, int s, int e1, int e3, int s2, int dtype) {
+  return fire_chain_eligible(s, e1, e3, s2, dtype) && chain_sizes_ok(n, h, w, e1, e3);
+}
+
 }  // namespace sqdet
 
 using namespace sqdet;
@@ -930,7 +938,8 @@ int sqdet::fire_chain_launch_ride(const void* sq_in, const void* stream_buf, con
   SQDET_REQUIRE(y || sq_out, "fire_chain_fwd: no output");
   SQDET_UNSUPPORTED(!fire_chain_eligible(s1x1, e1x1, e3x3, next_s1x1, dtype), "fire_chain_fwd: shape/dtype not covered");
   const long px = (long)n * h * w;
-  SQDET_UNSUPPORTED(px * (e1x1 + e3x3) * 2 >= (1L << 31), "fire_chain_fwd: tensor too large for 32-bit offsets");
+  SQDET_UNSUPPORTED(!chain_sizes_ok(n, h, w, e1x1, e3x3), "fire_chain_fwd: %d x %d x %d x %d: a concat tensor of 2^31 bytes or more (32-bit offsets)",
+                    n, h, w, e1x1 + e3x3);
   const ChainGeom g = chain_geom(s1x1, e1x1, e3x3, next_s1x1);
   ChainArgs a;
   a.sq_in = sq_in; a.sq_out = sq_out; a.y = y; a.stream = reinterpret_cast<const unsigned char*>(stream_buf);

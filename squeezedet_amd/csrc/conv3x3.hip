@@ -165,6 +165,9 @@ bool conv3x3_pair_eligible(int n, int h, int w, int s, int e1, int e3, int dtype
   if (conv_algo() != 0 || tune(TUNE_DBG) == 93 || dtype != SQDET_F16 || e1 != e3 || e1 % 64 != 0 || s % 8 != 0) return false;
   const ConvGeom g1 = conv_geom(1, s, e1, dtype), g3 = conv_geom(3, s, e3, dtype);
   if (g1.gather || g3.gather || g3.nt != 4 || g1.nt != 4 || g3.ngroups < 2 || g1.ngroups != g3.ngroups || g1.nchunk != g3.nchunk) return false;
+  // the squeeze tile is staged by LDS-DMA with 32-bit offsets (the concat tensor is stored through 64-bit pointers; bounded as before)
+  const long px = (long)n * h * w;
+  if (px > (1L << 30) || px * s * 2 >= (1L << 31) || px * (e1 + e3) * 2 >= (1L << 31)) return false;
   if (g3.nchunk <= 6) return true;
   if (g3.nchunk > 12) return false;
   const long wgs = (long)n * ((w + TCOLS - 1) / TCOLS) * ((h + TROWS - 1) / TROWS) * ((g3.ngroups + 1) / 2);
@@ -176,8 +179,7 @@ int conv3x3_pair_launch(const void* x, const void* w3, const float* b3, const vo
   *handled = false;
   if (!conv3x3_pair_eligible(n, h, w, s, e1, e3, dtype)) return SQDET_OK;
   const ConvGeom g = conv_geom(3, s, e3, dtype);
-  const long px = (long)n * h * w;
-  if (px * (e1 + e3) * 2 >= (1L << 31) || px > (1L << 30)) return SQDET_OK;
+  const long px = (long)n * h * w;              // (sizes: conv3x3_pair_eligible)
   TileArgs a;
   ConvArgs& c = a.c;
   c.x = x; c.wp = w3; c.bias = b3; c.y = y;

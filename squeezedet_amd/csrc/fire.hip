@@ -394,10 +394,8 @@ static bool dispatch_fire(const FireArgs& a, int nts, int ntw, size_t lds, hipSt
   }
 }
 
-// Same checks as fire_fused_launch, for the executor's plan-time decision.
-bool fire_fused_eligible(int cin, int s, int e1, int e3, int dtype) {
-  if (conv_algo() != 0) return false;
-  if (tune(TUNE_FIRE_FUSE) != 3 && fire_stream_eligible(cin, s, e1, e3, dtype)) return true;
+// the channel shapes fire_fused's own kernel (not the streaming one) takes
+static bool fused_shape(int cin, int s, int e1, int e3, int dtype) {
   const int esz = dtype == SQDET_F16 ? 2 : 4;
   const ConvGeom gs = conv_geom(1, cin, s, dtype), g1 = conv_geom(1, s, e1, dtype), g3 = conv_geom(3, s, e3, dtype);
   if (gs.gather || g1.gather || g3.gather || gs.ngroups != 1) return false;
@@ -408,6 +406,25 @@ bool fire_fused_eligible(int cin, int s, int e1, int e3, int dtype) {
   if (!ntw) return false;
   if ((g1.nt * g1.ngroups) % ntw || (g3.nt * g3.ngroups) % ntw) return false;
   return (size_t)g1.nchunk * FCHUNK + (size_t)(e1 + e3 + s) * 4 + 16 + 5 * (size_t)gs.nt * 1024 <= 80000;
+}
+
+// x goes through a buffer resource with 32-bit offsets; y and sq_out through 64-bit pointers, so their sizes do not matter
+static bool fused_sizes_ok(int n, int h, int w, int cin, int dtype) {
+  const long tiles = (long)((w + FCOLS - 1) / FCOLS) * ((h + FROWS - 1) / FROWS);
+  return (long)n * h * w * cin * (dtype == SQDET_F16 ? 2 : 4) < (1L << 31) && (long)n * tiles <= 0x7fffffffL - 7;   // (the grid rounds up to 8)
+}
+
+// Same checks as fire_fused_launch, for the executor's plan-time decision.
+bool fire_fused_eligible(int cin, int s, int e1, int e3, int dtype) {
+  if (conv_algo() != 0) return false;
+  if (tune(TUNE_FIRE_FUSE) != 3 && fire_stream_eligible(cin, s, e1, e3, dtype)) return true;
+  return fused_shape(cin, s, e1, e3, dtype);
+}
+
+bool fire_fused_eligible_at(int n, int h, int w, int cin, int s, int e1, int e3, int dtype) {
+  if (conv_algo() != 0) return false;
+  if (tune(TUNE_FIRE_FUSE) != 3 && fire_stream_eligible_at(n, h, w, cin, s, e1, e3, dtype, 0)) return true;
+  return fused_shape(cin, s, e1, e3, dtype) && fused_sizes_ok(n, h, w, cin, dtype);
 }
 
 // *handled = false: not eligible, run the three convs separately.
@@ -427,19 +444,13 @@ int fire_fused_launch_keep(const void* x, const void* ws, const float* bs, const
     const int rc = fire_stream_launch_keep(x, ws, bs, w1, b1, w3, b3, sq_out, y, n, h, w, cin, s, e1, e3, dtype, st, handled);
     if (rc != SQDET_OK || *handled) return rc;
   }
+  if (!fused_shape(cin, s, e1, e3, dtype) || !fused_sizes_ok(n, h, w, cin, dtype)) return SQDET_OK;   // (fire_fused_eligible_at)
   const int esz = dtype == SQDET_F16 ? 2 : 4;
   const ConvGeom gs = conv_geom(1, cin, s, dtype), g1 = conv_geom(1, s, e1, dtype), g3 = conv_geom(3, s, e3, dtype);
-  if (gs.gather || g1.gather || g3.gather || gs.ngroups != 1) return SQDET_OK;
-  if (g1.nt != g3.nt || g1.nchunk != g3.nchunk) return SQDET_OK;
-  if ((cin * esz) % 16 != 0 || (s * esz) % 16 != 0 || s % 4 != 0 || e1 % 8 != 0 || e3 % 8 != 0) return SQDET_OK;
-  int ntw = g1.nt == 6 ? 3 : (g1.nt == 4 ? 4 : (g1.nt == 2 ? 2 : 0));
-  if (!ntw) return SQDET_OK;
+  const int ntw = g1.nt == 6 ? 3 : (g1.nt == 4 ? 4 : 2);
   const int e1_tiles = g1.nt * g1.ngroups, e3_tiles = g3.nt * g3.ngroups;
-  if (e1_tiles % ntw || e3_tiles % ntw) return SQDET_OK;
   // squeeze tile + biases + the 5-slot squeeze-weight ring
   const size_t lds = (size_t)g1.nchunk * FCHUNK + (size_t)(e1 + e3 + s) * 4 + 16 + 5 * (size_t)gs.nt * 1024;
-  if (lds > 80000) return SQDET_OK;
-  if ((long)n * h * w * cin * esz >= (1L << 31)) return SQDET_OK;   // 32-bit buffer offsets
   FireArgs a;
   a.x = x; a.y = y; a.ws = ws; a.w1 = w1; a.w3 = w3; a.bs = bs; a.b1 = b1; a.b3 = b3;
   a.N = n; a.H = h; a.W = w; a.Cin = cin; a.S = s; a.E1 = e1; a.E3 = e3;
@@ -448,7 +459,6 @@ int fire_fused_launch_keep(const void* x, const void* ws, const float* bs, const
   a.e_nt = g1.nt; a.e1_tiles = e1_tiles; a.e3_tiles = e3_tiles;
   a.x_bytes = (unsigned)((long)n * h * w * cin * esz);
   a.sq_out = sq_out;
-  if ((long)n * a.tiles_x * a.tiles_y > 0x7fffffffL) return SQDET_OK;
   const bool ok = dtype == SQDET_F16 ? dispatch_fire<f16>(a, gs.nt, ntw, lds, st) : dispatch_fire<float>(a, gs.nt, ntw, lds, st);
   if (!ok) return SQDET_OK;
   SQDET_CHECK_HIP(hipGetLastError());

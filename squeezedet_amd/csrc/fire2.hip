@@ -681,6 +681,24 @@ bool fire_stream_eligible(int cin, int s, int e1, int e3, int dtype) {
   return stream_shape(cin, s, e1, e3, dtype, &a, &b, &c);
 }
 
+// The size half of every fire_stream launch's gate, shared by the *_eligible_at predicates (plan creation, net.cpp) and the
+// launchers below: the tile counter is an int, and x -- and y, where the kernel stores it through a buffer resource (y_px_bytes
+// != 0; the squeeze tensors sq_keep / s_out go through 64-bit pointers) -- are addressed with 32-bit offsets whose out-of-range
+// marks (OOB, OOBL) need every real offset below 2^31.  *xb / *yb: the two extents in bytes.
+static bool stream_sizes_ok(int n, int h, int w, int pool, long x_px_bytes, long y_px_bytes, long* xb = nullptr, long* yb = nullptr) {
+  const long hp = out_size(h, 3, 2, SQDET_PAD_SAME), wp = out_size(w, 3, 2, SQDET_PAD_SAME);
+  const long tiles = pool ? ((wp + 6) / 7) * ((hp + 3) / 4) : (long)((w + SCOLS - 1) / SCOLS) * ((h + 7) / 8);
+  const long x_bytes = (long)n * h * w * x_px_bytes, y_bytes = (pool ? (long)n * hp * wp : (long)n * h * w) * y_px_bytes;
+  if (xb) *xb = x_bytes;
+  if (yb) *yb = y_bytes;
+  return (long)n * tiles <= 0x3fffffffL && x_bytes < (1L << 31) && y_bytes < (1L << 31);
+}
+
+bool fire_stream_eligible_at(int n, int h, int w, int cin, int s, int e1, int e3, int dtype, int pool) {
+  const long esz = dtype == SQDET_F16 ? 2 : 4;
+  return fire_stream_eligible(cin, s, e1, e3, dtype) && stream_sizes_ok(n, h, w, pool, cin * esz, 2 * e1 * esz);
+}
+
 template <typename T, int NCHX, int NTS, int NWAVES, bool POOL, int RS, bool SQIN = false>
 static void launch_stream(const FireSArgs& a, hipStream_t st) {
   const size_t lds = 2 * (size_t)Geo<POOL>::TILE + (size_t)NCHX * NTS * 1024 + (size_t)(NWAVES / RS / 2) * 4 * 1024 + (size_t)(2 * a.E + a.S) * 4;
@@ -767,13 +785,11 @@ static int fire_stream_launch_full(const void* x, const void* ws, const float* b
   a.ptp = pad_before(h, 3, 2, SQDET_PAD_SAME); a.plp = pad_before(w, 3, 2, SQDET_PAD_SAME);
   if (pool) { a.tiles_x = (a.Wp + 6) / 7; a.tiles_y = (a.Hp + 3) / 4; }
   else { a.tiles_x = (w + SCOLS - 1) / SCOLS; a.tiles_y = (h + 7) / 8; }
-  const long nt = (long)n * a.tiles_x * a.tiles_y;
-  if (nt > 0x3fffffffL) return SQDET_OK;
-  a.ntiles = (int)nt;
   const int esz = dtype == SQDET_F16 ? 2 : 4;
+  long xb, yb;
+  if (!stream_sizes_ok(n, h, w, pool, (long)cin * esz, 2L * e1 * esz, &xb, &yb)) return SQDET_OK;   // (fire_stream_eligible_at)
+  a.ntiles = n * a.tiles_x * a.tiles_y;
   a.x_pieces = cin * esz / 16;
-  const long xb = (long)n * h * w * cin * esz, yb = pool ? (long)n * a.Hp * a.Wp * 2 * e1 * esz : (long)n * h * w * 2 * e1 * esz;
-  if (xb >= (1L << 31) || yb >= (1L << 31)) return SQDET_OK;   // 32-bit buffer offsets
   a.x_bytes = (unsigned)xb; a.y_bytes = (unsigned)yb;
   if (tune(TUNE_DBG) == 40) a.x_bytes = 16;   // EXPERIMENT: every input load out of range (no read traffic)
   if (tune(TUNE_DBG) == 41) a.y_bytes = 16;   // EXPERIMENT: every store dropped (no write traffic)
@@ -793,6 +809,10 @@ bool fire_squeeze_next_eligible(int cin, int s, int e1, int e3, int s2, int dtyp
   int nchx, nts, nwaves;
   if (!stream_shape(cin, s, e1, e3, dtype, &nchx, &nts, &nwaves)) return false;
   return (nchx == 2 && nts == 1 && nwaves == 4 && s == 16 && s2 == 16) || (nchx == 4 && nts == 2 && nwaves == 8 && s2 == 32);
+}
+
+bool fire_squeeze_next_eligible_at(int n, int h, int w, int cin, int s, int e1, int e3, int s2, int dtype) {
+  return fire_squeeze_next_eligible(cin, s, e1, e3, s2, dtype) && stream_sizes_ok(n, h, w, 0, cin * 2L, 0);
 }
 
 template <int NCHX, int NTS, int NWAVES, bool PAIR, int NTS2, bool POOL = false, bool SQIN = false>
@@ -819,11 +839,17 @@ bool fire_expand_squeeze_next_eligible(int s, int e1, int e3, int s2, int pool, 
          (s == 32 && e1 == 128 && s2 == 32 && !pool) || (s == 32 && e1 == 128 && s2 == 48 && pool);
 }
 
+// (the squeeze tensor in: the only tensor of this launch behind 32-bit offsets in the fire_stream forms; fire_dma, which also
+// bounds s_out, hands over to them when it declines)
+bool fire_expand_squeeze_next_eligible_at(int n, int h, int w, int s, int e1, int e3, int s2, int pool, int dtype) {
+  return fire_expand_squeeze_next_eligible(s, e1, e3, s2, pool, dtype) && stream_sizes_ok(n, h, w, pool, s * 2L, 0);
+}
+
 int fire_expand_squeeze_next_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3,
                                     const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int s, int e1, int e3,
                                     int s2, int pool, int dtype, hipStream_t st, bool* handled) {
   *handled = false;
-  if (!fire_expand_squeeze_next_eligible(s, e1, e3, s2, pool, dtype)) return SQDET_OK;
+  if (!fire_expand_squeeze_next_eligible_at(n, h, w, s, e1, e3, s2, pool, dtype)) return SQDET_OK;
   {   // the DMA-fed four-waves-per-SIMD kernel (fire3.hip) takes SqueezeDet's four shapes ("dbg" 70: the forms below)
     const int rc = fire_dma_launch(sq_in, w1, b1, w3, b3, ws2, bs2, s_out, n, h, w, s, e1, e3, s2, pool, dtype, st, handled);
     if (rc != SQDET_OK || *handled) return rc;
@@ -836,13 +862,9 @@ int fire_expand_squeeze_next_launch(const void* sq_in, const void* w1, const flo
   a.ptp = pad_before(h, 3, 2, SQDET_PAD_SAME); a.plp = pad_before(w, 3, 2, SQDET_PAD_SAME);
   if (pool) { a.tiles_x = (a.Wp + 6) / 7; a.tiles_y = (a.Hp + 3) / 4; }
   else { a.tiles_x = (w + SCOLS - 1) / SCOLS; a.tiles_y = (h + 7) / 8; }
-  const long nt = (long)n * a.tiles_x * a.tiles_y;
-  if (nt > 0x3fffffffL) return SQDET_OK;
-  a.ntiles = (int)nt;
+  a.ntiles = n * a.tiles_x * a.tiles_y;                  // (counter and extent bounded by fire_expand_squeeze_next_eligible_at)
   a.x_pieces = s * 2 / 16;
-  const long xb = (long)n * h * w * s * 2;
-  if (xb >= (1L << 31)) return SQDET_OK;
-  a.x_bytes = (unsigned)xb; a.y_bytes = 0;
+  a.x_bytes = (unsigned)((long)n * h * w * s * 2); a.y_bytes = 0;
   int rc;
   if (s == 16 && !pool) rc = launch_stream_sq<1, 1, 4, true, 1, false, true>(a, st);   // fire2 (from the stem's squeeze tensor) -> fire3's squeeze
   else if (s == 16) rc = launch_stream_sq<1, 1, 4, true, 2, true, true>(a, st);
@@ -857,20 +879,16 @@ int fire_squeeze_next_launch(const void* x, const void* ws, const float* bs, con
                              const float* b3, const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int cin,
                              int s, int e1, int e3, int s2, int dtype, hipStream_t st, bool* handled) {
   *handled = false;
-  if (!fire_squeeze_next_eligible(cin, s, e1, e3, s2, dtype)) return SQDET_OK;
+  if (!fire_squeeze_next_eligible_at(n, h, w, cin, s, e1, e3, s2, dtype)) return SQDET_OK;
   FireSArgs a;
   a.x = x; a.y = nullptr; a.ws = ws; a.w1 = w1; a.w3 = w3; a.bs = bs; a.b1 = b1; a.b3 = b3;
   a.ws2 = ws2; a.bs2 = bs2; a.s_out = s_out; a.S2 = s2; a.sq_keep = nullptr;
   a.N = n; a.H = h; a.W = w; a.Cin = cin; a.S = s; a.E = e1;
   a.Hp = a.Wp = a.ptp = a.plp = 0;
   a.tiles_x = (w + SCOLS - 1) / SCOLS; a.tiles_y = (h + 7) / 8;
-  const long nt = (long)n * a.tiles_x * a.tiles_y;
-  if (nt > 0x3fffffffL) return SQDET_OK;
-  a.ntiles = (int)nt;
+  a.ntiles = n * a.tiles_x * a.tiles_y;                  // (counter and extent bounded by fire_squeeze_next_eligible_at)
   a.x_pieces = cin * 2 / 16;
-  const long xb = (long)n * h * w * cin * 2;
-  if (xb >= (1L << 31)) return SQDET_OK;
-  a.x_bytes = (unsigned)xb; a.y_bytes = 0;
+  a.x_bytes = (unsigned)((long)n * h * w * cin * 2); a.y_bytes = 0;
   const int rc = s == 16 ? launch_stream_sq<2, 1, 4, true, 1>(a, st) : launch_stream_sq<4, 2, 8, false, 2>(a, st);
   if (rc != SQDET_OK) return rc;
   *handled = true;
@@ -886,11 +904,15 @@ bool fire_expand_stream_eligible(int s, int e1, int e3, int dtype) {
   return (s * 2) % 16 == 0 && s % 4 == 0;
 }
 
+bool fire_expand_stream_eligible_at(int n, int h, int w, int s, int e1, int e3, int dtype, int pool) {
+  return fire_expand_stream_eligible(s, e1, e3, dtype) && stream_sizes_ok(n, h, w, pool, s * 2L, 2L * e1 * 2);
+}
+
 // y = concat(relu(conv1x1(sq_in)), relu(conv3x3(sq_in))), or its 3x3/s2 SAME max-pool when pool != 0
 int fire_expand_stream_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3, void* y,
                               int n, int h, int w, int s, int e1, int e3, int dtype, int pool, hipStream_t st, bool* handled) {
   *handled = false;
-  if (!fire_expand_stream_eligible(s, e1, e3, dtype)) return SQDET_OK;
+  if (!fire_expand_stream_eligible_at(n, h, w, s, e1, e3, dtype, pool)) return SQDET_OK;
   FireSArgs a;
   a.x = sq_in; a.y = y; a.ws = nullptr; a.w1 = w1; a.w3 = w3; a.bs = nullptr; a.b1 = b1; a.b3 = b3;
   a.ws2 = nullptr; a.bs2 = nullptr; a.s_out = nullptr; a.S2 = 0; a.sq_keep = nullptr;
@@ -899,12 +921,10 @@ int fire_expand_stream_launch(const void* sq_in, const void* w1, const float* b1
   a.ptp = pad_before(h, 3, 2, SQDET_PAD_SAME); a.plp = pad_before(w, 3, 2, SQDET_PAD_SAME);
   if (pool) { a.tiles_x = (a.Wp + 6) / 7; a.tiles_y = (a.Hp + 3) / 4; }
   else { a.tiles_x = (w + SCOLS - 1) / SCOLS; a.tiles_y = (h + 7) / 8; }
-  const long nt = (long)n * a.tiles_x * a.tiles_y;
-  if (nt > 0x3fffffffL) return SQDET_OK;
-  a.ntiles = (int)nt;
+  a.ntiles = n * a.tiles_x * a.tiles_y;                  // (counter and extents bounded by fire_expand_stream_eligible_at)
   a.x_pieces = s * 2 / 16;
-  const long xb = (long)n * h * w * s * 2, yb = pool ? (long)n * a.Hp * a.Wp * 2 * e1 * 2 : (long)n * h * w * 2 * e1 * 2;
-  if (xb >= (1L << 31) || yb >= (1L << 31)) return SQDET_OK;
+  long xb, yb;
+  stream_sizes_ok(n, h, w, pool, s * 2L, 2L * e1 * 2, &xb, &yb);
   a.x_bytes = (unsigned)xb; a.y_bytes = (unsigned)yb;
   const int nwaves = 4 * (e1 / 64);
   if (pool) {

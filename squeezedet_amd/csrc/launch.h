@@ -70,7 +70,12 @@ int stem_squeeze_launch(const void* x, const void* w_packed, const float* bias, 
 bool stem_squeeze_eligible(int h, int w, int cout, int k, int conv_pad, int pool_pad, int s2, int dtype, int n);
 
 // ---- fire.hip: a fire module in one launch (the *_keep forms also write the module's squeeze tensor: training)
+// Two predicates per fused fire launch.  *_eligible: the channel shape and dtype alone (the *_supported probes, weight packing).
+// *_eligible_at: the same AND the sizes of a launch on n images of h x w -- every tensor the kernel addresses with 32-bit buffer
+// offsets below 2^31 bytes, the tile counter in range.  The launcher declines exactly where its *_eligible_at is false, and the
+// planner (net.cpp) asks the same function with the plan's batch, so a plan never holds a launch that will decline by size.
 bool fire_fused_eligible(int cin, int s, int e1, int e3, int dtype);
+bool fire_fused_eligible_at(int n, int h, int w, int cin, int s, int e1, int e3, int dtype);
 int fire_fused_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
                       const float* b3, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
                       hipStream_t st, bool* handled);
@@ -80,6 +85,7 @@ int fire_fused_launch_keep(const void* x, const void* ws, const float* bs, const
 
 // ---- fire2.hip: persistent streaming fused fire for the large, few-channel modules
 bool fire_stream_eligible(int cin, int s, int e1, int e3, int dtype);
+bool fire_stream_eligible_at(int n, int h, int w, int cin, int s, int e1, int e3, int dtype, int pool);
 int fire_stream_launch_keep(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
                             const float* b3, void* sq_out, void* y, int n, int h, int w, int cin, int s, int e1, int e3, int dtype,
                             hipStream_t st, bool* handled);
@@ -92,14 +98,17 @@ int fire_stream_launch_ex(const void* x, const void* ws, const float* bs, const 
                           int pool, hipStream_t st, bool* handled);
 // the expand half of a fire module from its squeeze tensor (+ the 3x3/s2 SAME max-pool behind it when pool != 0)
 bool fire_expand_stream_eligible(int s, int e1, int e3, int dtype);
+bool fire_expand_stream_eligible_at(int n, int h, int w, int s, int e1, int e3, int dtype, int pool);
 int fire_expand_stream_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3, void* y,
                               int n, int h, int w, int s, int e1, int e3, int dtype, int pool, hipStream_t st, bool* handled);
 // whole fire module from x, its concat tensor replaced by the NEXT module's squeeze tensor (fire2 / fire4 of SqueezeDet)
 bool fire_squeeze_next_eligible(int cin, int s, int e1, int e3, int s2, int dtype);
+bool fire_squeeze_next_eligible_at(int n, int h, int w, int cin, int s, int e1, int e3, int s2, int dtype);
 int fire_squeeze_next_launch(const void* x, const void* ws, const float* bs, const void* w1, const float* b1, const void* w3,
                              const float* b3, const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int cin,
                              int s, int e1, int e3, int s2, int dtype, hipStream_t st, bool* handled);
 bool fire_expand_squeeze_next_eligible(int s, int e1, int e3, int s2, int pool, int dtype);
+bool fire_expand_squeeze_next_eligible_at(int n, int h, int w, int s, int e1, int e3, int s2, int pool, int dtype);
 int fire_expand_squeeze_next_launch(const void* sq_in, const void* w1, const float* b1, const void* w3, const float* b3,
                                     const void* ws2, const float* bs2, void* s_out, int n, int h, int w, int s, int e1, int e3,
                                     int s2, int pool, int dtype, hipStream_t st, bool* handled);
@@ -110,5 +119,6 @@ int fire_dma_launch(const void* sq_in, const void* w1, const float* b1, const vo
 
 // ---- chain.hip (its launchers: chain.h)
 bool fire_chain_eligible(int s, int e1, int e3, int s2, int dtype);
+bool fire_chain_eligible_at(int n, int h, int w, int s, int e1, int e3, int s2, int dtype);
 
 }  // namespace sqdet

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <set>
 #include <string>
 #include <vector>
 
@@ -98,6 +99,11 @@ struct sqdet_net {
   size_t buf_elems[NUM_BUFS] = {0, 0, 0, 0};
   size_t buf_off[NUM_BUFS] = {0, 0, 0, 0};
   size_t workspace_bytes = 0;
+  // plan creation, later attempts (plan_layers): the fire modules (by name, "fire3") that fuse_fires / fuse_fire_pools fuse only
+  // where the module's own launch fits the batch; fuse_all_by_size: every module (the last attempt)
+  std::set<std::string> fuse_by_size;
+  bool fuse_all_by_size = false;
+  bool by_size(const std::string& module) const { return fuse_all_by_size || fuse_by_size.count(module) != 0; }
   int gh = 0, gw = 0, out_ch = 0;
   char* param_mem = nullptr;
   char* workspace = nullptr;
@@ -307,10 +313,13 @@ const sqdet::ChainRide* deal_riders(const sqdet_net* net, const Layer& L, sqdet:
   return ride;
 }
 
-// A launcher the plan chose at creation declined the shape at launch time (*handled false): the options changed in between.
-int still_eligible(int rc, bool handled, const char* what) {
+// A launcher the plan chose at creation declined at launch time (*handled false).  Plan creation asks the launchers' own
+// *_eligible_at predicates with the plan's batch and map sizes, so tensor size is not the cause: an option the launcher reads
+// (conv_algo, fire_fuse, stem_algo, dbg) changed after net_create.
+int still_eligible(int rc, bool handled, const Layer& L, int nb, const char* launch) {
   if (rc != SQDET_OK || handled) return rc;
-  set_error("%s", what);
+  set_error("net: layer %s (%d x %d x %d): the %s launch chosen at net_create declines it now -- conv_algo, fire_fuse, stem_algo or dbg "
+            "changed after net_create (tensor sizes were checked there, with the same predicate)", L.name.c_str(), nb, L.h, L.w, launch);
   return SQDET_ESTATE;
 }
 
@@ -338,18 +347,18 @@ int run_layer_part(sqdet_net* net, const Layer& L, const void* input, void* pred
     case L_STEM:
       rc = stem_launch(x, net->kernel(L.kparam), net->bias(L.bparam, L.fold), y, nb, L.h, L.w, L.cout, L.k, L.pad_mode, L.pool_pad_mode, dt,
                        L.y_cstride, L.y_coffset, st, &handled);
-      return still_eligible(rc, handled, "net: fused stem no longer eligible (conv_algo changed after net_create?)");
+      return still_eligible(rc, handled, L, nb, "fused stem");
     case L_STEMSQ:
       rc = stem_squeeze_launch(x, net->kernel(L.kparam), net->bias(L.bparam), net->kernel(L.kp_s2), net->bias(L.bp_s2), y, nb, L.h, L.w,
                                L.cout, L.k, L.pad_mode, L.pool_pad_mode, L.fs2, dt, st, &handled);
-      return still_eligible(rc, handled, "net: stem + squeeze launch no longer eligible (options changed after net_create?)");
+      return still_eligible(rc, handled, L, nb, "stem + squeeze");
     case L_FIRE:
       rc = L.fire_pool
           ? fire_stream_launch_ex(x, net->kernel(L.kp_s), net->bias(L.bp_s), net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3),
                                   net->bias(L.bp_3), y, nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, dt, 1, st, &handled)
           : fire_fused_launch(x, net->kernel(L.kp_s), net->bias(L.bp_s), net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3),
                               net->bias(L.bp_3), y, nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, dt, st, &handled);
-      return still_eligible(rc, handled, "net: fused fire no longer eligible (options changed after net_create?)");
+      return still_eligible(rc, handled, L, nb, L.fire_pool ? "fused fire + pool" : "fused fire");
     case L_FIRESQ:
       return sqdet_fire_squeeze_next_fwd(x, net->kernel(L.kp_s), net->bias(L.bp_s), net->kernel(L.kp_1), net->bias(L.bp_1), net->kernel(L.kp_3),
                                          net->bias(L.bp_3), net->kernel(L.kp_s2), net->bias(L.bp_s2), y, nb, L.h, L.w, L.cin, L.fs, L.fe1,
@@ -470,6 +479,9 @@ void fuse_fires(sqdet_net* net, size_t esz) {
     if (!trio || !(ff != 10 || pixels <= 100000 || streams) ||
         !fire_fused_eligible(in[i].cin, in[i].cout, in[i + 1].cout, in[i + 2].cout, net->dtype))
       return 0;
+    if (net->by_size(in[i].name.substr(0, in[i].name.find('/'))) &&
+        !fire_fused_eligible_at(net->batch, in[i].h, in[i].w, in[i].cin, in[i].cout, in[i + 1].cout, in[i + 2].cout, net->dtype))
+      return 0;
     const Layer &s = in[i], &e1 = in[i + 1], &e3 = in[i + 2];
     Layer f = s;
     f.type = L_FIRE;
@@ -499,6 +511,8 @@ void fuse_fire_pools(sqdet_net* net, size_t esz) {
                     in[i + 1].stride == 2 && in[i + 1].pad_mode == SQDET_PAD_SAME && in[i + 1].in_buf == in[i].out_buf &&
                     fire_stream_eligible(in[i].cin, in[i].fs, in[i].fe1, in[i].fe3, net->dtype);
     if (!ok) return 0;
+    if (net->by_size(in[i].name) && !fire_stream_eligible_at(net->batch, in[i].h, in[i].w, in[i].cin, in[i].fs, in[i].fe1, in[i].fe3, net->dtype, 1))
+      return 0;
     out.push_back(absorb_pool(net, in, i, esz));
     out.back().fire_pool = 1;
     return 2;
@@ -521,7 +535,7 @@ void fuse_chains(sqdet_net* net, size_t esz) {
   if (conv_algo() != 0 || ff == 2 || ff == 5) return;
   const std::vector<Layer> in = net->layers;
   std::vector<Layer> out;
-  const int dt = net->dtype;
+  const int dt = net->dtype, nb = net->batch;
   auto base = [](const Layer& f) { return f.name.substr(0, f.name.find('+')); };
   // how member k of a run could run when it has a successor (0 = it cannot: the run ends before / at it)
   // the first module right behind a fused stem: its squeeze1x1 moves INTO the stem launch (fuse_stem_squeeze below) when the
@@ -529,18 +543,18 @@ void fuse_chains(sqdet_net* net, size_t esz) {
   auto stem_takes_squeeze = [&](const Layer& f, const Layer& nx) {
     return ff != 9 && ff != 8 && in.size() > 1 && &f == &in[1] && in[0].type == L_STEM && f.in_buf == in[0].out_buf && !f.fire_pool &&
            stem_squeeze_eligible(in[0].h, in[0].w, in[0].cout, in[0].k, in[0].pad_mode, in[0].pool_pad_mode, f.fs, dt, net->batch) &&
-           fire_expand_squeeze_next_eligible(f.fs, f.fe1, f.fe3, nx.fs, 0, dt);
+           fire_expand_squeeze_next_eligible_at(nb, f.h, f.w, f.fs, f.fe1, f.fe3, nx.fs, 0, dt);
   };
   auto mid_impl = [&](const Layer& f, const Layer& nx, bool first) -> int {
     if (first && ff != 7 && !f.fire_pool && !stem_takes_squeeze(f, nx) &&
-        fire_squeeze_next_eligible(f.cin, f.fs, f.fe1, f.fe3, nx.fs, dt)) return L_FIRESQ;
-    if (ff != 8 && fire_expand_squeeze_next_eligible(f.fs, f.fe1, f.fe3, nx.fs, f.fire_pool, dt)) return L_EXPSQ;
-    if (!f.fire_pool && fire_chain_eligible(f.fs, f.fe1, f.fe3, nx.fs, dt)) return L_CHAIN;
+        fire_squeeze_next_eligible_at(nb, f.h, f.w, f.cin, f.fs, f.fe1, f.fe3, nx.fs, dt)) return L_FIRESQ;
+    if (ff != 8 && fire_expand_squeeze_next_eligible_at(nb, f.h, f.w, f.fs, f.fe1, f.fe3, nx.fs, f.fire_pool, dt)) return L_EXPSQ;
+    if (!f.fire_pool && fire_chain_eligible_at(nb, f.h, f.w, f.fs, f.fe1, f.fe3, nx.fs, dt)) return L_CHAIN;
     return 0;
   };
   auto last_impl = [&](const Layer& f) -> int {
-    if (f.fire_pool) return fire_expand_stream_eligible(f.fs, f.fe1, f.fe3, dt) ? L_EXPAND : 0;
-    return fire_chain_eligible(f.fs, f.fe1, f.fe3, 0, dt) ? L_CHAIN : 0;
+    if (f.fire_pool) return fire_expand_stream_eligible_at(nb, f.h, f.w, f.fs, f.fe1, f.fe3, dt, 1) ? L_EXPAND : 0;
+    return fire_chain_eligible_at(nb, f.h, f.w, f.fs, f.fe1, f.fe3, 0, dt) ? L_CHAIN : 0;
   };
   for (size_t i = 0; i < in.size();) {
     if (in[i].type != L_FIRE) { out.push_back(in[i]); ++i; continue; }
@@ -731,6 +745,67 @@ void fuse_stem(sqdet_net* net, size_t esz) {
   net->layers[0] = f;
 }
 
+// The fusion passes over the freshly built layer list.  A fire module becomes one launch by its channel shape first: most such
+// launches end up inside a chain (fuse_chains), where only squeeze tensors travel and the module's own x / concat sizes no
+// longer matter -- fuse_chains itself asks the size-aware predicates.  Where that plan still holds a launch whose launcher
+// declines the batch (a fused module left on its own with a tensor of 2^31 bytes or more), the passes run again from the
+// unfused list with THAT module fused by size only: it stays three convs (+ pool), which have kernels for every size, and
+// every other module is planned as before.  A module a re-plan newly leaves on its own joins the set; the last attempt fuses
+// every module by size, which leaves nothing to decline.
+int layer_launchable(const sqdet_net* net, const Layer& L);
+int plan_layers(sqdet_net* net, size_t esz) {
+  const std::vector<Layer> unfused = net->layers;
+  size_t elems[NUM_BUFS];
+  for (int i = 0; i < NUM_BUFS; ++i) elems[i] = net->buf_elems[i];
+  const size_t param_bytes = net->param_bytes;
+  const int kAttempts = 6;
+  for (int attempt = 0; attempt < kAttempts; ++attempt) {
+    net->fuse_all_by_size = attempt == kAttempts - 1;
+    net->layers = unfused;
+    for (int i = 0; i < NUM_BUFS; ++i) net->buf_elems[i] = elems[i];
+    net->param_bytes = param_bytes;
+    fuse_stem(net, esz);
+    fuse_fires(net, esz);
+    fuse_fire_pools(net, esz);
+    fuse_chains(net, esz);
+    fuse_expand_pairs(net, esz);
+    fuse_stem_squeeze(net, esz);
+    fuse_conv_pools(net, esz);
+    const Layer* bad = nullptr;
+    bool grew = false;
+    for (const Layer& L : net->layers) {
+      if (layer_launchable(net, L)) continue;
+      if (!bad) bad = &L;
+      if (L.type == L_FIRE) grew = net->fuse_by_size.insert(L.name.substr(0, L.name.find('+'))).second || grew;
+    }
+    if (!bad) return SQDET_OK;
+    if (net->fuse_all_by_size) {
+      set_error("net_create: layer %s at batch %d, %d x %d: no launch takes it (the fused launches address tensors of less than 2^31 bytes)",
+                bad->name.c_str(), net->batch, bad->h, bad->w);
+      return SQDET_EUNSUPPORTED;
+    }
+    if (!grew) attempt = kAttempts - 2;   // nothing new to single out: straight to the last attempt
+  }
+  return SQDET_OK;
+}
+
+// (sqdet_net_layer_launchable)
+int layer_launchable(const sqdet_net* net, const Layer& L) {
+  const int nb = net->batch, dt = net->dtype;
+  switch (L.type) {
+    case L_STEMSQ: return stem_squeeze_eligible(L.h, L.w, L.cout, L.k, L.pad_mode, L.pool_pad_mode, L.fs2, dt, nb) ? 1 : 0;
+    case L_FIRE:
+      return (L.fire_pool ? fire_stream_eligible_at(nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, dt, 1)
+                          : fire_fused_eligible_at(nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, dt)) ? 1 : 0;
+    case L_FIRESQ: return fire_squeeze_next_eligible_at(nb, L.h, L.w, L.cin, L.fs, L.fe1, L.fe3, L.fs2, dt) ? 1 : 0;
+    case L_EXPSQ: return fire_expand_squeeze_next_eligible_at(nb, L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2, L.fire_pool, dt) ? 1 : 0;
+    case L_EXPAND: return (!L.fire_pool || fire_expand_stream_eligible_at(nb, L.h, L.w, L.fs, L.fe1, L.fe3, dt, 1)) ? 1 : 0;
+    case L_CHAIN: return fire_chain_eligible_at(nb, L.h, L.w, L.fs, L.fe1, L.fe3, L.fs2, dt) ? 1 : 0;
+    case L_CONV: return (!L.conv_pool || conv2d_maxpool2_eligible(nb, L.h, L.w, L.cin, L.cout, dt)) ? 1 : 0;
+    default: return 1;
+  }
+}
+
 }  // namespace
 
 extern "C" int sqdet_net_create(sqdet_net_t** out, int arch, int dtype, int batch, int img_h, int img_w, int classes,
@@ -790,13 +865,8 @@ extern "C" int sqdet_net_create(sqdet_net_t** out, int arch, int dtype, int batc
   // dropout11 / drop4 / drop6 is the identity at inference (keep_prob = 1.0, nn_skeleton.py:78)
   b.conv_layer(arch == SQDET_ARCH_RESNET50 ? "conv5" : arch == SQDET_ARCH_VGG16 ? "conv6" : "conv12", nout, 3, 1, SQDET_PAD_SAME, 0, true);
   net->gh = b.h; net->gw = b.w; net->out_ch = nout;
-  fuse_stem(net, b.esz);
-  fuse_fires(net, b.esz);
-  fuse_fire_pools(net, b.esz);
-  fuse_chains(net, b.esz);
-  fuse_expand_pairs(net, b.esz);
-  fuse_stem_squeeze(net, b.esz);
-  fuse_conv_pools(net, b.esz);
+  const int prc = plan_layers(net, b.esz);
+  if (prc != SQDET_OK) { delete net; return prc; }
   net->fold_scratch_off = net->param_bytes;
   net->param_bytes = align_up(net->param_bytes + net->fold_scratch_bytes, 256);
   size_t off = 0;
@@ -1015,6 +1085,13 @@ extern "C" int sqdet_net_read_probe(sqdet_net_t* net, float* host_ms, int capaci
 }
 
 extern "C" int sqdet_net_num_layers(const sqdet_net_t* net) { return net ? (int)net->layers.size() : 0; }
+
+// Would layer `index`'s launcher take the layer at the plan's batch under the current options?  The fused launches ask the
+// predicate their launcher declines by (launch.h: *_eligible_at); convs and pools have a kernel for every size.
+extern "C" int sqdet_net_layer_launchable(const sqdet_net_t* net, int index) {
+  if (!net || index < 0 || index >= (int)net->layers.size()) return 0;
+  return layer_launchable(net, net->layers[index]);
+}
 
 extern "C" int sqdet_net_layer_info(const sqdet_net_t* net, int index, char* name, size_t name_cap, double* flops,
                                     double* bytes) {

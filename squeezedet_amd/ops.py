@@ -1298,6 +1298,11 @@ class NetPlan:
                                            n, gh, gw, int(anchors_per_grid), int(classes), float(img_w), float(img_h), float(exp_thresh),
                                            int(top_n), int(ob.shape[1]), float(nms_thresh), dtype_code(preds.dtype)), "sqdet_net_set_post_job")
 
+    def layers_launchable(self):
+        """Per layer of the plan: whether its launcher takes it at the plan's batch under the current options
+        (sqdet_net_layer_launchable; all True for a plan created under the same options)."""
+        return [bool(lib().sqdet_net_layer_launchable(self._h, i)) for i in range(lib().sqdet_net_num_layers(self._h))]
+
     def scores_supported(self):
         """The plan's ConvDet launch can also write interpret_output's det_probs (float16 SqueezeDet-style head)."""
         return bool(lib().sqdet_net_scores_supported(self._h))

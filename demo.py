@@ -79,7 +79,9 @@ def parse_args(argv=None):
                     help="video, with --track: labelled objects to score the tracks against (MOTA, MOTP, IDF1), printed at the end")
     ap.add_argument("--track_gt_format", default=argparse.SUPPRESS, choices=["kitti", "mot"],
                     help="video, with --track_gt: a KITTI tracking label file (default) or a MOTChallenge gt.txt")
+    drivers.add_nms_args(ap)        # (these too exist on the namespace only when given)
     a = ap.parse_args(argv)
+    drivers.check_nms_args(ap, a)
     if (hasattr(a, "track_gt") and not hasattr(a, "track")) or (hasattr(a, "track_gt_format") and not hasattr(a, "track_gt")):
         ap.error("--track_gt needs --track, --track_gt_format needs --track_gt")
     if hasattr(a, "track") and a.mode != "video":
@@ -97,6 +99,7 @@ def make_model(a, batch):
     from squeezedet_amd import synthetic, weights
     mc = drivers.make_config(a.demo_net, anchor_shapes=drivers.driver_anchor_shapes(a.anchor_shapes, a.weights))
     model = drivers.build_model(mc, a.demo_net, a.gpu, a.dtype, batch)     # parameters are restored below (demo.py:171-172)
+    drivers.nms_policy(a, model.mc)     # --nms ...: image, video and tracking modes all filter through the model
     model.load_params(weights.load_params(a.weights) if a.weights else synthetic.synthetic_params(model, seed=0))
     return mc, model, drivers.torch_dtype(a.dtype)
 

@@ -66,8 +66,10 @@ def parse_args(argv=None):
                     help="anchor shapes the checkpoint was trained with (default: anchor_shapes.json beside the checkpoint, else the config's)")
     ap.add_argument("--coco_metrics", action="store_true", default=argparse.SUPPRESS,
                     help="also score the detections COCO-style: AP over IoU 0.50:0.95 by object size, AR at 1 / 10 / 100 detections")
+    drivers.add_nms_args(ap)
     a = ap.parse_args(argv, namespace=EvalArgs())
     drivers.check_dataset_args(ap, a)
+    drivers.check_nms_args(ap, a)
     return a
 
 
@@ -276,6 +278,8 @@ def eval_once(a, model, data, ckpt_path, evaluator, coco=None):
 
     print("Evaluation summary:")
     print("  Average number of detections per image: {}:".format(num_detection / float(n)))
+    policy = drivers.config_nms_policy(model.mc)         # (what the model filtered with: main set it from the --nms flags)
+    print("  Suppression: {}".format(drivers.format_nms_policy(policy)))
     print("  Timing:")
     print("    detect: {:.3f}s misc: {:.3f}s eval: {:.3f}s".format(t_detect / nb, t_misc / nb, t_eval))
     print("  Average precisions:")
@@ -290,6 +294,8 @@ def eval_once(a, model, data, ckpt_path, evaluator, coco=None):
         rec["analysis"] = analyze_kitti(a, model, data, evaluator, result_dir)
     if coco is not None:
         rec["coco"] = score_coco(coco, result_dir)
+    if not policy["default"]:           # (a run without the --nms flags writes the record it always wrote)
+        rec["nms"] = policy
     with open(os.path.join(a.eval_dir, "eval_log.jsonl"), "a") as f:
         f.write(json.dumps(rec) + "\n")
     return rec
@@ -319,6 +325,7 @@ def main(argv=None):
         from squeezedet_amd.kitti_ap import KittiEvaluator as Evaluator
     shapes = drivers.driver_anchor_shapes(a.anchor_shapes, a.checkpoint_path)
     mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, shapes, a.image_size, a.dataset)
+    drivers.nms_policy(a, model.mc)         # --nms ...: the rule model.filter_prediction_batch thins every image's rows with
     data = drivers.load_index(a.dataset, a.data_path, a.year, a.image_set, mc)
     evaluator = Evaluator(mc, data.gt, model.device)
     coco = None

@@ -320,6 +320,29 @@ int sqdet_detect_filter_scored(const void* preds, const float* anchors, const fl
                                int classes, float img_w, float img_h, float exp_thresh, int top_n, int max_out,
                                double nms_thresh, int dtype, int max_workgroups, sqdet_stream_t stream);
 
+/* A second suppression stage over the rows a filter call above emitted (OURS): greedy NMS, Soft-NMS (linear /
+ * Gaussian), DIoU-NMS and class-agnostic suppression.  The filter is called with nms_thresh = +inf (it then only selects and
+ * orders the top-N rows); this call applies the rule IN PLACE on its five outputs: boxes float32 [n,rows,4] (cx,cy,w,h), probs
+ * float32 [n,rows], cls int32 [n,rows], index int32 [n,rows], count int32 [n]; 1 <= rows <= 64.  One launch, one workgroup per
+ * image.  Rows are ranked by (prob, anchor index) descending -- the filter's own total order.
+ *   method   NONGREEDY: r is dropped iff some higher-ranked i has (double)ov(i,r) > nms_thresh (sqdet_filter_prediction's rule);
+ *            GREEDY: the same, but only a kept i suppresses; SOFT_LINEAR / SOFT_GAUSSIAN (Bodla et al. 2017), float64 scores
+ *            starting at prob: pick the remaining row of the largest score (ties: higher rank), stop when it is < score_floor,
+ *            keep it, then decay every remaining row j under the class test: linear s_j *= 1 - iou where (double)iou >
+ *            nms_thresh; Gaussian s_j *= exp(-(iou*iou) / sigma) for every j.  The output prob is (float)s.
+ *   overlap  IOU: the filter's float32 IoU; DIOU (Zheng et al. 2020; hard methods only), in float64: iou - d^2 / c^2 with d the
+ *            centre distance and c the diagonal of the enclosing box.  A NaN overlap never suppresses.
+ *   class_agnostic  != 0: rows of different classes suppress / decay each other too.
+ * Output as the filter's: kept rows ordered by class, then pick order; rows [kept, rows) zeroed (boxes 0, prob 0, cls -1,
+ * index -1); count = kept.  An image whose count is outside [0, rows] (the filter's overflow report) is left untouched.
+ * NULL pointers, rows outside 1..64, an unknown method / overlap, DIOU with a soft method, sigma <= 0 or a non-finite
+ * score_floor: SQDET_EINVAL, nothing launched. */
+enum { SQDET_NMS_NONGREEDY = 0, SQDET_NMS_GREEDY = 1, SQDET_NMS_SOFT_LINEAR = 2, SQDET_NMS_SOFT_GAUSSIAN = 3 };
+enum { SQDET_NMS_OVERLAP_IOU = 0, SQDET_NMS_OVERLAP_DIOU = 1 };
+typedef struct { int method; int overlap; int class_agnostic; double nms_thresh; double sigma; double score_floor; } sqdet_nms_options_t;
+int sqdet_suppress_rows(float* boxes, float* probs, int32_t* cls, int32_t* index, int32_t* count, int n, int rows, int classes,
+                        const sqdet_nms_options_t* opt, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------ training --
  * Replaces the gradient half of the reference's TF graph for the trainable convs (stride 1,
  * SAME: every conv but the frozen conv1, nets/squeezeDet.py:40-42), the loss graph

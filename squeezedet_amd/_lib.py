@@ -60,6 +60,7 @@ SIGNATURES = {
     "sqdet_filter_prediction": (ci, [vp] * 8 + [ci] * 5 + [cd, cf, vp]),
     "sqdet_detect_filter": (ci, [vp] * 8 + [ci] * 5 + [cf, cf, cf, ci, ci, cd, ci, vp]),
     "sqdet_detect_filter_scored": (ci, [vp] * 8 + [ci] * 5 + [cf, cf, cf, ci, ci, cd, ci, ci, vp]),
+    "sqdet_suppress_rows": (ci, [vp] * 5 + [ci, ci, ci, vp, vp]),
     "sqdet_net_set_signal": (ci, [vp, ci, vp]),
     "sqdet_net_set_post_job": (ci, [vp] * 9 + [ci] * 5 + [cf, cf, cf, ci, ci, cd, ci]),
     "sqdet_net_rider_capacity": (ci, [vp]),

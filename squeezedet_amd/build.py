@@ -53,6 +53,9 @@ SOURCES = [
     ("anchors.hip", ["-ffp-contract=off"]),
     ("postproc.hip", ["-ffp-contract=off"]),
     ("filter_fast.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the second suppression stage shares postproc.h's IoU with the filter and restates DIoU and the Soft-NMS
+    # decays as single IEEE operations, compared bit for bit with the sequential NumPy restatement)
+    ("suppress.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: overlaps, recall steps and the '%.2f' / '%.3f' rounding are bitwise those of the host programs)
     ("kitti_eval.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: the '+1' overlaps, recall / precision and the '{:.1f}' / '{:.3f}' rounding are bitwise NumPy's)

@@ -151,3 +151,66 @@ def loss_policy(a, mc):
                   bbox_loss_coef=float(getattr(a, "bbox_loss_coef", off["bbox_loss_coef"])))
     mc.BBOX_LOSS, mc.FOCAL_GAMMA, mc.LOSS_COEF_BBOX = policy["bbox_loss"], policy["focal_gamma"], policy["bbox_loss_coef"]
     return policy, off
+
+
+def add_nms_args(ap):
+    """--nms, --nms_overlap, --nms_sigma, --nms_score_floor, --nms_class_agnostic (eval.py, demo.py).  A flag that is not given
+    leaves no attribute behind: nms_policy supplies the defaults."""
+    import argparse
+    from .nms import NMS_METHODS, NMS_OVERLAPS
+    ap.add_argument("--nms", default=argparse.SUPPRESS, choices=NMS_METHODS,
+                    help="the suppression rule over the top-N rows: reference (default), a row is dropped when ANY higher-scored row of its "
+                         "class overlaps it; greedy, only a kept row suppresses; soft_linear, soft_gaussian: Soft-NMS, overlapped rows "
+                         "lose score instead (DESIGN.md section 3.17)")
+    ap.add_argument("--nms_overlap", default=argparse.SUPPRESS, choices=NMS_OVERLAPS,
+                    help="what the config's NMS_THRESH is compared with: iou (default), or diou = IoU minus the squared centre distance "
+                         "over the squared enclosing diagonal (reference and greedy only)")
+    ap.add_argument("--nms_sigma", type=float, default=argparse.SUPPRESS, metavar="S", help="soft_gaussian: scores decay by exp(-iou^2 / S) (default 0.5)")
+    ap.add_argument("--nms_score_floor", type=float, default=argparse.SUPPRESS, metavar="X",
+                    help="soft methods: rows whose decayed score falls below X are dropped (default 0.001)")
+    ap.add_argument("--nms_class_agnostic", action="store_true", default=argparse.SUPPRESS, help="rows of different classes suppress each other too")
+
+
+def check_nms_args(ap, a):
+    soft = str(getattr(a, "nms", "reference")).startswith("soft")
+    if getattr(a, "nms_overlap", "iou") == "diou" and soft:
+        ap.error("--nms_overlap diou goes with --nms reference or greedy, not with a soft method")
+    if not (0.0 < float(getattr(a, "nms_sigma", 0.5)) < float("inf")):
+        ap.error("--nms_sigma S needs a finite S > 0")
+    if not (abs(float(getattr(a, "nms_score_floor", 0.0))) < float("inf")):
+        ap.error("--nms_score_floor X needs a finite X")
+    if hasattr(a, "nms_sigma") and getattr(a, "nms", "reference") != "soft_gaussian":
+        ap.error("--nms_sigma needs --nms soft_gaussian")
+    if hasattr(a, "nms_score_floor") and not soft:
+        ap.error("--nms_score_floor needs --nms soft_linear or soft_gaussian")
+
+
+def nms_policy(a, mc):
+    """The suppression policy of the --nms flags as a dict (what eval.py prints and records); sets mc.NMS_METHOD, mc.NMS_OVERLAP,
+    mc.NMS_SIGMA, mc.NMS_SCORE_FLOOR and mc.NMS_CLASS_AGNOSTIC, which every filtering call site reads through nms.nms_options."""
+    from . import nms
+    d = nms.DEFAULTS
+    mc.NMS_METHOD = str(getattr(a, "nms", d["NMS_METHOD"]))
+    mc.NMS_OVERLAP = str(getattr(a, "nms_overlap", d["NMS_OVERLAP"]))
+    mc.NMS_SIGMA = float(getattr(a, "nms_sigma", d["NMS_SIGMA"]))
+    mc.NMS_SCORE_FLOOR = float(getattr(a, "nms_score_floor", d["NMS_SCORE_FLOOR"]))
+    mc.NMS_CLASS_AGNOSTIC = bool(getattr(a, "nms_class_agnostic", d["NMS_CLASS_AGNOSTIC"]))
+    opt = nms.nms_options(mc)
+    if not nms.is_default(opt) and not (0 < int(mc.TOP_N_DETECTION) <= nms.MAX_ROWS):
+        raise SystemExit("--nms / --nms_overlap / --nms_class_agnostic work on the top-N rows: the config needs 0 < TOP_N_DETECTION <= %d, "
+                         "it has %d" % (nms.MAX_ROWS, int(mc.TOP_N_DETECTION)))
+    return config_nms_policy(mc)
+
+
+def config_nms_policy(mc):
+    """The suppression policy a config holds, as a dict: what the model built on it filters with."""
+    from . import nms
+    opt = nms.nms_options(mc)
+    return dict(opt._asdict(), nms_thresh=float(mc.NMS_THRESH), default=nms.is_default(opt))
+
+
+def format_nms_policy(policy):
+    return "{method}, {overlap} > {nms_thresh:g}, {scope}{soft}".format(
+        scope="class-agnostic" if policy["class_agnostic"] else "per class",
+        soft=(", sigma {sigma:g}".format(**policy) if policy["method"] == "soft_gaussian" else "")
+        + (", score floor {score_floor:g}".format(**policy) if policy["method"].startswith("soft") else ""), **policy)

@@ -12,7 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import ops
+from . import nms, ops
 from ._lib import SqdetError
 from .serving import Serving
 
@@ -495,8 +495,10 @@ class ModelSkeleton:
         """Batched, device-resident filter_prediction: returns (boxes [B,M,4], probs [B,M], cls [B,M] i32,
         anchor_index [B,M] i32, count [B] i32) device tensors."""
         mc = self.mc
-        return ops.filter_prediction(det_boxes, det_probs, det_class, mc.CLASSES, mc.TOP_N_DETECTION, mc.NMS_THRESH,
-                                     mc.PROB_THRESH, max_out)
+        opt = nms.nms_options(mc)     # (the default policy: the filter's own rule at mc.NMS_THRESH, nothing else is launched)
+        out = ops.filter_prediction(det_boxes, det_probs, det_class, mc.CLASSES, mc.TOP_N_DETECTION, nms.first_stage_thresh(opt, mc),
+                                    mc.PROB_THRESH, max_out)
+        return out if nms.is_default(opt) else nms.apply(opt, mc, out)
 
     def filter_prediction(self, boxes, probs, cls_idx):
         """Filter bounding box predictions with probability threshold and non-maximum

@@ -422,6 +422,33 @@ def detect_filter(preds, anchors_f32, classes, anchors_per_grid, img_w, img_h, e
     return ob, op, oc, oi, cnt
 
 
+class _NmsOptions(C.Structure):        # sqdet_nms_options_t
+    _fields_ = [("method", C.c_int), ("overlap", C.c_int), ("class_agnostic", C.c_int), ("nms_thresh", C.c_double), ("sigma", C.c_double),
+                ("score_floor", C.c_double)]
+
+
+def suppress_rows(out, classes, opt):
+    """The second suppression stage (sqdet_suppress_rows), IN PLACE on the five outputs of filter_prediction /
+    detect_filter called with nms_thresh = inf: out = (boxes [N,M,4] f32, probs [N,M] f32, cls [N,M] i32, index [N,M] i32, count [N]
+    i32), M <= 64.  opt: dict(method in nms.KERNEL_METHODS (or its number), overlap in nms.NMS_OVERLAPS (or its number),
+    class_agnostic, nms_thresh, sigma, score_floor).  A refused option raises and leaves the tensors as they were.  Returns out."""
+    from .nms import KERNEL_METHODS, NMS_OVERLAPS
+    ob, op, oc, oi, cnt = out
+    n, rows = int(op.shape[0]), int(op.shape[1])
+    if tuple(ob.shape) != (n, rows, 4) or tuple(oc.shape) != (n, rows) or tuple(oi.shape) != (n, rows) or tuple(cnt.shape) != (n,):
+        raise _lib.SqdetError("suppress_rows: out tensors must be [N,M,4], [N,M], [N,M], [N,M], [N]")
+    def code(v, names):               # (a number passes through: the library refuses a bad one)
+        if isinstance(v, str) and v not in names:
+            raise _lib.SqdetError("suppress_rows: %r is not one of %s" % (v, ", ".join(names)))
+        return names.index(v) if isinstance(v, str) else int(v)
+    o = _NmsOptions(code(opt["method"], KERNEL_METHODS), code(opt["overlap"], NMS_OVERLAPS), int(bool(opt["class_agnostic"])),
+                    float(opt["nms_thresh"]), float(opt["sigma"]), float(opt["score_floor"]))
+    check(lib().sqdet_suppress_rows(_dev(ob, "boxes", torch.float32), _dev(op, "probs", torch.float32), _dev(oc, "cls", torch.int32),
+                                    _dev(oi, "index", torch.int32), _dev(cnt, "count", torch.int32), n, rows, int(classes),
+                                    C.cast(C.pointer(o), C.c_void_p), stream_ptr()), "sqdet_suppress_rows")
+    return out
+
+
 def convdet_scores_supported(cin, anchors_per_grid, classes, dtype):
     return bool(lib().sqdet_convdet_scores_supported(int(cin), int(anchors_per_grid), int(classes), dtype_code(dtype)))
 

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import nms, ops
 from ._lib import SqdetError
 
 # Every environment knob of the serving step and its default.  Read through knob() at each use, never cached: callers (bench.py,
@@ -57,7 +57,7 @@ def _probed(probe, which, call, *args):
 class Slot:
     """One set of a pipe's static buffers, its events, and the flags of the call that last used it."""
     __slots__ = ("preds", "det", "flat", "out", "views", "host_flat", "host", "fwd_done", "post_done", "sig",
-                 "fused_post", "scored", "to_host", "ride", "post_wgs", "used")
+                 "fused_post", "scored", "to_host", "ride", "post_wgs", "used", "nms")
 
     def __init__(self, model, plan, B, cur):
         A, N, f32, dev = model.mc.ANCHORS, model.mc.TOP_N_DETECTION, torch.float32, model.device
@@ -71,7 +71,7 @@ class Slot:
         self.out, self.host_flat, self.host = self.views(self.flat), None, None
         self.fwd_done, self.post_done = torch.cuda.Event(), torch.cuda.Event()
         self.fused_post = self.scored = self.to_host = self.ride = self.used = False
-        self.post_wgs = 0
+        self.post_wgs, self.nms = 0, None           # (nms: the suppression policy of the call that last used the slot)
 
 
 class Pipe:
@@ -109,7 +109,10 @@ class Pipe:
         # SqueezeDet head): what is left for the side stream is ONE filter launch + the row copy
         s.scored = s.fused_post and plan.scores_supported() and knob("SQDET_SCORE_EPILOGUE") != "0"
         mode = knob("SQDET_POST_DEFER") if defer and s.scored else None
-        s.ride = mode == "ride" and plan.rider_capacity() >= B
+        # a non-default suppression policy (nms.py) is a second launch behind the filter: the riders write their rows straight into
+        # pinned host memory, where it cannot follow, so the post work then runs on the side stream
+        s.nms = nms.nms_options(mc)
+        s.ride = mode == "ride" and plan.rider_capacity() >= B and nms.is_default(s.nms)
         s.to_host, s.post_wgs = to_host, int(knob("SQDET_POST_WGS")) if B > 16 else 0
         if to_host and s.host is None:
             s.host_flat = torch.empty(s.flat.shape, dtype=torch.uint8).pin_memory()
@@ -176,6 +179,7 @@ class Pipe:
     def _post(self, model, s, gate, stream=None):
         """Decode + filter + row copy of slot s on the side stream, behind its forward (and `gate`, an event of a later forward)."""
         mc = model.mc
+        thresh = nms.first_stage_thresh(s.nms, mc)          # (mc.NMS_THRESH itself under the default policy)
         pstream = stream if stream is not None else (torch.cuda.current_stream() if knob("SQDET_POST_INLINE") == "1" else self.post_stream)
         with torch.cuda.stream(pstream):
             pstream.wait_event(s.fwd_done)
@@ -184,13 +188,15 @@ class Pipe:
             if s.fused_post:
                 # decode + top-N + NMS in one call (score kernel unless scored + filter kernel): boxes / classes are decoded for the selected anchors only
                 ops.detect_filter(s.preds, model.anchors_f32(), mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT,
-                                  mc.EXP_THRESH, mc.TOP_N_DETECTION, mc.NMS_THRESH, scratch=s.det[1], out=s.out,
+                                  mc.EXP_THRESH, mc.TOP_N_DETECTION, thresh, scratch=s.det[1], out=s.out,
                                   scores_ready=s.scored, max_workgroups=s.post_wgs if gate is not None else 0)
             else:
                 ops.interpret_output(s.preds, model.anchors_f32(), mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH,
                                      mc.IMAGE_HEIGHT, mc.EXP_THRESH, out=s.det)
-                ops.filter_prediction(s.det[0], s.det[1], s.det[2], mc.CLASSES, mc.TOP_N_DETECTION, mc.NMS_THRESH,
+                ops.filter_prediction(s.det[0], s.det[1], s.det[2], mc.CLASSES, mc.TOP_N_DETECTION, thresh,
                                       mc.PROB_THRESH, out=s.out)
+            if not nms.is_default(s.nms):
+                nms.apply(s.nms, mc, s.out)                             # the second stage, ahead of the row copy on the same stream
             if s.to_host:
                 ops.copy_to_pinned_host(s.flat, s.host_flat)            # all five outputs in one launch (never blocks the host)
             s.post_done.record(pstream)

@@ -7,6 +7,7 @@ libsqdet_hip.so -- never on PyTorch compute ops.  Call shapes follow the referen
   sqdet::fire(x, ws, bs, w1, b1, w3, b3)                      SqueezeDet._fire_layer      nets/squeezeDet.py:81-106
   sqdet::conv2d_nhwc / maxpool_nhwc                           the same two on PRE-PACKED kernels (inference: no pack per call)
   sqdet::interpret_output / filter_prediction / detect_filter _add_interpretation_graph :142-283, filter_prediction :696-734
+  sqdet::suppress_rows(boxes, probs, cls, index, count, ...)  OURS: the second suppression stage (DESIGN.md 3.17), functional
   sqdet::net_forward(x, plan_id)                              _add_forward_graph as one native plan (register_plan() -> id)
 
 conv2d / maxpool / fire are differentiable (stride-1 SAME convs, like every trainable conv of the reference's nets); their
@@ -222,6 +223,19 @@ def _register():
         f = lambda shape, dt: preds.new_empty(shape, dtype=dt)
         return (f((n, top_n, 4), torch.float32), f((n, top_n), torch.float32), f((n, top_n), torch.int32), f((n, top_n), torch.int32),
                 f((n,), torch.int32))
+
+    @custom_op("sqdet::suppress_rows", mutates_args=())
+    def _supp(boxes: torch.Tensor, probs: torch.Tensor, cls: torch.Tensor, index: torch.Tensor, count: torch.Tensor, classes: int,
+              method: str, overlap: str, class_agnostic: bool, nms_thresh: float, sigma: float,
+              score_floor: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        # (functional: the kernel works in place on copies of the filter's five outputs)
+        out = tuple(t.clone() for t in (boxes, probs, cls, index, count))
+        return ops.suppress_rows(out, classes, dict(method=method, overlap=overlap, class_agnostic=class_agnostic, nms_thresh=nms_thresh,
+                                                    sigma=sigma, score_floor=score_floor))
+
+    @_supp.register_fake
+    def _(boxes, probs, cls, index, count, classes, method, overlap, class_agnostic, nms_thresh, sigma, score_floor):
+        return tuple(torch.empty_like(t) for t in (boxes, probs, cls, index, count))
 
     @custom_op("sqdet::net_forward", mutates_args=())
     def _net(image_input: torch.Tensor, plan_id: int) -> torch.Tensor:

@@ -207,16 +207,20 @@ class ImageSummary:
     def filtered(self, preds):
         """The filtered rows of preds, as _viz_prediction_result's model.filter_prediction gives them: (boxes, probs, classes,
         anchor indices, counts) on the device."""
-        from . import ops
+        from . import nms, ops
         mc = self.mc
         n, gh, gw, _ = (int(v) for v in preds.shape)
         A = gh * gw * mc.ANCHOR_PER_GRID
+        opt = nms.nms_options(mc)     # (the model's suppression policy: what eval.py and demo.py filter with)
+        thresh = nms.first_stage_thresh(opt, mc)
         if ops.detect_filter_supported(A, mc.TOP_N_DETECTION):
-            return ops.detect_filter(preds, self.anchors, mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT, mc.EXP_THRESH,
-                                     mc.TOP_N_DETECTION, mc.NMS_THRESH)
-        boxes, probs, cls = ops.interpret_output(preds, self.anchors, mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT,
-                                                 mc.EXP_THRESH)
-        return ops.filter_prediction(boxes, probs, cls, mc.CLASSES, mc.TOP_N_DETECTION, mc.NMS_THRESH, mc.PROB_THRESH)
+            out = ops.detect_filter(preds, self.anchors, mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT, mc.EXP_THRESH,
+                                    mc.TOP_N_DETECTION, thresh)
+        else:
+            boxes, probs, cls = ops.interpret_output(preds, self.anchors, mc.CLASSES, mc.ANCHOR_PER_GRID, mc.IMAGE_WIDTH, mc.IMAGE_HEIGHT,
+                                                     mc.EXP_THRESH)
+            out = ops.filter_prediction(boxes, probs, cls, mc.CLASSES, mc.TOP_N_DETECTION, thresh, mc.PROB_THRESH)
+        return out if nms.is_default(opt) else nms.apply(opt, mc, out)
 
     def render(self, batch, preds):
         """uint8 RGB [n, H, W, 3] on the device, n = min(max_images, batch size)."""

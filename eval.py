@@ -27,6 +27,9 @@ localisation metric over KITTI's boxes, not KITTI's protocol (CocoGroundTruth.fr
 --anchor_shapes FILE: the net's anchors take the shapes of that file (tools/fit_anchors.py, train.py --anchor_shapes); without
 the flag an anchor_shapes.json beside the checkpoint -- train.py leaves one in its --train_dir -- is used, else the config's own.
 
+--ema: evaluate the exponential moving average of the weights that train.py --ema_decay keeps: under
+--run_once the file <dir>/ema/<name> of --checkpoint_path <dir>/<name>, which must exist; otherwise <checkpoint_path>/ema is polled.
+
 Checkpoints are .npz files from squeezedet_amd.weights.save_params.  --run_once: --checkpoint_path is that file;
 otherwise it is a directory polled every --eval_interval_secs for the newest '*-<step>.npz'.  Every image is scored
 once (the last batch is padded; the reference's reader wraps around instead).
@@ -46,6 +49,7 @@ class EvalArgs(argparse.Namespace):
     """parse_args' result.  --coco_metrics is off through this class attribute, not through an argparse default, so vars() of
     a run without the flag holds exactly the options it held before the flag existed; with the flag it is an instance attribute."""
     coco_metrics = False
+    ema = False                 # (--ema, likewise)
 
 
 def parse_args(argv=None):
@@ -66,6 +70,9 @@ def parse_args(argv=None):
                     help="anchor shapes the checkpoint was trained with (default: anchor_shapes.json beside the checkpoint, else the config's)")
     ap.add_argument("--coco_metrics", action="store_true", default=argparse.SUPPRESS,
                     help="also score the detections COCO-style: AP over IoU 0.50:0.95 by object size, AR at 1 / 10 / 100 detections")
+    ap.add_argument("--ema", action="store_true", default=argparse.SUPPRESS,
+                    help="evaluate the averaged weights of a run trained with --ema_decay: <dir>/ema/<name> of the file under --run_once, "
+                         "else the directory <checkpoint_path>/ema is polled")
     drivers.add_nms_args(ap)
     a = ap.parse_args(argv, namespace=EvalArgs())
     drivers.check_dataset_args(ap, a)
@@ -312,8 +319,26 @@ def latest_checkpoint(directory):
     return best[1] if best else None
 
 
+def ema_checkpoint_path(checkpoint_path, run_once):
+    """--ema: where the averaged weights of train.py --ema_decay lie.  A file (--run_once) <dir>/<name> resolves to
+    <dir>/ema/<name> and must exist; a directory to poll becomes <dir>/ema."""
+    from squeezedet_amd import checkpoint
+    if not run_once:
+        return os.path.join(checkpoint_path, checkpoint.EMA_DIR)
+    path = checkpoint.ema_of(checkpoint_path)
+    if not os.path.isfile(path):
+        raise SystemExit("--ema: %s does not exist (train.py writes it beside a checkpoint when it runs with --ema_decay)" % path)
+    return path
+
+
 def main(argv=None):
     a = parse_args(argv)
+    if a.ema:
+        if a.synthetic_weights:
+            raise SystemExit("--ema reads a checkpoint's averaged weights: not with --synthetic_weights")
+    raw_checkpoint_path = a.checkpoint_path           # (anchor_shapes.json lies beside the raw checkpoint, not under ema/)
+    if a.ema:
+        a.checkpoint_path = ema_checkpoint_path(a.checkpoint_path, a.run_once)
     if a.dataset == "PASCAL_VOC":
         for flag, given in (("--eval_tool", a.eval_tool), ("--visualize", a.visualize)):
             if given:
@@ -323,7 +348,7 @@ def main(argv=None):
         if a.image_size is not None:
             raise SystemExit("--image_size is for --dataset PASCAL_VOC (the KITTI nets run at their configs' size)")
         from squeezedet_amd.kitti_ap import KittiEvaluator as Evaluator
-    shapes = drivers.driver_anchor_shapes(a.anchor_shapes, a.checkpoint_path)
+    shapes = drivers.driver_anchor_shapes(a.anchor_shapes, raw_checkpoint_path)
     mc, model = make_model(a.net, a.gpu, a.dtype, a.batch_size, shapes, a.image_size, a.dataset)
     drivers.nms_policy(a, model.mc)         # --nms ...: the rule model.filter_prediction_batch thins every image's rows with
     data = drivers.load_index(a.dataset, a.data_path, a.year, a.image_set, mc)

@@ -531,6 +531,42 @@ int sqdet_optimizer_step(sqdet_optimizer_t* opt, float* params, float* grads, fl
                          float momentum, float max_grad_norm, float grad_scale, int32_t* found_inf,
                          sqdet_stream_t stream);
 
+/* The update step with options (OURS): the same three launches over the same segment table and workspace.
+ * All element-wise arithmetic is float32, one rounding per operator in the order written; scalars derived per step are formed
+ * in float64 and rounded to float32 once.
+ *   state   device, 4 doubles: (t, p1, p2, unused) = the number of applied updates, beta1^t and beta2^t as running products
+ *           (p1 *= beta1 -- not pow), starting at (0, 1, 1).  A skipped step leaves it untouched.
+ *   pass 1  g = g * grad_scale; momentum / nesterov: variables with decay != 0 then get g = g + decay * w (coupled, as above);
+ *           adamw: nothing is added.  Per-block float64 partial sums of squares in sqdet_optimizer_step's partition and order.
+ *   pass 2  per-variable float64 sums as above; bad = any norm inf / NaN (found_inf, the step is skipped in every buffer).
+ *           clip 0: scale[v] = max_norm / fmaxf(n_v, max_norm) (tf.clip_by_norm).  clip 1: the per-variable sums added in
+ *           variable-index order, N = (float)sqrt(S), every variable max_norm / fmaxf(N, max_norm) (tf.clip_by_global_norm; a
+ *           non-finite N is bad too).  Not bad: t += 1; p1 *= beta1; p2 *= beta2; c1 = (float)(1 / (1 - p1));
+ *           c2 = (float)(1 / (1 - p2)); om = (float)(1 - d), d = ema_decay or -- ema_warmup -- min(ema_decay, (1 + t) / (10 + t)).
+ *   pass 3  gc = g * scale[v], then
+ *           momentum  a = mom*a + gc;  w = w - lr*a                       (the bits of sqdet_optimizer_step)
+ *           nesterov  a = mom*a + gc;  w = w - lr*(gc + mom*a)
+ *           adamw     m = b1*m + (1-b1)*gc;  v = b2*v + (1-b2)*(gc*gc);  u = (m*c1) / (sqrtf(v*c2) + eps);
+ *                     decay != 0: u = u + decay*w;  w = w - lr*u          (m = accum, v = accum2; 1-b1, 1-b2 rounded once)
+ *           ema       e = e + om*(w - e), on the value just written.
+ * accum2: adamw's second moment, else NULL; ema: NULL without EMA (ema_decay 0).  16-byte vectors where a segment's offset and
+ * every base pointer allow it, a scalar path elsewhere -- the same bits; gaps between segments are neither read as data nor
+ * written in any buffer.  SQDET_EINVAL, nothing launched: a rule outside 0..2, a clip outside 0..1, accum2 NULL under adamw, ema
+ * NULL with ema_decay > 0, momentum / beta1 / beta2 / ema_decay outside [0, 1), eps not finite and positive, a variable's decay
+ * negative or non-finite. */
+enum { SQDET_OPT_MOMENTUM = 0, SQDET_OPT_NESTEROV = 1, SQDET_OPT_ADAMW = 2 };
+enum { SQDET_CLIP_PER_VARIABLE = 0, SQDET_CLIP_GLOBAL = 1 };
+typedef struct {
+  int rule;            /* SQDET_OPT_* */
+  int clip;            /* SQDET_CLIP_* */
+  float momentum, beta1, beta2, eps;
+  double ema_decay;    /* 0: no EMA */
+  int ema_warmup;      /* != 0: d = min(ema_decay, (1 + t) / (10 + t)) */
+} sqdet_optimizer_options_t;
+int sqdet_optimizer_step_opt(sqdet_optimizer_t* opt, float* params, float* grads, float* accum, float* accum2, float* ema,
+                             double* state, void* workspace, float lr, float max_grad_norm, float grad_scale,
+                             const sqdet_optimizer_options_t* options, int32_t* found_inf, sqdet_stream_t stream);
+
 /* ------------------------------------------------------------- network --
  * Replaces SqueezeDet.__init__/_add_forward_graph (nets/squeezeDet.py:19-79,
  * nets/squeezeDetPlus.py:19-79) + the sess.run([det_boxes,det_probs,det_class])

@@ -101,6 +101,7 @@ SIGNATURES = {
     "sqdet_optimizer_destroy": (None, [vp]),
     "sqdet_optimizer_workspace_bytes": (sz, [vp]),
     "sqdet_optimizer_step": (ci, [vp, vp, vp, vp, vp, cf, cf, cf, cf, vp, vp]),
+    "sqdet_optimizer_step_opt": (ci, [vp] * 8 + [cf, cf, cf, vp, vp, vp]),
     "sqdet_net_create": (ci, [C.POINTER(vp), ci, ci, ci, ci, ci, ci, ci]),
     "sqdet_net_destroy": (None, [vp]),
     "sqdet_net_num_params": (ci, [vp]),

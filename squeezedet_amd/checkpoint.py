@@ -6,6 +6,8 @@ A checkpoint of step S is a PAIR of files:
   * ``<train_dir>/state/step-<S>.npz``: what continuing needs on top -- the trainer's and the reader's state_dict() and a few
     run settings (``extra``).  It sits in a sub-directory on purpose: eval.latest_checkpoint globs '*-*.npz' in the directory
     itself and must never pick a state file up.
+A run that keeps an EMA of its weights (train.py --ema_decay) adds ``<train_dir>/ema/model.ckpt-<S>.npz``: the model file with the
+trainable variables taken from the average -- written before the raw model file, pruned with its pair, read by eval.py --ema.
 Both are written under a hidden temporary name and moved into place with os.replace, because eval.py polls while training
 writes; the model file goes last, so a checkpoint that eval.py can see is always complete.
 """
@@ -18,6 +20,7 @@ import numpy as np
 from . import weights
 
 MODEL_FMT, STATE_FMT = "model.ckpt-%d.npz", os.path.join("state", "step-%d.npz")
+EMA_DIR = "ema"
 
 
 def _steps(paths):
@@ -65,6 +68,12 @@ def save(train_dir, step, model, trainer, reader, extra=None, keep=0):
     tmp = os.path.join(os.path.dirname(state_path), ".tmp-%d.npz" % os.getpid())
     np.savez(tmp, **arrays)
     os.replace(tmp, state_path)
+    if getattr(trainer, "flat_ema", None) is not None:      # (--ema_decay: ahead of the raw model file, so a visible checkpoint has it)
+        path = ema_path(train_dir, step)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        tmp = os.path.join(os.path.dirname(path), ".tmp-%d.npz" % os.getpid())
+        weights.save_params(tmp, dict(model.params, **trainer.ema_params()))
+        os.replace(tmp, path)
     tmp = os.path.join(train_dir, ".tmp-%d.npz" % os.getpid())
     weights.save_params(tmp, model)
     os.replace(tmp, model_path)
@@ -72,7 +81,20 @@ def save(train_dir, step, model, trainer, reader, extra=None, keep=0):
         for s in steps(train_dir)[:-int(keep)]:
             for p in paths(train_dir, s):
                 os.remove(p)
+            if os.path.exists(ema_path(train_dir, s)):
+                os.remove(ema_path(train_dir, s))
     return model_path
+
+
+def ema_path(train_dir, step):
+    """The EMA weights of step `step` (a run with --ema_decay): every model variable, the trainable ones averaged.  In a
+    sub-directory, like the state file: eval.latest_checkpoint's '*-*.npz' glob over <train_dir> must not pick it up."""
+    return os.path.join(train_dir, EMA_DIR, MODEL_FMT % int(step))
+
+
+def ema_of(model_path):
+    """<dir>/model.ckpt-<S>.npz -> <dir>/ema/model.ckpt-<S>.npz (eval.py --ema on a file)."""
+    return os.path.join(os.path.dirname(model_path), EMA_DIR, os.path.basename(model_path))
 
 
 def load(train_dir, step, model, trainer, reader):

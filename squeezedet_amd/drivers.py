@@ -153,6 +153,70 @@ def loss_policy(a, mc):
     return policy, off
 
 
+def add_optim_args(ap):
+    """The update step's flags (train.py, tools/bench_train.py).  A flag that is not given leaves no
+    attribute behind: optim.optim_policy supplies the defaults."""
+    import argparse
+    from .optim import CLIP_MODES, RULES, SCHEDULES
+    S = argparse.SUPPRESS
+    ap.add_argument("--optimizer", default=S, choices=RULES,
+                    help="momentum (default): the reference's MomentumOptimizer; nesterov: with the look-ahead; adamw: Adam with bias "
+                         "correction and decoupled weight decay")
+    ap.add_argument("--adam_beta1", type=float, default=S, metavar="B", help="adamw: decay of the first moment (default 0.9)")
+    ap.add_argument("--adam_beta2", type=float, default=S, metavar="B", help="adamw: decay of the second moment (default 0.999)")
+    ap.add_argument("--adam_eps", type=float, default=S, metavar="E", help="adamw: added to the root of the second moment (default 1e-8)")
+    ap.add_argument("--weight_decay", type=float, default=S, metavar="X", help="overrides the config's WEIGHT_DECAY (kernels only)")
+    ap.add_argument("--clip_norm", default=S, choices=CLIP_MODES,
+                    help="per_variable (default): tf.clip_by_norm on every variable; global: tf.clip_by_global_norm over all of them")
+    ap.add_argument("--lr", type=float, default=S, metavar="X", help="the base learning rate (default: the config's LEARNING_RATE)")
+    ap.add_argument("--lr_schedule", default=S, choices=SCHEDULES,
+                    help="staircase (default): the reference's LR_DECAY_FACTOR every DECAY_STEPS; constant; cosine, linear: from the base "
+                         "rate down to base * --min_lr_ratio over --lr_total_steps")
+    ap.add_argument("--warmup_steps", type=int, default=S, metavar="N",
+                    help="the first N updates run at --warmup_factor .. 1 times the schedule, linearly (default 0)")
+    ap.add_argument("--warmup_factor", type=float, default=S, metavar="F", help="the multiplier of update 0 under --warmup_steps (default 0.001)")
+    ap.add_argument("--min_lr_ratio", type=float, default=S, metavar="R", help="cosine, linear: the final rate over the base rate (default 0)")
+    ap.add_argument("--lr_total_steps", type=int, default=S, metavar="T", help="cosine, linear: the update at which the final rate is reached (default --max_steps)")
+    ap.add_argument("--ema_decay", type=float, default=S, metavar="D",
+                    help="D > 0: keep an exponential moving average of the trainable variables, e += (1 - D) * (w - e) after every update; "
+                         "checkpoints add ema/model.ckpt-<step>.npz, which eval.py --ema reads (default 0: none)")
+    ap.add_argument("--ema_warmup", action="store_true", default=S, help="--ema_decay: use min(D, (1 + t) / (10 + t)) at update t")
+
+
+def check_optim_args(ap, a):
+    import math
+    given = lambda key: hasattr(a, key)
+    rule, sched = getattr(a, "optimizer", "momentum"), getattr(a, "lr_schedule", "staircase")
+    for key in ("adam_beta1", "adam_beta2", "adam_eps"):
+        if given(key) and rule != "adamw":
+            ap.error("--%s needs --optimizer adamw" % key)
+    for key in ("min_lr_ratio", "lr_total_steps"):
+        if given(key) and sched not in ("cosine", "linear"):
+            ap.error("--%s needs --lr_schedule cosine or linear" % key)
+    fin = lambda key, default: float(getattr(a, key, default)) if math.isfinite(float(getattr(a, key, default))) else float("nan")
+    for key in ("adam_beta1", "adam_beta2"):
+        if not (0.0 <= fin(key, 0.9) < 1.0):
+            ap.error("--%s B needs 0 <= B < 1" % key)
+    if not (fin("adam_eps", 1e-8) > 0.0):
+        ap.error("--adam_eps E needs a finite E > 0")
+    if not (fin("weight_decay", 0.0) >= 0.0):
+        ap.error("--weight_decay X needs a finite X >= 0")
+    if not (fin("lr", 1.0) > 0.0):
+        ap.error("--lr X needs a finite X > 0")
+    if getattr(a, "warmup_steps", 0) < 0:
+        ap.error("--warmup_steps N needs N >= 0")
+    if not (0.0 <= fin("warmup_factor", 0.001) <= 1.0):
+        ap.error("--warmup_factor F needs 0 <= F <= 1")
+    if not (0.0 <= fin("min_lr_ratio", 0.0) <= 1.0):
+        ap.error("--min_lr_ratio R needs 0 <= R <= 1")
+    if getattr(a, "lr_total_steps", 1) < 1:
+        ap.error("--lr_total_steps T needs T >= 1")
+    if not (0.0 <= fin("ema_decay", 0.0) < 1.0):
+        ap.error("--ema_decay D needs 0 <= D < 1")
+    if getattr(a, "ema_warmup", False) and not fin("ema_decay", 0.0) > 0.0:
+        ap.error("--ema_warmup needs --ema_decay D with D > 0")
+
+
 def add_nms_args(ap):
     """--nms, --nms_overlap, --nms_sigma, --nms_score_floor, --nms_class_agnostic (eval.py, demo.py).  A flag that is not given
     leaves no attribute behind: nms_policy supplies the defaults."""

@@ -921,6 +921,45 @@ class MomentumOptimizer:
             pass
 
 
+from .optim import CLIP_MODES, RULES      # sqdet_optimizer_options_t.rule / .clip, by index (optim imports no torch: the flags use the same lists)
+
+
+class _OptimizerOptions(C.Structure):
+    _fields_ = [("rule", C.c_int), ("clip", C.c_int), ("momentum", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("ema_decay", C.c_double), ("ema_warmup", C.c_int)]
+
+
+class Optimizer(MomentumOptimizer):
+    """sqdet_optimizer_step_opt: Momentum / Nesterov / AdamW, per-variable or global clip, optional EMA of the
+    weights, over the segment table and workspace of MomentumOptimizer.  options: a dict with any of rule ('momentum' |
+    'nesterov' | 'adamw'), clip ('per_variable' | 'global'), momentum, beta1, beta2, eps, ema_decay, ema_warmup -- optim.OPTIONS
+    holds the defaults.  `state` is the device state, float64 [4] = (t, beta1^t, beta2^t, unused), starting at (0, 1, 1)."""
+
+    def __init__(self, offsets, counts, decays, device, options=None):
+        from .optim import OPTIONS
+        o = dict(OPTIONS, **(options or {}))
+        unknown = sorted(set(o) - set(OPTIONS))
+        if unknown:
+            raise _lib.SqdetError("Optimizer: unknown option %s" % ", ".join(unknown))
+        if o["rule"] not in RULES or o["clip"] not in CLIP_MODES:
+            raise _lib.SqdetError("Optimizer: rule is one of %s, clip one of %s" % (", ".join(RULES), ", ".join(CLIP_MODES)))
+        MomentumOptimizer.__init__(self, offsets, counts, decays, device)
+        self.options = o
+        self._o = _OptimizerOptions(RULES.index(o["rule"]), CLIP_MODES.index(o["clip"]), float(o["momentum"]), float(o["beta1"]),
+                                    float(o["beta2"]), float(o["eps"]), float(o["ema_decay"]), int(bool(o["ema_warmup"])))
+        self.state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=device)
+
+    def step(self, params, grads, accum, lr, max_grad_norm, grad_scale=1.0, accum2=None, ema=None, found_inf=None):
+        """accum2: AdamW's second moment; ema: the averaged weights (options['ema_decay'] > 0).  found_inf as MomentumOptimizer.step:
+        a skipped step leaves params, accum, accum2, ema and the state untouched."""
+        opt = lambda t, what, dt=torch.float32: _dev(t, what, dt) if t is not None else None
+        check(lib().sqdet_optimizer_step_opt(self._h, _dev(params, "params", torch.float32), _dev(grads, "grads", torch.float32),
+                                             _dev(accum, "accum", torch.float32), opt(accum2, "accum2"), opt(ema, "ema"),
+                                             _dev(self.state, "state", torch.float64), _dev(self.ws, "ws"), float(lr),
+                                             float(max_grad_norm), float(grad_scale), C.cast(C.pointer(self._o), C.c_void_p),
+                                             opt(found_inf, "found_inf", torch.int32), stream_ptr()), "sqdet_optimizer_step_opt")
+
+
 def build_labels(anchor_box, gt_boxes, gt_classes, gt_counts, classes, device=None):
     """Anchor assignment + dense label tensors on the GPU (imdb.py:195-239, train.py:163-224).
     anchor_box: mc.ANCHOR_BOX [A,4] float64; gt_boxes [B,M,4] float64 (cx,cy,w,h in network-input pixels, rows

@@ -104,7 +104,7 @@ class _TrainerBase:
     the optimizer kernel and halves the scale; `growth_interval` clean steps double it."""
 
     def __init__(self, model, process_group=None, loss_scale=1024.0, growth_interval=200, lazy_overflow_check=None,
-                 global_num_objects=False, seed=0, overlap_wgrad=True):
+                 global_num_objects=False, seed=0, overlap_wgrad=True, optim=None):
         if model.dtype not in (torch.float32, torch.float16):
             raise SqdetError("training runs in float32 (the reference's training dtype) or float16 (mixed precision)")
         self.adt = model.dtype                       # activation dtype
@@ -165,7 +165,18 @@ class _TrainerBase:
             self.gview[n] = self.flat_grads[off:off + c].view(shp)
         model._packed.clear()
         model._plan_stale = True
-        self.opt = ops.MomentumOptimizer(offs, cnts, decs, self.dev)
+        # optim: a policy record of squeezedet_amd.optim -- another rule, clip mode or schedule, an EMA of the
+        # weights; None: the reference's update, the launches, buffers and state keys of every run before the policy existed
+        self.optim, self.flat_accum2, self.flat_ema = (dict(optim) if optim is not None else None), None, None
+        if self.optim is None:
+            self.opt = ops.MomentumOptimizer(offs, cnts, decs, self.dev)
+        else:
+            from .optim import trainer_options
+            self.opt = ops.Optimizer(offs, cnts, decs, self.dev, trainer_options(self.optim))
+            if self.optim["optimizer"] == "adamw":
+                self.flat_accum2 = torch.zeros(o, dtype=torch.float32, device=self.dev)
+            if self.optim["ema_decay"] > 0.0:
+                self.flat_ema = self.flat_params.clone()
         self.found_inf = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self._labels_forked = False
         self._flag_host, self._flag_event = None, None     # lazy_overflow_check's pinned flag + its event, made at the first lazy step
@@ -175,6 +186,9 @@ class _TrainerBase:
             src0 = torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0
             torch.distributed.broadcast(self.flat_params, src=src0, group=self.pg)
             torch.distributed.broadcast(self.flat_accum, src=src0, group=self.pg)
+            for t in (self.flat_accum2, self.flat_ema, self.opt.state if self.optim is not None else None):
+                if t is not None:
+                    torch.distributed.broadcast(t, src=src0, group=self.pg)
             # ... and from rank 0's FROZEN variables (conv1 of SqueezeDet, conv1 .. res3d and the batch-norm statistics of ResNet50):
             # they are not in the flat buffers, and a replica that loaded other values would compute other gradients for good
             for n in model.params:
@@ -254,6 +268,9 @@ class _TrainerBase:
 
     def learning_rate(self):
         mc = self.mc
+        if getattr(self, "optim", None) is not None:
+            from .optim import lr_at
+            return lr_at(self.global_step, self.optim, mc)
         return mc.LEARNING_RATE * mc.LR_DECAY_FACTOR ** (self.global_step // mc.DECAY_STEPS)   # staircase decay
 
     def _labels(self, B, input_mask, box_delta_input, box_input, labels, num_objects=None, num_objects_is_global=False):
@@ -316,8 +333,12 @@ class _TrainerBase:
                 # float32 overflow raises here with global_step / skipped_steps describing exactly the updates applied
                 self.flush()
             # (the kernel skips the whole update when any gradient norm is inf / NaN, in either precision: found_inf tells)
-            self.opt.step(self.flat_params, self.flat_grads, self.flat_accum, self.learning_rate(), self.mc.MOMENTUM,
-                          self.mc.MAX_GRAD_NORM, grad_scale, found_inf=self.found_inf)
+            if self.optim is None:
+                self.opt.step(self.flat_params, self.flat_grads, self.flat_accum, self.learning_rate(), self.mc.MOMENTUM,
+                              self.mc.MAX_GRAD_NORM, grad_scale, found_inf=self.found_inf)
+            else:
+                self.opt.step(self.flat_params, self.flat_grads, self.flat_accum, self.learning_rate(), self.mc.MAX_GRAD_NORM,
+                              grad_scale, accum2=self.flat_accum2, ema=self.flat_ema, found_inf=self.found_inf)
             # packed / BN-folded kernels of the layers whose variables just changed are stale; the frozen layers'
             # (conv1 of SqueezeDet, conv1 .. res3d of ResNet50 -- re-folded and re-packed every step before) are not
             tr = self.model.trainable
@@ -382,13 +403,35 @@ class _TrainerBase:
     def state_dict(self):
         """Everything a run needs to continue bitwise, as host values: the flat float32 variables and momentum, the variable
         names and shapes they were packed from, global_step, the mixed-precision loss scale with its counters, and the dropout
-        counter stream (seed, _mask_calls).  Settles a pending overflow flag first (flush)."""
+        counter stream (seed, _mask_calls); under an optim policy also flat_accum2 (AdamW), flat_ema (an EMA) and optim_state (the
+        device's float64 step count and beta powers), each only when it exists.  Settles a pending overflow flag first (flush)."""
         self.flush()
-        return dict(names=list(self.names), shapes=[list(self.view[n].shape) for n in self.names],
-                    flat_params=self.flat_params.detach().cpu().numpy().copy(), flat_accum=self.flat_accum.detach().cpu().numpy().copy(),
-                    global_step=int(self.global_step), loss_scale=float(self.loss_scale), clean_steps=int(self._clean_steps),
-                    skipped_steps=int(self.skipped_steps), seed=int(self.seed), rank=int(self.rank), mask_calls=int(self._mask_calls),
-                    half=bool(self.half))
+        d = dict(names=list(self.names), shapes=[list(self.view[n].shape) for n in self.names],
+                 flat_params=self.flat_params.detach().cpu().numpy().copy(), flat_accum=self.flat_accum.detach().cpu().numpy().copy(),
+                 global_step=int(self.global_step), loss_scale=float(self.loss_scale), clean_steps=int(self._clean_steps),
+                 skipped_steps=int(self.skipped_steps), seed=int(self.seed), rank=int(self.rank), mask_calls=int(self._mask_calls),
+                 half=bool(self.half))
+        for key, t in self._optim_arrays().items():       # (a trainer without an optim policy adds nothing: the twelve keys above)
+            d[key] = t.detach().cpu().numpy().copy()
+        return d
+
+    def _optim_arrays(self):
+        """The device arrays an optim policy adds to the state, by state_dict key; only those that exist."""
+        if getattr(self, "optim", None) is None:
+            return {}
+        arrays = dict(flat_accum2=self.flat_accum2, flat_ema=self.flat_ema, optim_state=self.opt.state)
+        return {k: t for k, t in arrays.items() if t is not None}
+
+    def ema_params(self):
+        """{name: view of the EMA buffer, shaped like self.view[name]} (--ema_decay)."""
+        if self.flat_ema is None:
+            raise SqdetError("this trainer keeps no EMA of the weights (optim policy: ema_decay 0)")
+        base = self.flat_params.data_ptr()
+        out = {}
+        for n in self.names:
+            off = (self.view[n].data_ptr() - base) // 4
+            out[n] = self.flat_ema[off:off + self.view[n].numel()].view(self.view[n].shape)
+        return out
 
     def load_state_dict(self, d):
         """Restores state_dict()'s values into this trainer (same model, same precision).  The frozen variables are not part of
@@ -402,10 +445,19 @@ class _TrainerBase:
         p, a = np.asarray(d["flat_params"], np.float32), np.asarray(d["flat_accum"], np.float32)
         if p.shape != (self.total,) or a.shape != (self.total,):
             raise SqdetError("trainer state: flat buffers of %s / %s elements, expected %d" % (p.shape, a.shape, self.total))
+        mine = self._optim_arrays()
+        for key in ("flat_accum2", "flat_ema", "optim_state"):
+            if (key in d) != (key in mine):
+                raise SqdetError("trainer state: %s is %s the saved state and %s this trainer (another optimizer policy)"
+                                 % (key, "in" if key in d else "not in", "in" if key in mine else "not in"))
+            if key in d and tuple(np.asarray(d[key]).shape) != tuple(mine[key].shape):
+                raise SqdetError("trainer state: %s of shape %s, expected %s" % (key, np.asarray(d[key]).shape, tuple(mine[key].shape)))
         self.flush()
         with torch.cuda.device(self.dev):
             self.flat_params.copy_(torch.from_numpy(p))
             self.flat_accum.copy_(torch.from_numpy(a))
+            for key, t in mine.items():
+                t.copy_(torch.from_numpy(np.ascontiguousarray(d[key], np.float64 if key == "optim_state" else np.float32)))
         self.global_step, self.loss_scale = int(d["global_step"]), float(d["loss_scale"])
         self._clean_steps, self.skipped_steps = int(d["clean_steps"]), int(d["skipped_steps"])
         self.seed, self._mask_calls = int(d["seed"]) - int(d["rank"]) + self.rank, int(d["mask_calls"])

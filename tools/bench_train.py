@@ -56,8 +56,10 @@ def parse_args(argv=None):
                     help="with --augment: a batch image is a mosaic of four images with probability P (train.py --mosaic P)")
     from squeezedet_amd import drivers
     drivers.add_loss_args(ap)             # --bbox_loss, --focal_gamma, --bbox_loss_coef as train.py takes them
+    drivers.add_optim_args(ap)            # --optimizer ... --ema_warmup as train.py takes them
     args = ap.parse_args(argv)
     drivers.check_loss_args(ap, args)
+    drivers.check_optim_args(ap, args)
     if not 0.0 <= args.mosaic <= 1.0 or (args.mosaic > 0.0 and not args.augment):
         ap.error("--mosaic P needs 0 <= P <= 1 and --augment")
     if args.batch <= 0:
@@ -77,6 +79,16 @@ def make_config(args):
     return mc, loss_policy
 
 
+def make_optim(args, mc):
+    """The optimizer policy as train.py records it (sets mc.WEIGHT_DECAY), or None without any of its flags: the trainer's own
+    update.  cosine / linear without --lr_total_steps run over this benchmark's own length, as train.py's over --max_steps."""
+    from squeezedet_amd.optim import optim_policy
+    if not hasattr(args, "max_steps"):
+        args.max_steps = args.warmup + args.steps
+    optim, optim_off = optim_policy(args, mc)
+    return None if optim == optim_off else optim
+
+
 def main():
     args = parse_args()
     rank, local_rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -90,11 +102,12 @@ def main():
     from squeezedet_amd import nets, synthetic
     from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer, VGG16ConvDetTrainer
     mc, loss_policy = make_config(args)
+    optim = make_optim(args, mc)
     cls, trainer = {"squeezeDet": (nets.SqueezeDet, SqueezeDetTrainer), "resnet50": (nets.ResNet50ConvDet, ResNet50ConvDetTrainer),
                     "vgg16": (nets.VGG16ConvDet, VGG16ConvDetTrainer)}[args.arch]
     model = cls(mc, gpu_id=str(local_rank), dtype=torch.float32 if args.dtype == "f32" else torch.float16)
     model.load_params(synthetic.synthetic_params(model, seed=0))      # same weights on every rank
-    tr = trainer(model, lazy_overflow_check=True)
+    tr = trainer(model, lazy_overflow_check=True, optim=optim)
     x = synthetic.synthetic_images(args.batch, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, seed=100 + rank).to(dev)
     # ground truth lives on the device; the anchor assignment + dense label build (imdb.py:195-239,
     # train.py:163-224) runs on the GPU inside every step, like the reference's per-batch _load_data
@@ -143,7 +156,7 @@ def main():
                                    + (" + mosaic %g" % args.mosaic if args.mosaic > 0.0 else "")) if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
-                          "loss": loss_policy, "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
+                          "loss": loss_policy, **({"optim": optim} if optim is not None else {}), "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
                           "losses": {k: float(out[k]) for k in ("class_loss", "conf_loss", "bbox_loss")}}))
     if world > 1:
         dist.destroy_process_group()

@@ -8,6 +8,7 @@ with on-device summaries.
     python train.py ... --resume                                                  # continue from the newest checkpoint
     python train.py ... --anchor_shapes anchors.json --anchor_report             # shapes from tools/fit_anchors.py; coverage report
     python train.py ... --bbox_loss giou --focal_gamma 2                          # a GIoU box term and a focal class term
+    python train.py ... --optimizer adamw --lr_schedule cosine --warmup_steps 500 --ema_decay 0.999   # AdamW, warm-up + cosine, EMA weights
 
 Per step as the reference (train.py:266-330): a summary step (step % summary_step == 0) runs the eager trainer step with the
 activations kept and hands it to squeezedet_amd.summary.TrainSummary (-> <train_dir>/summaries.jsonl, in place of TF event
@@ -30,7 +31,14 @@ probability P, a mosaic of four training images (one sqdet_augment_bgr_mosaic la
 `mosaic`, and --resume under another P is refused (a checkpoint without the key was trained with 0).  --bbox_loss
 {delta_l2,iou,giou,diou,ciou}, --focal_gamma G and --bbox_loss_coef X choose the box term, the class term's focal exponent and
 mc.LOSS_COEF_BBOX (the defaults are the reference's loss); the three are recorded under the key `loss`, and
---resume under another loss policy is refused (a checkpoint without the key was trained with the defaults).  --anchor_report writes
+--resume under another loss policy is refused (a checkpoint without the key was trained with the defaults).  --optimizer
+{momentum,nesterov,adamw} (--adam_beta1, --adam_beta2, --adam_eps), --weight_decay, --clip_norm {per_variable,global}, --lr,
+--lr_schedule {staircase,constant,cosine,linear} (--warmup_steps, --warmup_factor, --min_lr_ratio, --lr_total_steps) and --ema_decay D
+(--ema_warmup) choose the update rule, the clip, the learning-rate schedule and an exponential moving average of the weights (DESIGN.md
+section 3.18; the defaults are the reference's update, and a run without any of them launches what it always launched).  A policy that
+differs from the defaults is recorded under the key `optim`, and --resume under another one -- --lr_total_steps included -- is refused.
+With --ema_decay every checkpoint adds <train_dir>/ema/model.ckpt-<step>.npz, the model file with the averaged weights, which eval.py
+--ema reads.  --anchor_report writes
 <train_dir>/anchor_coverage.json (squeezedet_amd.anchors.dataset_coverage of the training set) once, before the first step.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
@@ -83,9 +91,11 @@ def parse_args(argv=None):
                     help="with probability P a batch image is a mosaic: four training images, each cropped into its own pane of the "
                          "network input (default 0: never)")
     drivers.add_loss_args(ap)
+    drivers.add_optim_args(ap)
     a = ap.parse_args(argv)
     drivers.check_dataset_args(ap, a)
     drivers.check_loss_args(ap, a)
+    drivers.check_optim_args(ap, a)
     if not 0.0 <= getattr(a, "mosaic", 0.0) <= 1.0:
         ap.error("--mosaic P needs 0 <= P <= 1")
     if a.resume and a.overwrite:
@@ -109,13 +119,18 @@ def augment_policy(a, mc=None):
     return policy
 
 
-def check_resume_record(saved, extra, loss_off):
+def check_resume_record(saved, extra, loss_off, optim_off=None):
     """--resume: what the checkpoint records (`saved`) against what this run asks for (`extra`); SystemExit on the first key that
-    differs.  A checkpoint from before a key existed was trained with that key's defaults (`loss_off`: drivers.loss_policy's)."""
+    differs.  A checkpoint from before a key existed was trained with that key's defaults (`loss_off`: drivers.loss_policy's;
+    `optim_off`: optim.optim_policy's)."""
     saved = dict(saved)
     saved.setdefault("augment", AUGMENT_OFF)
     saved.setdefault("mosaic", 0.0)
     saved.setdefault("loss", loss_off)
+    if optim_off is not None:             # (a run without the optimizer flags records no `optim` key: its state file is what it was)
+        saved.setdefault("optim", optim_off)
+        extra = dict(extra)
+        extra.setdefault("optim", optim_off)
     for key, now in extra.items():
         if saved.get(key) != now:
             raise SystemExit("--resume: the checkpoint was trained with %s %r, this run asks for %r" % (key, saved.get(key), now))
@@ -236,17 +251,22 @@ class Run:
         if mosaic > 0.0 and not mc.DATA_AUGMENTATION:
             raise SystemExit("--mosaic needs a config with DATA_AUGMENTATION on")
         loss, loss_off = drivers.loss_policy(a, mc)         # (before the model is built: a padded head's config is a copy of mc)
+        from squeezedet_amd.optim import optim_policy
+        optim, optim_off = optim_policy(a, mc)              # (sets mc.WEIGHT_DECAY: before the trainer reads it)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
-        self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale)
+        # (a run without any of the optimizer flags takes the trainer's own path: the launches and state keys of every run before)
+        self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale, optim=None if optim == optim_off else optim)
         images, rois = load_dataset(a, mc)
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
         self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE),
                           anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy, mosaic=mosaic, loss=loss)
+        if optim != optim_off:
+            self.extra["optim"] = optim
         self.first = 0
         if resume_step is not None:
-            check_resume_record(checkpoint.read_extra(a.train_dir, resume_step), self.extra, loss_off)
+            check_resume_record(checkpoint.read_extra(a.train_dir, resume_step), self.extra, loss_off, optim_off)
             checkpoint.load(a.train_dir, resume_step, self.model, self.tr, self.reader)
             self.first = resume_step + 1
         self.anchors = torch.from_numpy(np.asarray(mc.ANCHOR_BOX, np.float64)).to(dev)

@@ -661,6 +661,36 @@ int sqdet_build_labels(const double* anchors_f64, const double* gt_boxes_f64, co
                        int* anchor_index, int batch, int num_anchors, int max_objects, int classes,
                        sqdet_stream_t stream);
 
+/* sqdet_build_labels_opt: OURS -- more than one positive anchor per object (squeezedet_amd/csrc/assign.hip).  Every box keeps
+ * the anchor sqdet_build_labels gives it (anchor_index and that anchor's rows are bit for bit sqdet_build_labels'); the anchors
+ * no box claimed are then offered to the boxes by one of two rules, per image, boxes i < gt_counts[b] (clipped to [0, max_objects]):
+ *   mode 1 (iou)   anchor a is eligible for box i iff iou(i,a) > 0, iou(i,a) >= iou_thresh and a is among the first max_per_box
+ *                  of box i's anchors with iou > 0 in the order larger IoU, ties -> higher index (taken over all anchors, claimed
+ *                  ones included): at most max_per_box + 1 positives per box; iou_thresh 0 is a plain top-K;
+ *   mode 2 (atss)  candidates: per shape s (anchor a has shape a % anchors_per_grid) the topk anchors of smallest
+ *                  d = (gx-ax)*(gx-ax) + (gy-ay)*(gy-ay), ties -> lower index, all of them if the shape has fewer; mean = the
+ *                  candidates' IoUs summed in ascending anchor index / their number, var = sum of (iou-mean)*(iou-mean) in the
+ *                  same order / their number; a candidate is eligible iff iou > 0, e = iou - mean >= 0 and e*e >= var, and its
+ *                  centre lies strictly inside the box (gx - 0.5*gw < ax < gx + 0.5*gw, likewise in y).
+ * An unclaimed anchor eligible for several boxes goes to the box of largest IoU, ties -> the lower box index.  iou(i,a) is the
+ * float64 expression of util.batch_iou, as in sqdet_build_labels.  Every positive anchor gets sqdet_build_labels' rows (mask 1,
+ * the float64 delta rounded once, the box, the one-hot class if 0 <= class < classes); everything else is 0.
+ * Further outputs (device int32, fully written): assigned_box [batch,num_anchors] the box index or -1; positives
+ * [batch,max_objects] the number of positives per box, 0 behind the image's count.  workspace: device scratch of
+ * sqdet_build_labels_opt_workspace_bytes(...) bytes (0: bad arguments), 8-byte aligned; anchors_f64 16-byte aligned.
+ * Five launches (sqdet_build_labels' three and two more), no memset node, no synchronisation: capturable in a hipGraph.
+ * opt NULL, a mode other than 1 / 2, iou_thresh not >= 0, max_per_box / topk < 1, num_anchors % anchors_per_grid != 0 or any
+ * argument sqdet_build_labels refuses: SQDET_EINVAL (its limits: SQDET_EUNSUPPORTED); max_per_box > 64, topk > 32 or
+ * anchors_per_grid * min(topk, num_anchors / anchors_per_grid) > 1024: SQDET_EUNSUPPORTED.  Nothing is launched on either. */
+enum { SQDET_ASSIGN_IOU = 1, SQDET_ASSIGN_ATSS = 2 };
+typedef struct { int mode; double iou_thresh; int max_per_box; int topk; } sqdet_assign_options_t;
+size_t sqdet_build_labels_opt_workspace_bytes(int batch, int num_anchors, int max_objects, int anchors_per_grid,
+                                              const sqdet_assign_options_t* opt);
+int sqdet_build_labels_opt(const double* anchors_f64, const double* gt_boxes_f64, const int* gt_classes, const int* gt_counts,
+                           float* input_mask, float* box_delta_input, float* box_input, float* labels, int* anchor_index,
+                           int* assigned_box, int* positives, void* workspace, int batch, int num_anchors, int max_objects,
+                           int classes, int anchors_per_grid, const sqdet_assign_options_t* opt, sqdet_stream_t stream);
+
 /* --------------------------------------------------------- anchor shapes --
  * OURS for the fitting: the reference ships fixed anchor shapes (config/kitti_squeezeDet_config.py:45-79, the nine k-means
  * shapes of KITTI's objects) and no way to get them for another dataset.

@@ -120,6 +120,8 @@ SIGNATURES = {
     "sqdet_net_set_probe": (ci, [vp, ci, ci]),
     "sqdet_net_read_probe": (ci, [vp, C.POINTER(cf), ci, C.POINTER(ci)]),
     "sqdet_build_labels": (ci, [vp] * 9 + [ci] * 4 + [vp]),
+    "sqdet_build_labels_opt_workspace_bytes": (sz, [ci, ci, ci, ci, vp]),
+    "sqdet_build_labels_opt": (ci, [vp] * 12 + [ci] * 5 + [vp, vp]),
     "sqdet_anchor_kmeans_workspace_bytes": (sz, [ci, ci, ci]),
     "sqdet_anchor_kmeans": (ci, [vp] * 7 + [ci] * 4 + [vp]),
     "sqdet_anchor_coverage": (ci, [vp] * 7 + [ci] * 3 + [vp]),

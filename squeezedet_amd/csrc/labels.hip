@@ -22,61 +22,21 @@
 //     dtype of the reference's placeholders (nn_skeleton.py:86-97).
 // A box assigned to an anchor that an earlier box of the same image already owns cannot happen here (the
 // claimed set is per image), which is exactly the duplicate filter of train.py:175-186.
-#include "common.h"
+#include "labels_common.h"
 
 namespace sqdet {
-
-struct Cand {
-  double v;
-  int idx;
-};
-
-// better(a, b): a wins over b.  MAXMODE: larger v, ties -> higher idx.  else: smaller v, ties -> lower idx.
-template <bool MAXMODE>
-__device__ __forceinline__ bool better(const Cand& a, const Cand& b) {
-  if (a.idx < 0) return false;
-  if (b.idx < 0) return true;
-  if (MAXMODE) return a.v > b.v || (a.v == b.v && a.idx > b.idx);
-  return a.v < b.v || (a.v == b.v && a.idx < b.idx);
-}
-
-template <bool MAXMODE>
-__device__ __forceinline__ Cand block_best(Cand c, Cand* red) {
-  // wave reduction, then one candidate per wave through LDS
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Cand o;
-    o.v = __shfl_down(c.v, off);
-    o.idx = __shfl_down(c.idx, off);
-    if (better<MAXMODE>(o, c)) c = o;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();                       // red[] free (previous use finished)
-  if (lane == 0) red[wave] = c;
-  __syncthreads();
-  Cand b = red[0];
-  for (int w = 1; w < (int)(blockDim.x >> 6); ++w)
-    if (better<MAXMODE>(red[w], b)) b = red[w];
-  return b;
-}
 
 // The best anchor of box g among the anchors whose bit in `taken` is clear (taken == nullptr: among all): largest
 // overlap > 0, else nearest.  All threads of the workgroup call it and get the result.
 __device__ int best_anchor(const double* __restrict__ anchors, int A, const double* g, const unsigned int* taken, Cand* red) {
-    const double gx = g[0], gy = g[1], gw = g[2], gh = g[3];
-    const double gl = gx - 0.5 * gw, gr = gx + 0.5 * gw, gtp = gy - 0.5 * gh, gb = gy + 0.5 * gh;
-    const double garea = gw * gh;
+    const GtBox q = gt_box(g);
+    const double gx = q.gx, gy = q.gy, gw = q.gw, gh = q.gh;
     Cand c;
     c.v = 0.0; c.idx = -1;
     for (int a = threadIdx.x; a < A; a += blockDim.x) {
       if (taken && (taken[a >> 5] & (1u << (a & 31)))) continue;
       const double ax = anchors[a * 4], ay = anchors[a * 4 + 1], aw = anchors[a * 4 + 2], ah = anchors[a * 4 + 3];
-      double lr = fmin(ax + 0.5 * aw, gr) - fmax(ax - 0.5 * aw, gl);
-      lr = lr > 0.0 ? lr : 0.0;
-      double tb = fmin(ay + 0.5 * ah, gb) - fmax(ay - 0.5 * ah, gtp);
-      tb = tb > 0.0 ? tb : 0.0;
-      const double inter = lr * tb;
-      const double iou = inter / (aw * ah + garea - inter);
+      const double iou = iou_from_inter(q, anchor_inter(q, ax, ay, aw, ah), aw, ah);
       Cand t;
       t.v = iou; t.idx = a;
       if (iou > 0.0 && better<true>(t, c)) c = t;
@@ -151,23 +111,38 @@ __global__ __launch_bounds__(1024) void labels_resolve_kernel(const double* __re
     const int a = mine;
     aidx_out[(size_t)b * M + i] = a;
     if (a >= 0) {
-      const double* g = gt + ((size_t)b * M + i) * 4;
-      const double gx = g[0], gy = g[1], gw = g[2], gh = g[3];
-      float* m = mask + (size_t)b * A;
-      float* d = delta + (size_t)b * A * 4;
-      float* bx = box + (size_t)b * A * 4;
-      float* lb = labels + (size_t)b * A * C;
-      const double ax = anchors[a * 4], ay = anchors[a * 4 + 1], aw = anchors[a * 4 + 2], ah = anchors[a * 4 + 3];
-      m[a] = 1.f;
-      d[a * 4 + 0] = (float)((gx - ax) / aw);
-      d[a * 4 + 1] = (float)((gy - ay) / ah);
-      d[a * 4 + 2] = (float)log(gw / aw);
-      d[a * 4 + 3] = (float)log(gh / ah);
-      bx[a * 4 + 0] = (float)gx; bx[a * 4 + 1] = (float)gy; bx[a * 4 + 2] = (float)gw; bx[a * 4 + 3] = (float)gh;
-      const int cls = gt_cls[(size_t)b * M + i];
-      if (cls >= 0 && cls < C) lb[a * C + cls] = 1.f;
+      const GtBox q = gt_box(gt + ((size_t)b * M + i) * 4);
+      write_positive_rows(q, anchors[a * 4], anchors[a * 4 + 1], anchors[a * 4 + 2], anchors[a * 4 + 3], gt_cls[(size_t)b * M + i], a, C,
+                          mask + (size_t)b * A, delta + (size_t)b * A * 4, box + (size_t)b * A * 4, labels + (size_t)b * A * C);
     }
   }
+}
+
+int labels_check_args(const void* anchors_f64, const void* gt_boxes_f64, const void* gt_classes, const void* gt_counts,
+                      const void* input_mask, const void* box_delta_input, const void* box_input, const void* labels,
+                      const void* anchor_index, int batch, int num_anchors, int max_objects, int classes) {
+  SQDET_REQUIRE(anchors_f64 && gt_boxes_f64 && gt_classes && gt_counts && input_mask && box_delta_input && box_input &&
+                    labels && anchor_index, "build_labels: null pointer");
+  SQDET_REQUIRE(batch > 0 && num_anchors > 0 && max_objects > 0 && classes > 0, "build_labels: bad dims");
+  SQDET_UNSUPPORTED(max_objects > num_anchors, "build_labels: more boxes per image than anchors");
+  const size_t lds = (size_t)((num_anchors + 31) / 32) * 4;
+  SQDET_UNSUPPORTED(lds > 60000, "build_labels: too many anchors (%d)", num_anchors);
+  SQDET_UNSUPPORTED(max_objects > 1024, "build_labels: more than 1024 boxes per image");
+  return SQDET_OK;
+}
+
+void labels_launch_reference(const double* anchors_f64, const double* gt_boxes_f64, const int* gt_classes, const int* gt_counts,
+                             float* input_mask, float* box_delta_input, float* box_input, float* labels, int* anchor_index,
+                             int batch, int num_anchors, int max_objects, int classes, hipStream_t st) {
+  const size_t lds = (size_t)((num_anchors + 31) / 32) * 4;
+  const size_t ba = (size_t)batch * num_anchors;
+  hipLaunchKernelGGL(labels_zero_kernel, dim3(2048), dim3(256), 0, st, input_mask, ba, box_delta_input, ba * 4, box_input, ba * 4,
+                     labels, ba * classes);
+  hipLaunchKernelGGL(labels_best_kernel, dim3((unsigned)max_objects, (unsigned)batch), dim3(256), 0, st, anchors_f64, gt_boxes_f64,
+                     gt_counts, anchor_index, num_anchors, max_objects);
+  hipLaunchKernelGGL(labels_resolve_kernel, dim3((unsigned)batch), dim3(1024), lds, st, anchors_f64, gt_boxes_f64,
+                     gt_classes, gt_counts, input_mask, box_delta_input, box_input, labels, anchor_index, num_anchors,
+                     max_objects, classes);
 }
 
 }  // namespace sqdet
@@ -177,22 +152,11 @@ extern "C" int sqdet_build_labels(const double* anchors_f64, const double* gt_bo
                                   float* labels, int* anchor_index, int batch, int num_anchors, int max_objects,
                                   int classes, sqdet_stream_t stream) {
   using namespace sqdet;
-  SQDET_REQUIRE(anchors_f64 && gt_boxes_f64 && gt_classes && gt_counts && input_mask && box_delta_input && box_input &&
-                    labels && anchor_index, "build_labels: null pointer");
-  SQDET_REQUIRE(batch > 0 && num_anchors > 0 && max_objects > 0 && classes > 0, "build_labels: bad dims");
-  SQDET_UNSUPPORTED(max_objects > num_anchors, "build_labels: more boxes per image than anchors");
-  const size_t lds = (size_t)((num_anchors + 31) / 32) * 4;
-  SQDET_UNSUPPORTED(lds > 60000, "build_labels: too many anchors (%d)", num_anchors);
-  SQDET_UNSUPPORTED(max_objects > 1024, "build_labels: more than 1024 boxes per image");
-  hipStream_t st = as_stream(stream);
-  const size_t ba = (size_t)batch * num_anchors;
-  hipLaunchKernelGGL(labels_zero_kernel, dim3(2048), dim3(256), 0, st, input_mask, ba, box_delta_input, ba * 4, box_input, ba * 4,
-                     labels, ba * classes);
-  hipLaunchKernelGGL(labels_best_kernel, dim3((unsigned)max_objects, (unsigned)batch), dim3(256), 0, st, anchors_f64, gt_boxes_f64,
-                     gt_counts, anchor_index, num_anchors, max_objects);
-  hipLaunchKernelGGL(labels_resolve_kernel, dim3((unsigned)batch), dim3(1024), lds, st, anchors_f64, gt_boxes_f64,
-                     gt_classes, gt_counts, input_mask, box_delta_input, box_input, labels, anchor_index, num_anchors,
-                     max_objects, classes);
+  const int rc = labels_check_args(anchors_f64, gt_boxes_f64, gt_classes, gt_counts, input_mask, box_delta_input, box_input, labels,
+                                   anchor_index, batch, num_anchors, max_objects, classes);
+  if (rc != SQDET_OK) return rc;
+  labels_launch_reference(anchors_f64, gt_boxes_f64, gt_classes, gt_counts, input_mask, box_delta_input, box_input, labels,
+                          anchor_index, batch, num_anchors, max_objects, classes, as_stream(stream));
   SQDET_CHECK_HIP(hipGetLastError());
   return SQDET_OK;
 }

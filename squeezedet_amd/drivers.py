@@ -153,6 +153,46 @@ def loss_policy(a, mc):
     return policy, off
 
 
+def add_assign_args(ap):
+    """--assign, --assign_iou, --assign_max, --assign_topk (train.py, tools/bench_train.py).  A flag that
+    is not given leaves no attribute behind: assign_policy supplies the defaults."""
+    import argparse
+    from .assign import ASSIGN_MODES, MAX_PER_BOX, MAX_TOPK
+    S = argparse.SUPPRESS
+    ap.add_argument("--assign", default=S, choices=ASSIGN_MODES,
+                    help="which anchors are trained as positives: reference (default), the one anchor per object the reference picks; "
+                         "iou: also every unclaimed anchor with IoU >= --assign_iou, at most --assign_max per object; atss: also the "
+                         "anchors ATSS selects (mean + std of the IoUs of the --assign_topk nearest anchors per shape)")
+    ap.add_argument("--assign_iou", type=float, default=S, metavar="T", help="--assign iou: the IoU threshold (default 0.5)")
+    ap.add_argument("--assign_max", type=int, default=S, metavar="K", help="--assign iou: at most K more positives per object, 1..%d (default 16)" % MAX_PER_BOX)
+    ap.add_argument("--assign_topk", type=int, default=S, metavar="K", help="--assign atss: candidates per anchor shape, 1..%d (default 9)" % MAX_TOPK)
+
+
+add_assign_flags = add_assign_args
+
+
+def check_assign_args(ap, a):
+    from ._lib import SqdetError
+    from .assign import assign_options
+    mode = getattr(a, "assign", "reference")
+    for key, needs in (("assign_iou", "iou"), ("assign_max", "iou"), ("assign_topk", "atss")):
+        if hasattr(a, key) and mode != needs:
+            ap.error("--%s needs --assign %s" % (key, needs))
+    try:
+        assign_options(mode, getattr(a, "assign_iou", 0.5), getattr(a, "assign_max", 16), getattr(a, "assign_topk", 9))
+    except SqdetError as e:
+        ap.error(str(e))
+
+
+def assign_policy(a, mc=None):
+    """(the assignment policy of --assign ... as a checkpoint records it, the policy of a run without the flags -- what a
+    checkpoint without the record was trained with).  assign.from_dict(policy) is the record the trainers take."""
+    from .assign import as_dict, assign_options
+    off = dict(mode="reference")
+    opt = assign_options(getattr(a, "assign", "reference"), getattr(a, "assign_iou", 0.5), getattr(a, "assign_max", 16), getattr(a, "assign_topk", 9))
+    return as_dict(opt), off
+
+
 def add_optim_args(ap):
     """The update step's flags (train.py, tools/bench_train.py).  A flag that is not given leaves no
     attribute behind: optim.optim_policy supplies the defaults."""

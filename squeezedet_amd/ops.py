@@ -960,11 +960,19 @@ class Optimizer(MomentumOptimizer):
                                              opt(found_inf, "found_inf", torch.int32), stream_ptr()), "sqdet_optimizer_step_opt")
 
 
-def build_labels(anchor_box, gt_boxes, gt_classes, gt_counts, classes, device=None):
+class _AssignOptions(C.Structure):     # sqdet_assign_options_t
+    _fields_ = [("mode", C.c_int), ("iou_thresh", C.c_double), ("max_per_box", C.c_int), ("topk", C.c_int)]
+
+
+def build_labels(anchor_box, gt_boxes, gt_classes, gt_counts, classes, device=None, assign=None, anchors_per_grid=None):
     """Anchor assignment + dense label tensors on the GPU (imdb.py:195-239, train.py:163-224).
     anchor_box: mc.ANCHOR_BOX [A,4] float64; gt_boxes [B,M,4] float64 (cx,cy,w,h in network-input pixels, rows
     beyond gt_counts[b] ignored); gt_classes [B,M]; gt_counts [B].  Returns (input_mask [B,A], box_delta_input
-    [B,A,4], box_input [B,A,4], labels [B,A,C]) float32 and anchor_index [B,M] int32, all on the device."""
+    [B,A,4], box_input [B,A,4], labels [B,A,C]) float32 and anchor_index [B,M] int32, all on the device.
+    assign: an assign.assign_options record.  None or mode `reference` is the call above (sqdet_build_labels, five outputs); `iou` /
+    `atss` (sqdet_build_labels_opt) need anchors_per_grid and return two more tensors: assigned_box int32
+    [B,A], the box an anchor is a positive of or -1, and positives int32 [B,M], the number of positives per box."""
+    from .assign import ASSIGN_MODES, is_default
     dev = torch.device(device) if device is not None else (gt_boxes.device if isinstance(gt_boxes, torch.Tensor) else torch.device("cuda", torch.cuda.current_device()))
     to = lambda v, dt: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(dev, dt).contiguous()
     anc, gt = to(anchor_box, torch.float64), to(gt_boxes, torch.float64)
@@ -976,10 +984,25 @@ def build_labels(anchor_box, gt_boxes, gt_classes, gt_counts, classes, device=No
     box = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
     lab = torch.empty((B, A, int(classes)), dtype=torch.float32, device=dev)
     aidx = torch.empty((B, M), dtype=torch.int32, device=dev)
-    check(lib().sqdet_build_labels(_dev(anc, "anchors"), _dev(gt, "gt_boxes"), _dev(cls, "gt_classes"), _dev(cnt, "gt_counts"),
-                                   _dev(mask, "mask"), _dev(delta, "delta"), _dev(box, "box"), _dev(lab, "labels"),
-                                   _dev(aidx, "aidx"), B, A, M, int(classes), stream_ptr()), "sqdet_build_labels")
-    return mask, delta, box, lab, aidx
+    if is_default(assign):
+        check(lib().sqdet_build_labels(_dev(anc, "anchors"), _dev(gt, "gt_boxes"), _dev(cls, "gt_classes"), _dev(cnt, "gt_counts"),
+                                       _dev(mask, "mask"), _dev(delta, "delta"), _dev(box, "box"), _dev(lab, "labels"),
+                                       _dev(aidx, "aidx"), B, A, M, int(classes), stream_ptr()), "sqdet_build_labels")
+        return mask, delta, box, lab, aidx
+    if anchors_per_grid is None:
+        raise _lib.SqdetError("build_labels: assign mode %s needs anchors_per_grid" % assign.mode)
+    apg = int(anchors_per_grid)
+    o = _AssignOptions(ASSIGN_MODES.index(assign.mode), float(assign.iou_thresh), int(assign.max_per_box), int(assign.topk))
+    po = C.cast(C.pointer(o), C.c_void_p)
+    ws_bytes = int(lib().sqdet_build_labels_opt_workspace_bytes(B, A, M, apg, po))
+    ws = torch.empty(max(8, ws_bytes), dtype=torch.uint8, device=dev)     # (0 bytes: bad arguments -- the entry says which)
+    abox = torch.empty((B, A), dtype=torch.int32, device=dev)
+    pos = torch.empty((B, M), dtype=torch.int32, device=dev)
+    check(lib().sqdet_build_labels_opt(_dev(anc, "anchors"), _dev(gt, "gt_boxes"), _dev(cls, "gt_classes"), _dev(cnt, "gt_counts"),
+                                       _dev(mask, "mask"), _dev(delta, "delta"), _dev(box, "box"), _dev(lab, "labels"),
+                                       _dev(aidx, "aidx"), _dev(abox, "assigned_box"), _dev(pos, "positives"), _dev(ws, "workspace"),
+                                       B, A, M, int(classes), apg, po, stream_ptr()), "sqdet_build_labels_opt")
+    return mask, delta, box, lab, aidx, abox, pos
 
 
 ANCHOR_KMEANS_MAX_K = 64             # SQDET_ANCHOR_KMEANS_MAX_K / _MAX_RESTARTS (include/sqdet.h)

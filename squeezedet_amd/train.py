@@ -104,7 +104,7 @@ class _TrainerBase:
     the optimizer kernel and halves the scale; `growth_interval` clean steps double it."""
 
     def __init__(self, model, process_group=None, loss_scale=1024.0, growth_interval=200, lazy_overflow_check=None,
-                 global_num_objects=False, seed=0, overlap_wgrad=True, optim=None):
+                 global_num_objects=False, seed=0, overlap_wgrad=True, optim=None, assign=None):
         if model.dtype not in (torch.float32, torch.float16):
             raise SqdetError("training runs in float32 (the reference's training dtype) or float16 (mixed precision)")
         self.adt = model.dtype                       # activation dtype
@@ -177,6 +177,9 @@ class _TrainerBase:
                 self.flat_accum2 = torch.zeros(o, dtype=torch.float32, device=self.dev)
             if self.optim["ema_decay"] > 0.0:
                 self.flat_ema = self.flat_params.clone()
+        # assign: a record of squeezedet_amd.assign -- which anchors the label build marks as positives; None or
+        # mode `reference`: sqdet_build_labels, the launches of every run before the policy existed
+        self.assign = assign
         self.found_inf = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self._labels_forked = False
         self._flag_host, self._flag_event = None, None     # lazy_overflow_check's pinned flag + its event, made at the first lazy step
@@ -913,8 +916,9 @@ class GraphedStep:
 
     MAX_GRAPHS = 4
 
-    def __init__(self, trainer, anchors_f64, classes):
+    def __init__(self, trainer, anchors_f64, classes, assign=None):
         self.tr, self.anchors, self.classes = trainer, anchors_f64, int(classes)
+        self.assign = assign if assign is not None else trainer.assign       # (assign.assign_options; None: the reference's pick)
         self.graph, self.static, self.out, self.key = None, None, None, None
         self.cache = {}      # (loss scale, input shape) -> (graph, static buffers, outputs): a scale seen before is not re-captured
         self.eager_nobj = False      # global_num_objects at world > 1 (set by _capture, restored with a cached graph)
@@ -924,6 +928,11 @@ class GraphedStep:
         """Drops every captured graph (and the static buffers it pins): the next step captures again."""
         self.graph, self.static, self.out, self.key = None, None, None, None
         self.cache = {}
+
+    def build_labels(self, st):
+        """ops.build_labels on the static inputs under this stepper's assignment policy."""
+        return ops.build_labels(self.anchors, st["gt"], st["gcls"], st["gcnt"], self.classes, assign=self.assign,
+                                anchors_per_grid=int(self.tr.mc.ANCHOR_PER_GRID))
 
     def _capture(self, x, gt, gcls, gcnt):
         tr = self.tr
@@ -940,7 +949,7 @@ class GraphedStep:
         if self.eager_nobj:
             st["nobj"] = torch.ones(1, dtype=torch.float32, device=tr.dev)
         def build():       # label build + num_objects = sum(input_mask): on the trainer's side stream, beside the forward
-            lab = ops.build_labels(self.anchors, st["gt"], st["gcls"], st["gcnt"], self.classes)[:4]
+            lab = self.build_labels(st)[:4]
             return lab, (st["nobj"] if self.eager_nobj else ops.sum_f32(lab[0].reshape(int(x.shape[0]), -1)))
 
         def run():
@@ -978,7 +987,7 @@ class GraphedStep:
             if tr.model.keep_prob != 1.0:
                 ops.dropout_mask_into(st["mask"], tr.model.keep_prob, tr._next_mask_seed())
             if self.eager_nobj:
-                mask = ops.build_labels(self.anchors, st["gt"], st["gcls"], st["gcnt"], self.classes)[0]
+                mask = self.build_labels(st)[0]
                 ops.sum_f32(mask, out=st["nobj"])
                 reduce_num_objects(st["nobj"], tr.world, tr.pg)
             self.graph.replay()

@@ -57,9 +57,11 @@ def parse_args(argv=None):
     from squeezedet_amd import drivers
     drivers.add_loss_args(ap)             # --bbox_loss, --focal_gamma, --bbox_loss_coef as train.py takes them
     drivers.add_optim_args(ap)            # --optimizer ... --ema_warmup as train.py takes them
+    drivers.add_assign_flags(ap)          # --assign ... --assign_topk as train.py takes them
     args = ap.parse_args(argv)
     drivers.check_loss_args(ap, args)
     drivers.check_optim_args(ap, args)
+    drivers.check_assign_args(ap, args)
     if not 0.0 <= args.mosaic <= 1.0 or (args.mosaic > 0.0 and not args.augment):
         ap.error("--mosaic P needs 0 <= P <= 1 and --augment")
     if args.batch <= 0:
@@ -99,7 +101,7 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     import squeezedet_amd as S
-    from squeezedet_amd import nets, synthetic
+    from squeezedet_amd import drivers, nets, synthetic
     from squeezedet_amd.train import ResNet50ConvDetTrainer, SqueezeDetTrainer, VGG16ConvDetTrainer
     mc, loss_policy = make_config(args)
     optim = make_optim(args, mc)
@@ -107,7 +109,11 @@ def main():
                     "vgg16": (nets.VGG16ConvDet, VGG16ConvDetTrainer)}[args.arch]
     model = cls(mc, gpu_id=str(local_rank), dtype=torch.float32 if args.dtype == "f32" else torch.float16)
     model.load_params(synthetic.synthetic_params(model, seed=0))      # same weights on every rank
-    tr = trainer(model, lazy_overflow_check=True, optim=optim)
+    from squeezedet_amd import assign as assign_mod
+    assign_policy, _ = drivers.assign_policy(args, mc)
+    assign = assign_mod.from_dict(assign_policy)
+    assign = None if assign_mod.is_default(assign) else assign
+    tr = trainer(model, lazy_overflow_check=True, optim=optim, assign=assign)
     x = synthetic.synthetic_images(args.batch, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, seed=100 + rank).to(dev)
     # ground truth lives on the device; the anchor assignment + dense label build (imdb.py:195-239,
     # train.py:163-224) runs on the GPU inside every step, like the reference's per-batch _load_data
@@ -115,7 +121,9 @@ def main():
     anchors = torch.from_numpy(np.asarray(mc.ANCHOR_BOX, np.float64)).to(dev)
     gt, gcls, gcnt = [torch.from_numpy(a).to(dev) for a in synthetic_ground_truth(mc, args.batch, seed=200 + rank)]
     nobj = float(gcnt.sum().item())      # known to the host: no per-step device -> host sync for sum(input_mask)
-    one_step = lambda: tr.step(x, *ops.build_labels(anchors, gt, gcls, gcnt, mc.CLASSES)[:4], num_objects=nobj)
+    # (under --assign iou / atss the normaliser is the number of positives, sum(input_mask): the trainer sums it on the device)
+    build = lambda g, c, n: ops.build_labels(anchors, g, c, n, mc.CLASSES, assign=assign, anchors_per_grid=int(mc.ANCHOR_PER_GRID))[:4]
+    one_step = lambda: tr.step(x, *build(gt, gcls, gcnt), num_objects=nobj if assign is None else None)
     if args.augment:
         if args.augment == "ssd":
             mc.AUG_GEOMETRY, mc.AUG_ZOOM_OUT_MAX, mc.AUG_COLOR = "ssd", 2.0, True
@@ -125,8 +133,8 @@ def main():
 
         def one_step():
             b = reader.read_batch()
-            return tr.step(b.image_input, *ops.build_labels(anchors, b.gt_boxes, b.gt_classes, b.gt_counts, mc.CLASSES)[:4],
-                           num_objects=float(sum(len(l) for l in b.label_per_batch)))
+            return tr.step(b.image_input, *build(b.gt_boxes, b.gt_classes, b.gt_counts),
+                           num_objects=float(sum(len(l) for l in b.label_per_batch)) if assign is None else None)
     for _ in range(args.warmup):
         out = one_step()
     torch.cuda.synchronize()
@@ -156,7 +164,7 @@ def main():
                                    + (" + mosaic %g" % args.mosaic if args.mosaic > 0.0 else "")) if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
-                          "loss": loss_policy, **({"optim": optim} if optim is not None else {}), "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
+                          "loss": loss_policy, **({"assign": assign_policy} if assign is not None else {}), **({"optim": optim} if optim is not None else {}), "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
                           "losses": {k: float(out[k]) for k in ("class_loss", "conf_loss", "bbox_loss")}}))
     if world > 1:
         dist.destroy_process_group()

@@ -92,10 +92,12 @@ def parse_args(argv=None):
                          "network input (default 0: never)")
     drivers.add_loss_args(ap)
     drivers.add_optim_args(ap)
+    drivers.add_assign_flags(ap)
     a = ap.parse_args(argv)
     drivers.check_dataset_args(ap, a)
     drivers.check_loss_args(ap, a)
     drivers.check_optim_args(ap, a)
+    drivers.check_assign_args(ap, a)
     if not 0.0 <= getattr(a, "mosaic", 0.0) <= 1.0:
         ap.error("--mosaic P needs 0 <= P <= 1")
     if a.resume and a.overwrite:
@@ -119,11 +121,15 @@ def augment_policy(a, mc=None):
     return policy
 
 
+ASSIGN_OFF = dict(mode="reference")      # what a checkpoint without the `assign` record was trained with (drivers.assign_policy's)
+
+
 def check_resume_record(saved, extra, loss_off, optim_off=None):
     """--resume: what the checkpoint records (`saved`) against what this run asks for (`extra`); SystemExit on the first key that
     differs.  A checkpoint from before a key existed was trained with that key's defaults (`loss_off`: drivers.loss_policy's;
-    `optim_off`: optim.optim_policy's)."""
+    `optim_off`: optim.optim_policy's; `assign`: the reference's one anchor per object)."""
     saved = dict(saved)
+    saved.setdefault("assign", ASSIGN_OFF)
     saved.setdefault("augment", AUGMENT_OFF)
     saved.setdefault("mosaic", 0.0)
     saved.setdefault("loss", loss_off)
@@ -253,15 +259,20 @@ class Run:
         loss, loss_off = drivers.loss_policy(a, mc)         # (before the model is built: a padded head's config is a copy of mc)
         from squeezedet_amd.optim import optim_policy
         optim, optim_off = optim_policy(a, mc)              # (sets mc.WEIGHT_DECAY: before the trainer reads it)
+        from squeezedet_amd import assign as assign_mod
+        assign, _ = drivers.assign_policy(a, mc)
+        self.assign = assign_mod.from_dict(assign)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
         # (a run without any of the optimizer flags takes the trainer's own path: the launches and state keys of every run before)
-        self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale, optim=None if optim == optim_off else optim)
+        self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale, optim=None if optim == optim_off else optim,
+                              assign=None if assign_mod.is_default(self.assign) else self.assign)
         images, rois = load_dataset(a, mc)
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
         self.extra = dict(image_size=[int(mc.IMAGE_HEIGHT), int(mc.IMAGE_WIDTH)], net=a.net, dtype=a.dtype, batch_size=int(mc.BATCH_SIZE),
-                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy, mosaic=mosaic, loss=loss)
+                          anchor_shapes=None if self.anchor_shapes is None else self.anchor_shapes.tolist(), augment=policy, mosaic=mosaic, loss=loss,
+                          assign=assign)
         if optim != optim_off:
             self.extra["optim"] = optim
         self.first = 0
@@ -291,6 +302,13 @@ class Run:
         wd = sum(float(r["sumsq"]) for n, r in zip(tr.names, rec) if n.endswith("/kernels")) * self.mc.WEIGHT_DECAY / 2
         return float(out["class_loss"]) + float(out["conf_loss"]) + float(out["bbox_loss"]) + wd
 
+    def positives_note(self, labels, b):
+        """The summaries line's tail under --assign iou / atss: the mean number of positive anchors per object of this batch."""
+        if len(labels) < 7:
+            return ""
+        from squeezedet_amd.assign import positives_summary
+        return ", positives per object: {:.2f}".format(positives_summary(labels[6], b.gt_counts)[1])
+
     def step(self, step):
         """train.py:273-325 for one step."""
         from squeezedet_amd import ops
@@ -300,8 +318,9 @@ class Run:
         lr = tr.learning_rate()
         b = self.reader.read_batch()
         if is_summary or self.stepper is None:
-            out = tr.step(b.image_input, *ops.build_labels(self.anchors, b.gt_boxes, b.gt_classes, b.gt_counts, mc.CLASSES)[:4],
-                          keep_activations=is_summary)
+            labels = ops.build_labels(self.anchors, b.gt_boxes, b.gt_classes, b.gt_counts, mc.CLASSES, assign=tr.assign,
+                                      anchors_per_grid=int(mc.ANCHOR_PER_GRID))
+            out = tr.step(b.image_input, *labels[:4], keep_activations=is_summary)
         else:
             out = self.stepper.step(b.image_input, b.gt_boxes, b.gt_classes, b.gt_counts)
         if is_summary:
@@ -310,7 +329,7 @@ class Run:
                 self.images.record(step, b, out["preds"])
             if self.rank == 0:
                 print("conf_loss: {}, bbox_loss: {}, class_loss: {}".format(float(out["conf_loss"]), float(out["bbox_loss"]),
-                                                                           float(out["class_loss"])))
+                                                                           float(out["class_loss"])) + self.positives_note(labels, b))
         elif summary is not None:
             summary.poll()
             if self.images is not None:

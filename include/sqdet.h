@@ -501,6 +501,30 @@ int sqdet_loss_fwd_bwd_opt(const void* preds, int preds_dtype, const float* anch
                            float coef_class, float coef_conf_pos, float coef_conf_neg, float coef_bbox, float num_objects,
                            const float* num_objects_dev, int global_batch, const sqdet_loss_options_t* opt,
                            sqdet_stream_t stream);
+/* ---- distillation (OURS): a teacher net's ConvDet output as a second target of the loss.
+ * preds (the student's) and teacher_preds are [B,gh,gw,K*(C+5)] with loss_kernel's channels: class logits at k*C + c, the
+ * confidence logit at K*C + k, the four deltas at K*(C+1) + 4k + d.  Per anchor a of image b, with the student's values zs, us, ds
+ * and the teacher's zt, ut, dt, A = gh*gw*K anchors per image and Bg = global_batch (<= 0: batch; as in sqdet_loss_fwd_bwd):
+ *   ct = sigmoid(ut), cs = sigmoid(us);  w = ct if ct >= conf_floor (inclusive), else 0 -- a constant of the backward pass.
+ *   class  q = softmax(zt/T), p = softmax(zs/T), through the max-subtracted log-softmax lq, lp:
+ *          L_cls  = class_coef * T^2 / Bg * sum_{b,a} w * sum_j q_j (lq_j - lp_j);    dL/dzs_j = class_coef * T * w * (p_j - q_j) / Bg
+ *   conf   the Bernoulli KL in logit form, softplus(z) = max(z,0) + log1p(exp(-|z|)):
+ *          L_conf = conf_coef / (Bg*A) * sum_{b,a} [ ct (ut - us) + softplus(us) - softplus(ut) ];   dL/dus = conf_coef * (cs - ct) / (Bg*A)
+ *   box    L_box  = bbox_coef / Bg * sum_{b,a} w * sum_d (ds_d - dt_d)^2;             dL/dds_d = 2 bbox_coef w (ds_d - dt_d) / Bg
+ * No normaliser depends on the data: a data-parallel replica's share needs no all-reduce of its own.  The teacher gets no
+ * gradient; non-finite teacher values are UNDEFINED behaviour of the arithmetic (the caller's problem).
+ * The call runs AFTER the loss launch that wrote dpreds_inout: every channel's gradient g is computed completely, then
+ * dpreds = dpreds + g (one float32 add) and -- float16 student -- dpreds_scaled_f16 = (float16)(dpreds * loss_scale) on that sum,
+ * sqdet_convert_scale's expression, in the same pass.  distill3 = {class, conf, box} term; workspace:
+ * sqdet_distill_workspace_bytes() of device scratch.  preds_dtype / teacher_dtype: SQDET_F32 or SQDET_F16, any pair; the
+ * arithmetic is float32 on the stored values.  Deterministic (fixed-order sums, no atomics), capturable in a hipGraph.
+ * SQDET_EINVAL, nothing launched: temperature <= 0 or non-finite, a negative or non-finite coefficient, all three coefficients
+ * zero, conf_floor outside [0, 1], an unknown dtype, float16 preds without dpreds_scaled_f16 / a loss scale > 0. */
+typedef struct { float temperature, class_coef, conf_coef, bbox_coef, conf_floor; } sqdet_distill_options_t;
+size_t sqdet_distill_workspace_bytes(void);
+int sqdet_distill_fwd_bwd(const void* preds, int preds_dtype, const void* teacher_preds, int teacher_dtype, float* dpreds_inout,
+                          void* dpreds_scaled_f16, float loss_scale, float* distill3, float* workspace, int batch, int gh, int gw,
+                          int apg, int classes, int global_batch, const sqdet_distill_options_t* opt, sqdet_stream_t stream);
 /* out[0] = sum(x[0..count)) in a fixed order (deterministic): tf.reduce_sum(self.input_mask), nn_skeleton.py:180. */
 int sqdet_sum_f32(const float* x, size_t count, float* out, sqdet_stream_t stream);
 /* y = max(a + b, 0): tf.nn.relu(shortcut + branch) (nets/resnet50_convDet.py:55) where the producing conv could not take

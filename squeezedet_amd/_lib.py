@@ -93,6 +93,8 @@ SIGNATURES = {
     "sqdet_loss_fwd_bwd_dev": (ci, [vp] * 10 + [ci] * 5 + [cf] * 8 + [vp, ci, vp]),
     "sqdet_loss_fwd_bwd_mixed": (ci, [vp] * 8 + [cf] + [vp] * 3 + [ci] * 5 + [cf] * 9 + [vp, ci, vp]),
     "sqdet_loss_fwd_bwd_opt": (ci, [vp, ci] + [vp] * 7 + [cf] + [vp] * 3 + [ci] * 5 + [cf] * 9 + [vp, ci, vp, vp]),
+    "sqdet_distill_workspace_bytes": (sz, []),
+    "sqdet_distill_fwd_bwd": (ci, [vp, ci, vp, ci, vp, vp, cf, vp, vp] + [ci] * 6 + [vp, vp]),
     "sqdet_sum_f32": (ci, [vp, sz, vp, vp]),
     "sqdet_add_relu": (ci, [vp, vp, vp, sz, ci, vp]),
     "sqdet_copy_channels": (ci, [vp, vp, sz, ci, ci, ci, ci, vp]),

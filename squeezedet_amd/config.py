@@ -56,6 +56,9 @@ def base_model_config(dataset="PASCAL_VOC"):
     # OURS (the reference has neither): what the box term is, and the class term's focal exponent
     cfg.BBOX_LOSS = "delta_l2"                  # "delta_l2": the reference's squared delta error; "iou", "giou", "diou", "ciou"
     cfg.FOCAL_GAMMA = 0.0                       # 0.0: the reference's unweighted log loss
+    # OURS: the distillation policy of a run trained towards a teacher net's output (drivers.distill_policy's
+    # record: the teacher net, its checkpoint's path, the options of squeezedet_amd.distill); None: no teacher
+    cfg.DISTILL = None
     cfg.DECAY_STEPS = 10000
     cfg.LR_DECAY_FACTOR = 0.1
     cfg.LEARNING_RATE = 0.005

@@ -562,6 +562,97 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
   if (lane == 0 && j < 3) losses3[j] = s;
 }
 
+// ------------------------------------------------------------------ distillation (OURS: not in the reference)
+// A teacher's preds as a second target (sqdet_distill_fwd_bwd; the definition stands in include/sqdet.h and, sequentially, in
+// tests/distill_reference.py).  loss_kernel's shape: a thread per anchor in a grid-stride loop, per-thread sums in index order,
+// the LDS tree, at most 512 partials, loss_finish_kernel.  Runs after the loss launch: every channel's own gradient g is formed
+// completely, then dpreds = dpreds + g and -- float16 student -- the loss-scaled float16 copy of that sum.  The softmaxes are
+// re-evaluated per class instead of kept in a per-thread array (C is a run-time value: an array would live in scratch).
+// Every division by the batch is the last operation of its expression and the sums are divided once per thread, so that
+// global_batch = 2 * batch halves every output exactly.
+struct DistillArgs {
+  const void* preds;       // student [B, cells, K*(C+5)], float32 or float16
+  const void* teacher;     // teacher, the same shape, float32 or float16
+  float* dpreds;           // [B, cells, K*(C+5)], read and written
+  f16* g16;                // float16 student: (float16)(dpreds * gscale)
+  float gscale;
+  float* partial;          // [blocks][4]: class, conf, box partial sums (+ unused)
+  int B, cells, K, C;
+  float Bg, BgA;           // (float)global batch, and times the anchors per image
+  float T, c_cls, c_conf, c_box, floor;
+};
+
+__device__ __forceinline__ float softplusf(float z) { return fmaxf(z, 0.0f) + log1pf(expf(-fabsf(z))); }
+
+template <typename PT, typename TT>
+__global__ __launch_bounds__(256) void distill_kernel(DistillArgs a) {
+  __shared__ float red[3][256];
+  const int A = a.cells * a.K;
+  const int ch = a.K * (a.C + 5);
+  const long total = (long)a.B * A;
+  float l_cls = 0.f, l_conf = 0.f, l_box = 0.f;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(idx / A);
+    const int an = (int)(idx - (long)b * A);
+    const int cell = an / a.K, k = an - cell * a.K;
+    const size_t base = ((size_t)b * a.cells + cell) * ch;
+    const PT* s = reinterpret_cast<const PT*>(a.preds) + base;
+    const TT* t = reinterpret_cast<const TT*>(a.teacher) + base;
+    float* dp = a.dpreds + base;
+    f16* gp = a.g16 ? a.g16 + base : nullptr;
+    auto add = [&](int off, float g) {
+      const float v = dp[off] + g;
+      dp[off] = v;
+      if (sizeof(PT) == 2) gp[off] = scaled_to<f16>(v, a.gscale);
+    };
+    // teacher confidence -> the anchor's weight; the confidence term
+    const float us = (float)s[a.K * a.C + k], ut = (float)t[a.K * a.C + k];
+    const float cs = 1.0f / (1.0f + expf(-us)), ct = 1.0f / (1.0f + expf(-ut));
+    const float w = ct >= a.floor ? ct : 0.0f;
+    l_conf += ct * (ut - us) + softplusf(us) - softplusf(ut);
+    add(a.K * a.C + k, a.c_conf * (cs - ct) / a.BgA);
+    // class term: KL(q || p) of the tempered softmaxes, through max-subtracted log-softmax
+    const PT* zs = s + k * a.C;
+    const TT* zt = t + k * a.C;
+    float ms = (float)zs[0] / a.T, mt = (float)zt[0] / a.T;
+    for (int c = 1; c < a.C; ++c) { ms = fmaxf(ms, (float)zs[c] / a.T); mt = fmaxf(mt, (float)zt[c] / a.T); }
+    float ss = expf((float)zs[0] / a.T - ms), st = expf((float)zt[0] / a.T - mt);
+    for (int c = 1; c < a.C; ++c) { ss = ss + expf((float)zs[c] / a.T - ms); st = st + expf((float)zt[c] / a.T - mt); }
+    const float ls = logf(ss), lt = logf(st);
+    float kl = 0.f;
+    for (int c = 0; c < a.C; ++c) {
+      const float lp = ((float)zs[c] / a.T - ms) - ls, lq = ((float)zt[c] / a.T - mt) - lt;
+      const float p = expf(lp), q = expf(lq);
+      kl += q * (lq - lp);
+      add(k * a.C + c, a.c_cls * a.T * w * (p - q) / a.Bg);
+    }
+    l_cls += w * kl;
+    // box term: squared error on the four deltas
+    const PT* ds = s + a.K * (a.C + 1) + 4 * k;
+    const TT* dt = t + a.K * (a.C + 1) + 4 * k;
+    float sq = 0.f;
+    for (int d = 0; d < 4; ++d) {
+      const float df = (float)ds[d] - (float)dt[d];
+      sq += df * df;
+      add(a.K * (a.C + 1) + 4 * k + d, 2.0f * a.c_box * w * df / a.Bg);
+    }
+    l_box += w * sq;
+  }
+  red[0][threadIdx.x] = a.c_cls * a.T * a.T * l_cls / a.Bg;
+  red[1][threadIdx.x] = a.c_conf * l_conf / a.BgA;
+  red[2][threadIdx.x] = a.c_box * l_box / a.Bg;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + off];
+      red[1][threadIdx.x] += red[1][threadIdx.x + off];
+      red[2][threadIdx.x] += red[2][threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 4) a.partial[blockIdx.x * 4 + threadIdx.x] = threadIdx.x < 3 ? red[threadIdx.x][0] : 0.f;
+}
+
 // ------------------------------------------------------------------ loss with options (OURS: not in the reference)
 // loss_kernel with two of its three terms replaceable (sqdet_loss_fwd_bwd_opt); the confidence term, the
 // decode, `ious`, the partial sums and loss_finish_kernel are loss_kernel's, expression for expression.
@@ -1478,6 +1569,47 @@ extern "C" int sqdet_loss_fwd_bwd_opt(const void* preds, int preds_dtype, const 
 }
 
 extern "C" size_t sqdet_loss_workspace_bytes(void) { return (4 * 512 + 4) * sizeof(float); }
+
+// Distillation: distill_kernel onto the dpreds the loss launch wrote, then loss_finish_kernel into distill3.
+extern "C" size_t sqdet_distill_workspace_bytes(void) { return (4 * 512 + 4) * sizeof(float); }
+
+extern "C" int sqdet_distill_fwd_bwd(const void* preds, int preds_dtype, const void* teacher_preds, int teacher_dtype,
+                                     float* dpreds_inout, void* dpreds_scaled_f16, float loss_scale, float* distill3,
+                                     float* workspace, int batch, int gh, int gw, int apg, int classes, int global_batch,
+                                     const sqdet_distill_options_t* opt, sqdet_stream_t stream) {
+  SQDET_REQUIRE(preds && teacher_preds && dpreds_inout && distill3 && workspace && opt, "distill_fwd_bwd: null pointer");
+  SQDET_REQUIRE(batch > 0 && gh > 0 && gw > 0 && apg > 0 && classes > 0, "distill_fwd_bwd: bad arguments");
+  SQDET_REQUIRE(global_batch <= 0 || global_batch >= batch, "distill_fwd_bwd: global_batch smaller than batch");
+  SQDET_REQUIRE(opt->temperature > 0.f && opt->temperature < INFINITY, "distill_fwd_bwd: temperature must be finite and > 0");
+  const float coefs[3] = {opt->class_coef, opt->conf_coef, opt->bbox_coef};
+  for (int i = 0; i < 3; ++i)
+    SQDET_REQUIRE(coefs[i] >= 0.f && coefs[i] < INFINITY, "distill_fwd_bwd: coefficients must be finite and >= 0");
+  SQDET_REQUIRE(coefs[0] > 0.f || coefs[1] > 0.f || coefs[2] > 0.f, "distill_fwd_bwd: all three coefficients are zero");
+  SQDET_REQUIRE(opt->conf_floor >= 0.f && opt->conf_floor <= 1.f, "distill_fwd_bwd: conf_floor must lie in [0, 1]");
+  SQDET_REQUIRE((preds_dtype == SQDET_F32 || preds_dtype == SQDET_F16) && (teacher_dtype == SQDET_F32 || teacher_dtype == SQDET_F16),
+                "distill_fwd_bwd: bad dtype");
+  const bool half = preds_dtype == SQDET_F16, thalf = teacher_dtype == SQDET_F16;
+  SQDET_REQUIRE(!half || (dpreds_scaled_f16 && loss_scale > 0.f), "distill_fwd_bwd: float16 preds need dpreds_scaled_f16 and a loss scale");
+  DistillArgs a;
+  a.preds = preds; a.teacher = teacher_preds; a.dpreds = dpreds_inout; a.partial = workspace;
+  a.g16 = half ? static_cast<f16*>(dpreds_scaled_f16) : nullptr; a.gscale = half ? loss_scale : 1.f;
+  a.B = batch; a.cells = gh * gw; a.K = apg; a.C = classes;
+  a.Bg = (float)(global_batch > 0 ? global_batch : batch);
+  a.BgA = a.Bg * (float)(gh * gw * apg);
+  a.T = opt->temperature; a.c_cls = opt->class_coef; a.c_conf = opt->conf_coef; a.c_box = opt->bbox_coef; a.floor = opt->conf_floor;
+  const long total = (long)batch * gh * gw * apg;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 512) blocks = 512;
+  hipStream_t st = as_stream(stream);
+  if (half && thalf) hipLaunchKernelGGL((distill_kernel<f16, f16>), dim3(blocks), dim3(256), 0, st, a);
+  else if (half) hipLaunchKernelGGL((distill_kernel<f16, float>), dim3(blocks), dim3(256), 0, st, a);
+  else if (thalf) hipLaunchKernelGGL((distill_kernel<float, f16>), dim3(blocks), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((distill_kernel<float, float>), dim3(blocks), dim3(256), 0, st, a);
+  SQDET_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, workspace, distill3, blocks);
+  SQDET_CHECK_HIP(hipGetLastError());
+  return SQDET_OK;
+}
 
 // ---- optimizer: host-side segment table lives in a small opaque object ----
 struct sqdet_optimizer {

@@ -193,6 +193,95 @@ def assign_policy(a, mc=None):
     return as_dict(opt), off
 
 
+def add_distill_args(ap):
+    """--teacher_net ... --distill_conf_floor (train.py, tools/bench_train.py).  A flag that is not given
+    leaves no attribute behind: distill_policy supplies the defaults, and without --teacher_net there is no policy at all."""
+    import argparse
+    S = argparse.SUPPRESS
+    ap.add_argument("--teacher_net", default=S, choices=NETS,
+                    help="train towards this net's ConvDet output as well as the labels: a second, inference-only model on the same "
+                         "device, whose grid, anchors and classes must be the student's (default: no teacher)")
+    ap.add_argument("--teacher_checkpoint", default=S, metavar="PATH",
+                    help="the teacher's variables: an .npz, or a train dir, whose newest checkpoint is used (synthetic data without "
+                         "it: seeded synthetic variables, seed + 1)")
+    ap.add_argument("--teacher_dtype", default=S, choices=["fp32", "fp16"], help="the teacher's storage dtype (default: the run's)")
+    ap.add_argument("--distill_temperature", type=float, default=S, metavar="T", help="softens both class distributions, T > 0 (default 1)")
+    ap.add_argument("--distill_class_coef", type=float, default=S, metavar="X", help="weight of the class term, the tempered KL (default 1)")
+    ap.add_argument("--distill_conf_coef", type=float, default=S, metavar="X", help="weight of the confidence term, a Bernoulli KL (default 1)")
+    ap.add_argument("--distill_bbox_coef", type=float, default=S, metavar="X", help="weight of the box term, squared error on the deltas (default 1)")
+    ap.add_argument("--distill_conf_floor", type=float, default=S, metavar="F",
+                    help="anchors whose teacher confidence is below F take no part in the class and box terms, 0 <= F <= 1 (default 0)")
+
+
+DISTILL_FLAGS = ("teacher_checkpoint", "teacher_dtype", "distill_temperature", "distill_class_coef", "distill_conf_coef",
+                 "distill_bbox_coef", "distill_conf_floor")
+
+
+def _distill_options_of(a):
+    from .distill import distill_options
+    return distill_options(getattr(a, "distill_temperature", 1.0), getattr(a, "distill_class_coef", 1.0), getattr(a, "distill_conf_coef", 1.0),
+                           getattr(a, "distill_bbox_coef", 1.0), getattr(a, "distill_conf_floor", 0.0))
+
+
+def check_distill_args(ap, a):
+    from ._lib import SqdetError
+    if not hasattr(a, "teacher_net"):
+        for key in DISTILL_FLAGS:
+            if hasattr(a, key):
+                ap.error("--%s needs --teacher_net" % key)
+        return
+    if not getattr(a, "teacher_checkpoint", "") and not getattr(a, "synthetic", 1):      # (tools/bench_train.py is always synthetic)
+        ap.error("--teacher_net needs --teacher_checkpoint (only --synthetic runs may draw the teacher's variables)")
+    try:
+        _distill_options_of(a)
+    except SqdetError as e:
+        ap.error(str(e))
+
+
+def distill_policy(a, mc=None):
+    """(the distillation policy of --teacher_net ... as a checkpoint records it under `distill` -- the teacher net, its dtype,
+    the five options and the teacher checkpoint's path, as a string only -- or None without --teacher_net; None: what a checkpoint
+    without the record was trained with).  Sets mc.DISTILL when mc is given."""
+    from .distill import as_dict
+    policy = None
+    if hasattr(a, "teacher_net"):
+        policy = dict(teacher_net=str(a.teacher_net), teacher_checkpoint=str(getattr(a, "teacher_checkpoint", "")),
+                      teacher_dtype=str(getattr(a, "teacher_dtype", getattr(a, "dtype", "fp32"))), **as_dict(_distill_options_of(a)))
+    if mc is not None:
+        mc.DISTILL = policy
+    return policy, None
+
+
+def teacher_checkpoint_file(path):
+    """--teacher_checkpoint: the .npz itself, or the newest model.ckpt-<step>.npz of a train dir."""
+    import glob
+    import os
+    from . import checkpoint
+    if os.path.isdir(path):
+        found = sorted(checkpoint._steps(glob.glob(os.path.join(path, "model.ckpt-*.npz"))))
+        if not found:
+            raise SystemExit("--teacher_checkpoint: no model.ckpt-<step>.npz in %s" % path)
+        return os.path.join(path, checkpoint.MODEL_FMT % found[-1])
+    if not os.path.isfile(path):
+        raise SystemExit("--teacher_checkpoint: %s is neither a file nor a directory" % path)
+    return path
+
+
+def make_teacher(policy, mc, gpu, seed=0):
+    """The distill.Teacher of a policy beside a student on mc, or None without one.  Its variables: the checkpoint's, or --
+    no path recorded -- synthetic ones of seed + 1 (the student's are of `seed`)."""
+    from . import distill, weights
+    if distill.is_default(policy):
+        return None
+    params = None
+    if policy["teacher_checkpoint"]:
+        path = teacher_checkpoint_file(policy["teacher_checkpoint"])
+        print("Teacher {} from {}".format(policy["teacher_net"], path))
+        params = weights.load_params(path)
+    return distill.Teacher(policy["teacher_net"], mc, gpu=gpu, dtype=policy["teacher_dtype"], params=params, seed=int(seed) + 1,
+                           options=distill.from_dict(policy))
+
+
 def add_optim_args(ap):
     """The update step's flags (train.py, tools/bench_train.py).  A flag that is not given leaves no
     attribute behind: optim.optim_policy supplies the defaults."""

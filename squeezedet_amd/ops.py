@@ -892,6 +892,43 @@ def loss_fwd_bwd(preds, anchors_f32, input_mask, box_delta_input, box_input, lab
     return dpreds, ious, losses
 
 
+class _DistillOptions(C.Structure):     # sqdet_distill_options_t
+    _fields_ = [("temperature", C.c_float), ("class_coef", C.c_float), ("conf_coef", C.c_float), ("bbox_coef", C.c_float),
+                ("conf_floor", C.c_float)]
+
+
+def distill_workspace(device):
+    """A workspace of sqdet_distill_workspace_bytes() for distill_fwd_bwd."""
+    return torch.empty(int(lib().sqdet_distill_workspace_bytes()) // 4 + 16, dtype=torch.float32, device=device)
+
+
+def distill_fwd_bwd(preds, teacher_preds, dpreds, anchors_per_grid, classes, opt, g16=None, loss_scale=1.0, global_batch=0,
+                    distill3=None, ws=None):
+    """The distillation terms of a teacher's preds and their gradient (sqdet_distill_fwd_bwd), issued
+    after the loss call that wrote `dpreds`: dpreds += g in place and -- float16 preds -- g16 = (float16)(dpreds * loss_scale) of
+    the sum.  preds / teacher_preds [B,gh,gw,K*(C+5)], each float32 or float16; opt: a record of distill.distill_options (or
+    any object with its five fields; the library refuses bad values).  Returns distill3 = {class, conf, box} term, float32."""
+    n, gh, gw, ch = [int(v) for v in preds.shape]
+    if tuple(teacher_preds.shape) != tuple(preds.shape) or tuple(dpreds.shape) != tuple(preds.shape):
+        raise _lib.SqdetError("distill_fwd_bwd: preds %s, teacher_preds %s and dpreds %s must have one shape"
+                              % (tuple(preds.shape), tuple(teacher_preds.shape), tuple(dpreds.shape)))
+    if ch != int(anchors_per_grid) * (int(classes) + 5):
+        raise _lib.SqdetError("distill_fwd_bwd: %d channels are not %d anchors x (%d classes + 5)" % (ch, anchors_per_grid, classes))
+    half = preds.dtype == torch.float16
+    if half and (g16 is None or tuple(g16.shape) != tuple(preds.shape)):
+        raise _lib.SqdetError("distill_fwd_bwd: float16 preds need g16 of the same shape")
+    distill3 = torch.empty((3,), dtype=torch.float32, device=preds.device) if distill3 is None else distill3
+    ws = distill_workspace(preds.device) if ws is None else ws
+    o = _DistillOptions(float(opt.temperature), float(opt.class_coef), float(opt.conf_coef), float(opt.bbox_coef), float(opt.conf_floor))
+    check(lib().sqdet_distill_fwd_bwd(_dev(preds, "preds"), dtype_code(preds.dtype), _dev(teacher_preds, "teacher_preds"),
+                                      dtype_code(teacher_preds.dtype), _dev(dpreds, "dpreds", torch.float32),
+                                      _dev(g16, "g16", torch.float16) if half else None, float(loss_scale),
+                                      _dev(distill3, "distill3", torch.float32), _dev(ws, "ws", torch.float32), n, gh, gw,
+                                      int(anchors_per_grid), int(classes), int(global_batch), C.cast(C.pointer(o), C.c_void_p),
+                                      stream_ptr()), "sqdet_distill_fwd_bwd")
+    return distill3
+
+
 class MomentumOptimizer:
     """sqdet_optimizer_*: Momentum + per-variable clip_by_norm (+ weight decay) over flat buffers."""
 

@@ -154,6 +154,10 @@ def _json_safe(o):
     return o
 
 
+LOSS_TERMS = ("class_loss", "conf_loss", "bbox_loss")
+DISTILL_TERMS = ("distill_class_loss", "distill_conf_loss", "distill_bbox_loss")       # a trainer with a teacher adds them to its step's outputs
+
+
 class TrainSummary:
     """``TrainSummary(trainer, train_dir)``; at a summary step ``record(step, out, learning_rate)`` with the dict of the eager
     ``trainer.step(..., keep_activations=True)``.  It issues one statistics call over ``flat_params``, one over ``flat_grads``
@@ -189,7 +193,7 @@ class TrainSummary:
         if rows != self._rows:
             self._dev = torch.empty((rows, self.rb), dtype=torch.uint8, device=self.tr.dev)
             self._host = torch.empty((rows, self.rb), dtype=torch.uint8).pin_memory()
-            self._loss_host = torch.zeros(3, dtype=torch.float32).pin_memory()
+            self._loss_host = torch.zeros(6, dtype=torch.float32).pin_memory()      # (three terms; six under a teacher)
             self._rows = rows
 
     def record(self, step, out, learning_rate):
@@ -207,9 +211,11 @@ class TrainSummary:
                 if plan is None:
                     plan = self._act_plans[n] = StatsPlan([0], [n], n, tr.dev, self.edges)
                 plan.run(t.reshape(-1) if t.is_contiguous() else t.contiguous().reshape(-1), out=self._dev[2 * nv + k:2 * nv + k + 1])
-            losses = torch.stack([out["class_loss"].reshape(()), out["conf_loss"].reshape(()), out["bbox_loss"].reshape(())]).float()
+            # (a trainer with a teacher -- DESIGN.md 3.20 -- reports three more terms; without one the three, as ever)
+            terms = LOSS_TERMS + (DISTILL_TERMS if DISTILL_TERMS[0] in out else ())
+            losses = torch.stack([out[k].reshape(()) for k in terms]).float()
             self._host.copy_(self._dev, non_blocking=True)
-            self._loss_host.copy_(losses, non_blocking=True)
+            self._loss_host[:len(terms)].copy_(losses, non_blocking=True)
             self._event.record(torch.cuda.current_stream())
         meta = dict(step=int(step), learning_rate=float(learning_rate))
         if tr.half:
@@ -230,11 +236,12 @@ class TrainSummary:
         self.drain()
 
     def _emit(self):
-        meta, act_names, _ = self._pending
-        self._pending = None
+        meta, act_names, losses = self._pending
+        self._pending, self._pending_terms = None, losses
         tr, nv, mc = self.tr, len(self.tr.names), self.tr.mc
         rec = decode(self._host, self.n_bins)
-        cl, co, bb = [float(v) for v in self._loss_host]
+        cl, co, bb = [float(v) for v in self._loss_host[:3]]
+        distill = {k: float(v) for k, v in zip(DISTILL_TERMS, self._loss_host[3:])} if len(self._pending_terms) > 3 else {}
         variables, wd = {}, 0.0
         for i, n in enumerate(tr.names):
             variables[n] = _entry(rec[i])
@@ -250,8 +257,8 @@ class TrainSummary:
             e = _entry(rec[2 * nv + k])
             e["sparsity"] = e["zeros"] / e["count"] if e["count"] else 0.0
             activations["activation_summary/" + n] = e
-        line = dict(meta, loss=cl + co + bb + wd, class_loss=cl, conf_loss=co, bbox_loss=bb, weight_decay_loss=wd,
-                    n_bins=self.n_bins, variables=variables, activations=activations)
+        line = dict(meta, loss=cl + co + bb + sum(distill.values()) + wd, class_loss=cl, conf_loss=co, bbox_loss=bb, **distill,
+                    weight_decay_loss=wd, n_bins=self.n_bins, variables=variables, activations=activations)
         self.last = line
         self.lines += 1
         if self.write:

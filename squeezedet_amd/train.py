@@ -104,7 +104,7 @@ class _TrainerBase:
     the optimizer kernel and halves the scale; `growth_interval` clean steps double it."""
 
     def __init__(self, model, process_group=None, loss_scale=1024.0, growth_interval=200, lazy_overflow_check=None,
-                 global_num_objects=False, seed=0, overlap_wgrad=True, optim=None, assign=None):
+                 global_num_objects=False, seed=0, overlap_wgrad=True, optim=None, assign=None, teacher=None):
         if model.dtype not in (torch.float32, torch.float16):
             raise SqdetError("training runs in float32 (the reference's training dtype) or float16 (mixed precision)")
         self.adt = model.dtype                       # activation dtype
@@ -180,6 +180,13 @@ class _TrainerBase:
         # assign: a record of squeezedet_amd.assign -- which anchors the label build marks as positives; None or
         # mode `reference`: sqdet_build_labels, the launches of every run before the policy existed
         self.assign = assign
+        # teacher: a distill.Teacher -- an inference-mode model whose preds for the step's images are a second
+        # target: one launch behind the loss adds its terms' gradient onto dpreds; None: the launches of every run before it existed.
+        # _teacher_preds: set by GraphedStep around its captured calls (the static tensor its eager teacher forward fills)
+        self.teacher, self._teacher_preds, self._step_images, self._distill3 = teacher, None, None, None
+        if teacher is not None:
+            from .distill import check_compatible
+            check_compatible(self.mc, teacher.mc)
         self.found_inf = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self._labels_forked = False
         self._flag_host, self._flag_event = None, None     # lazy_overflow_check's pinned flag + its event, made at the first lazy step
@@ -221,6 +228,9 @@ class _TrainerBase:
                                       dpreds=dpreds, num_objects=num_objects)
         if acts is not None:
             out["activations"] = acts
+        if self.teacher is not None:
+            d = self._distill3
+            out.update(distill_class_loss=d[0], distill_conf_loss=d[1], distill_bbox_loss=d[2])
         return out
 
     def _wgrad(self, fn, *reads):
@@ -321,9 +331,22 @@ class _TrainerBase:
         # reduce_mean over the batch (nn_skeleton.py:304-312) divides by the global batch too; the bucket is then SUMMED
         gb, _ = step_normalisation(self.global_num_objects, int(preds.shape[0]), self.world)
         if self.half:     # float16 preds in, float32 dpreds + its loss-scaled float16 copy out: one launch, no conversions around it
-            return ops.loss_fwd_bwd_mixed(preds, self.model.anchors_f32(), mask, delta, box, lab, self.mc, num_objects, self.loss_scale, global_batch=gb)
-        dpreds, ious, losses = ops.loss_fwd_bwd(preds, self.model.anchors_f32(), mask, delta, box, lab, self.mc, num_objects, global_batch=gb)
-        return dpreds, dpreds, ious, losses
+            out = ops.loss_fwd_bwd_mixed(preds, self.model.anchors_f32(), mask, delta, box, lab, self.mc, num_objects, self.loss_scale, global_batch=gb)
+        else:
+            dpreds, ious, losses = ops.loss_fwd_bwd(preds, self.model.anchors_f32(), mask, delta, box, lab, self.mc, num_objects, global_batch=gb)
+            out = dpreds, dpreds, ious, losses
+        if self.teacher is not None:
+            self._distill(preds, out[0], out[1], gb)
+        return out
+
+    def _distill(self, preds, g, dpreds, gb):
+        """The teacher's terms behind the loss launch: the teacher's preds for the step's images -- its own
+        inference forward, or the static tensor a GraphedStep filled ahead of the replay -- then ONE launch that adds the terms'
+        gradient onto dpreds (and rewrites the loss-scaled float16 copy) and leaves the three terms in self._distill3.  The
+        divisor is the loss's global_batch: a replica's share of the global batch needs no collective of its own."""
+        tp = self._teacher_preds if self._teacher_preds is not None else self.teacher.preds(self._step_images)
+        self._distill3 = ops.distill_fwd_bwd(preds, tp, dpreds, self.mc.ANCHOR_PER_GRID, self.mc.CLASSES, self.teacher.options,
+                                             g16=g if self.half else None, loss_scale=self.loss_scale, global_batch=gb)
 
     def _finish_step(self, apply_update):
         """Gradient all-reduce (the one collective) + clipped Momentum update on the flat buffers."""
@@ -532,6 +555,7 @@ class SqueezeDetTrainer(_TrainerBase):
         """Forward + loss + backward into the flat gradient bucket: kernel launches and stream-ordered allocations only,
         no host round trip (hipGraph-capturable).  _finish_step (all-reduce + update) completes the step."""
         m = self.model
+        self._step_images = images if self.teacher is not None else None      # (what a teacher is shown: _loss)
         self.packplan.run()          # the variables may have changed since the last step (optimizer, load_params): one launch
         # the boundary: the image itself, or the last frozen activation on the inference graph (its fused launches, nothing kept)
         (xb,) = m.run([self.boundary], {m.image_input: images}, use_plan=False)
@@ -789,6 +813,7 @@ class ResNet50ConvDetTrainer(_TrainerBase):
     def forward_backward(self, images, input_mask, box_delta_input, box_input, labels, dropout_mask=None,
                          keep_activations=False, num_objects=None, num_objects_is_global=False):
         m, mc, P = self.model, self.mc, self.model.params
+        self._step_images = images if self.teacher is not None else None      # (what a teacher is shown: _loss)
         eps = mc.BATCH_NORM_EPSILON
         if self._plans_for != self._bn_pointers():     # load_params replaced the (non-trainable) moving statistics
             self._build_plans()
@@ -948,14 +973,22 @@ class GraphedStep:
         self.eager_nobj = tr.global_num_objects and tr.world > 1
         if self.eager_nobj:
             st["nobj"] = torch.ones(1, dtype=torch.float32, device=tr.dev)
+        # a teacher: its inference forward runs eagerly AHEAD of the replay, like the all-reduce above (step() fills
+        # st["tpreds"]); the captured distill launch reads that static tensor
+        if tr.teacher is not None:
+            st["tpreds"] = tr.teacher.preds(st["x"]).clone()
         def build():       # label build + num_objects = sum(input_mask): on the trainer's side stream, beside the forward
             lab = self.build_labels(st)[:4]
             return lab, (st["nobj"] if self.eager_nobj else ops.sum_f32(lab[0].reshape(int(x.shape[0]), -1)))
 
         def run():
             lab, nobj = tr.fork_labels(build)
-            return tr.forward_backward(st["x"], *lab, dropout_mask=st["mask"] if keep != 1.0 else None,
-                                       num_objects=nobj, num_objects_is_global=self.eager_nobj)
+            tr._teacher_preds = st.get("tpreds")
+            try:
+                return tr.forward_backward(st["x"], *lab, dropout_mask=st["mask"] if keep != 1.0 else None,
+                                           num_objects=nobj, num_objects_is_global=self.eager_nobj)
+            finally:
+                tr._teacher_preds = None
         side = torch.cuda.Stream(device=tr.dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -990,6 +1023,8 @@ class GraphedStep:
                 mask = self.build_labels(st)[0]
                 ops.sum_f32(mask, out=st["nobj"])
                 reduce_num_objects(st["nobj"], tr.world, tr.pg)
+            if "tpreds" in st:
+                st["tpreds"].copy_(tr.teacher.preds(st["x"]))
             self.graph.replay()
             tr._finish_step(apply_update)
         return self.out

@@ -58,7 +58,9 @@ def parse_args(argv=None):
     drivers.add_loss_args(ap)             # --bbox_loss, --focal_gamma, --bbox_loss_coef as train.py takes them
     drivers.add_optim_args(ap)            # --optimizer ... --ema_warmup as train.py takes them
     drivers.add_assign_flags(ap)          # --assign ... --assign_topk as train.py takes them
+    drivers.add_distill_args(ap)          # --teacher_net ... --distill_conf_floor as train.py takes them
     args = ap.parse_args(argv)
+    drivers.check_distill_args(ap, args)
     drivers.check_loss_args(ap, args)
     drivers.check_optim_args(ap, args)
     drivers.check_assign_args(ap, args)
@@ -113,7 +115,12 @@ def main():
     assign_policy, _ = drivers.assign_policy(args, mc)
     assign = assign_mod.from_dict(assign_policy)
     assign = None if assign_mod.is_default(assign) else assign
-    tr = trainer(model, lazy_overflow_check=True, optim=optim, assign=assign)
+    # --teacher_net: a second, inference-only model at the step's batch and size (synthetic variables of seed 1 without a checkpoint)
+    if hasattr(args, "teacher_net") and not hasattr(args, "teacher_dtype"):
+        args.teacher_dtype = "fp32" if args.dtype == "f32" else "fp16"
+    distill_policy, _ = drivers.distill_policy(args, mc)
+    teacher = drivers.make_teacher(distill_policy, mc, local_rank, seed=0)
+    tr = trainer(model, lazy_overflow_check=True, optim=optim, assign=assign, **({} if teacher is None else {"teacher": teacher}))
     x = synthetic.synthetic_images(args.batch, mc.IMAGE_HEIGHT, mc.IMAGE_WIDTH, seed=100 + rank).to(dev)
     # ground truth lives on the device; the anchor assignment + dense label build (imdb.py:195-239,
     # train.py:163-224) runs on the GPU inside every step, like the reference's per-batch _load_data
@@ -164,7 +171,7 @@ def main():
                                    + (" + mosaic %g" % args.mosaic if args.mosaic > 0.0 else "")) if args.augment else "synthetic",
                           "config": {"workload": "%s %s training, batch=%d per GPU, forward+loss+backward+"
                                                  "all-reduce+clipped Momentum" % (label, prec, args.batch), "parallelism": "dp%d" % world},
-                          "loss": loss_policy, **({"assign": assign_policy} if assign is not None else {}), **({"optim": optim} if optim is not None else {}), "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
+                          "loss": loss_policy, **({"assign": assign_policy} if assign is not None else {}), **({"optim": optim} if optim is not None else {}), **({"distill": distill_policy, "distill_losses": {k: float(out[k]) for k in ("distill_class_loss", "distill_conf_loss", "distill_bbox_loss")}} if teacher is not None else {}), "skipped_steps": tr.skipped_steps, "loss_scale": tr.loss_scale,
                           "losses": {k: float(out[k]) for k in ("class_loss", "conf_loss", "bbox_loss")}}))
     if world > 1:
         dist.destroy_process_group()

@@ -9,6 +9,7 @@ with on-device summaries.
     python train.py ... --anchor_shapes anchors.json --anchor_report             # shapes from tools/fit_anchors.py; coverage report
     python train.py ... --bbox_loss giou --focal_gamma 2                          # a GIoU box term and a focal class term
     python train.py ... --optimizer adamw --lr_schedule cosine --warmup_steps 500 --ema_decay 0.999   # AdamW, warm-up + cosine, EMA weights
+    python train.py ... --teacher_net vgg16 --teacher_checkpoint logs/vgg16 --distill_temperature 2   # train towards a bigger net's output
 
 Per step as the reference (train.py:266-330): a summary step (step % summary_step == 0) runs the eager trainer step with the
 activations kept and hands it to squeezedet_amd.summary.TrainSummary (-> <train_dir>/summaries.jsonl, in place of TF event
@@ -38,7 +39,11 @@ mc.LOSS_COEF_BBOX (the defaults are the reference's loss
 section 3.18; the defaults are the reference's update, and a run without any of them launches what it always launched).  A policy that
 differs from the defaults is recorded under the key `optim`, and --resume under another one -- --lr_total_steps included -- is refused.
 With --ema_decay every checkpoint adds <train_dir>/ema/model.ckpt-<step>.npz, the model file with the averaged weights, which eval.py
---ema reads.  --anchor_report writes
+--ema reads.  --teacher_net NET [--teacher_checkpoint PATH --teacher_dtype D --distill_temperature T --distill_class_coef X
+--distill_conf_coef X --distill_bbox_coef X --distill_conf_floor F] adds a teacher: a second, inference-only
+model whose ConvDet output for the step's images is a further target of the loss -- its grid, anchors and classes must be the
+student's, which SqueezeDet+'s are not.  The policy is recorded under the key `distill` (the checkpoint's path as a string only), and
+--resume with another one, or with none, is refused; a checkpoint without the key was trained without a teacher.  --anchor_report writes
 <train_dir>/anchor_coverage.json (squeezedet_amd.anchors.dataset_coverage of the training set) once, before the first step.
 Under torch.distributed.run every rank trains its own batches (reader seeded seed + rank) and rank 0 writes the files.
 """
@@ -93,11 +98,13 @@ def parse_args(argv=None):
     drivers.add_loss_args(ap)
     drivers.add_optim_args(ap)
     drivers.add_assign_flags(ap)
+    drivers.add_distill_args(ap)
     a = ap.parse_args(argv)
     drivers.check_dataset_args(ap, a)
     drivers.check_loss_args(ap, a)
     drivers.check_optim_args(ap, a)
     drivers.check_assign_args(ap, a)
+    drivers.check_distill_args(ap, a)
     if not 0.0 <= getattr(a, "mosaic", 0.0) <= 1.0:
         ap.error("--mosaic P needs 0 <= P <= 1")
     if a.resume and a.overwrite:
@@ -121,21 +128,24 @@ def augment_policy(a, mc=None):
     return policy
 
 
+DISTILL_TERMS = ("distill_class_loss", "distill_conf_loss", "distill_bbox_loss")      # a step's extra outputs under --teacher_net
 ASSIGN_OFF = dict(mode="reference")      # what a checkpoint without the `assign` record was trained with (drivers.assign_policy's)
 
 
 def check_resume_record(saved, extra, loss_off, optim_off=None):
     """--resume: what the checkpoint records (`saved`) against what this run asks for (`extra`); SystemExit on the first key that
     differs.  A checkpoint from before a key existed was trained with that key's defaults (`loss_off`: drivers.loss_policy's;
-    `optim_off`: optim.optim_policy's; `assign`: the reference's one anchor per object)."""
-    saved = dict(saved)
+    `optim_off`: optim.optim_policy's; `assign`: the reference's one anchor per object; `distill`: no teacher -- a key a run
+    without a teacher does not record either, so it is compared in both directions)."""
+    saved, extra = dict(saved), dict(extra)
+    saved.setdefault("distill", None)
+    extra.setdefault("distill", None)
     saved.setdefault("assign", ASSIGN_OFF)
     saved.setdefault("augment", AUGMENT_OFF)
     saved.setdefault("mosaic", 0.0)
     saved.setdefault("loss", loss_off)
     if optim_off is not None:             # (a run without the optimizer flags records no `optim` key: its state file is what it was)
         saved.setdefault("optim", optim_off)
-        extra = dict(extra)
         extra.setdefault("optim", optim_off)
     for key, now in extra.items():
         if saved.get(key) != now:
@@ -262,11 +272,19 @@ class Run:
         from squeezedet_amd import assign as assign_mod
         assign, _ = drivers.assign_policy(a, mc)
         self.assign = assign_mod.from_dict(assign)
+        distill, _ = drivers.distill_policy(a, mc)          # (None without --teacher_net: nothing below changes then)
         self.model, trainer_cls = make_trainer(a, mc, local_rank)
         self.model.load_params(initial_params(a, self.model))
+        # (every rank builds its own teacher, from the same file or seed: a second, inference-only model on this rank's device)
+        from squeezedet_amd._lib import SqdetError
+        try:
+            self.teacher = drivers.make_teacher(distill, self.model.mc, local_rank, seed=a.seed)
+        except SqdetError as e:
+            raise SystemExit("--teacher_net: %s" % e)
+        more = {} if self.teacher is None else dict(teacher=self.teacher)
         # (a run without any of the optimizer flags takes the trainer's own path: the launches and state keys of every run before)
         self.tr = trainer_cls(self.model, seed=a.seed, loss_scale=a.loss_scale, optim=None if optim == optim_off else optim,
-                              assign=None if assign_mod.is_default(self.assign) else self.assign)
+                              assign=None if assign_mod.is_default(self.assign) else self.assign, **more)
         images, rois = load_dataset(a, mc)
         resident = int(sum(im.nbytes for im in images)) <= RESIDENT_BYTES
         self.reader = S.BatchReader(mc, images, rois, seed=a.seed + rank, device=dev, dtype=self.model.dtype, resident=resident)
@@ -275,6 +293,8 @@ class Run:
                           assign=assign)
         if optim != optim_off:
             self.extra["optim"] = optim
+        if distill is not None:
+            self.extra["distill"] = distill
         self.first = 0
         if resume_step is not None:
             check_resume_record(checkpoint.read_extra(a.train_dir, resume_step), self.extra, loss_off, optim_off)
@@ -300,7 +320,8 @@ class Run:
                                       [int(tr.view[n].numel()) for n in tr.names], tr.total, self.dev)
         rec = decode(self._wd_plan.run(tr.flat_params).cpu(), self._wd_plan.n_bins)
         wd = sum(float(r["sumsq"]) for n, r in zip(tr.names, rec) if n.endswith("/kernels")) * self.mc.WEIGHT_DECAY / 2
-        return float(out["class_loss"]) + float(out["conf_loss"]) + float(out["bbox_loss"]) + wd
+        terms = ("class_loss", "conf_loss", "bbox_loss") + (() if self.teacher is None else DISTILL_TERMS)
+        return sum(float(out[k]) for k in terms) + wd
 
     def positives_note(self, labels, b):
         """The summaries line's tail under --assign iou / atss: the mean number of positive anchors per object of this batch."""
@@ -329,7 +350,8 @@ class Run:
                 self.images.record(step, b, out["preds"])
             if self.rank == 0:
                 print("conf_loss: {}, bbox_loss: {}, class_loss: {}".format(float(out["conf_loss"]), float(out["bbox_loss"]),
-                                                                           float(out["class_loss"])) + self.positives_note(labels, b))
+                                                                           float(out["class_loss"])) + self.positives_note(labels, b)
+                      + ("" if self.teacher is None else "".join(", {}: {}".format(k, float(out[k])) for k in DISTILL_TERMS)))
         elif summary is not None:
             summary.poll()
             if self.images is not None:

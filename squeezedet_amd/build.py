@@ -66,6 +66,11 @@ SOURCES = [
     # (-ffp-contract=off: the IoU, recall and precision expressions are single IEEE operations, compared bit for bit with NumPy's)
     ("coco_eval.hip", ["-ffp-contract=off"]),
     ("train.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: the decode matches interpret_output operation for operation, and the terms shared by the reference loss and
+    # the loss with options are inlined functions: no contraction, so no rounding depends on where an expression stands)
+    ("loss.hip", ["-ffp-contract=off"]),
+    # (-ffp-contract=off: every operator of the update rules is one float32 IEEE operation, bit for bit tests/optimizer_reference.py)
+    ("optim.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: sumsq adds the exact float64 square; nothing to contract, and the sums keep the order written)
     ("summary.hip", ["-ffp-contract=off"]),
     # (-ffp-contract=off: the pixel restore rint(x + mean) and bbox_transform's cx - w/2 are single roundings, the label's '%.2f' is

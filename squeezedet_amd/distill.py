@@ -1,6 +1,6 @@
 """Knowledge distillation (OURS): a teacher net's ConvDet output as a second target of the loss.
 
-The student trains as ever; after the loss launch one more launch (sqdet_distill_fwd_bwd, squeezedet_amd/csrc/train.hip) adds the
+The student trains as ever; after the loss launch one more launch (sqdet_distill_fwd_bwd, squeezedet_amd/csrc/loss.hip) adds the
 gradient of three terms -- a tempered KL on the class logits, a Bernoulli KL on the confidence logit, a squared error on the box
 deltas, the first and the last weighted by the teacher's confidence -- onto dpreds.  The teacher is a second model of the run in
 inference mode on the same device; it gets no gradient and its parameters never change.  The definition stands in

@@ -805,22 +805,27 @@ def loss_options(mc):
     return name, gamma
 
 
+def _loss_args(preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, ious, losses, ws):
+    """What the four loss entry points share, in their order: [anchors .. dpreds], [ious, losses, workspace, the grid, the config's
+    scalars], and num_objects as (host value, device pointer or None)."""
+    n, gh, gw, ch = [int(v) for v in preds.shape]
+    on_dev = isinstance(num_objects, torch.Tensor)
+    return ([_dev(anchors_f32, "anchors", torch.float32), _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
+             _dev(box_input, "box", torch.float32), _dev(labels, "labels", torch.float32), _dev(dpreds, "dpreds", torch.float32)],
+            [_dev(ious, "ious"), _dev(losses, "losses"), _dev(ws, "ws"), n, gh, gw, int(mc.ANCHOR_PER_GRID), int(mc.CLASSES),
+             float(mc.IMAGE_WIDTH), float(mc.IMAGE_HEIGHT), float(mc.EXP_THRESH), float(mc.EPSILON), float(mc.LOSS_COEF_CLASS),
+             float(mc.LOSS_COEF_CONF_POS), float(mc.LOSS_COEF_CONF_NEG), float(mc.LOSS_COEF_BBOX)],
+            (1.0 if on_dev else float(num_objects), _dev(num_objects, "num_objects", torch.float32) if on_dev else None))
+
+
 def _loss_fwd_bwd_opt(opt, preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, g16, loss_scale,
                       ious, losses, ws, global_batch):
     """sqdet_loss_fwd_bwd_opt: the one entry for float32 / float16 preds and host / device num_objects."""
-    n, gh, gw, ch = [int(v) for v in preds.shape]
-    on_dev = isinstance(num_objects, torch.Tensor)
+    tensors, rest, nobj = _loss_args(preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, ious, losses, ws)
     o = _LossOptions(BOX_LOSSES.index(opt[0]), opt[1])
-    check(lib().sqdet_loss_fwd_bwd_opt(_dev(preds, "preds", torch.float32 if g16 is None else torch.float16), dtype_code(preds.dtype), _dev(anchors_f32, "anchors", torch.float32),
-                                       _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
-                                       _dev(box_input, "box", torch.float32), _dev(labels, "labels", torch.float32),
-                                       _dev(dpreds, "dpreds", torch.float32), None if g16 is None else _dev(g16, "g16", torch.float16),
-                                       float(loss_scale), _dev(ious, "ious"), _dev(losses, "losses"), _dev(ws, "ws"), n, gh, gw,
-                                       int(mc.ANCHOR_PER_GRID), int(mc.CLASSES), float(mc.IMAGE_WIDTH), float(mc.IMAGE_HEIGHT),
-                                       float(mc.EXP_THRESH), float(mc.EPSILON), float(mc.LOSS_COEF_CLASS), float(mc.LOSS_COEF_CONF_POS),
-                                       float(mc.LOSS_COEF_CONF_NEG), float(mc.LOSS_COEF_BBOX), 1.0 if on_dev else float(num_objects),
-                                       _dev(num_objects, "num_objects", torch.float32) if on_dev else None, int(global_batch),
-                                       C.cast(C.pointer(o), C.c_void_p), stream_ptr()), "sqdet_loss_fwd_bwd_opt")
+    check(lib().sqdet_loss_fwd_bwd_opt(_dev(preds, "preds", torch.float32 if g16 is None else torch.float16), dtype_code(preds.dtype), *tensors,
+                                       None if g16 is None else _dev(g16, "g16", torch.float16), float(loss_scale), *rest, *nobj,
+                                       int(global_batch), C.cast(C.pointer(o), C.c_void_p), stream_ptr()), "sqdet_loss_fwd_bwd_opt")
 
 
 def loss_fwd_bwd_mixed(preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, loss_scale, global_batch=0):
@@ -839,18 +844,10 @@ def loss_fwd_bwd_mixed(preds, anchors_f32, input_mask, box_delta_input, box_inpu
     if opt != ("delta_l2", 0.0):      # (mc.BBOX_LOSS / mc.FOCAL_GAMMA: DESIGN.md 3.16; the defaults take the call below, as ever)
         _loss_fwd_bwd_opt(opt, preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, g16, loss_scale,
                           ious, losses, ws, global_batch)
-        return g16, dpreds, ious, losses
-    on_dev = isinstance(num_objects, torch.Tensor)
-    check(lib().sqdet_loss_fwd_bwd_mixed(_dev(preds, "preds", torch.float16), _dev(anchors_f32, "anchors", torch.float32),
-                                         _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
-                                         _dev(box_input, "box", torch.float32), _dev(labels, "labels", torch.float32),
-                                         _dev(dpreds, "dpreds"), _dev(g16, "g16"), float(loss_scale), _dev(ious, "ious"),
-                                         _dev(losses, "losses"), _dev(ws, "ws"), n, gh, gw, int(mc.ANCHOR_PER_GRID), int(mc.CLASSES),
-                                         float(mc.IMAGE_WIDTH), float(mc.IMAGE_HEIGHT), float(mc.EXP_THRESH), float(mc.EPSILON),
-                                         float(mc.LOSS_COEF_CLASS), float(mc.LOSS_COEF_CONF_POS), float(mc.LOSS_COEF_CONF_NEG),
-                                         float(mc.LOSS_COEF_BBOX), 1.0 if on_dev else float(num_objects),
-                                         _dev(num_objects, "num_objects", torch.float32) if on_dev else None, int(global_batch),
-                                         stream_ptr()), "sqdet_loss_fwd_bwd_mixed")
+    else:
+        tensors, rest, nobj = _loss_args(preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, ious, losses, ws)
+        check(lib().sqdet_loss_fwd_bwd_mixed(_dev(preds, "preds", torch.float16), *tensors, _dev(g16, "g16"), float(loss_scale), *rest, *nobj,
+                                             int(global_batch), stream_ptr()), "sqdet_loss_fwd_bwd_mixed")
     return g16, dpreds, ious, losses
 
 
@@ -871,24 +868,13 @@ def loss_fwd_bwd(preds, anchors_f32, input_mask, box_delta_input, box_input, lab
         _loss_fwd_bwd_opt(opt, preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, None, 1.0,
                           ious, losses, ws, global_batch)
         return dpreds, ious, losses
-    if isinstance(num_objects, torch.Tensor):
-        check(lib().sqdet_loss_fwd_bwd_dev(_dev(preds, "preds", torch.float32), _dev(anchors_f32, "anchors", torch.float32),
-                                           _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
-                                           _dev(box_input, "box", torch.float32), _dev(labels, "labels", torch.float32),
-                                           _dev(dpreds, "dpreds"), _dev(ious, "ious"), _dev(losses, "losses"), _dev(ws, "ws"),
-                                           n, gh, gw, int(mc.ANCHOR_PER_GRID), int(mc.CLASSES), float(mc.IMAGE_WIDTH),
-                                           float(mc.IMAGE_HEIGHT), float(mc.EXP_THRESH), float(mc.EPSILON), float(mc.LOSS_COEF_CLASS),
-                                           float(mc.LOSS_COEF_CONF_POS), float(mc.LOSS_COEF_CONF_NEG), float(mc.LOSS_COEF_BBOX),
-                                           _dev(num_objects, "num_objects", torch.float32), int(global_batch), stream_ptr()), "sqdet_loss_fwd_bwd_dev")
-        return dpreds, ious, losses
-    check(lib().sqdet_loss_fwd_bwd(_dev(preds, "preds", torch.float32), _dev(anchors_f32, "anchors", torch.float32),
-                                   _dev(input_mask, "mask", torch.float32), _dev(box_delta_input, "delta", torch.float32),
-                                   _dev(box_input, "box", torch.float32), _dev(labels, "labels", torch.float32),
-                                   _dev(dpreds, "dpreds"), _dev(ious, "ious"), _dev(losses, "losses"), _dev(ws, "ws"),
-                                   n, gh, gw, int(mc.ANCHOR_PER_GRID), int(mc.CLASSES), float(mc.IMAGE_WIDTH),
-                                   float(mc.IMAGE_HEIGHT), float(mc.EXP_THRESH), float(mc.EPSILON), float(mc.LOSS_COEF_CLASS),
-                                   float(mc.LOSS_COEF_CONF_POS), float(mc.LOSS_COEF_CONF_NEG), float(mc.LOSS_COEF_BBOX),
-                                   float(num_objects), int(global_batch), stream_ptr()), "sqdet_loss_fwd_bwd")
+    tensors, rest, nobj = _loss_args(preds, anchors_f32, input_mask, box_delta_input, box_input, labels, mc, num_objects, dpreds, ious, losses, ws)
+    if nobj[1] is not None:
+        check(lib().sqdet_loss_fwd_bwd_dev(_dev(preds, "preds", torch.float32), *tensors, *rest, nobj[1], int(global_batch), stream_ptr()),
+              "sqdet_loss_fwd_bwd_dev")
+    else:
+        check(lib().sqdet_loss_fwd_bwd(_dev(preds, "preds", torch.float32), *tensors, *rest, nobj[0], int(global_batch), stream_ptr()),
+              "sqdet_loss_fwd_bwd")
     return dpreds, ious, losses
 
 

@@ -1,4 +1,4 @@
-"""GPU tests of distillation (sqdet_distill_fwd_bwd, distill_kernel in squeezedet_amd/csrc/train.hip) against
+"""GPU tests of distillation (sqdet_distill_fwd_bwd, distill_kernel in squeezedet_amd/csrc/loss.hip) against
 the float64 restatement of tests/distill_reference.py on the cases of tests/distill_cases.py.
 
 The metric and the bound are those of tests/test_gpu_loss_options.py: the error of a quantity -- the three terms, the gradient -- is

@@ -1,4 +1,4 @@
-"""GPU tests of the loss with options (sqdet_loss_fwd_bwd_opt, loss_opt_kernel in squeezedet_amd/csrc/train.hip; DESIGN.md
+"""GPU tests of the loss with options (sqdet_loss_fwd_bwd_opt, loss_kernel<PT, true> in squeezedet_amd/csrc/loss.hip; DESIGN.md
 section 3.16): IoU / GIoU / DIoU / CIoU box terms and the focal class term, against the float64 restatement of
 tests/loss_options_reference.py on the cases of tests/loss_options_cases.py.
 

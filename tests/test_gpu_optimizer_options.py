@@ -123,7 +123,7 @@ def test_unaligned_base_pointers_take_the_scalar_path_to_the_same_bits(rule):
 
 
 def test_300_variables_under_the_global_clip():
-    """More variables than opt_norm_opt_kernel has threads: its laps of 256 add the per-variable sums in variable-index order."""
+    """More variables than opt_norm_kernel has threads: its laps of 256 add the per-variable sums in variable-index order."""
     offs, cnts, decs, total = opt_layout()
     ops = _ops()
     P, G, M, inside = opt_buffers(offs, cnts, total, seed=1)

@@ -1,4 +1,4 @@
-"""GPU tests of the training step's NON-convolution kernels (squeezedet_amd/csrc/train.hip) at their edges: sum_f32, the
+"""GPU tests of the training step's NON-convolution kernels (squeezedet_amd/csrc/train.hip, loss.hip, optim.hip) at their edges: sum_f32, the
 dropout mask generator, the element-wise kernels past their grid caps and at float16's edges, the max-pool backward tie rule,
 the loss at a size that loops, and the optimizer with more variables than opt_norm_kernel has threads.
 
@@ -28,7 +28,7 @@ The kernel is as accurate as the float32 oracle everywhere (mostly to the digit:
 for op); the well-conditioned cases also sit inside the 2e-5 / 5e-5 of tests/test_gpu_train.py, asserted here again.  No input
 class had to be dropped in any section.
 
-Two defects these tests found, both fixed in train.hip with them: dropout_mask_kernel stored a 2 where keep_prob = 1 meets the
+Two defects these tests found, both fixed in train.hip (scaled_to now stands in train_common.h) with them: dropout_mask_kernel stored a 2 where keep_prob = 1 meets the
 top draw (section 2), and convert_scale float32 -> float16 (and some of the mixed loss kernel's float16 stores) lost the sign of
 a zero product, because hipcc fuses multiply + convert into an FMA with a +0 addend (section 3's edge table, section 5's mixed
 form, which compares bit patterns where torch.equal takes -0 == +0).
